@@ -9,7 +9,14 @@ Multi-GPU: logs shard by vertex across ranks (weak scaling), no data-path collec
 
 Prints ONE JSON line on rank 0 (contract in the task description), with a `roofline`
 object for the dominant kernel (HIP-event durations measured inside the engine on the
-stream the kernels run on) and a `cpu_baseline` object (the C++ oracle on host cores).
+stream the kernels run on).
+
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline figure needs: set-up,
+warm-up, the N timed steps, the result line.  `--full` adds every leg that takes runs of
+its own: the isolated per-kernel pass, the `cpu_baseline` object (the C++ oracle on host
+cores) and the secondary configs (1, 3, 4, 5, the in-flight replay); the `--no-*` options
+leave single legs out of a full run.  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -38,6 +45,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--logs", type=int, default=N_LOGS)
     ap.add_argument("--records", type=int, default=N_REC)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the isolated per-kernel pass, the CPU baselines and the secondary configs "
+                         "(the --no-* options below leave single legs out of such a run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -246,10 +258,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     stats = eng.kernel_stats()
-    # isolated pass (after the timed region): decode, then the slices, each waited for, so
-    # every kernel's duration is its own (no overlap)
+    if args.dump_outputs and rank == 0:
+        d_last, b_last, t_last = outs[(state["k"] - 1) % depth]
+        dump_outputs(args.dump_outputs, torch, d_last, b_last, t_last, o_slice, slice_total, cres, n_req)
+    # isolated pass (--full, after the timed region): decode, then the slices, each waited for,
+    # so every kernel's duration is its own (no overlap)
     eng.kernel_stats_reset()
-    for _ in range(0 if args.no_isolated else min(args.steps, 5)):
+    for _ in range(min(args.steps, 5) if args.full and not args.no_isolated else 0):
         eng.decode_logs_device(handles, starts, dec, base)
         eng.seek_consumers_raw(creq, seek_offs, n_req)
         eng.slice_batch_raw(creq, cres, n_req, o_slice.data_ptr(), o_slice.numel(), device=True)
@@ -315,27 +330,28 @@ def main():
     step_gbs = (dec_bytes + slice_bytes) / (elapsed / args.steps) / 1e9
 
     # ---------------- CPU baseline (rank 0, N=1 only) ----------------
+    # (this and every secondary leg below: --full only)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(bufs, log_bytes, cons, args)
     # ---------------- secondary: config 1 latency (rank 0, N=1 only) ----------------
     # before the larger legs: measured after config 3 and the in-flight leg in the same process,
     # its decode took 0.60 ms instead of 0.25 ms
     c1 = None
-    if rank == 0 and world == 1 and not args.no_config1:
+    if args.full and rank == 0 and world == 1 and not args.no_config1:
         c1 = config1(args, torch)
     # ---------------- secondary: config 3 decode (rank 0, N=1 only) ----------------
     c3 = None
-    if rank == 0 and world == 1 and not args.no_config3:
+    if args.full and rank == 0 and world == 1 and not args.no_config3:
         eng.close()
         del outs, o_slice, dec
         torch.cuda.empty_cache()
         c3 = config3(args, torch, dev)
     ifl = None
-    if rank == 0 and world == 1 and not args.no_inflight:
+    if args.full and rank == 0 and world == 1 and not args.no_inflight:
         ifl = inflight_replay(args, torch, dev)
     c4 = c5 = None
-    if not args.no_config4:  # every rank: the exchange is a collective
+    if args.full and not args.no_config4:  # every rank: the exchange is a collective
         if world == 1:
             eng.close()
         c4, c5 = config4(args, torch, dev, rank, world, dist, rehearse)
@@ -348,6 +364,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -393,6 +410,52 @@ def main():
     eng.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 0xC105_D0
+DUMP_RECORDS = 1 << 20      # decoded records sampled (20 B each as written)
+DUMP_SLICE_BYTES = 1 << 22  # slice output bytes sampled (4 B each as written)
+
+
+def dump_outputs(path, torch, dec, base, tens, o_slice, slice_total, cres, n_req):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy in
+    float64 (float32 for bytes), so two builds can be compared output for output (the
+    inputs are seeded: the same arguments give the same logs and consumers).
+      decode_off / decode_tag / decode_v0   the decode's SoA outputs (record offset, tag, first
+                                            value; the values are exact in float64 below 2^53)
+      decode_w_*                            its wide-record side arrays (written if it has any)
+      decode_base                           every log's first record index, and the total
+      decode_counts                         n_rec, n_wide, err_status
+      slice_bytes                           the packed delta slices of every (consumer, log) pair
+      slice_res                             per request: status, has_delta, offset_from_epoch,
+                                            len, out_off
+    An array longer than its sample size is written as a fixed sample: the elements at
+    unique(default_rng(DUMP_SEED).integers(0, n, size)), the record arrays sharing one draw --
+    about 36 MB in all at the default shape."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    dev = o_slice.device
+
+    def pick(n, size):
+        return None if n <= size else torch.from_numpy(np.unique(rng.integers(0, n, size))).to(dev)
+
+    def save(name, t, n, idx, dtype):
+        v = t[:n] if idx is None else t[idx]
+        np.save(os.path.join(path, name + ".npy"), v.cpu().numpy().astype(dtype))
+
+    n_rec, n_wide = int(dec.n_rec), int(dec.n_wide)
+    idx = pick(n_rec, DUMP_RECORDS)
+    save("decode_off", tens[0], n_rec, idx, np.float64)
+    save("decode_tag", tens[1], n_rec, idx, np.float32)
+    save("decode_v0", tens[2], n_rec, idx, np.float64)
+    if n_wide:
+        for name, t in zip(("w_idx", "w_rc", "w_v1", "w_var_off", "w_var_len", "w_sub"), tens[3:]):
+            save("decode_" + name, t, min(n_wide, t.numel()), None, np.float64)
+    np.save(os.path.join(path, "decode_base.npy"), base.astype(np.float64))
+    np.save(os.path.join(path, "decode_counts.npy"), np.array([n_rec, n_wide, dec.err_status], np.float64))
+    save("slice_bytes", o_slice, slice_total, pick(slice_total, DUMP_SLICE_BYTES), np.float32)
+    res = np.array([[r.status, r.has_delta, r.offset_from_epoch, r.len, r.out_off] for r in cres[:n_req]], np.float64)
+    np.save(os.path.join(path, "slice_res.npy"), res.reshape(n_req, 5))
 
 
 def dist_info(torch, dist, world, rehearse):

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"; out=gpurun_out/ab; rm -rf 
 rounds=$1; shift
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
-    CLONOS_LIB=$PWD/ab/lib$v.so timeout -k 10 150 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-config3 --no-inflight --no-config4 > $out/c2_${v}_$r.json 2>$out/c2_${v}_$r.err || exit 1
+    CLONOS_LIB=$PWD/ab/lib$v.so timeout -k 10 150 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-config3 --no-inflight --no-config4 > $out/c2_${v}_$r.json 2>$out/c2_${v}_$r.err || exit 1
     [ -n "$NO_C3" ] || CLONOS_LIB=$PWD/ab/lib$v.so timeout -k 10 200 python3 tools/bench_config3.py --logs 128 --steps 3 > $out/c3_${v}_$r.json 2>$out/c3_${v}_$r.err || exit 1
   done
 done

@@ -8,7 +8,7 @@ rounds=$1; shift
 for r in $(seq 1 $rounds); do
   for spec in "$@"; do
     name=${spec%%=*}; vars=${spec#*=}
-    env $vars timeout -k 10 150 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-config3 --no-inflight --no-config4 --no-config1 > $out/c2_${name}_$r.json 2>$out/c2_${name}_$r.err || exit 1
+    env $vars timeout -k 10 150 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-config3 --no-inflight --no-config4 --no-config1 > $out/c2_${name}_$r.json 2>$out/c2_${name}_$r.err || exit 1
     [ -n "$NO_C3" ] || env $vars timeout -k 10 200 python3 tools/bench_config3.py --logs 128 --steps 3 > $out/c3_${name}_$r.json 2>$out/c3_${name}_$r.err || exit 1
   done
 done

@@ -6,7 +6,7 @@
 # included) ends the call.  Output under $OUT (default gpurun_out/run).
 #   tests[=files]      pytest -m gpu (all of tests/, or the comma-separated files)
 #   smoke              __graft_entry__.smoke()
-#   bench[=args]       bench.py (default arguments: the driver's default line)
+#   bench[=args]       bench.py --full (every leg; default arguments otherwise)
 #   c2[=N]             N config-2-only bench lines (default 3), $OUT/c2_<i>.json
 #   trace              rocprofv3 --kernel-trace --stats of a short config-2 bench
 #   pmc                tools/pmc.sh counter passes over the decode and gather kernels
@@ -19,7 +19,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 2
 OUT=${OUT:-gpurun_out/run}
 mkdir -p "$OUT"
-C2="--steps 20 --warmup 5 --no-cpu-baseline --no-config3 --no-inflight --no-config4 --no-config1"
+C2="--full --steps 20 --warmup 5 --no-cpu-baseline --no-config3 --no-inflight --no-config4 --no-config1"
 run() {  # name, limit, command...
   local name=$1 lim=$2
   shift 2
@@ -47,7 +47,7 @@ for step in "$@"; do
       tail -2 "$OUT/smoke.log"
       ;;
     bench)
-      run bench 500 env $BENCH_ENV python3 bench.py $val > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+      run bench 500 env $BENCH_ENV python3 bench.py --full $val > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
       cat "$OUT/bench.json"
       ;;
     c2)
@@ -72,7 +72,7 @@ for step in "$@"; do
       ;;
     rehearse)
       n=${val:-2}
-      run "rehearse $n" 900 env CLONOS_BENCH_REHEARSAL=1 python3 bench.py --gpus "$n" --steps 5 --warmup 2 \
+      run "rehearse $n" 900 env CLONOS_BENCH_REHEARSAL=1 python3 bench.py --full --gpus "$n" --steps 5 --warmup 2 \
         --no-cpu-baseline $BENCH_ARGS > "$OUT/rehearse_w$n.json" 2> "$OUT/rehearse_w$n.err" || exit $?
       cat "$OUT/rehearse_w$n.json"
       ;;

@@ -12,5 +12,5 @@ rc=$?
 echo "pytest rc=$rc"
 [ $rc -le 1 ] || exit $rc
 echo smoke && timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 &&
-echo bench && timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" &&
+echo bench && timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" &&
 echo done

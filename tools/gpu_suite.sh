@@ -12,5 +12,5 @@ timeout -k 10 1500 python -u -m pytest $tests -m gpu -x -q --timeout 120 --timeo
 rc=$?
 echo "pytest rc=$rc"; tail -3 $out/pytest.log
 [ $rc -le 1 ] || exit $rc
-echo bench && timeout -k 10 400 python3 bench.py > $out/bench.json 2> $out/bench.err
+echo bench && timeout -k 10 400 python3 bench.py --full > $out/bench.json 2> $out/bench.err
 echo "bench rc=$?"

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=${1:-gpurun_out/probe}
 mkdir -p "$OUT"
-C2="--steps 20 --warmup 3 --no-cpu-baseline --no-config3 --no-inflight --no-config4 --no-config1"
+C2="--full --steps 20 --warmup 3 --no-cpu-baseline --no-config3 --no-inflight --no-config4 --no-config1"
 echo probe && CLONOS_STEP_PROBE=1 CLONOS_HOST_PROF=1 timeout -k 10 300 python -u bench.py $C2 > "$OUT/probe.json" 2> "$OUT/probe.err" &&
 echo trace && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
     python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-config3 --no-inflight --no-isolated --no-config4 --no-config1 > "$OUT/trace.log" 2>&1 &&

@@ -24,7 +24,7 @@ pmc() {  # pmc <dir> <counters> <program...>
   local d=$1 c=$2; shift 2
   timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $c -d "$OUT/$d" -o run --output-format csv -- "$@" > "$OUT/$d.log" 2>&1
 }
-echo "bench" && timeout -k 10 600 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" &&
+echo "bench" && timeout -k 10 600 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" &&
 echo "trace" && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
     python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-config3 --no-inflight --no-isolated --no-config4 --no-config1 > "$OUT/trace.log" 2>&1 &&
 echo "c2 pmc" && pmc c2_fetch FETCH_SIZE python3 bench.py $C2 && pmc c2_write WRITE_SIZE python3 bench.py $C2 &&
