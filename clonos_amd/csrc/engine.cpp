@@ -1934,7 +1934,6 @@ struct clg_engine {
     clg::DecodeOut o{};
     bool span_local = false;
     bool lookback_bad = false;  // emit found a scan offset other than its predecessor's prefix
-    bool one = false;           // the one-pass decode (k_decode_one) ran, not the three passes
     // its decode slot (read-back buffer, staged plan, jser arena note), and for a queued
     // decode the event after its read-back, which its completion waits for (not the stream:
     // a later decode may be queued behind it)
@@ -1943,16 +1942,6 @@ struct clg_engine {
     int note() const { return slot ? int(1 + slot) : 0; }
   };
   FusedRun zlast;  // the last finished fast run
-  // The one-pass decode (k_decode_one, decode_fused.hip): off by default, since on MI355X it is
-  // slower than the three passes (config 2: 0.58 against 0.43 ms, DESIGN.md section 4, "One
-  // pass").  CLONOS_ONE_PASS=1 uses it for batches of more than kZSmallTilesMax tiles without
-  // tables or small whole spans; =2 for every batch the three passes would take (the tests).
-  // An abort goes to the three passes (after_abort), and so does a run with allow_one cleared.
-  const int one_pass = [] {
-    const char* v = getenv("CLONOS_ONE_PASS");
-    return v ? atoi(v) : 0;
-  }();
-  bool allow_one = true;
   int launch_fused(DecodePlan& p, uint64_t log_bytes, clg_decoded* out, bool jser, FusedRun* r) {
     HostTimer ht(this, "host_decode_launch");
     const uint32_t nt = p.n_tiles, ns = uint32_t(p.spans.size());
@@ -1963,13 +1952,8 @@ struct clg_engine {
     const char* prof_path = getenv("CLONOS_SCAN_PHASES");  // developer diagnostics: phase stamps
     // pass 0 (small whole spans, a lane each) for batches without Serializable tables
     const bool tiny = p.n_tiny && !jser && !prof_path;
-    // (default: logs in segments of at least two tiles, or host input -- tiles of a few hundred
-    // bytes give canonical exits from too few bytes, which often miss, and the batch goes again)
-    const bool one = one_pass && allow_one && !jser && !p.n_tiny && !zdbg &&
-                     ((nt > clg::kZSmallTilesMax && (!p.run_count() || C() >= 2 * clg::kZTile)) || one_pass == 2);
-    r->one = one;
     const uint32_t G = clg::decode_count_grid(jser, nt);
-    const bool chunked = G && nt > G && ns > 1 && !one;
+    const bool chunked = G && nt > G && ns > 1;
     std::optional<HostTimer> hsub(std::in_place, this, "host_launch_chunks");  // (CLONOS_HOST_PROF sub-stages)
     if (chunked) count_chunks(p, G, tiny, chunk_buf);
     PlanLayout L;
@@ -1990,8 +1974,7 @@ struct clg_engine {
     const size_t nbk = (size_t(nt) + 1023) / 1024, fw = (size_t(nt) + 7) / 8;
     const size_t o_cnt = 2 * size_t(nt) + fw, n_ab = clg::kZAbortWords / 2;
     const size_t o_span = o_cnt + 2 * size_t(nt) + nbk, o_ab = o_span + 2 * size_t(ns), o_lb = o_ab + n_ab;
-    // (ent: G words for the count pass's chunks, or the one-pass decode's 65 counters, 128 B apart)
-    const size_t n_ent = std::max<size_t>(one ? 65 * 16 : 1, G);
+    const size_t n_ent = std::max<size_t>(1, G);  // (ent: a word per chunk of the count pass)
     const size_t o_ent = o_lb + 1 + nbk, words = o_ent + n_ent;
     CHK(d_zctl.ensure(words * 8));
     CHK(d_zbits.ensure(std::max<size_t>(1, nt) * 64 * 16));
@@ -2003,7 +1986,7 @@ struct clg_engine {
     uint64_t* w = d_zctl.as<uint64_t>();
     uint32_t* ab = reinterpret_cast<uint32_t*>(w + o_ab);
     if (zdbg) CHK(d_dbg.ensure(clg::kZDbgTiles * 4 + size_t(nt) * 16));
-    if (prof_path) CHK(d_prof.ensure(size_t(nt) * (one ? 128 : 64)));  // (one pass: its phase stamps too)
+    if (prof_path) CHK(d_prof.ensure(size_t(nt) * 64));
     const uint32_t jwork_cap = std::max<uint32_t>(uint32_t(nt) * 16 + 1024, zjwork_min);
     if (jser) {
       CHK(d_zjpos.ensure((size_t(nt) * clg::kZJCap + zjovf_cap) * 4));
@@ -2022,7 +2005,7 @@ struct clg_engine {
     ctl.jovf_cap = zjovf_cap;
     ctl.span_bad = d_zbad.as<uint32_t>();
     ctl.skip_bad = 0;
-    ctl.span_err = keep_errors && !one ? d_zerr.as<uint64_t>() : nullptr;  // (one pass: errors abort it)
+    ctl.span_err = keep_errors ? d_zerr.as<uint64_t>() : nullptr;
     ctl.chunk = chunked ? reinterpret_cast<const uint32_t*>(d_plan.as<uint8_t>() + L.o_chunk) : nullptr;
     ctl.tiny = tiny ? 1u : 0u;
     ctl.ex = w + nt;
@@ -2084,21 +2067,20 @@ struct clg_engine {
       }
       hsub->lap("host_enq_prep");
       if (zdbg) HIPCHK(hipMemsetAsync(d_dbg.p, 0, clg::kZDbgTiles * 4 + size_t(nt) * 16, stream));
-      if (prof_path) HIPCHK(hipMemsetAsync(d_prof.p, 0, size_t(nt) * (one ? 128 : 64), stream));
+      if (prof_path) HIPCHK(hipMemsetAsync(d_prof.p, 0, size_t(nt) * 64, stream));
       if (evp) HIPCHK(hipEventRecord(evp[0], stream));
-      if (tiny) CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, o, stream, 4));  // small whole spans
-      if (one) {  // count, look-back and emit in one launch
-        if (ev) HIPCHK(hipEventRecord(ev[2], stream));
-        CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, o, stream, 6));
-        if (ev) HIPCHK(hipEventRecord(ev[3], stream));
-      }
-      for (int ph : {3, 0, 5, 2}) {  // jser tables, count, offsets (one launch), emit
-        if (one) break;
-        if (ph == 3 && !jser) continue;
-        const int k = ph == 3 ? 0 : ph == 0 ? 1 : ph == 5 ? 2 : 3;
-        if (ev) HIPCHK(hipEventRecord(ev[2 * k], stream));
-        CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, o, stream, uint32_t(ph)));
-        if (ev) HIPCHK(hipEventRecord(ev[2 * k + 1], stream));
+      if (tiny) CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, o, stream, clg::FusedPhase::CountTiny));
+      // the passes in launch order, each bracketed by the event pair ev[2 * slot], ev[2 * slot + 1]
+      static constexpr struct {
+        clg::FusedPhase phase;
+        int slot;
+      } kPasses[] = {{clg::FusedPhase::JserTables, 0}, {clg::FusedPhase::Count, 1}, {clg::FusedPhase::Scan, 2},
+                     {clg::FusedPhase::Emit, 3}};
+      for (const auto& ps : kPasses) {
+        if (ps.phase == clg::FusedPhase::JserTables && !jser) continue;
+        if (ev) HIPCHK(hipEventRecord(ev[2 * ps.slot], stream));
+        CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, o, stream, ps.phase));
+        if (ev) HIPCHK(hipEventRecord(ev[2 * ps.slot + 1], stream));
       }
       if (evp) HIPCHK(hipEventRecord(evp[1], stream));
       hsub->lap("host_enq_kernels");
@@ -2126,11 +2108,7 @@ struct clg_engine {
       for (auto& e : evp) e = get_event();
     }
     CHK(enqueue(timing ? ev : nullptr, timing ? evp : nullptr));
-    if (timing && one) {  // the one kernel's duration: its bytes need the record count (finish_fused)
-      ev_pool.insert(ev_pool.end(), {ev[0], ev[1], ev[4], ev[5], ev[6], ev[7]});
-      r->ea = ev[2];
-      r->eb = ev[3];
-    } else if (timing) {  // per-kernel durations, read back by sync(); emit's bytes need the record count
+    if (timing) {  // per-kernel durations, read back by sync(); emit's bytes need the record count
       if (jser) timings.push_back(PendingTiming{"decode_jser", ev[0], ev[1], log_bytes});
       else ev_pool.insert(ev_pool.end(), {ev[0], ev[1]});
       timings.push_back(PendingTiming{"decode_count", ev[2], ev[3], log_bytes});
@@ -2160,7 +2138,7 @@ struct clg_engine {
     }
     HostTimer ht(this, "host_decode_finish");
     if (const char* prof_path = getenv("CLONOS_SCAN_PHASES")) {
-      std::vector<uint64_t> hp(size_t(nt) * (r.one ? 16 : 8));
+      std::vector<uint64_t> hp(size_t(nt) * 8);
       hipMemcpy(hp.data(), d_prof.p, hp.size() * 8, hipMemcpyDeviceToHost);
       if (FILE* fp = fopen(prof_path, "wb")) {
         fwrite(hp.data(), 8, hp.size(), fp);
@@ -2210,8 +2188,7 @@ struct clg_engine {
       // (entries guessed across them), so the tables decide; a second abort goes robust
       // (a table arena that was full, now grown: the same, once)
       *need_jser = (!jser && hab[5] && !spilled) || (jser && (spilled || grown));
-      r.span_local = !r.one && !*need_jser && !spilled && !hab[4] && !hab[6] && !hab[10];
-      if (r.one) stats["decode_one_abort"].launches++;  // (the three passes decode it again)
+      r.span_local = !*need_jser && !spilled && !hab[4] && !hab[6] && !hab[10];
       r.lookback_bad = hab[10] != 0;
       if (hab[10]) stats["decode_lookback_check"].launches++;  // a look-back read gave a wrong offset
       zlast = r;
@@ -2255,7 +2232,7 @@ struct clg_engine {
     uint64_t nrec = 0, nwide = 0;
     span_totals(p, hz, span_rec_base, &nrec, &nwide);
     if (!jser) lean_hint = nwide * 16 < nrec;
-    if (ea) timings.push_back(PendingTiming{r.one ? "decode_one" : "decode_emit", ea, eb, log_bytes + 13 * nrec + 25 * nwide});
+    if (ea) timings.push_back(PendingTiming{"decode_emit", ea, eb, log_bytes + 13 * nrec + 25 * nwide});
     // the pipeline's algorithmic bytes: log bytes read + the SoA rows
     if (r.pa) timings.push_back(PendingTiming{"decode_pipeline", r.pa, r.pb, log_bytes + 13 * nrec + 25 * nwide});
     return finish_out(out, nrec, nwide);
@@ -2665,8 +2642,8 @@ struct clg_engine {
     CHK(clg::launch_decode_inject(zs, reinterpret_cast<const uint32_t*>(d_sf_meta.as<uint8_t>() + size_t(nb) * 8),
                                   d_sf_meta.as<uint64_t>(), nb, ctl, stream));
     HIPCHK(hipMemsetAsync(ctl.abort, 0, 32, stream));
-    CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, zlast.o, stream, 1));
-    CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, zlast.o, stream, 2));
+    CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, zlast.o, stream, clg::FusedPhase::Scan3));
+    CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, zlast.o, stream, clg::FusedPhase::Emit));
     // the robust records into place, at the bases the scan gave the bad spans (one launch)
     const clg::DecodeOut sc{s_off, s_tag, s_v0, s_widx, s_wrc, s_wv1, s_wvo, s_wvl, s_wsub, RC, WC};
     CHK(clg::launch_sf_place(reinterpret_cast<const clg::SfPlace*>(d_sf_meta.as<uint8_t>() + o_place), nb, sc, zlast.o,
@@ -2702,15 +2679,6 @@ struct clg_engine {
       pf.reset();
       build(pf, clg::kZTile);
       CHK(plan_ok(pf));
-    }
-    // the one-pass decode aborted (a case its rules leave to the three passes): those
-    if (zlast.one) {
-      allow_one = false;
-      const int st = run_fused(pf, log_bytes, out, span_rec_base, &aborted, zlast.jser || need_jser, &nj);
-      allow_one = true;
-      CHK(st);
-      if (!aborted) return CLG_OK;
-      need_jser = nj;
     }
     // a look-back read gave a wrong offset (emit's check): the fast path once more, as it was
     if (zlast.lookback_bad && !need_jser) {

@@ -302,7 +302,19 @@ constexpr uint32_t kZTinySpan = 1024;   // whole spans up to this many bytes: pa
 // 4 wait timeout, 5 Serializable record met without tables, 6 a Serializable arena or work
 // list full (the host grows it and runs again);
 // abort[7] != 0: phase 3 found Serializable candidates (any tile)
-// phase 0: count, 1: scan, 2: emit, 3: Serializable tables, 4: small whole spans (before 0)
+// The launches of the fused decode (launch_decode_fused).  A batch takes Count, Scan, Emit in
+// that order, after one optional launch: JserTables when it builds tables, or CountTiny when it
+// holds small whole spans and builds none (the two never occur together).
+// (Comments elsewhere name them by number: "phase 3" the tables, "phase 5" the one-launch scan,
+// "pass 0" the small whole spans.)
+enum class FusedPhase : uint32_t {
+  Count = 0,       // count and chunk repair over a resident grid
+  Scan3 = 1,       // the offsets in three launches, no look-back words (the per-span fallback's re-run)
+  Emit = 2,        // the records out, a block per tile
+  JserTables = 3,  // Serializable length tables (from the sidecar's lists where there are any)
+  CountTiny = 4,   // small whole spans, a lane each
+  Scan = 5,        // scan, block offsets and span ranges in one launch (ctl.lb zeroed)
+};
 // Per-span fallback: cnt[t] of every tile of bad span bad[i] := t == its first tile ?
 // packed[i] (the robust decode's wide << 31 | records) : 0.
 int launch_decode_inject(const SpanDesc* d_spans, const uint32_t* d_bad, const uint64_t* d_packed, uint32_t n_bad,
@@ -325,7 +337,7 @@ int launch_sf_place(const SfPlace* d_place, uint32_t n_bad, DecodeOut scratch, D
 int launch_err_classify(const TileDesc* d_tiles, const SpanDesc* d_spans, const uint32_t* d_bad, uint32_t n_bad,
                         FusedCtl ctl, int32_t* d_res, JArena ar, void* stream);
 int launch_decode_fused(const TileDesc* d_tiles, uint32_t n_tiles, const SpanDesc* d_spans, uint32_t n_spans,
-                        FusedCtl ctl, DecodeOut out, void* stream, uint32_t phase);
+                        FusedCtl ctl, DecodeOut out, void* stream, FusedPhase phase);
 // The count pass's grid for n_tiles tiles (the blocks the device keeps resident, at most one
 // per tile); CLG_E_DEVICE as 0.
 uint32_t decode_count_grid(bool jser, uint32_t n_tiles);

@@ -8,12 +8,14 @@ robust pipeline and still match.
 """
 import numpy as np
 import pytest
+import torch
 
 import _oracle as O
-from clonos_amd import CausalLogID, ClonosError, Engine
+from clonos_amd import CausalLogID, ClonosError, Engine, _lib
 from clonos_amd import determinants as D
 from clonos_amd import synth
 from test_gpu_decode import assert_span_equal
+from test_gpu_decode_async import DevOut
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +38,7 @@ def test_fused_random_no_serializable(feng, seed):
     dec = feng.decode_host(buf)
     assert_span_equal(dec, 0, buf)
     st = feng.kernel_stats()
-    assert ("decode_one" in st or "decode_count" in st) and not fell_back(feng)
+    assert "decode_count" in st and not fell_back(feng)
 
 
 def test_fused_config2_multi_span(feng):
@@ -300,3 +302,152 @@ def test_fused_dense_serializable_error_past_lds_entries(feng, where):
     with pytest.raises(ClonosError) as ei:
         feng.decode_host(buf)
     assert ei.value.status == st and ei.value.err_off == eo and ei.value.err_tag == et
+
+
+# ---------------------------------------------------------------------------------------
+# The three passes on every batch the fast path takes, small ones included (engines opened by
+# the case itself, so that each chooses its segment size and flags).
+# ---------------------------------------------------------------------------------------
+def _count(eng, name):
+    return eng.kernel_stats().get(name, {}).get("launches", 0)
+
+
+@pytest.fixture
+def three_pass():
+    engines = []
+
+    def make(**kw):
+        e = Engine(timing=True, decode="three_pass", **kw)
+        engines.append(e)
+        return e
+
+    yield make
+    for e in engines:
+        e.close()
+
+
+def _config2_spans(rng, n, lo, hi):
+    parts = [synth.config2_log(int(rng.integers(lo, hi)), rng)[0].tobytes() for _ in range(n)]
+    blob, spans = b"", []
+    for p in parts:
+        pad = int(rng.integers(0, 17))
+        blob += bytes(pad)
+        spans.append((len(blob), len(p)))
+        blob += p
+    return parts, blob, spans
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_fused_config2_host_input(three_pass, seed):
+    eng = three_pass()
+    rng = np.random.default_rng(200 + seed)
+    parts, blob, spans = _config2_spans(rng, 7, 0 if seed == 0 else 1000, 120_000)
+    dec = eng.decode_host(blob, spans)
+    for s, p in enumerate(parts):
+        assert_span_equal(dec, s, p)
+
+
+@pytest.mark.parametrize("seg", [256, 16384])
+def test_fused_logs_in_hbm(three_pass, seg):
+    eng = three_pass(segment_bytes=seg, pool_segments=(1 << 26) // seg)
+    rng = np.random.default_rng(seg)
+    logs, blobs = [], []
+    for v in range(9):
+        b, _ = synth.config2_log(int(rng.integers(2000, 90_000)), rng)
+        log = eng.open_log(CausalLogID.main(v))
+        log.processUpstreamDelta(b.tobytes(), 0, 0)
+        logs.append(log)
+        blobs.append(b.tobytes())
+    dec = eng.decode_logs(logs, [0] * len(logs))
+    for s, b in enumerate(blobs):
+        assert_span_equal(dec, s, b)
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_fused_mixed_fixed_and_wide_records(three_pass, seed):
+    """Every tag but Serializable, with long TimerTrigger names now and then: a record longer
+    than the canonical walk's reach across a tile end is repaired by the count pass, and the
+    batch stays on the fast path."""
+    eng = three_pass()
+    rng = np.random.default_rng(300 + seed)
+    buf = synth.random_log(150_000, rng, allow_serializable=False)
+    dec = eng.decode_host(buf)
+    assert_span_equal(dec, 0, buf)
+    assert _count(eng, "decode_fallback") == 0
+
+
+def test_fused_long_records(three_pass):
+    """TimerTrigger names of 3-20 KB, longer than a tile, between runs of Order records."""
+    eng = three_pass()
+    rng = np.random.default_rng(11)
+    recs = []
+    for i in range(400):
+        if i % 3 == 0:
+            recs.append(D.encode(D.TimerTriggerDeterminant(i, i, D.INTERNAL, b"n" * int(rng.integers(3000, 20000)))))
+        else:
+            recs.append(D.encode(D.OrderDeterminant(1)) * int(rng.integers(1, 400)))
+    buf = b"".join(recs)
+    dec = eng.decode_host(buf)
+    assert_span_equal(dec, 0, buf)
+    assert _count(eng, "decode_fallback") == 0
+
+
+def test_fused_zero_runs(three_pass):
+    eng = three_pass()
+    for n in (5, 4096, 40_000, 300_001):
+        buf = D.encode(D.OrderDeterminant(0)) * n
+        dec = eng.decode_host(buf)
+        assert dec.n_rec == n
+        np.testing.assert_array_equal(dec.off, np.arange(n, dtype=np.uint32) * 2)
+
+
+@pytest.mark.parametrize("prefix_n,bad", [(50_000, b"\x08"), (20_000, b"\x01\x00\x00"),
+                                          (30_000, b"\x04" + b"\x00" * 12 + b"\x07" + b"\x00")])
+def test_fused_errors_match_the_oracle(three_pass, prefix_n, bad):
+    eng = three_pass()
+    rng = np.random.default_rng(prefix_n)
+    buf = synth.random_log(prefix_n, rng, allow_serializable=False) + bad + synth.random_log(50, rng, False)
+    st, _, eo, et = O.decode(buf)
+    assert st != 0
+    with pytest.raises(ClonosError) as ex:
+        eng.decode_host(buf)
+    assert ex.value.status == st and ex.value.err_off == eo and ex.value.err_tag == et
+
+
+def test_fused_two_in_flight_device_outputs(three_pass):
+    """The bench's pipelined step on the three passes: two decodes queued into device outputs,
+    slices gathered on the second stream between them, each compared with the oracle."""
+    eng = three_pass(segment_bytes=16384, pool_segments=1 << 13, async_slice=True)
+    rng = np.random.default_rng(41)
+    blobs = [synth.config2_log(int(rng.integers(20_000, 80_000)), rng)[0] for _ in range(8)]
+    logs = []
+    for v, b in enumerate(blobs):
+        lg = eng.open_log(CausalLogID.main(v))
+        lg.processUpstreamDelta(b.tobytes(), 0, 1)
+        logs.append(lg)
+    n, total = len(logs), sum(int(b.size) for b in blobs)
+    ref = eng.decode_logs(logs, [1] * n)
+    for s, b in enumerate(blobs):
+        assert_span_equal(ref, s, b.tobytes())
+    sets = [DevOut(total // 2 + n + 1, total // 6 + n + 1) for _ in range(2)]
+    h = np.array([lg.handle for lg in logs], np.uint32)
+    creq = (_lib.SliceReq * n)()
+    cres = (_lib.SliceRes * n)()
+    for i, lg in enumerate(logs):
+        creq[i].log, creq[i].consumer, creq[i].epoch = lg.handle, _lib.ChannelId(7, i), 1
+    sl = torch.empty(total + 64, dtype=torch.uint8, device="cuda")
+    queued = []
+    for k in range(6):
+        so = sets[k % 2]
+        if len(queued) == 2:
+            eng.decode_wait()
+            queued.pop(0).check(ref)
+        so.base = np.zeros(n + 1, np.uint64)
+        eng.decode_logs_device_async(h, np.ones(n, np.int64), so.dec, so.base)
+        queued.append(so)
+        eng.seek_consumers_raw(creq, np.zeros(n, np.int32), n)
+        assert eng.slice_batch_raw(creq, cres, n, sl.data_ptr(), sl.numel(), device=True) == total
+    while queued:
+        eng.decode_wait()
+        queued.pop(0).check(ref)
+    assert _count(eng, "decode_async_redo") == 0
