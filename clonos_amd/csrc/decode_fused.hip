@@ -702,14 +702,14 @@ __device__ __forceinline__ void st_agent(uint64_t* p, uint64_t v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // The words other blocks poll: pk_word / pk_state / pk_val (handoff.h).
-// abort[0]: nonzero once any tile aborted (polled by waiting tiles); abort[r], r = 1..4:
-// ~(lowest tile that aborted for reason r), for diagnostics.
+// abort[kZAbortAny]: nonzero once any tile aborted (polled by waiting tiles); abort[r], r a
+// reason of ZAbort (kernels.h): ~(lowest tile that aborted for reason r), for diagnostics.
 // An invalid record at span offset so on a true chain of span `span` (the lowest one wins).
 __device__ __forceinline__ void note_error(const FusedCtl& ctl, uint32_t span, uint64_t so) {
   if (ctl.span_err && so != ~0ull) atomicMin(reinterpret_cast<unsigned long long*>(ctl.span_err + span), (unsigned long long)so);
 }
-__device__ __forceinline__ void raise_abort(const FusedCtl& c, uint32_t reason, uint32_t t) {
-  __hip_atomic_store(c.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+__device__ __forceinline__ void raise_abort(const FusedCtl& c, ZAbort reason, uint32_t t) {
+  __hip_atomic_store(c.abort + kZAbortAny, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_fetch_max(c.abort + reason, ~t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -1144,13 +1144,13 @@ __device__ __forceinline__ uint32_t warm_start(uint32_t rs, uint32_t lo, uint32_
 // Pass 1 for one tile, given its true entry e_true (aligned coordinate): spec walks,
 // true chain, exit checks, then the tile's record / wide-record counts and its
 // record-start bitmap (1 KiB) for the emit pass.  *x_true = the tile's exit.  must_exit:
-// the exit the successor already uses (kZCanon: none).  Returns 0, or the reason the chain
-// went wrong (the caller decides what it means): 1 an invalid record, 2 the last record
-// does not end at the span end, 5 a Serializable record without tables -- no counts
-// written -- or 3: the exit is not must_exit (counts written: the tile itself is right,
-// the successor entered at the wrong place).
+// the exit the successor already uses (kZCanon: none).  Returns kZAbortNone, or the reason the
+// chain went wrong (the caller decides what it means): kZAbortBad an invalid record, kZAbortEnd
+// the last record does not end at the span end, kZAbortSerializable a Serializable record
+// without tables -- no counts written -- or kZAbortExit: the exit is not must_exit (counts
+// written: the tile itself is right, the successor entered at the wrong place).
 template <bool J>
-__device__ __forceinline__ uint32_t count_tile(const uint32_t t, const ZTile& z, const uint32_t e_true,
+__device__ __forceinline__ ZAbort count_tile(const uint32_t t, const ZTile& z, const uint32_t e_true,
                                            const uint32_t must_exit, const FusedCtl& ctl, const uint32_t* s_img,
                                            const uint32_t lane, uint32_t* x_out, const JL& jl,
                                            const TileDesc* __restrict__ tiles = nullptr,
@@ -1219,24 +1219,25 @@ __device__ __forceinline__ uint32_t count_tile(const uint32_t t, const ZTile& z,
   }
   const uint32_t x_true = lane63(r.exit);
   *x_out = x_true;
-  // the true chain meets an invalid record (1) or a Serializable one without tables (5):
-  // the lowest such lane decides (lanes above it may have run from guessed entries)
+  // the true chain meets an invalid record (a walk's bad 1) or a Serializable one without
+  // tables (bad 2): the lowest such lane decides (lanes above it may have run from guessed entries)
   const uint64_t badm = __ballot(r.bad != 0u);
-  uint32_t reason = badm ? (__shfl(r.bad, (int)__builtin_ctzll(badm)) == 2u ? 5u : 1u) : 0u;
+  ZAbort reason = badm ? (__shfl(r.bad, (int)__builtin_ctzll(badm)) == 2u ? kZAbortSerializable : kZAbortBad) : kZAbortNone;
   if (z.last) {
-    if (x_true != end_a) reason = reason ? reason : 2u;  // the last record must end at the span end
+    if (x_true != end_a) reason = reason ? reason : kZAbortEnd;  // the last record must end at the span end
   } else if (must_exit != kZCanon && x_true != must_exit) {
-    reason = reason ? reason : 3u;  // the successor already entered at the published exit
+    reason = reason ? reason : kZAbortExit;  // the successor already entered at the published exit
   }
   if (reason && ctl.dbg) {  // developer diagnostics: the first aborting tile's lane state
     uint32_t claim = 0;
-    if (lane == 0) claim = atomicCAS(ctl.dbg, 0u, 1u) == 0u ? 1u : 0u;
+    if (lane == 0) claim = atomicCAS(ctl.dbg + kZDbgClaim, 0u, 1u) == 0u ? 1u : 0u;
     if (__shfl(claim, 0)) {
       if (lane == 0) {
-        ctl.dbg[1] = t; ctl.dbg[2] = reason; ctl.dbg[3] = must_exit; ctl.dbg[4] = x_true; ctl.dbg[5] = e_true;
-        ctl.dbg[6] = lo; ctl.dbg[7] = z.hi; ctl.dbg[8] = end_a;
+        ctl.dbg[kZDbgTile] = t; ctl.dbg[kZDbgReason] = reason; ctl.dbg[kZDbgMustExit] = must_exit;
+        ctl.dbg[kZDbgXTrue] = x_true; ctl.dbg[kZDbgETrue] = e_true;
+        ctl.dbg[kZDbgLo] = lo; ctl.dbg[kZDbgHi] = z.hi; ctl.dbg[kZDbgEndA] = end_a;
       }
-      uint32_t* d = ctl.dbg + 24 + 8 * lane;
+      uint32_t* d = ctl.dbg + kZDbgLanes + kZDbgLaneWords * lane;
       d[0] = rs; d[1] = re; d[2] = sp.exit; d[3] = sp.bad; d[4] = sp.first; d[5] = 0; d[6] = entry;
       d[7] = r.exit | r.bad << 31;
     }
@@ -1245,7 +1246,7 @@ __device__ __forceinline__ uint32_t count_tile(const uint32_t t, const ZTile& z,
   // bits cover the records before it -- the lanes below the failing one, and its starts before
   // the failing record -- so that a confirmed error costs its span no second decode
   uint32_t fail_a = 0xFFFFFFFFu;
-  if (reason == 1u && badm && ctl.span_err) {
+  if (reason == kZAbortBad && badm && ctl.span_err) {
     const uint32_t bl = (uint32_t)__builtin_ctzll(badm);
     fail_a = (uint32_t)__shfl((int)r.fail, (int)bl);
     if (lane > bl) {
@@ -1254,7 +1255,7 @@ __device__ __forceinline__ uint32_t count_tile(const uint32_t t, const ZTile& z,
     }
   }
   if (fail_out) *fail_out = fail_a;
-  if (reason && reason != 3u && fail_a == 0xFFFFFFFFu) return reason;
+  if (reason && reason != kZAbortExit && fail_a == 0xFFFFFFFFu) return reason;
 
   ZPHASE(3);
   // ---- counts and the record-start bitmap for the emit pass
@@ -1295,7 +1296,7 @@ __device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
 
 __global__ __launch_bounds__(256) void k_decode_scan1(FusedCtl ctl) {
   __shared__ uint64_t s_w[4];
-  if (ld_agent32(ctl.abort)) return;
+  if (ld_agent32(ctl.abort + kZAbortAny)) return;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
   const uint32_t nt = ctl.n_tiles, blk = blockIdx.x, i0 = blk * kZScanBlock + tid * 4u;
   uint64_t v[4], sum = 0;
@@ -1321,7 +1322,7 @@ __global__ __launch_bounds__(256) void k_decode_scan1(FusedCtl ctl) {
 // 16 free wave slots while the slice gather (beside the decode) held them.
 __global__ __launch_bounds__(256) void k_decode_scan2(FusedCtl ctl, uint32_t n_blocks) {
   __shared__ uint64_t s_w[4];
-  if (ld_agent32(ctl.abort)) return;
+  if (ld_agent32(ctl.abort + kZAbortAny)) return;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6, i0 = 4u * tid;
   uint64_t v[4], sum = 0;
 #pragma unroll
@@ -1346,7 +1347,7 @@ __global__ __launch_bounds__(256) void k_decode_scan2(FusedCtl ctl, uint32_t n_b
 __global__ __launch_bounds__(256) void k_decode_spans(const SpanDesc* __restrict__ spans, uint32_t n_spans,
                                                       FusedCtl ctl) {
   const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-  if (s >= n_spans || ld_agent32(ctl.abort)) return;
+  if (s >= n_spans || ld_agent32(ctl.abort + kZAbortAny)) return;
   const SpanDesc sd = spans[s];
   if (!sd.n_tiles) return;
   const uint32_t t0 = sd.first_tile, t1 = sd.first_tile + sd.n_tiles - 1;
@@ -1374,10 +1375,11 @@ __global__ __launch_bounds__(256) void k_decode_scan(const TileDesc* __restrict_
   if (tid == 0) s_blk = atomicAdd(reinterpret_cast<unsigned int*>(ctl.lb), 1u);
   __syncthreads();
   const uint32_t blk = s_blk;
-  volatile uint32_t* hab = ctl.h_res ? reinterpret_cast<volatile uint32_t*>(ctl.h_res + 2ull * n_spans) : nullptr;
+  const FusedReadback rb = fused_readback(n_spans);
+  volatile uint32_t* hab = ctl.h_res ? reinterpret_cast<volatile uint32_t*>(ctl.h_res + rb.abort) : nullptr;
   if (blk == 0 && hab && tid < kZAbortWords) hab[tid] = ld_agent32(ctl.abort + tid);  // final: count and repair ran
-  if (blk == 0 && hab && ctl.jwork && tid < 2u) hab[kZAbortWords + tid] = ld_agent32(ctl.jwork + tid);  // table work used
-  if (ld_agent32(ctl.abort)) return;  // (every block: nothing writes it during this kernel)
+  if (blk == 0 && hab && ctl.jwork && tid < kZJWorkHead) hab[kZHabJWork + tid] = ld_agent32(ctl.jwork + tid);  // table work used
+  if (ld_agent32(ctl.abort + kZAbortAny)) return;  // (every block: nothing writes it during this kernel)
   const uint32_t i0 = blk * kZScanBlock + tid * 4u;
   uint64_t v[4], sum = 0;
 #pragma unroll
@@ -1411,10 +1413,10 @@ __global__ __launch_bounds__(256) void k_decode_scan(const TileDesc* __restrict_
         const uint32_t st = pk_state(x);
         if (!st) {
           if (__builtin_amdgcn_s_memtime() - t0 > kZSpinLimit) {  // (cannot happen: earlier tickets run)
-            raise_abort(ctl, 4, 0u);  // a wait timed out: the batch goes robust
+            raise_abort(ctl, kZAbortTimeout, 0u);  // a wait timed out: the batch goes robust
             if (hab) {
-              hab[4] = ~0u;
-              hab[0] = 1u;
+              hab[kZAbortTimeout] = ~0u;
+              hab[kZAbortAny] = 1u;
             }
             break;
           }
@@ -1442,7 +1444,7 @@ __global__ __launch_bounds__(256) void k_decode_scan(const TileDesc* __restrict_
     if (t + 1 == sd.first_tile + sd.n_tiles) {  // the span's last tile
       const uint64_t hi = pre + lb_[j] + v[j];
       gp(ctl.span_hi)[sp] = hi;
-      if (ctl.h_res) reinterpret_cast<volatile uint64_t*>(ctl.h_res)[n_spans + sp] = hi;
+      if (ctl.h_res) reinterpret_cast<volatile uint64_t*>(ctl.h_res)[rb.span_hi + sp] = hi;
     }
   }
 }
@@ -1451,17 +1453,17 @@ __global__ __launch_bounds__(256) void k_decode_scan(const TileDesc* __restrict_
 // block k's offset must equal block k - 1's final inclusive prefix.  Block 0's offset is 0 and
 // each block's total is summed from the counts locally, so when every block k >= 1 passes,
 // by induction every offset is the sum of the totals before it -- whatever value a look-back
-// poll read.  A mismatch aborts the batch, which the host decodes again (rep[2] counts it;
+// poll read.  A mismatch aborts the batch, which the host decodes again (rep[kZRepLookback] counts it;
 // emit's stores so far are overwritten then).  One lane of emit's block for tile 1024 k.
 __device__ __forceinline__ void lookback_check(const FusedCtl& ctl, uint32_t k) {
   const uint64_t w = ld_agent(ctl.lb + k);  // W[k - 1] (W = lb + 1)
   if (pk_state(w) == kLbPre && pk_val(w) == ld_agent(&ctl.boff[k])) return;
-  atomicAdd(ctl.rep + 2, 1u);
-  __hip_atomic_store(ctl.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  atomicAdd(ctl.rep + kZRepLookback, 1u);
+  __hip_atomic_store(ctl.abort + kZAbortAny, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (ctl.h_res) {  // (the scan copied the abort words into the host's read-back already)
-    volatile uint32_t* hab = reinterpret_cast<volatile uint32_t*>(ctl.h_res + 2ull * ctl.n_spans);
-    hab[10] = 1u;
-    hab[0] = 1u;
+    volatile uint32_t* hab = reinterpret_cast<volatile uint32_t*>(ctl.h_res + fused_readback(ctl.n_spans).abort);
+    hab[zhab_rep(kZRepLookback)] = 1u;
+    hab[kZAbortAny] = 1u;
   }
 }
 
@@ -1506,7 +1508,7 @@ __device__ __forceinline__ void jl_overflow(const FusedCtl& ctl, uint32_t t, uin
 // (an invalid stream) or 0x80 (longer than kZLmMax): so the LDS list holds just the entries
 // longer than kZLmMax -- at most a tile / kZLmMax of them, whatever the tile's entry count --
 // in position order (a ballot per 64), and a position not in it reads as invalid.  More than
-// kZJCap such entries (overlapping false candidates): abort reason 6, the batch goes robust.
+// kZJCap such entries (overlapping false candidates): kZAbortOverflow, the batch goes robust.
 __device__ __forceinline__ JL load_jl_map(const FusedCtl& ctl, uint32_t t, uint32_t* s_j, uint32_t lane, uint32_t* lm,
                                          const JLPre& pre) {
   uint32_t* pos = s_j;
@@ -1532,7 +1534,7 @@ __device__ __forceinline__ JL load_jl_map(const FusedCtl& ctl, uint32_t t, uint3
     }
     kept += (uint32_t)__popcll(m);
   }
-  if (kept > kZJCap && lane == 0) raise_abort(ctl, 6, t);
+  if (kept > kZJCap && lane == 0) raise_abort(ctl, kZAbortOverflow, t);
   __syncthreads();  // the map's rows (written before the call) and the codes above
   JL j{nullptr, nullptr, len, lm};
   j.pos = pos;
@@ -1803,7 +1805,7 @@ __global__ __launch_bounds__(64) void k_decode_emit(const TileDesc* __restrict__
                                                     FusedCtl ctl, DecodeOut out) {
   __shared__ EmitLds<J> L;
   const uint32_t t = blockIdx.x, lane = threadIdx.x;
-  if (ld_agent32(ctl.abort)) return;  // (then the scan returned before its look-back too)
+  if (ld_agent32(ctl.abort + kZAbortAny)) return;  // (then the scan returned before its look-back too)
   if (ctl.lb_check && t && t % kZScanBlock == 0 && lane == 0) lookback_check(ctl, t / kZScanBlock);
   if (ctl.skip_bad && gp(ctl.span_bad)[tiles[t].span]) return;  // the robust output fills this span
   if (ctl.span_err && tiles[t].span_off > gp(ctl.span_err)[tiles[t].span]) return;  // past a kept error
@@ -1820,7 +1822,7 @@ __global__ __launch_bounds__(64) void k_decode_emit(const TileDesc* __restrict__
 // reaches) and marks the tile done in st_x (unused for a whole-span tile: no successor
 // enters at its exit), so the count pass skips it.  A TimerTrigger / SourceCheckpoint /
 // Serializable record leaves the tile to the count pass; an invalid record marks the span
-// bad (abort reason 1), as count_tile does.  A separate kernel: inside the count kernel the
+// bad (kZAbortBad), as count_tile does.  A separate kernel: inside the count kernel the
 // walk's registers cost the wave path 16 VGPRs and an occupancy step.
 constexpr uint64_t kZTinyDone = 1ull << 62;  // st_x word of a tile pass 0 counted
 __device__ __forceinline__ bool tiny_tile(const TileDesc& td, const SpanDesc& sd) {
@@ -1832,7 +1834,9 @@ __global__ __launch_bounds__(64) void k_decode_count_tiny(const TileDesc* __rest
   if (ti >= ctl.n_tiles) return;
   const TileDesc td = tiles[ti];
   if (!tiny_tile(td, spans[td.span]) || (ctl.skip_bad && gp(ctl.span_bad)[td.span])) return;
-  // 0 ok, 1 invalid record (a bad tag or a record past the span end), 3 a tag this path leaves
+  // 0 ok, kZAbortBad an invalid record (a bad tag or a record past the span end), kLeave a tag
+  // this path leaves to the count pass
+  constexpr uint32_t kLeave = 3u;
   uint32_t why = 0, rec = 0, wide = 0;
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
@@ -1853,11 +1857,11 @@ __global__ __launch_bounds__(64) void k_decode_count_tiny(const TileDesc* __rest
     const uint32_t tg = (dw >> (8u * (q & 3u))) & 0xFFu;
     const uint32_t L = tg < 8u ? (kLut >> (4u * tg)) & 0xFu : 0u;
     if (!L) {
-      why = (tg == CLG_TAG_SERIALIZABLE || tg == CLG_TAG_TIMER_TRIGGER || tg == CLG_TAG_SOURCE_CHECKPOINT) ? 3u : 1u;
+      why = (tg == CLG_TAG_SERIALIZABLE || tg == CLG_TAG_TIMER_TRIGGER || tg == CLG_TAG_SOURCE_CHECKPOINT) ? kLeave : kZAbortBad;
       break;
     }
-    if (a + L > end) {  // (the true chain's bound: an invalid record, count_tile's reason 1)
-      why = 1u;
+    if (a + L > end) {  // (the true chain's bound: an invalid record, count_tile's kZAbortBad)
+      why = kZAbortBad;
       break;
     }
     for (const uint32_t r = a >> 7; cur < r; ++cur) {  // the regions before this start are complete
@@ -1873,7 +1877,7 @@ __global__ __launch_bounds__(64) void k_decode_count_tiny(const TileDesc* __rest
     wide += tg == CLG_TAG_IGNORE_CHECKPOINT ? 1u : 0u;
     a += L;
   }
-  if (why == 3u) return;  // the count pass takes this tile (its words are rewritten there)
+  if (why == kLeave) return;  // the count pass takes this tile (its words are rewritten there)
   if (why == 0u || ctl.span_err) {  // (an invalid record with errors kept: the records before it)
     for (const uint32_t r = (end - 1) >> 7; cur <= r; ++cur) {
       u64x2 v;
@@ -1885,7 +1889,7 @@ __global__ __launch_bounds__(64) void k_decode_count_tiny(const TileDesc* __rest
     gp(ctl.cnt)[ti] = pack_cnt(rec, wide);
   }
   if (why) {
-    raise_abort(ctl, why, ti);
+    raise_abort(ctl, ZAbort(why), ti);
     if (ctl.span_bad) __hip_atomic_store(ctl.span_bad + td.span, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     note_error(ctl, td.span, (uint64_t)(a - td.delta));  // (a whole span: span offset = a - delta)
   }
@@ -1908,9 +1912,9 @@ constexpr uint64_t kZExFail = 1ull << 62;   // ex[t] (not valid): its chain met 
 // request count, which lets k_decode_repair return at once in the usual batch.
 __device__ __forceinline__ void push_repair(const FusedCtl& ctl, uint32_t c) {
   gp(ctl.rep_flag)[c] = 1u;
-  atomicAdd(ctl.rep + 1, 1u);
+  atomicAdd(ctl.rep + kZRepFiled, 1u);
 }
-__device__ __forceinline__ void mark_bad(const FusedCtl& ctl, uint32_t reason, uint32_t t, uint32_t span) {
+__device__ __forceinline__ void mark_bad(const FusedCtl& ctl, ZAbort reason, uint32_t t, uint32_t span) {
   raise_abort(ctl, reason, t);
   if (ctl.span_bad) __hip_atomic_store(ctl.span_bad + span, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1933,7 +1937,7 @@ __device__ __forceinline__ void check_chunk(const FusedCtl& ctl, const TileDesc*
   }
   const uint64_t m = __ballot(bad != 0xFFFFFFFFu);
   if (m && lane == (uint32_t)__builtin_ctzll(m)) {
-    mark_bad(ctl, 1, bad, span);
+    mark_bad(ctl, kZAbortBad, bad, span);
     // the chain that failed there is the true one (the repair walk met it before): its position
     const uint64_t e = ld_agent(&ctl.ex[bad]);
     if (e & kZExFail) note_error(ctl, span, e & ~kZExFail);
@@ -1943,7 +1947,7 @@ __device__ __forceinline__ void check_chunk(const FusedCtl& ctl, const TileDesc*
 // Tile t staged (image, and with tables the map and table) and counted from entry xs (span
 // offset); *x = its exit (span offset).  count_tile's reason.
 template <bool J>
-__device__ __forceinline__ uint32_t count_staged(const TileDesc* __restrict__ tiles, const SpanDesc* __restrict__ spans,
+__device__ __forceinline__ ZAbort count_staged(const TileDesc* __restrict__ tiles, const SpanDesc* __restrict__ spans,
                                                  const FusedCtl& ctl, uint32_t* s_img, uint32_t* s_j, uint32_t lane,
                                                  uint32_t t, const ZTile& z, uint64_t xs, uint32_t must_exit,
                                                  const SpecR* walked, uint64_t* x, uint64_t* cnt_out = nullptr,
@@ -1961,8 +1965,8 @@ __device__ __forceinline__ uint32_t count_staged(const TileDesc* __restrict__ ti
   if (J) build_lm(z, s_img, s_j, lane);  // the image becomes the step-code map
   if (J) jl = load_jl_map(ctl, t, s_j, lane, s_img, pre);
   uint32_t x_true, fa = 0xFFFFFFFFu;
-  const uint32_t why = count_tile<J>(t, z, e_true, must_exit, ctl, s_img, lane, &x_true, jl, tiles, walked, cnt_out,
-                                     bm_out, fail_so ? &fa : nullptr);
+  const ZAbort why = count_tile<J>(t, z, e_true, must_exit, ctl, s_img, lane, &x_true, jl, tiles, walked, cnt_out,
+                                   bm_out, fail_so ? &fa : nullptr);
   *x = z.td.span_off + (x_true - z.lo);
   if (fail_so) *fail_so = fa != 0xFFFFFFFFu ? z.td.span_off + (fa - z.lo) : ~0ull;
   return why;
@@ -2036,7 +2040,7 @@ __device__ __forceinline__ void serve_chunk(const TileDesc* __restrict__ tiles, 
   if (f >= *walk_end) {  // (else a walk has rewritten this chunk's entry already)
     const uint64_t xe = ld_agent(&ctl.ex[f - 1]);
     if (!(xe & kZExValid)) {  // the tile before failed: its span (this chunk's first) is bad
-      if (lane == 0) mark_bad(ctl, 1, f - 1, tiles[f].span);
+      if (lane == 0) mark_bad(ctl, kZAbortBad, f - 1, tiles[f].span);
       return;
     }
     uint64_t xs = xe & ~kZExValid;
@@ -2049,7 +2053,7 @@ __device__ __forceinline__ void serve_chunk(const TileDesc* __restrict__ tiles, 
         const ZTile z = ztile(tiles, spans, t, lane);
         *walk_end = t + 1;
         uint64_t x = xs, fso = ~0ull;
-        uint32_t why = 0;
+        ZAbort why = kZAbortNone;
         bool zero = false;
         if (!z.last && xs >= z.td.span_off + z.td.len) {  // wholly inside a record: no starts
           typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
@@ -2061,14 +2065,14 @@ __device__ __forceinline__ void serve_chunk(const TileDesc* __restrict__ tiles, 
           why = count_staged<J>(tiles, spans, ctl, s_img, s_j, lane, t, z, xs, kZCanon, nullptr, &x, nullptr, nullptr,
                                 &fso);
           __syncthreads();  // the image is reused
-          if (why == 1u && lane == 0) note_error(ctl, z.td.span, fso);  // (the walk's entry is the true one)
+          if (why == kZAbortBad && lane == 0) note_error(ctl, z.td.span, fso);  // (the walk's entry is the true one)
         }
         if (why) {
           if (lane == 0) {
             mark_bad(ctl, why, t, z.td.span);
             // the tile's word: this chain's failure, not the count pass's from another entry
             // (a later chunk check of this tile must not take that one for real)
-            st_agent(&ctl.ex[t], why == 1u && fso != ~0ull ? kZExFail | fso : 0ull);
+            st_agent(&ctl.ex[t], why == kZAbortBad && fso != ~0ull ? kZExFail | fso : 0ull);
           }
           break;
         }
@@ -2088,10 +2092,12 @@ __device__ __forceinline__ void serve_chunk(const TileDesc* __restrict__ tiles, 
         if (old == 1u || z.last) break;  // resynchronised, or the span ends
         if (old == 2u && !zero && ++disagree > kZWalkDisagree) {  // chains that do not meet: the span goes robust
           if (lane == 0) {
-            mark_bad(ctl, 3, t, z.td.span);
+            mark_bad(ctl, kZAbortExit, t, z.td.span);
             if (ctl.dbg) {  // developer diagnostics (CLONOS_FUSED_DEBUG): the walk that gave up
-              ctl.dbg[9] = 0xD15A; ctl.dbg[10] = f; ctl.dbg[11] = t; ctl.dbg[12] = (uint32_t)(xs - z.td.span_off);
-              ctl.dbg[13] = (uint32_t)(x - z.td.span_off); ctl.dbg[14] = z.td.span; ctl.dbg[15] = disagree;
+              ctl.dbg[kZDbgWalkMark] = kZDbgWalkGaveUp; ctl.dbg[kZDbgWalkFrom] = f; ctl.dbg[kZDbgWalkAt] = t;
+              ctl.dbg[kZDbgWalkEntry] = (uint32_t)(xs - z.td.span_off);
+              ctl.dbg[kZDbgWalkExit] = (uint32_t)(x - z.td.span_off); ctl.dbg[kZDbgWalkSpan] = z.td.span;
+              ctl.dbg[kZDbgWalkDisagree] = disagree;
             }
           }
           break;
@@ -2145,7 +2151,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kZCountWaves
       // of the canonical walk: publish the tile end instead (a guess; this chunk's last tile
       // checks it against its true exit and files a repair when they differ), and count it.
       if (x_pub < z.hi) {
-        if (lane == 0) atomicAdd(ctl.rep + 3, 1u);
+        if (lane == 0) atomicAdd(ctl.rep + kZRepCanonEarly, 1u);
         x_pub = z.hi;
       }
       // (64-bit: the exit's span offset, never wrapped)
@@ -2179,14 +2185,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kZCountWaves
         // not taken, the poll goes on
         if (pk_state(v) && pk_val(v) >= z.td.span_off) break;
         if (pk_state(v) && ctl.dbg && lane == 0) {  // developer diagnostics: the reads not taken
-          if (atomicAdd(ctl.dbg + 16, 1u) == 0u) {
-            ctl.dbg[17] = t; ctl.dbg[18] = (uint32_t)v; ctl.dbg[19] = (uint32_t)(v >> 32);
-            ctl.dbg[20] = (uint32_t)z.td.span_off; ctl.dbg[21] = nb;
+          if (atomicAdd(ctl.dbg + kZDbgSkipN, 1u) == 0u) {
+            ctl.dbg[kZDbgSkipTile] = t; ctl.dbg[kZDbgSkipWordLo] = (uint32_t)v; ctl.dbg[kZDbgSkipWordHi] = (uint32_t)(v >> 32);
+            ctl.dbg[kZDbgSkipOff] = (uint32_t)z.td.span_off; ctl.dbg[kZDbgSkipPolls] = nb;
           }
         }
-        if (ld_agent32(ctl.abort + 4)) return;  // another wait timed out: the batch goes robust
+        if (ld_agent32(ctl.abort + kZAbortTimeout)) return;  // another wait timed out: the batch goes robust
         if (!backoff(nb, w0)) {
-          if (lane == 0) raise_abort(ctl, 4, t);
+          if (lane == 0) raise_abort(ctl, kZAbortTimeout, t);
           return;
         }
       }
@@ -2198,9 +2204,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kZCountWaves
     const bool reuse = t + 1 == t1 && x_pub != kZCanon;
     uint64_t x;
     uint64_t fso = ~0ull;
-    const uint32_t why = count_staged<J>(tiles, spans, ctl, s_img, s_j, lane, t, z, xs, t + 1 == t1 ? x_pub : kZCanon,
-                                         reuse ? &sp_last : nullptr, &x, nullptr, nullptr, &fso);
-    if (why == 0u || why == 3u) {
+    const ZAbort why = count_staged<J>(tiles, spans, ctl, s_img, s_j, lane, t, z, xs, t + 1 == t1 ? x_pub : kZCanon,
+                                       reuse ? &sp_last : nullptr, &x, nullptr, nullptr, &fso);
+    if (why == kZAbortNone || why == kZAbortExit) {
       x_prev = x;
       if (lane == 0) {
         st_agent(&ctl.ex[t], kZExValid | x);
@@ -2209,21 +2215,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kZCountWaves
           w[0] = xs;
           w[1] = 1ull << 60 | (uint64_t)blockIdx.x << 32 | (uint64_t)(t0 & 0xFFFFFF) << 4 | why;
         }
-        if (why == 3u) {  // the chunk holding the next tile entered elsewhere (empty chunks skipped)
+        if (why == kZAbortExit) {  // the chunk holding the next tile entered elsewhere (empty chunks skipped)
           uint32_t c = blockIdx.x + 1;
           while (chunk_first(ctl, c + 1, K, gridDim.x) == t1) ++c;
           push_repair(ctl, c);
         }
       }
     } else {
-      const bool soft = why != 5u && z.td.span == sus_span;  // the published entry may be wrong
+      const bool soft = why != kZAbortSerializable && z.td.span == sus_span;  // the published entry may be wrong
       if (lane == 0) {
         if (soft) {
           push_repair(ctl, blockIdx.x);
-          if (why == 1u && fso != ~0ull) st_agent(&ctl.ex[t], kZExFail | fso);  // for check_chunk, if real
+          if (why == kZAbortBad && fso != ~0ull) st_agent(&ctl.ex[t], kZExFail | fso);  // for check_chunk, if real
         } else {
           mark_bad(ctl, why, t, z.td.span);
-          if (why == 1u) note_error(ctl, z.td.span, fso);  // the entry is the true chain's
+          if (why == kZAbortBad) note_error(ctl, z.td.span, fso);  // the entry is the true chain's
         }
       }
       if (!soft && !ctl.span_bad) return;
@@ -2247,9 +2253,11 @@ __global__ __launch_bounds__(64) void k_decode_repair(const TileDesc* __restrict
                                                       FusedCtl ctl) {
   __shared__ uint32_t s_img[kZImgDw];
   __shared__ uint32_t s_j[J ? 2 * kZJBitsDw + kZJCap : 1];
-  // the batch goes again anyway (4 a wait timed out, 5 Serializable records without tables:
-  // again with them, 6 a table overflowed)
-  if (ld_agent32(ctl.abort + 4) || ld_agent32(ctl.abort + 5) || ld_agent32(ctl.abort + 6)) return;
+  // the batch goes again anyway (a wait timed out; Serializable records without tables: again
+  // with them; a table overflowed)
+  if (ld_agent32(ctl.abort + kZAbortTimeout) || ld_agent32(ctl.abort + kZAbortSerializable) ||
+      ld_agent32(ctl.abort + kZAbortOverflow))
+    return;
   const uint32_t G = gridDim.x, b = blockIdx.x, lane = threadIdx.x, K = (ctl.n_tiles + G - 1) / G;
   const uint32_t fb = chunk_first(ctl, b, K, G);
   if (fb >= chunk_first(ctl, b + 1, K, G)) return;  // (an empty chunk is never asked for)
@@ -2280,7 +2288,7 @@ __global__ __launch_bounds__(64) void k_decode_repair(const TileDesc* __restrict
       if (!wrong_entry(ctl, c, f)) continue;
       // counted (the bench line and the tests read it) where the tile before has an exit: else
       // it failed, and its span is bad already
-      if (lane == 0 && (ld_agent(&ctl.ex[f - 1]) & kZExValid)) atomicAdd(ctl.rep, 1u);
+      if (lane == 0 && (ld_agent(&ctl.ex[f - 1]) & kZExValid)) atomicAdd(ctl.rep + kZRepServed, 1u);
     }
     serve_chunk<J>(tiles, spans, ctl, s_img, s_j, lane, c, f, ce, &walk_end);
   }
@@ -2297,8 +2305,8 @@ __global__ __launch_bounds__(64) void k_decode_repair(const TileDesc* __restrict
 // the image it holds.  A tile whose chain goes wrong -- an invalid record, a Serializable
 // record (no tables here) -- flags the batch and the host decodes it the usual way, which
 // classifies the error; a wait past kZSpinLimit flags it too.  agg: counts at [t], exits at
-// [nt + t]; res: see launch_decode_small (kernels.h), res[3 + s] for the spans with tiles (the
-// host fills the empty ones).
+// [nt + t]; res: the words of ZSmallRes (kernels.h), a span's first record for the spans with
+// tiles (the host fills the empty ones).
 // ---------------------------------------------------------------------------------
 constexpr uint32_t kZAggSet = 2u, kZAggBad = 3u;  // pk_word states: published, published and bad
 
@@ -2342,9 +2350,9 @@ __device__ __forceinline__ void decode_small_tiles(const TileDesc* __restrict__ 
     const uint64_t ee = xs - z.td.span_off + z.lo;
     const uint32_t e_true = ee > 0xFFFFFF00ull ? 0xFFFFFF00u : (uint32_t)ee;
     uint32_t x_true;
-    const uint32_t why = count_tile<false>(t, z, e_true, kZCanon, ctl, L.img, lane, &x_true, jl, tiles, &sp, &c, bm);
+    const ZAbort why = count_tile<false>(t, z, e_true, kZCanon, ctl, L.img, lane, &x_true, jl, tiles, &sp, &c, bm);
     x = z.td.span_off + (x_true - z.lo);
-    bad = why != 0u;
+    bad = why != kZAbortNone;
   }
   if (lane == 0) {
     st_agent(&agg[nt + t], pk_word(bad ? kZAggBad : kZAggSet, x));
@@ -2373,7 +2381,7 @@ __device__ __forceinline__ void decode_small_tiles(const TileDesc* __restrict__ 
     pre += cj;
   }
   if (any_bad) {
-    if (lane == 0) __hip_atomic_store(res + 2, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (lane == 0) __hip_atomic_store(res + kZSmallFailed, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     return;
   }
   emit_tile<false, true>(tiles, spans, ctl, out, t, lane, pre, L, bm);
@@ -2382,14 +2390,14 @@ __device__ __forceinline__ void decode_small_tiles(const TileDesc* __restrict__ 
     // but a span's first entered at the exit of the tile before; every base is the one before
     // it plus that tile's counts): entry | exit << 32 (span offsets, a small span < 4 GiB),
     // base, counts
-    uint64_t* ck = res + 3 + ctl.n_spans + 3ull * t;
-    ck[0] = (uint64_t)(uint32_t)xs | (uint64_t)(uint32_t)x << 32;
-    ck[1] = pre;
-    ck[2] = c;
-    if (z.first) res[3 + z.td.span] = pre;
+    uint64_t* ck = res + small_check_at(ctl.n_spans, t);
+    ck[kZCheckEntryExit] = (uint64_t)(uint32_t)xs | (uint64_t)(uint32_t)x << 32;
+    ck[kZCheckBase] = pre;
+    ck[kZCheckCount] = c;
+    if (z.first) res[kZSmallSpan0 + z.td.span] = pre;
     if (t + 1 == nt) {
-      res[0] = (pre + c) & ((1ull << 31) - 1);
-      res[1] = (pre + c) >> 31;
+      res[kZSmallRec] = (pre + c) & ((1ull << 31) - 1);
+      res[kZSmallWide] = (pre + c) >> 31;
     }
   }
 }
@@ -2557,15 +2565,15 @@ __device__ __forceinline__ void jser_tile(const TileDesc* __restrict__ tiles, co
   }
   const uint32_t total = __shfl(ex, 63);
   // past kZJCap candidates the rest go to the overflow arena (a tile of short Serializable
-  // strings holds up to ~300); arena exhausted: abort reason 6, the host grows it and retries
+  // strings holds up to ~300); arena exhausted: kZAbortOverflow, the host grows it and retries
   uint32_t ob = 0;
   if (lane == 0) {
     uint32_t n = total;
-    if (total && !*flagged) __hip_atomic_store(ctl.abort + 7, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (total && !*flagged) __hip_atomic_store(ctl.abort + kZAbortJserSeen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (total > kZJCap) {
-      ob = atomicAdd(ctl.jwork + 1, total - kZJCap);
+      ob = atomicAdd(ctl.jwork + kZJWorkOvf, total - kZJCap);
       if (ob + (total - kZJCap) > ctl.jovf_cap) {
-        raise_abort(ctl, 6, t);
+        raise_abort(ctl, kZAbortOverflow, t);
         n = kZJCap;  // (the batch runs again: no pass reads past the arena meanwhile)
       } else {
         gp(ctl.jbase)[t] = ob;
@@ -2586,12 +2594,12 @@ __device__ __forceinline__ void jser_tile(const TileDesc* __restrict__ tiles, co
     gp(ctl.jpos)[sl] = a;
     gp(ctl.jlen)[sl] = general ? kZJGeneral : (L <= 0x7FFFFFF0ull ? (uint32_t)L : 0u);
     if (general) {  // nested objects, arrays, ...: k_decode_jser_general walks the grammar
-      const uint32_t w = atomicAdd(ctl.jwork, 1u);
+      const uint32_t w = atomicAdd(ctl.jwork + kZJWorkItems, 1u);
       if (w < ctl.jwork_cap) {
-        ctl.jwork[2 + w] = (uint32_t)sl;
-        ctl.jwork[2 + ctl.jwork_cap + w] = t;
+        ctl.jwork[kZJWorkHead + w] = (uint32_t)sl;
+        ctl.jwork[kZJWorkHead + ctl.jwork_cap + w] = t;
       } else {
-        raise_abort(ctl, 6, t);
+        raise_abort(ctl, kZAbortOverflow, t);
       }
     }
   };
@@ -2691,9 +2699,9 @@ __device__ __forceinline__ bool side_tile(const TileDesc* __restrict__ tiles, co
   if (lane == 0) {  // as jser_tile: the batch flag, the overflow arena, the tile's count
     uint32_t nn = total;
     if (total > kZJCap) {  // (the batch flag: set once per block by the caller, k_decode_jser_side)
-      ob = atomicAdd(ctl.jwork + 1, total - kZJCap);
+      ob = atomicAdd(ctl.jwork + kZJWorkOvf, total - kZJCap);
       if (ob + (total - kZJCap) > ctl.jovf_cap) {
-        raise_abort(ctl, 6, t);
+        raise_abort(ctl, kZAbortOverflow, t);
         nn = kZJCap;
       } else {
         gp(ctl.jbase)[t] = ob;
@@ -2730,7 +2738,7 @@ __device__ __forceinline__ bool side_tile(const TileDesc* __restrict__ tiles, co
     const bool gen = sl != ~0ull && !known;  // the general walker measures it (jser_tile's measure)
     const uint64_t gm = __ballot(gen);
     uint32_t wb = 0;
-    if (gm && lane == 0) wb = atomicAdd(ctl.jwork, (uint32_t)__popcll(gm));
+    if (gm && lane == 0) wb = atomicAdd(ctl.jwork + kZJWorkItems, (uint32_t)__popcll(gm));
     wb = __shfl(wb, 0);
     ngen += (uint32_t)__popcll(gm);
     if (sl == ~0ull) continue;
@@ -2741,10 +2749,10 @@ __device__ __forceinline__ bool side_tile(const TileDesc* __restrict__ tiles, co
       gp(ctl.jlen)[sl] = kZJGeneral;
       const uint32_t w = wb + (uint32_t)__popcll(gm & ((1ull << lane) - 1ull));
       if (w < ctl.jwork_cap) {
-        ctl.jwork[2 + w] = (uint32_t)sl;
-        ctl.jwork[2 + ctl.jwork_cap + w] = t;
+        ctl.jwork[kZJWorkHead + w] = (uint32_t)sl;
+        ctl.jwork[kZJWorkHead + ctl.jwork_cap + w] = t;
       } else {
-        raise_abort(ctl, 6, t);
+        raise_abort(ctl, kZAbortOverflow, t);
       }
     }
   }
@@ -2758,7 +2766,7 @@ __device__ __forceinline__ bool side_tile(const TileDesc* __restrict__ tiles, co
 
 // The tiles the sidecar does not serve (side_tile false), for k_decode_jser: [0] their
 // count, then the tiles (after the general walker's work list; [0] zeroed per batch).
-__device__ __forceinline__ uint32_t* side_scan_list(const FusedCtl& ctl) { return ctl.jwork + 2 + 2 * ctl.jwork_cap; }
+__device__ __forceinline__ uint32_t* side_scan_list(const FusedCtl& ctl) { return ctl.jwork + kZJWorkHead + 2 * ctl.jwork_cap; }
 
 // Phase 3 from the sidecars: a wave per tile, four to a block, persistent over the tiles;
 // tiles it cannot serve are listed for the scan.  Per tile the work is a few dependent
@@ -2788,8 +2796,8 @@ __global__ __launch_bounds__(256) void k_decode_jser_side(const TileDesc* __rest
   // "the batch holds Serializable records" (the host's table hint): one store per block at most,
   // and none once another block's is visible -- a store per wave to this one word queued
   // behind each other and stalled the waves' next loads (the kernel 0.37 against 0.17 ms)
-  if (threadIdx.x == 0 && s_flag && !ld_agent32(ctl.abort + 7))
-    __hip_atomic_store(ctl.abort + 7, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0 && s_flag && !ld_agent32(ctl.abort + kZAbortJserSeen))
+    __hip_atomic_store(ctl.abort + kZAbortJserSeen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Persistent grid: block b takes tiles b, b + G, ... (with the sidecar: the listed tiles)
@@ -2811,9 +2819,9 @@ __global__ __launch_bounds__(64) void k_decode_jser(const TileDesc* __restrict__
 // walker (jser_device.h) reading the span from HBM.  Persistent grid over the work list.
 __global__ __launch_bounds__(64) void k_decode_jser_general(const TileDesc* __restrict__ tiles,
                                                             const SpanDesc* __restrict__ spans, FusedCtl ctl) {
-  const uint32_t n = min(ld_agent32(ctl.jwork), ctl.jwork_cap);
+  const uint32_t n = min(ld_agent32(ctl.jwork + kZJWorkItems), ctl.jwork_cap);
   for (uint32_t i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64) {
-    const uint32_t item = ctl.jwork[2 + i], t = ctl.jwork[2 + ctl.jwork_cap + i];
+    const uint32_t item = ctl.jwork[kZJWorkHead + i], t = ctl.jwork[kZJWorkHead + ctl.jwork_cap + i];
     const TileDesc td = tiles[t];
     const SpanDesc sd = spans[td.span];
     const uint32_t a = ctl.jpos[item];

@@ -521,8 +521,39 @@ namespace clg_internal {  // error text for the host-only translation units (res
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
 }  // namespace clg_internal
 
+// The CLONOS_* developer switches, read from the environment once per engine: a member of
+// clg_engine, filled when clg_engine_create constructs it.  No call reads the environment.
+static long long env_num(const char* name, long long dflt, int base = 10) {
+  const char* v = getenv(name);
+  return v ? strtoll(v, nullptr, base) : dflt;
+}
+static std::string env_str(const char* name) {
+  const char* v = getenv(name);
+  return v ? v : "";
+}
+struct DevSwitches {
+  bool robust_decode = env_str("CLONOS_DECODE") == "robust";  // the robust pipeline only
+  bool small_decode = env_num("CLONOS_SMALL", 1) != 0;        // 0: no single-launch small batches
+  bool sidecar = env_num("CLONOS_SIDECAR", 1) != 0;           // 0: no Serializable candidate lists (developer A/B)
+  bool keep_errors = env_num("CLONOS_KEEP_ERRORS", 1) != 0;   // 0: decode errors not kept on the fast path
+  uint32_t fused_perturb = uint32_t(env_num("CLONOS_FUSED_PERTURB", 0, 0));  // test switch (FusedCtl::perturb)
+  // initial spill arena bytes (tests: force its growth); 0: the default
+  size_t jser_arena = getenv("CLONOS_JSER_ARENA") ? std::max<size_t>(256, size_t(env_num("CLONOS_JSER_ARENA", 0, 0))) : 0;
+  int gather_prio = int(env_num("CLONOS_GATHER_PRIO", 1));     // the streams' priorities (clg_engine_create)
+  int host_threads = int(env_num("CLONOS_HOST_THREADS", 16));  // host threads for the per-log loops
+  int lean = int(env_num("CLONOS_LEAN", -1));  // 0/1: the count pass's lean walk forced off / on (-1: by the hint)
+  int warm = int(env_num("CLONOS_WARM", -1));  // speculative warm-up bytes (-1: the default, spec_warm)
+  bool host_prof = getenv("CLONOS_HOST_PROF") != nullptr;      // host-phase timing as "host_*" pseudo-stats
+  bool fused_debug = getenv("CLONOS_FUSED_DEBUG") != nullptr;  // the fused decode's diagnostics block (ZDbg), printed
+  bool small_prof = getenv("CLONOS_SMALL_PROF") != nullptr;    // the small path's phase stamps, printed
+  // files for per-tile phase stamps and the robust scan's state (empty: off)
+  std::string scan_phases = env_str("CLONOS_SCAN_PHASES"), robust_phases = env_str("CLONOS_ROBUST_PHASES"),
+              debug_dump = env_str("CLONOS_DEBUG_DUMP");
+};
+
 struct clg_engine {
   clg_config cfg{};
+  const DevSwitches sw;
   hipStream_t stream = nullptr;
   void* pool_alloc = nullptr;  // pool minus the guard bytes either side
   uint8_t* pool = nullptr;
@@ -575,10 +606,6 @@ struct clg_engine {
   // decode's records were almost all fixed-length (wide rows under 1/16): its result is the
   // same either way, its cost grows with wide records.  CLONOS_LEAN=0/1 forces it (developer).
   bool lean_hint = true;
-  static int lean_env() {
-    static const int v = getenv("CLONOS_LEAN") ? atoi(getenv("CLONOS_LEAN")) : -1;
-    return v;
-  }
   DevBuf d_rmeta, d_rsizes;          // replay-prep: subpartition span tables / BufferBuilt sizes
   DevBuf d_encin, d_encw, d_encout;  // encode: staged host input, block prefixes, host-output staging
   DevBuf d_hdr;                      // piggyback: delta headers staged for the gather
@@ -609,12 +636,11 @@ struct clg_engine {
   std::map<std::string, Stat> stats;
   // Developer host-phase timing (CLONOS_HOST_PROF set): the wall time of host-side work as
   // pseudo-stats "host_*" beside the kernels' (launches = calls, ms = host wall time).
-  const bool host_prof = getenv("CLONOS_HOST_PROF") != nullptr;
   struct HostTimer {
     clg_engine* e;
     const char* name;
     std::chrono::steady_clock::time_point t0;
-    HostTimer(clg_engine* en, const char* n) : e(en && en->host_prof ? en : nullptr), name(n) {
+    HostTimer(clg_engine* en, const char* n) : e(en && en->sw.host_prof ? en : nullptr), name(n) {
       if (e) t0 = std::chrono::steady_clock::now();
     }
     ~HostTimer() {
@@ -1446,8 +1472,7 @@ struct clg_engine {
   // median of four each: 2.09 / 2.20 / 2.40 ms with 16 / 14 / 12.
   WorkPool* workers() {
     if (!host_pool) {
-      const char* v = getenv("CLONOS_HOST_THREADS");
-      const int n = std::max(1, std::min(v ? atoi(v) : 16, usable_cpus()));
+      const int n = std::max(1, std::min(sw.host_threads, usable_cpus()));
       host_pool = std::make_unique<WorkPool>(unsigned(n));
     }
     return host_pool.get();
@@ -1875,13 +1900,7 @@ struct clg_engine {
   // and the staggered starts, 64-128 B within 2 %: pipeline 0.430-0.437 ms).  With Serializable
   // tables the count pass walks the step-code map, whose steps no longer diverge on wide
   // records, and 48-128 B are best too (config-3 subset: 0.43-0.44 ms, 0.451 at 16 B).
-  static uint32_t spec_warm(bool /*jser*/) {
-    static const int w = [] {
-      const char* v = getenv("CLONOS_WARM");
-      return v ? atoi(v) : -1;
-    }();
-    return w >= 0 ? uint32_t(w) : 96u;
-  }
+  uint32_t spec_warm() const { return sw.warm >= 0 ? uint32_t(sw.warm) : 96u; }
 
   // Fast three-pass decode (decode_fused.hip).  *aborted = true when the kernels met
   // anything outside its fast path; the caller then runs the robust pipeline.
@@ -1948,10 +1967,9 @@ struct clg_engine {
     r->log_bytes = log_bytes;
     r->jser = jser;
     // chunks of equal cost when blocks take several tiles of spans of different sizes
-    const bool zdbg = getenv("CLONOS_FUSED_DEBUG") != nullptr;
-    const char* prof_path = getenv("CLONOS_SCAN_PHASES");  // developer diagnostics: phase stamps
+    const bool zdbg = sw.fused_debug, zprof = !sw.scan_phases.empty();  // developer diagnostics
     // pass 0 (small whole spans, a lane each) for batches without Serializable tables
-    const bool tiny = p.n_tiny && !jser && !prof_path;
+    const bool tiny = p.n_tiny && !jser && !zprof;
     const uint32_t G = clg::decode_count_grid(jser, nt);
     const bool chunked = G && nt > G && ns > 1;
     std::optional<HostTimer> hsub(std::in_place, this, "host_launch_chunks");  // (CLONOS_HOST_PROF sub-stages)
@@ -1968,62 +1986,70 @@ struct clg_engine {
     clg::DecodeOut o{};
     CHK(prep_out(out, &o));
     hsub->lap("host_enq_out");
-    // words: st_x[nt] ex[nt] rep_flag[nt] (u8) cnt[nt] base[nt] boff[nb] | span_lo[ns] span_hi[ns] |
-    // abort[8] rep[4] (u32) | lb: ticket, look-back[nb] | ent[G]; bits apart.  st_x, ex,
-    // rep_flag, the abort and repair words, lb and ent are zeroed per batch.
-    const size_t nbk = (size_t(nt) + 1023) / 1024, fw = (size_t(nt) + 7) / 8;
-    const size_t o_cnt = 2 * size_t(nt) + fw, n_ab = clg::kZAbortWords / 2;
-    const size_t o_span = o_cnt + 2 * size_t(nt) + nbk, o_ab = o_span + 2 * size_t(ns), o_lb = o_ab + n_ab;
-    const size_t n_ent = std::max<size_t>(1, G);  // (ent: a word per chunk of the count pass)
-    const size_t o_ent = o_lb + 1 + nbk, words = o_ent + n_ent;
-    CHK(d_zctl.ensure(words * 8));
+    // the control words and their read-back: clg::fused_layout, clg::fused_readback (kernels.h)
+    const clg::FusedLayout Z = clg::fused_layout(nt, ns, G);
+    const clg::FusedReadback RB = clg::fused_readback(ns);
+    CHK(d_zctl.ensure(Z.words * 8));
     CHK(d_zbits.ensure(std::max<size_t>(1, nt) * 64 * 16));
     CHK(d_zbad.ensure(std::max<size_t>(1, ns) * 4));
     CHK(d_zerr.ensure(std::max<size_t>(1, ns) * 8));
     PinBuf& h_zres = h_zres_s[r->slot];
-    CHK(h_zres.ensure((2 * size_t(ns) + n_ab + 1) * 8));  // (+ the table work counters)
+    CHK(h_zres.ensure(RB.words * 8));
     hsub->lap("host_enq_bufs");
     uint64_t* w = d_zctl.as<uint64_t>();
-    uint32_t* ab = reinterpret_cast<uint32_t*>(w + o_ab);
     if (zdbg) CHK(d_dbg.ensure(clg::kZDbgTiles * 4 + size_t(nt) * 16));
-    if (prof_path) CHK(d_prof.ensure(size_t(nt) * 64));
+    if (zprof) CHK(d_prof.ensure(size_t(nt) * 64));
     const uint32_t jwork_cap = std::max<uint32_t>(uint32_t(nt) * 16 + 1024, zjwork_min);
     if (jser) {
       CHK(d_zjpos.ensure((size_t(nt) * clg::kZJCap + zjovf_cap) * 4));
       CHK(d_zjlen.ensure((size_t(nt) * clg::kZJCap + zjovf_cap) * 4));
       CHK(d_zjn.ensure(size_t(nt) * 8));  // jn, jbase
-      CHK(d_zjwork.ensure((2 * size_t(jwork_cap) + 3 + size_t(nt)) * 4));  // (+ the sidecar's scan list)
+      // (the header, the items' slots and tiles, the sidecar's scan list: its count and tiles)
+      CHK(d_zjwork.ensure((clg::kZJWorkHead + 2 * size_t(jwork_cap) + 1 + size_t(nt)) * 4));
     }
-    clg::FusedCtl ctl{w, w + o_cnt, w + o_cnt + nt, w + o_cnt + 2 * size_t(nt), d_zbits.as<uint64_t>(), w + o_span,
-                      w + o_span + ns, ab,
-                      zdbg ? d_dbg.as<uint32_t>() : nullptr, prof_path ? d_prof.as<uint64_t>() : nullptr, nt,
-                      jser ? d_zjpos.as<uint32_t>() : nullptr, jser ? d_zjlen.as<uint32_t>() : nullptr,
-                      jser ? d_zjn.as<uint32_t>() : nullptr, jser ? 1u : 0u, jwork_cap,
-                      jser ? d_zjwork.as<uint32_t>() : nullptr, spec_warm(jser), clg::JArena{}};
-    if (jser) CHK(jarena_reset(&ctl.jar));
-    ctl.jbase = jser ? d_zjn.as<uint32_t>() + nt : nullptr;
-    ctl.jovf_cap = zjovf_cap;
-    ctl.span_bad = d_zbad.as<uint32_t>();
-    ctl.skip_bad = 0;
-    ctl.span_err = keep_errors ? d_zerr.as<uint64_t>() : nullptr;
-    ctl.chunk = chunked ? reinterpret_cast<const uint32_t*>(d_plan.as<uint8_t>() + L.o_chunk) : nullptr;
-    ctl.tiny = tiny ? 1u : 0u;
-    ctl.ex = w + nt;
-    ctl.rep_flag = reinterpret_cast<uint8_t*>(w + 2 * size_t(nt));
-    ctl.rep = ab + 8;
-    ctl.ent = w + o_ent;
-    ctl.perturb = fused_perturb;
-    ctl.lb_check = 1;
-    ctl.n_spans = ns;
-    ctl.lb = w + o_lb;
-    ctl.lean = !jser && (lean_env() >= 0 ? lean_env() != 0 : lean_hint) ? 1u : 0u;
-    ctl.side = side;
     // the scan writes the result into the pinned read-back buffer itself (no copy queued after
     // emit) while the spans are few: each span_hi is its own write across the bus, and for
     // config 4's 66 k spans those took 2.5 ms -- there one copy after emit reads them back
     const bool host_res = ns <= kHostResSpans;
+    clg::FusedCtl ctl{};  // (every field, in the struct's order)
+    ctl.st_x = w;
+    ctl.cnt = w + Z.cnt;
+    ctl.base = w + Z.base;
+    ctl.boff = w + Z.boff;
+    ctl.bits = d_zbits.as<uint64_t>();
+    ctl.span_lo = w + Z.span_lo;
+    ctl.span_hi = w + Z.span_hi;
+    ctl.abort = reinterpret_cast<uint32_t*>(w + Z.abort);
+    ctl.dbg = zdbg ? d_dbg.as<uint32_t>() : nullptr;
+    ctl.prof = zprof ? d_prof.as<uint64_t>() : nullptr;
+    ctl.n_tiles = nt;
+    ctl.jpos = jser ? d_zjpos.as<uint32_t>() : nullptr;
+    ctl.jlen = jser ? d_zjlen.as<uint32_t>() : nullptr;
+    ctl.jn = jser ? d_zjn.as<uint32_t>() : nullptr;
+    ctl.jser = jser ? 1u : 0u;
+    ctl.jwork_cap = jwork_cap;
+    ctl.jwork = jser ? d_zjwork.as<uint32_t>() : nullptr;
+    ctl.warm = spec_warm();
+    if (jser) CHK(jarena_reset(&ctl.jar));
+    ctl.span_bad = d_zbad.as<uint32_t>();
+    ctl.skip_bad = 0;
+    ctl.chunk = chunked ? reinterpret_cast<const uint32_t*>(d_plan.as<uint8_t>() + L.o_chunk) : nullptr;
+    ctl.tiny = tiny ? 1u : 0u;
+    ctl.ex = w + Z.ex;
+    ctl.rep_flag = reinterpret_cast<uint8_t*>(w + Z.rep_flag);
+    ctl.rep = ctl.abort + clg::kZAbortFlagWords;
+    ctl.ent = w + Z.ent;
+    ctl.perturb = sw.fused_perturb;
+    ctl.lb_check = 1;
+    ctl.n_spans = ns;
+    ctl.span_err = sw.keep_errors ? d_zerr.as<uint64_t>() : nullptr;
+    ctl.jbase = jser ? d_zjn.as<uint32_t>() + nt : nullptr;
+    ctl.jovf_cap = zjovf_cap;
+    ctl.lb = w + Z.lb;
     ctl.h_res = host_res ? h_zres.as<uint64_t>() : nullptr;
-    memset(h_zres.p, 0, (2 * size_t(ns) + n_ab + 1) * 8);  // (a batch without tiles runs no scan)
+    ctl.lean = !jser && (sw.lean >= 0 ? sw.lean != 0 : lean_hint) ? 1u : 0u;
+    ctl.side = side;
+    memset(h_zres.p, 0, RB.words * 8);  // (a batch without tiles runs no scan)
     hsub->lap("host_enq_memset");
     r->ctl = ctl;
     r->o = o;
@@ -2055,19 +2081,20 @@ struct clg_engine {
         const size_t nsw = std::max<size_t>(1, ns);
         pa.r[0] = clg::PrepRange{d_spans.as<uint32_t>(), reinterpret_cast<const uint32_t*>(d_plan.as<uint8_t>() + L.o_spans),
                                  L.sb / 4, 0, 0};
-        pa.r[1] = clg::PrepRange{reinterpret_cast<uint32_t*>(w), nullptr, o_cnt * 2, 0, 0};
-        pa.r[2] = clg::PrepRange{ab, nullptr, clg::kZAbortWords + 2 * (1 + nbk + n_ent), 0, 0};  // abort words, repair counters, look-back, entries
+        // (st_x, ex, rep_flag; abort words, repair counters, look-back, entries: fused_layout's two zeroed runs)
+        pa.r[1] = clg::PrepRange{reinterpret_cast<uint32_t*>(w), nullptr, 2 * Z.cnt, 0, 0};
+        pa.r[2] = clg::PrepRange{ctl.abort, nullptr, 2 * (Z.words - Z.abort), 0, 0};
         pa.r[3] = clg::PrepRange{d_zbad.as<uint32_t>(), nullptr, nsw, 0, 0};
-        pa.r[4] = clg::PrepRange{d_zerr.as<uint32_t>(), nullptr, keep_errors ? nsw * 2 : 0, 0xFFFFFFFFu, 0};
-        pa.r[5] = clg::PrepRange{jser ? d_zjwork.as<uint32_t>() : nullptr, nullptr, jser ? 2u : 0u, 0, 0};
+        pa.r[4] = clg::PrepRange{d_zerr.as<uint32_t>(), nullptr, sw.keep_errors ? nsw * 2 : 0, 0xFFFFFFFFu, 0};
+        pa.r[5] = clg::PrepRange{ctl.jwork, nullptr, jser ? clg::kZJWorkHead : 0u, 0, 0};
         pa.r[6] = clg::PrepRange{d_ztiles.as<uint32_t>(), reinterpret_cast<const uint32_t*>(d_plan.p), runs ? 0 : L.tb / 4, 0, 0};
-        pa.r[7] = clg::PrepRange{jser ? d_zjwork.as<uint32_t>() + 2 + 2 * size_t(jwork_cap) : nullptr, nullptr,
+        pa.r[7] = clg::PrepRange{jser ? ctl.jwork + clg::kZJWorkHead + 2 * size_t(jwork_cap) : nullptr, nullptr,
                                  jser && side.hdr ? 1u : 0u, 0, 0};  // the sidecar's scan-list count
         CHK(clg::launch_decode_prep(pa, stream));
       }
       hsub->lap("host_enq_prep");
       if (zdbg) HIPCHK(hipMemsetAsync(d_dbg.p, 0, clg::kZDbgTiles * 4 + size_t(nt) * 16, stream));
-      if (prof_path) HIPCHK(hipMemsetAsync(d_prof.p, 0, size_t(nt) * 64, stream));
+      if (zprof) HIPCHK(hipMemsetAsync(d_prof.p, 0, size_t(nt) * 64, stream));
       if (evp) HIPCHK(hipEventRecord(evp[0], stream));
       if (tiny) CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, o, stream, clg::FusedPhase::CountTiny));
       // the passes in launch order, each bracketed by the event pair ev[2 * slot], ev[2 * slot + 1]
@@ -2087,11 +2114,12 @@ struct clg_engine {
       // the span ranges and abort words: in h_zres already (the scan wrote them) or read back
       // now (emit ran right behind the scan: it returns at once when the batch aborted, and its
       // stores are bounded by the output capacity)
-      if (!host_res) {  // span_hi and the abort words (adjacent; the host derives the ranges from span_hi)
-        HIPCHK(hipMemcpyAsync(h_zres.as<uint64_t>() + ns, ctl.span_hi, (size_t(ns) + n_ab) * 8, hipMemcpyDeviceToHost,
-                              stream));
+      if (!host_res) {  // span_hi, the abort words and counters (the host derives the ranges from span_hi)
+        HIPCHK(hipMemcpyAsync(h_zres.as<uint64_t>() + RB.span_hi, ctl.span_hi, (RB.jwork - RB.span_hi) * 8,
+                              hipMemcpyDeviceToHost, stream));
         if (jser)  // the table work counters beside them (the scan copies them when it writes h_res)
-          HIPCHK(hipMemcpyAsync(h_zres.as<uint64_t>() + 2 * size_t(ns) + n_ab, ctl.jwork, 8, hipMemcpyDeviceToHost, stream));
+          HIPCHK(hipMemcpyAsync(h_zres.as<uint64_t>() + RB.jwork, ctl.jwork, clg::kZJWorkHead * 4, hipMemcpyDeviceToHost,
+                                stream));
       }
       hsub->lap("host_enq_d2h");
       if (jser) CHK(jarena_note(r->note()));
@@ -2122,12 +2150,67 @@ struct clg_engine {
     }
     return CLG_OK;
   }
+  // Developer diagnostics: n bytes of device memory at `src`, as they are once the stream's
+  // queued work is done, into the file `path`.
+  void dump_device(const std::string& path, const void* src, size_t n) {
+    std::vector<uint8_t> h(n);
+    if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(h.data(), src, n, hipMemcpyDeviceToHost) != hipSuccess)
+      return;
+    if (FILE* fp = fopen(path.c_str(), "wb")) {
+      fwrite(h.data(), 1, n, fp);
+      fclose(fp);
+    }
+  }
+  // CLONOS_FUSED_DEBUG: the diagnostics block of a finished run (clg::ZDbg), printed.  Every
+  // run: the count pass's chunk-entry reads not taken.  An aborted one: the first tile per
+  // reason, the first aborting tile's state, a repair walk that gave up.
+  void print_fused_debug(const DecodePlan& p, const FusedRun& r, const uint32_t* hab, bool aborted) {
+    std::vector<uint32_t> hd(clg::kZDbgTiles);
+    hipMemcpy(hd.data(), d_dbg.p, hd.size() * 4, hipMemcpyDeviceToHost);
+    if (hd[clg::kZDbgSkipN])
+      fprintf(stderr, "[clonos] %u chunk-entry reads not taken; first: tile %u word %08x%08x tile span offset %u (poll %u)\n",
+              hd[clg::kZDbgSkipN], hd[clg::kZDbgSkipTile], hd[clg::kZDbgSkipWordHi], hd[clg::kZDbgSkipWordLo],
+              hd[clg::kZDbgSkipOff], hd[clg::kZDbgSkipPolls]);
+    if (!aborted) return;
+    fprintf(stderr, "[clonos] fused decode aborted (%u tiles, jser %d): first tile per reason bad=%d end=%d exit=%d "
+            "timeout=%d serializable=%d overflow=%d\n", p.n_tiles, int(r.jser), int(~hab[clg::kZAbortBad]),
+            int(~hab[clg::kZAbortEnd]), int(~hab[clg::kZAbortExit]), int(~hab[clg::kZAbortTimeout]),
+            int(~hab[clg::kZAbortSerializable]), int(~hab[clg::kZAbortOverflow]));
+    fprintf(stderr, "[clonos] tile %u reason %u x_pub %u x_true %u e_true %u lo %u hi %u end_a %u\n", hd[clg::kZDbgTile],
+            hd[clg::kZDbgReason], hd[clg::kZDbgMustExit], hd[clg::kZDbgXTrue], hd[clg::kZDbgETrue], hd[clg::kZDbgLo],
+            hd[clg::kZDbgHi], hd[clg::kZDbgEndA]);
+    if (hd[clg::kZDbgWalkMark] == clg::kZDbgWalkGaveUp) {
+      const uint32_t f = hd[clg::kZDbgWalkFrom], at = hd[clg::kZDbgWalkAt];
+      fprintf(stderr, "[clonos] repair walk from tile %u gave up at tile %u (entry %u exit %u, span %u, %u disagreements)\n",
+              f, at, hd[clg::kZDbgWalkEntry], hd[clg::kZDbgWalkExit], hd[clg::kZDbgWalkSpan], hd[clg::kZDbgWalkDisagree]);
+      // who wrote the exits before the walk (site 1 the count pass, 2 a repair walk)
+      std::vector<uint64_t> pp(size_t(p.n_tiles) * 2);
+      hipMemcpy(pp.data(), d_dbg.as<uint32_t>() + clg::kZDbgTiles, pp.size() * 8, hipMemcpyDeviceToHost);
+      for (uint32_t t = f >= 10 ? f - 10 : 0; t <= std::min(at + 1, p.n_tiles - 1); ++t) {
+        const uint64_t w = pp[size_t(t) * 2 + 1];
+        uint64_t exv = 0, stx = 0;
+        hipMemcpy(&exv, r.ctl.ex + t, 8, hipMemcpyDeviceToHost);
+        hipMemcpy(&stx, r.ctl.st_x + t, 8, hipMemcpyDeviceToHost);
+        fprintf(stderr, "[clonos]   tile %u: ex writer site %llu block %llu (chunk first / walk start %llu, why/old %llu) "
+                "entry %llu ex %llx st_x %llx\n",
+                t, (unsigned long long)(w >> 60), (unsigned long long)((w >> 32) & 0xFFFFFFF),
+                (unsigned long long)((w >> 4) & 0xFFFFFF), (unsigned long long)(w & 15),
+                (unsigned long long)pp[size_t(t) * 2], (unsigned long long)exv, (unsigned long long)stx);
+      }
+    }
+    for (int l = 0; l < 64; ++l) {
+      const uint32_t* d = &hd[clg::kZDbgLanes + clg::kZDbgLaneWords * l];
+      fprintf(stderr, "  lane %2d rs %5u re %5u spec_exit %5u spec_bad %5u canon_exit %5u canon_bad %u entry %5u exit %5u bad %u\n",
+              l, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7] & 0x7FFFFFFFu, d[7] >> 31);
+    }
+  }
+  // A queued run's result: wait, counters, grown tables, abort classification, totals.
   int finish_fused(const DecodePlan& p, FusedRun& r, clg_decoded* out, uint64_t* span_rec_base, bool* aborted,
                    bool* need_jser) {
     *aborted = false;
     *need_jser = false;
     const uint32_t nt = p.n_tiles, ns = uint32_t(p.spans.size());
-    const bool jser = r.jser, zdbg = getenv("CLONOS_FUSED_DEBUG") != nullptr;
+    const bool jser = r.jser;
     const uint64_t log_bytes = r.log_bytes;
     hipEvent_t ea = r.ea, eb = r.eb;
     uint64_t* hz = h_zres_s[r.slot].as<uint64_t>();
@@ -2137,40 +2220,31 @@ struct clg_engine {
       else HIPCHK(hipStreamSynchronize(stream));
     }
     HostTimer ht(this, "host_decode_finish");
-    if (const char* prof_path = getenv("CLONOS_SCAN_PHASES")) {
-      std::vector<uint64_t> hp(size_t(nt) * 8);
-      hipMemcpy(hp.data(), d_prof.p, hp.size() * 8, hipMemcpyDeviceToHost);
-      if (FILE* fp = fopen(prof_path, "wb")) {
-        fwrite(hp.data(), 8, hp.size(), fp);
-        fclose(fp);
-      }
-    }
-    const uint32_t* hab = reinterpret_cast<const uint32_t*>(hz + 2 * size_t(ns));
-    if (jser) jser_hint = hab[7] != 0;  // keep building tables while batches hold Serializable records
-    if (hab[9]) stats["decode_chunk_repair"].launches += hab[9];  // repair requests the count pass served
-    if (hab[8]) stats["decode_entry_repair"].launches += hab[8];  // chunks walked again for a wrong entry
-    if (hab[11]) stats["decode_canon_before_end"].launches += hab[11];  // canonical exits inside their tile
+    if (!sw.scan_phases.empty()) dump_device(sw.scan_phases, d_prof.p, size_t(nt) * 64);
+    const uint32_t* hab = reinterpret_cast<const uint32_t*>(hz + clg::fused_readback(ns).abort);
+    auto rep = [&](clg::ZRep k) { return hab[clg::zhab_rep(k)]; };
+    if (jser) jser_hint = hab[clg::kZAbortJserSeen] != 0;  // keep building tables while batches hold Serializable records
+    // repair requests the count pass served, chunks walked again for a wrong entry, canonical
+    // exits inside their tile
+    if (const uint32_t n = rep(clg::kZRepFiled)) stats["decode_chunk_repair"].launches += n;
+    if (const uint32_t n = rep(clg::kZRepServed)) stats["decode_entry_repair"].launches += n;
+    if (const uint32_t n = rep(clg::kZRepCanonEarly)) stats["decode_canon_before_end"].launches += n;
     const bool spilled = jser && jarena_spilled(r.note());  // a stream walk found the spill arena full
     if (spilled) CHK(jarena_grow());
-    // Serializable tables: the overflow arena or the walker's work list was full (reason 6)
+    // Serializable tables: the overflow arena or the walker's work list was full
     bool grown = false;
-    if (jser && hab[6]) {
+    if (jser && hab[clg::kZAbortOverflow]) {
       // the work list's and the overflow arena's use, from this run's own read-back (a later
       // decode queued behind it may have zeroed the device words already)
-      const uint32_t used[2] = {hab[clg::kZAbortWords], hab[clg::kZAbortWords + 1]};
-      if (used[0] > r.ctl.jwork_cap) zjwork_min = std::max(zjwork_min, 2 * used[0]);
-      if (used[1] > zjovf_cap) zjovf_cap = std::max<uint32_t>(2 * used[1], 2 * zjovf_cap);
-      grown = used[0] > r.ctl.jwork_cap || used[1] > r.ctl.jovf_cap;
+      const uint32_t items = hab[clg::kZHabJWork + clg::kZJWorkItems], ovf = hab[clg::kZHabJWork + clg::kZJWorkOvf];
+      if (items > r.ctl.jwork_cap) zjwork_min = std::max(zjwork_min, 2 * items);
+      if (ovf > zjovf_cap) zjovf_cap = std::max<uint32_t>(2 * ovf, 2 * zjovf_cap);
+      grown = items > r.ctl.jwork_cap || ovf > r.ctl.jovf_cap;
       stats["decode_jser_grow"].launches++;
     }
-    if (zdbg) {  // count-pass chunk entries read as published but before their tile (not taken)
-      uint32_t w8[8];
-      hipMemcpy(w8, d_dbg.as<uint32_t>() + 16, sizeof(w8), hipMemcpyDeviceToHost);
-      if (w8[0])
-        fprintf(stderr, "[clonos] %u chunk-entry reads not taken; first: tile %u word %08x%08x tile span offset %u (poll %u)\n",
-                w8[0], w8[1], w8[3], w8[2], w8[4], w8[5]);
-    }
-    if (hab[0] || spilled) {
+    const bool gave_up = hab[clg::kZAbortAny] || spilled;
+    if (sw.fused_debug) print_fused_debug(p, r, hab, gave_up);
+    if (gave_up) {
       if (ea) {
         ev_pool.push_back(ea);
         ev_pool.push_back(eb);
@@ -2180,53 +2254,17 @@ struct clg_engine {
         ev_pool.push_back(r.pb);
       }
       *aborted = true;
-      static const char* kWhy[7] = {nullptr, "decode_abort_bad", "decode_abort_end", "decode_abort_exit",
-                                    "decode_abort_timeout", "decode_abort_serializable", "decode_abort_overflow"};
-      for (int k = 1; k <= 6; ++k)  // (which reasons: the bench line lists them beside the kernels)
-        if (hab[k]) stats[kWhy[k]].launches++;
+      for (uint32_t k = 0; k < clg::kZAbortFlagWords; ++k)  // (which reasons: the bench line lists them beside the kernels)
+        if (clg::kZAbortStat[k] && hab[k]) stats[clg::kZAbortStat[k]].launches++;
       // Serializable records were met without tables: other aborts may be consequences
       // (entries guessed across them), so the tables decide; a second abort goes robust
       // (a table arena that was full, now grown: the same, once)
-      *need_jser = (!jser && hab[5] && !spilled) || (jser && (spilled || grown));
-      r.span_local = !*need_jser && !spilled && !hab[4] && !hab[6] && !hab[10];
-      r.lookback_bad = hab[10] != 0;
-      if (hab[10]) stats["decode_lookback_check"].launches++;  // a look-back read gave a wrong offset
+      *need_jser = (!jser && hab[clg::kZAbortSerializable] && !spilled) || (jser && (spilled || grown));
+      r.lookback_bad = rep(clg::kZRepLookback) != 0;  // a look-back read gave a wrong offset
+      r.span_local =
+          !*need_jser && !spilled && !hab[clg::kZAbortTimeout] && !hab[clg::kZAbortOverflow] && !r.lookback_bad;
+      if (r.lookback_bad) stats["decode_lookback_check"].launches++;
       zlast = r;
-      if (getenv("CLONOS_FUSED_DEBUG"))
-        fprintf(stderr, "[clonos] fused decode aborted (%u tiles, jser %d): first tile per reason bad=%d end=%d exit=%d "
-                "timeout=%d serializable=%d overflow=%d\n", nt, int(jser), int(~hab[1]), int(~hab[2]), int(~hab[3]),
-                int(~hab[4]), int(~hab[5]), int(~hab[6]));
-      if (zdbg) {
-        std::vector<uint32_t> hd(clg::kZDbgTiles);
-        hipMemcpy(hd.data(), d_dbg.p, hd.size() * 4, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[clonos] tile %u reason %u x_pub %u x_true %u e_true %u lo %u hi %u end_a %u\n", hd[1], hd[2],
-                hd[3], hd[4], hd[5], hd[6], hd[7], hd[8]);
-        if (hd[9] == 0xD15A) {
-          fprintf(stderr, "[clonos] repair walk from tile %u gave up at tile %u (entry %u exit %u, span %u, %u disagreements)\n",
-                  hd[10], hd[11], hd[12], hd[13], hd[14], hd[15]);
-          {  // who wrote the exits before the walk (site 1 the count pass, 2 a repair walk)
-            const uint32_t f = hd[10];
-            std::vector<uint64_t> pp(size_t(p.n_tiles) * 2);
-            hipMemcpy(pp.data(), d_dbg.as<uint8_t>() + clg::kZDbgTiles * 4, pp.size() * 8, hipMemcpyDeviceToHost);
-            for (uint32_t t = f >= 10 ? f - 10 : 0; t <= std::min(hd[11] + 1, p.n_tiles - 1); ++t) {
-              const uint64_t w = pp[size_t(t) * 2 + 1];
-              uint64_t exv = 0, stx = 0;
-              hipMemcpy(&exv, r.ctl.ex + t, 8, hipMemcpyDeviceToHost);
-              hipMemcpy(&stx, r.ctl.st_x + t, 8, hipMemcpyDeviceToHost);
-              fprintf(stderr, "[clonos]   tile %u: ex writer site %llu block %llu (chunk first / walk start %llu, why/old %llu) "
-                      "entry %llu ex %llx st_x %llx\n",
-                      t, (unsigned long long)(w >> 60), (unsigned long long)((w >> 32) & 0xFFFFFFF),
-                      (unsigned long long)((w >> 4) & 0xFFFFFF), (unsigned long long)(w & 15),
-                      (unsigned long long)pp[size_t(t) * 2], (unsigned long long)exv, (unsigned long long)stx);
-            }
-          }
-        }
-        for (int l = 0; l < 64; ++l) {
-          const uint32_t* d = &hd[24 + 8 * l];
-          fprintf(stderr, "  lane %2d rs %5u re %5u spec_exit %5u spec_bad %5u canon_exit %5u canon_bad %u entry %5u exit %5u bad %u\n",
-                  l, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7] & 0x7FFFFFFFu, d[7] >> 31);
-        }
-      }
       return CLG_OK;
     }
     uint64_t nrec = 0, nwide = 0;
@@ -2254,14 +2292,6 @@ struct clg_engine {
   // before it, and only spans whose chains went wrong otherwise go to the robust pipeline.
   // Test switch (CLONOS_FUSED_PERTURB, FusedCtl::perturb): wrong chunk entries and a wrong
   // look-back result, which the checks must catch (k_decode_repair, run_small, emit).
-  const uint32_t fused_perturb = [] {
-    const char* v = getenv("CLONOS_FUSED_PERTURB");
-    return v ? uint32_t(strtoul(v, nullptr, 0)) : 0u;
-  }();
-  const bool keep_errors = [] {
-    const char* v = getenv("CLONOS_KEEP_ERRORS");
-    return !(v && atoi(v) == 0);
-  }();
   DevBuf d_zerr, d_sf_cls;
   DevBuf d_small;
   clg::SmallPlanArg small_arg;
@@ -2315,11 +2345,13 @@ struct clg_engine {
   // A mismatch -- a poll that read a wrong word -- sends the batch the usual way.
   bool small_handoffs_ok(const DecodePlan& p, const uint64_t* res) {
     const uint32_t nt = p.n_tiles, ns = uint32_t(p.spans.size());
-    const uint64_t* ck = res + 3 + ns;
     for (uint32_t t = 0; t < nt; ++t) {
-      const uint64_t* k = ck + 3 * size_t(t);
+      const uint64_t* k = res + clg::small_check_at(ns, t);
+      const uint64_t* q = k - clg::kZSmallCheckWords;  // the tile before's (t > 0)
       const bool first = p.tiles[t].span_off == 0;
-      if ((t == 0 ? k[1] != 0 : k[1] != k[-2] + k[-1]) || (!first && uint32_t(k[0]) != uint32_t(k[-3] >> 32))) {
+      const uint64_t base = t == 0 ? 0 : q[clg::kZCheckBase] + q[clg::kZCheckCount];
+      if (k[clg::kZCheckBase] != base ||
+          (!first && uint32_t(k[clg::kZCheckEntryExit]) != uint32_t(q[clg::kZCheckEntryExit] >> 32))) {
         stats["decode_small_handoff"].launches++;
         return false;
       }
@@ -2368,9 +2400,9 @@ struct clg_engine {
     }
     // scratch: per-tile counts and record-start bitmaps, per-span look-back words
     CHK(d_zbits.ensure(std::max<size_t>(1, nt) * 64 * 16));
-    CHK(h_small_res.ensure((3 + size_t(ns) + 3 * size_t(nt)) * 8));  // (+ the per-tile hand-off words)
+    CHK(h_small_res.ensure(clg::small_res_words(ns, nt) * 8));
     uint64_t* res = h_small_res.as<uint64_t>();
-    res[0] = res[1] = res[2] = 0;
+    res[clg::kZSmallRec] = res[clg::kZSmallWide] = res[clg::kZSmallFailed] = 0;
     // look-back words: two buffers of kZSmallAggWords, zeroed once; each call zeroes the other;
     // then the per-tile counts
     constexpr size_t kAgg = clg::kZSmallAggWords;
@@ -2387,12 +2419,12 @@ struct clg_engine {
     ctl.bits = d_zbits.as<uint64_t>();
     ctl.n_tiles = nt;
     ctl.n_spans = ns;
-    ctl.perturb = fused_perturb;
+    ctl.perturb = sw.fused_perturb;
     // warm-up 32 B, not staggered: a lone wave per span waits on every step, and shorter
     // warm-ups cost fewer merges than they save (config 1: the kernel 65 -> 62 us at 32 or 16 B,
     // 63 at 48)
     ctl.warm = 32u | (1u << 31);
-    const bool sprof = getenv("CLONOS_SMALL_PROF") != nullptr;  // developer diagnostics: phase stamps
+    const bool sprof = sw.small_prof;  // developer diagnostics: phase stamps
     if (sprof) {
       CHK(d_prof.ensure(size_t(nt) * 64));
       HIPCHK(hipMemsetAsync(d_prof.p, 0, size_t(nt) * 64, stream));
@@ -2425,15 +2457,15 @@ struct clg_engine {
                 (unsigned long long)(q[5] >> 40));
       }
     }
-    if (res[2] || !small_handoffs_ok(p, res)) {
+    if (res[clg::kZSmallFailed] || !small_handoffs_ok(p, res)) {
       if (timing) timings.push_back(PendingTiming{"decode_small", ea, eb, 0});
       *aborted = true;
       return CLG_OK;
     }
     constexpr uint64_t kRecMask = (1ull << 31) - 1;
-    const uint64_t nrec = res[0], nwide = res[1];
+    const uint64_t nrec = res[clg::kZSmallRec], nwide = res[clg::kZSmallWide];
     if (span_rec_base) {
-      for (uint32_t s = 0; s < ns; ++s) span_rec_base[s] = res[3 + s] & kRecMask;
+      for (uint32_t s = 0; s < ns; ++s) span_rec_base[s] = res[clg::kZSmallSpan0 + s] & kRecMask;
       span_rec_base[ns] = nrec;
       for (uint32_t s = ns; s-- > 0;)  // (the kernel writes the spans with tiles: an empty one starts where the next does)
         if (!p.spans[s].n_tiles) span_rec_base[s] = span_rec_base[s + 1];
@@ -2641,18 +2673,19 @@ struct clg_engine {
     auto* zs = d_spans.as<clg::SpanDesc>();
     CHK(clg::launch_decode_inject(zs, reinterpret_cast<const uint32_t*>(d_sf_meta.as<uint8_t>() + size_t(nb) * 8),
                                   d_sf_meta.as<uint64_t>(), nb, ctl, stream));
-    HIPCHK(hipMemsetAsync(ctl.abort, 0, 32, stream));
+    HIPCHK(hipMemsetAsync(ctl.abort, 0, clg::kZAbortFlagWords * 4, stream));
     CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, zlast.o, stream, clg::FusedPhase::Scan3));
     CHK(clg::launch_decode_fused(zt, nt, zs, ns, ctl, zlast.o, stream, clg::FusedPhase::Emit));
     // the robust records into place, at the bases the scan gave the bad spans (one launch)
     const clg::DecodeOut sc{s_off, s_tag, s_v0, s_widx, s_wrc, s_wv1, s_wvo, s_wvl, s_wsub, RC, WC};
     CHK(clg::launch_sf_place(reinterpret_cast<const clg::SfPlace*>(d_sf_meta.as<uint8_t>() + o_place), nb, sc, zlast.o,
                              ctl, stream));
-    CHK(h_zres_s[0].ensure((2 * size_t(ns) + clg::kZAbortWords / 2) * 8));
+    const clg::FusedReadback RB = clg::fused_readback(ns);
+    CHK(h_zres_s[0].ensure(RB.words * 8));
     uint64_t* hz = h_zres_s[0].as<uint64_t>();
-    HIPCHK(hipMemcpyAsync(hz, ctl.span_lo, (2 * size_t(ns) + 4) * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(hz, ctl.span_lo, RB.abort_only * 8, hipMemcpyDeviceToHost, stream));  // ranges, abort flag words
     HIPCHK(hipStreamSynchronize(stream));
-    if (reinterpret_cast<const uint32_t*>(hz + 2 * size_t(ns))[0]) return CLG_OK;  // (cannot happen) whole batch
+    if (reinterpret_cast<const uint32_t*>(hz + RB.abort)[clg::kZAbortAny]) return CLG_OK;  // (cannot happen) whole batch
     uint64_t tr = 0, tw = 0;
     span_totals(pf, hz, span_rec_base, &tr, &tw);
     *done = true;
@@ -2922,17 +2955,16 @@ struct clg_engine {
     CHK(jarena_reset(&jar));
     clg::JserTabs J{d_jpos.as<uint32_t>(), d_jlen.as<uint32_t>(), d_jn.as<uint32_t>(), d_defer.as<uint32_t>(), jar};
     J.side = side;  // (k_jser_fill takes a tile's table from the sidecar where it can)
-    const char* rprof_path = getenv("CLONOS_ROBUST_PHASES");  // developer diagnostics (stamps per tile)
-    if (rprof_path && d_rprof.ensure(std::max<size_t>(1, nt) * 16 * 8) == CLG_OK) {
+    const std::string& rprof_path = sw.robust_phases;  // developer diagnostics (stamps per tile)
+    if (!rprof_path.empty() && d_rprof.ensure(std::max<size_t>(1, nt) * 16 * 8) == CLG_OK) {
       J.prof = d_rprof.as<uint64_t>();
       hipMemsetAsync(J.prof, 0, size_t(nt) * 128, stream);
     }
     uint32_t* dbg = nullptr;
-    if (getenv("CLONOS_DEBUG_DUMP") && d_dbg.ensure(std::max<size_t>(1, nt) * clg::kFPoints * 4) == CLG_OK)
+    if (!sw.debug_dump.empty() && d_dbg.ensure(std::max<size_t>(1, nt) * clg::kFPoints * 4) == CLG_OK)
       dbg = d_dbg.as<uint32_t>();
     uint64_t* prof = nullptr;  // developer diagnostics: per-phase s_memtime stamps of the scan
-    const char* prof_path = getenv("CLONOS_SCAN_PHASES");
-    if (prof_path && d_prof.ensure(std::max<size_t>(1, nt) * 8 * 8) == CLG_OK) {
+    if (!sw.scan_phases.empty() && d_prof.ensure(std::max<size_t>(1, nt) * 8 * 8) == CLG_OK) {
       prof = d_prof.as<uint64_t>();
       hipMemsetAsync(prof, 0, size_t(nt) * 64, stream);
     }
@@ -2940,15 +2972,7 @@ struct clg_engine {
       return clg::launch_fast_scan(dt, nt, ds, d_fconv.as<uint32_t>(), J, 0, d_lanes.as<clg::LaneSeg>(),
                                    d_sums.as<clg::TileSum>(), dbg, prof, stream);
     }));
-    if (prof) {
-      std::vector<uint64_t> hp(size_t(nt) * 8);
-      hipMemcpyAsync(hp.data(), prof, hp.size() * 8, hipMemcpyDeviceToHost, stream);
-      hipStreamSynchronize(stream);
-      if (FILE* fp = fopen(prof_path, "wb")) {
-        fwrite(hp.data(), 8, hp.size(), fp);
-        fclose(fp);
-      }
-    }
+    if (prof) dump_device(sw.scan_phases, prof, size_t(nt) * 64);
     CHK(timed("robust_jser", 0, [&] { return clg::launch_jser_fill(dt, nt, ds, J, stream); }));
     uint64_t* prof2 = nullptr;  // developer diagnostics: the deferred scan's phase stamps (CLONOS_ROBUST_PHASES)
     if (J.prof && d_prof2.ensure(std::max<size_t>(1, nt) * 64) == CLG_OK) {
@@ -2959,15 +2983,7 @@ struct clg_engine {
       return clg::launch_fast_scan(dt, nt, ds, d_fconv.as<uint32_t>(), J, 1, d_lanes.as<clg::LaneSeg>(),
                                    d_sums.as<clg::TileSum>(), dbg, prof2, stream);
     }));
-    if (prof2) {
-      std::vector<uint64_t> hp(size_t(nt) * 8);
-      hipMemcpyAsync(hp.data(), prof2, hp.size() * 8, hipMemcpyDeviceToHost, stream);
-      hipStreamSynchronize(stream);
-      if (FILE* fp = fopen((std::string(rprof_path) + ".scan").c_str(), "wb")) {
-        fwrite(hp.data(), 8, hp.size(), fp);
-        fclose(fp);
-      }
-    }
+    if (prof2) dump_device(rprof_path + ".scan", prof2, size_t(nt) * 64);
     CHK(timed("robust_resolve", uint64_t(nt) * 32, [&] {
       return clg::launch_fast_resolve(dt, ds, ns, d_fconv.as<uint32_t>(), d_lanes.as<clg::LaneSeg>(),
                                       d_sums.as<clg::TileSum>(), J, d_fres.as<clg::FastRes>(),
@@ -3011,37 +3027,24 @@ struct clg_engine {
       return clg::launch_decode_emit(dt, nt, ds, d_conv.as<clg::TileConv>(), d_tres.as<clg::TileRes>(),
                                      d_sres.as<clg::SpanRes>(), flags, o, jar, stream);
     }));
-    if (J.prof) {
-      std::vector<uint64_t> hp(size_t(nt) * 16);
-      hipMemcpyAsync(hp.data(), J.prof, hp.size() * 8, hipMemcpyDeviceToHost, stream);
+    if (J.prof) dump_device(rprof_path, J.prof, size_t(nt) * 128);
+    if (!sw.debug_dump.empty()) {  // developer diagnostics only: the robust scan's state in one file
       hipStreamSynchronize(stream);
-      if (FILE* fp = fopen(rprof_path, "wb")) {
-        fwrite(hp.data(), 8, hp.size(), fp);
-        fclose(fp);
-      }
-    }
-    if (const char* dump = getenv("CLONOS_DEBUG_DUMP")) {  // developer diagnostics only
-      std::vector<uint32_t> hc(size_t(nt) * clg::kFPoints), hf(ns);
-      std::vector<clg::TileSum> hs(nt);
-      hipMemcpyAsync(hc.data(), d_fconv.p, hc.size() * 4, hipMemcpyDeviceToHost, stream);
-      hipMemcpyAsync(hs.data(), d_sums.p, hs.size() * sizeof(clg::TileSum), hipMemcpyDeviceToHost, stream);
-      hipMemcpyAsync(hf.data(), d_flags.p, hf.size() * 4, hipMemcpyDeviceToHost, stream);
-      hipStreamSynchronize(stream);
-      if (FILE* fp = fopen(dump, "wb")) {
+      if (FILE* fp = fopen(sw.debug_dump.c_str(), "wb")) {
+        std::vector<uint8_t> h;
+        auto put = [&](const void* dev, size_t n) {  // n bytes of device memory
+          h.resize(n);
+          hipMemcpy(h.data(), dev, n, hipMemcpyDeviceToHost);
+          fwrite(h.data(), 1, n, fp);
+        };
         fwrite(&nt, 4, 1, fp);
         fwrite(&ns, 4, 1, fp);
-        fwrite(hc.data(), 4, hc.size(), fp);
-        fwrite(hs.data(), sizeof(clg::TileSum), hs.size(), fp);
-        fwrite(hf.data(), 4, hf.size(), fp);
-        std::vector<clg::TileDesc> ht(nt);
-        hipMemcpy(ht.data(), d_tiles.p, nt * sizeof(clg::TileDesc), hipMemcpyDeviceToHost);
-        fwrite(ht.data(), sizeof(clg::TileDesc), nt, fp);
-        std::vector<uint32_t> hd(size_t(nt) * clg::kFPoints);
-        hipMemcpy(hd.data(), d_dbg.p, hd.size() * 4, hipMemcpyDeviceToHost);
-        fwrite(hd.data(), 4, hd.size(), fp);
-        std::vector<clg::LaneSeg> hl(size_t(nt) * clg::kFPoints);
-        hipMemcpy(hl.data(), d_lanes.p, hl.size() * sizeof(clg::LaneSeg), hipMemcpyDeviceToHost);
-        fwrite(hl.data(), sizeof(clg::LaneSeg), hl.size(), fp);
+        put(d_fconv.p, size_t(nt) * clg::kFPoints * 4);
+        put(d_sums.p, size_t(nt) * sizeof(clg::TileSum));
+        put(d_flags.p, size_t(ns) * 4);
+        put(d_tiles.p, size_t(nt) * sizeof(clg::TileDesc));
+        put(d_dbg.p, size_t(nt) * clg::kFPoints * 4);
+        put(d_lanes.p, size_t(nt) * clg::kFPoints * sizeof(clg::LaneSeg));
         fclose(fp);
       }
     }
@@ -3156,11 +3159,9 @@ int clg_engine_create(const clg_config* cfg, clg_engine** out) {
   if (cfg->device < 0 || cfg->device >= ndev) return fail(CLG_E_INVALID_ARG, "device %d out of range", cfg->device);
   std::unique_ptr<clg_engine> e(new clg_engine());
   e->cfg = *cfg;
-  const char* dm = getenv("CLONOS_DECODE");
-  e->fused_decode = !(cfg->flags & CLG_F_ROBUST_DECODE) && !(dm && !strcmp(dm, "robust"));
-  e->small_decode = !(cfg->flags & CLG_F_NO_SMALL_DECODE) && !(getenv("CLONOS_SMALL") && atoi(getenv("CLONOS_SMALL")) == 0);
-  if (const char* ja = getenv("CLONOS_JSER_ARENA"))  // initial spill arena bytes (tests: force its growth)
-    e->jarena_bytes = std::max<size_t>(256, size_t(strtoull(ja, nullptr, 0)));
+  e->fused_decode = !(cfg->flags & CLG_F_ROBUST_DECODE) && !e->sw.robust_decode;
+  e->small_decode = !(cfg->flags & CLG_F_NO_SMALL_DECODE) && e->sw.small_decode;
+  if (e->sw.jser_arena) e->jarena_bytes = e->sw.jser_arena;
   HIPCHK(hipSetDevice(cfg->device));
   {
     // The device-output slice gather (HBM-bound) runs beside the next decode (VALU-bound):
@@ -3168,8 +3169,7 @@ int clg_engine_create(const clg_config* cfg, clg_engine** out) {
     // (CLONOS_GATHER_PRIO=0: same priority as the decode stream; 2: the decode stream's
     // queue higher instead, so the decode's short set-up, scan and read-back launches do not
     // wait behind the gather's workgroups).
-    const char* gp = getenv("CLONOS_GATHER_PRIO");
-    const int mode = gp ? atoi(gp) : 1;
+    const int mode = e->sw.gather_prio;
     int lo = 0, hi = 0;
     const bool prio = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo;
     if (prio && mode == 2) HIPCHK(hipStreamCreateWithPriority(&e->stream, hipStreamNonBlocking, hi));
@@ -3188,8 +3188,7 @@ int clg_engine_create(const clg_config* cfg, clg_engine** out) {
   e->seg_life.assign(cfg->pool_segments, 0u);
   // the sidecar: C / 64 entries per segment (256 for 16 KiB: config 3 averages ~100), its
   // positions 16 bits (segments up to 64 KiB); CLONOS_SIDECAR=0 turns it off (developer A/B)
-  const char* sc = getenv("CLONOS_SIDECAR");
-  if (cfg->segment_bytes <= 65536u && cfg->pool_segments && !(sc && atoi(sc) == 0)) {
+  if (cfg->segment_bytes <= 65536u && cfg->pool_segments && e->sw.sidecar) {
     const uint32_t cap = std::min<uint32_t>(clg::kSideCapMax, std::max<uint32_t>(8u, cfg->segment_bytes / 64u));
     const size_t hb = size_t(cfg->pool_segments) * 8, eb = size_t(cfg->pool_segments) * cap * 4;
     // (no room beside a pool sized to the HBM: the engine runs without it, the decode scans)

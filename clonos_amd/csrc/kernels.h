@@ -207,9 +207,90 @@ int launch_fast_emit(const TileDesc* d_tiles, uint32_t n_tiles, const SpanDesc* 
 // (record / wide bases per tile and per span), emit (SoA).  Any anomaly raises *abort and
 // the host re-decodes the batch with the robust pipeline above.
 constexpr uint32_t kZRegion = 128;
-constexpr uint32_t kZDbgTiles = 24 + 64 * 8;  // FusedCtl.dbg: the per-tile words' start (u32 index)
 constexpr uint32_t kZTile = 64 * kZRegion;  // 8192
 constexpr uint32_t kZHalo = 64;             // bytes of the span's next tile staged after a tile
+
+// ---- the words the fused decode's kernels and the host exchange ----------------------
+// FusedCtl::abort[k].  kZAbortAny is a flag, nonzero once any tile aborted (polled by waiting
+// tiles); each reason's word holds ~(the lowest tile that aborted for it), 0 while none did;
+// kZAbortJserSeen is a flag again.  As a value (count_tile's result) kZAbortNone: no abort.
+enum ZAbort : uint32_t {
+  kZAbortNone = 0,
+  kZAbortAny = 0,
+  kZAbortBad = 1,           // an invalid record on the true chain
+  kZAbortEnd = 2,           // a span's last record does not end at the span end
+  kZAbortExit = 3,          // a tile's exit is not the entry its successor took
+  kZAbortTimeout = 4,       // a wait timed out
+  kZAbortSerializable = 5,  // a Serializable record met without tables (the host runs again with them)
+  kZAbortOverflow = 6,      // a Serializable table arena or work list full (the host grows it and runs again)
+  kZAbortJserSeen = 7,      // phase 3 found Serializable candidates (any tile): the host keeps building tables
+};
+constexpr uint32_t kZAbortFlagWords = 8;
+// The host's stat per reason (a count of aborted runs that met it).
+constexpr const char* kZAbortStat[kZAbortFlagWords] = {
+    nullptr,                 // kZAbortAny
+    "decode_abort_bad",      // kZAbortBad
+    "decode_abort_end",      // kZAbortEnd
+    "decode_abort_exit",     // kZAbortExit
+    "decode_abort_timeout",  // kZAbortTimeout
+    "decode_abort_serializable",  // kZAbortSerializable
+    "decode_abort_overflow",      // kZAbortOverflow
+    nullptr,                 // kZAbortJserSeen
+};
+// FusedCtl::rep[k], the repair and check counters (zeroed per batch with the abort words).
+enum ZRep : uint32_t {
+  kZRepServed = 0,      // chunks walked again for a wrong entry (k_decode_repair)
+  kZRepFiled = 1,       // repair requests the count pass filed
+  kZRepLookback = 2,    // look-back checks failed (k_decode_emit; the batch is decoded again)
+  kZRepCanonEarly = 3,  // canonical exits found before their tile's end (published as the tile end)
+};
+constexpr uint32_t kZRepWords = 4;
+// abort[] and rep[] are one run of u32 words on the device (rep = abort + kZAbortFlagWords) and
+// in the host's read-back (`hab` in the kernels and finish_fused): counter k is hab[zhab_rep(k)].
+constexpr uint32_t kZAbortWords = kZAbortFlagWords + kZRepWords;
+constexpr uint32_t zhab_rep(ZRep k) { return kZAbortFlagWords + k; }
+// FusedCtl::jwork's header, then the work list ([kZJWorkHead, + cap) the items' table slots,
+// the next cap words their tiles).  The header follows the abort words in the read-back.
+enum ZJWork : uint32_t {
+  kZJWorkItems = 0,  // items filed (past jwork_cap: the list was full)
+  kZJWorkOvf = 1,    // overflow-arena entries taken (past jovf_cap: the arena was full)
+};
+constexpr uint32_t kZJWorkHead = 2;
+constexpr uint32_t kZHabJWork = kZAbortWords;
+static_assert(kZAbortFlagWords % 2 == 0 && kZAbortWords % 2 == 0 && kZJWorkHead % 2 == 0,
+              "the u32 word groups start and end on the u64 words the layouts below count in");
+// FusedCtl::dbg (CLONOS_FUSED_DEBUG), u32 words: the head, a record of kZDbgLaneWords words per
+// lane of the first aborting tile from kZDbgLanes (rs, re, speculative exit / bad / first,
+// 0, entry, exit | bad << 31), then from kZDbgTiles two u64 per tile: the entry its ex word
+// was written from, and the writer.
+enum ZDbg : uint32_t {
+  kZDbgClaim = 0,  // the first aborting tile (count_tile claims the words up to kZDbgEndA and the lanes)
+  kZDbgTile = 1,
+  kZDbgReason = 2,
+  kZDbgMustExit = 3,
+  kZDbgXTrue = 4,
+  kZDbgETrue = 5,
+  kZDbgLo = 6,
+  kZDbgHi = 7,
+  kZDbgEndA = 8,
+  kZDbgWalkMark = 9,  // kZDbgWalkGaveUp: a repair walk gave up, and then
+  kZDbgWalkFrom = 10,
+  kZDbgWalkAt = 11,
+  kZDbgWalkEntry = 12,
+  kZDbgWalkExit = 13,
+  kZDbgWalkSpan = 14,
+  kZDbgWalkDisagree = 15,
+  kZDbgSkipN = 16,  // chunk-entry reads not taken (published, but before their tile); the first one:
+  kZDbgSkipTile = 17,
+  kZDbgSkipWordLo = 18,
+  kZDbgSkipWordHi = 19,
+  kZDbgSkipOff = 20,
+  kZDbgSkipPolls = 21,
+};
+constexpr uint32_t kZDbgLanes = 24;  // (the head: [0, kZDbgLanes))
+constexpr uint32_t kZDbgWalkGaveUp = 0xD15A;
+constexpr uint32_t kZDbgLaneWords = 8;
+constexpr uint32_t kZDbgTiles = kZDbgLanes + 64 * kZDbgLaneWords;  // the per-tile words' start (u32 index)
 
 struct FusedCtl {
   uint64_t* st_x;     // per tile: pk_word(2, exit (span offset) the successor enters at)
@@ -219,11 +300,8 @@ struct FusedCtl {
   uint64_t* bits;     // per tile: 64 x 16 B record-start bitmaps (lane l: region l)
   uint64_t* span_lo;  // per span: base at its first tile
   uint64_t* span_hi;  // per span: base past its last tile
-  uint32_t* abort;    // [8]: flag, then ~(first tile) per abort reason 1..4 (4 = wait timed out)
-  uint32_t* dbg;      // optional diagnostics (CLONOS_FUSED_DEBUG): [0, 16) the first aborting tile and
-                      // a repair walk that gave up, [16, 24) chunk-entry reads not taken, [24, ..)
-                      // the first aborting tile's lane state, then from word kZDbgTiles per tile the
-                      // writer of its ex word and its entry
+  uint32_t* abort;    // [kZAbortFlagWords]: the batch's flag and ~(first tile) per abort reason (ZAbort)
+  uint32_t* dbg;      // optional diagnostics (CLONOS_FUSED_DEBUG): the words of ZDbg
   uint64_t* prof;     // optional per-tile phase stamps (CLONOS_SCAN_PHASES): s_memtime x 8
   uint32_t n_tiles;
   // Serializable record lengths per tile (phase 3, k_decode_jser), sorted by position:
@@ -234,12 +312,12 @@ struct FusedCtl {
   uint32_t* jn;
   uint32_t jser;
   uint32_t jwork_cap;  // capacity of the general-walker work list
-  uint32_t* jwork;     // [0]: items, [1]: overflow entries taken, then [2, 2 + cap): the items'
-                       // table slots, [2 + cap, 2 + 2 cap): their tiles; with the sidecar then
-                       // [2 + 2 cap]: tiles to scan, and those tiles (n_tiles words)
+  uint32_t* jwork;     // the header (ZJWork), then cap words of the items' table slots, cap words of
+                       // their tiles; with the sidecar then the count of tiles to scan and those
+                       // tiles (n_tiles words)
   uint32_t warm;    // speculative warm-up bytes before each region (| 1 << 31: not staggered by lane)
   JArena jar;       // the stream walker's spill arena (k_decode_jser_general)
-  // Per-span fallback: a tile whose chain goes wrong (reasons 1-3, 5) sets span_bad[span]
+  // Per-span fallback: a tile whose chain goes wrong (kZAbortBad, End, Exit, Serializable) sets span_bad[span]
   // and the count pass goes on with the next span; the host decodes the bad spans with the
   // robust pipeline, injects their counts (k_decode_inject) and re-runs scan + emit with
   // skip_bad set, so emit leaves the bad spans' records to the robust output.
@@ -256,10 +334,8 @@ struct FusedCtl {
   // ent[c] = pk_word(2, the span offset chunk c's first tile entered at) when it entered at a
   // published exit (0: it did not).  k_decode_repair compares every such entry with the true
   // exit ex[] of the tile before, after the count pass, so a chunk that took a wrong entry is
-  // walked again whatever the hand-off read returned.  rep[0]: chunks served for a wrong
-  // entry, rep[1]: requests filed, rep[2]: look-back checks failed (k_decode_emit; the batch
-  // is decoded again), rep[3]: canonical exits found before their tile's end (published as
-  // the tile end, a guess the repair checks).  All zeroed per batch.
+  // walked again whatever the hand-off read returned.  rep[]: the counters of ZRep (a canonical
+  // exit published as the tile end is a guess the repair checks).  All zeroed per batch.
   uint64_t* ex;
   uint8_t* rep_flag;
   uint32_t* rep;
@@ -278,15 +354,14 @@ struct FusedCtl {
   uint64_t* span_err;
   // Serializable tables past kZJCap entries: entry i >= kZJCap of tile t at slot
   // n_tiles * kZJCap + jbase[t] + i - kZJCap of jpos / jlen (jovf_cap slots in all, taken
-  // with jwork[1]; exhausted: abort reason 6, the host grows the arena and runs again).
+  // with jwork[kZJWorkOvf]; exhausted: kZAbortOverflow, the host grows the arena and runs again).
   uint32_t* jbase;
   uint32_t jovf_cap;
   // The one-launch scan (phase 5, k_decode_scan): lb[0] a ticket counter, lb[1 + b] block b's
   // look-back word (pk_word state 1 and its total, then state 2 and its inclusive prefix; the
   // state is held in both halves, see decode_fused.hip); all zeroed per
-  // batch.  h_res: host memory the host reads the batch's result from -- span_hi at
-  // [n_spans + s], the abort words as u32 at [2 n_spans] -- written by that kernel, so no
-  // read-back copy is queued (null: none).
+  // batch.  h_res: host memory the host reads the batch's result from (fused_readback below)
+  // -- written by that kernel, so no read-back copy is queued (null: none).
   uint64_t* lb;
   uint64_t* h_res;
   uint32_t lean;  // batches without tables: the lean speculative walk (wide tags step one byte)
@@ -294,14 +369,51 @@ struct FusedCtl {
   // from its segment's list instead of scanning the tile (hdr null: every tile is scanned).
   SideCar side;
 };
-constexpr uint32_t kZAbortWords = 12;  // abort[8] rep[4] (u32), adjacent
-constexpr uint32_t kZJCap = 256;  // Serializable candidates per tile in LDS (more: the overflow arena)
 constexpr uint32_t kZScanBlock = 1024;  // tiles per workgroup of the offsets scan
+static_assert(sizeof(FusedCtl) == 328, "the kernels' argument layout: no field added, resized or moved");
+
+// The device control block of one batch (FusedCtl's pointers into it), in u64 words from its
+// start.  This function alone knows the order
+//   st_x[nt] ex[nt] rep_flag[nt] (u8) | cnt[nt] base[nt] boff[nb] | span_lo[ns] span_hi[ns] |
+//   abort[kZAbortFlagWords] rep[kZRepWords] (u32) | lb: a ticket, look-back[nb] | ent[chunks]
+// (nb blocks of kZScanBlock tiles, a chunk per block of the count pass's grid; bits lie apart).
+// Three things rely on neighbours in it: the set-up zeroes [0, cnt) and [abort, words) as one
+// range each (st_x, ex, rep_flag; the abort and repair words, lb, ent); rep is abort +
+// kZAbortFlagWords; and span_lo | span_hi | abort | rep is the read-back's order, so a
+// read-back is one copy from span_lo or from span_hi.
+struct FusedLayout {
+  size_t ex, rep_flag, cnt, base, boff, span_lo, span_hi, abort, lb, ent, words;  // (st_x: 0)
+};
+inline FusedLayout fused_layout(uint32_t n_tiles, uint32_t n_spans, uint32_t grid) {
+  const size_t nt = n_tiles, ns = n_spans, nb = (nt + kZScanBlock - 1) / kZScanBlock;
+  FusedLayout L;
+  L.ex = nt;
+  L.rep_flag = L.ex + nt;
+  L.cnt = L.rep_flag + (nt + 7) / 8;
+  L.base = L.cnt + nt;
+  L.boff = L.base + nt;
+  L.span_lo = L.boff + nb;
+  L.span_hi = L.span_lo + ns;
+  L.abort = L.span_hi + ns;
+  L.lb = L.abort + kZAbortWords / 2;
+  L.ent = L.lb + 1 + nb;
+  L.words = L.ent + (grid ? grid : 1);
+  return L;
+}
+// The host's read-back of a batch (h_zres, FusedCtl::h_res), in u64 words:
+//   span_lo[ns] | span_hi[ns] | abort + rep (u32: `hab`) | the jwork header (u32, hab[kZHabJWork ..])
+// The first three in the control block's order.  abort_only: up to the abort flag words (the
+// per-span fallback's re-run reads no counters).
+struct FusedReadback {
+  uint32_t span_hi;
+  uint64_t abort, abort_only, jwork, words;
+};
+constexpr FusedReadback fused_readback(uint32_t n_spans) {
+  return FusedReadback{n_spans, 2ull * n_spans, 2ull * n_spans + kZAbortFlagWords / 2,
+                       2ull * n_spans + kZHabJWork / 2, 2ull * n_spans + (kZHabJWork + kZJWorkHead) / 2};
+}
+constexpr uint32_t kZJCap = 256;  // Serializable candidates per tile in LDS (more: the overflow arena)
 constexpr uint32_t kZTinySpan = 1024;   // whole spans up to this many bytes: pass 0, a lane each
-// abort reasons: 1 invalid record on the true chain, 2 span end, 3 exit mismatch,
-// 4 wait timeout, 5 Serializable record met without tables, 6 a Serializable arena or work
-// list full (the host grows it and runs again);
-// abort[7] != 0: phase 3 found Serializable candidates (any tile)
 // The launches of the fused decode (launch_decode_fused).  A batch takes Count, Scan, Emit in
 // that order, after one optional launch: JserTables when it builds tables, or CountTiny when it
 // holds small whole spans and builds none (the two never occur together).
@@ -345,9 +457,8 @@ uint32_t decode_count_grid(bool jser, uint32_t n_tiles);
 // Small batches in one launch (k_decode_small_tiles): a block per tile counts the tile from
 // its predecessor's published exit, publishes its own exit and counts, sums every earlier
 // tile's (look-back), emits.  Batches without Serializable tables.  Results go to `res`
-// (host-mapped pinned memory or device): res[0] records, res[1] wide rows, res[2] != 0 when any
-// tile failed (the host then decodes the batch the usual way), res[3 + s] span s's first record
-// (spans with tiles).  agg: kZSmallAggWords zeroed words; the kernel zeroes all of agg_next for
+// (host-mapped pinned memory or device), the words of ZSmallRes.  agg: kZSmallAggWords zeroed
+// words; the kernel zeroes all of agg_next for
 // the next call (the host alternates two buffers, so no memset is queued).  plan (host memory,
 // optional): a plan of at most kZSmallArgTiles tiles and kZSmallArgSpans spans goes in the
 // launch's own arguments instead of d_tiles / d_spans, so no copy is queued before the launch.
@@ -355,6 +466,24 @@ constexpr uint32_t kZSmallSpans = 4096;     // spans per small batch at most
 constexpr uint32_t kZSmallTilesMax = 4096;  // tiles per small batch at most
 constexpr uint32_t kZSmallAggWords = 2 * kZSmallTilesMax;  // look-back words per buffer: counts, exits
 constexpr uint32_t kZSmallArgTiles = 64, kZSmallArgSpans = 64;
+enum ZSmallRes : uint32_t {
+  kZSmallRec = 0,     // records
+  kZSmallWide = 1,    // wide rows
+  kZSmallFailed = 2,  // != 0 when any tile failed (the host then decodes the batch the usual way)
+  kZSmallSpan0 = 3,   // [kZSmallSpan0 + s]: span s's first record (spans with tiles), then per tile
+                      // the hand-offs it took, for the host's check: kZSmallCheckWords words
+};
+enum ZSmallCheck : uint32_t {
+  kZCheckEntryExit = 0,  // entry | exit << 32 (span offsets; a small span is under 4 GiB)
+  kZCheckBase = 1,       // the tile's base: every earlier tile's counts
+  kZCheckCount = 2,      // its own counts (wide << 31 | records)
+};
+constexpr uint32_t kZSmallCheckWords = 3;
+// Tile t's check words in `res` (host and device), and the words `res` holds in all.
+constexpr uint64_t small_check_at(uint32_t n_spans, uint32_t t) {
+  return uint64_t(kZSmallSpan0) + n_spans + uint64_t(kZSmallCheckWords) * t;
+}
+constexpr uint64_t small_res_words(uint32_t n_spans, uint32_t n_tiles) { return small_check_at(n_spans, n_tiles); }
 struct SmallPlanArg {  // 3 KiB: with the other arguments inside the 4 KiB kernel-argument limit
   TileDesc tiles[kZSmallArgTiles];
   SpanDesc spans[kZSmallArgSpans];
