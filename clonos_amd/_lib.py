@@ -62,6 +62,7 @@ EXPORTED = [
     "clg_ifl_open", "clg_ifl_open_typed", "clg_ifl_close", "clg_ifl_log_batch", "clg_ifl_notify_checkpoint_complete", "clg_ifl_state",
     "clg_ifl_replay_batch", "clg_replay_prepare_device", "clg_get_determinants_batch", "clg_response_put_batch",
     "clg_host_register", "clg_host_unregister",
+    "clg_digest_logs", "clg_digest_spans", "clg_digest_host",
 ]
 
 
@@ -232,6 +233,10 @@ class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("total_ms", C.c_double), ("bytes", C.c_uint64)]
 
 
+class Digest(C.Structure):  # clg_digest: equal only when both fields are equal
+    _fields_ = [("hash", C.c_uint64), ("len", C.c_uint64)]
+
+
 def _load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -309,6 +314,9 @@ def _load() -> C.CDLL:
                                        C.c_uint32, u64p]),
         "clg_process_delta": (C.c_int, [P, C.c_uint32, C.c_uint32, P, C.c_uint64, C.c_uint32, i64p, P, C.c_uint32, u32p,
                                         u64p]),
+        "clg_digest_logs": (C.c_int, [P, P, P, C.c_uint32, P]),
+        "clg_digest_spans": (C.c_int, [P, P, P, P, C.c_uint32, C.c_uint32, P]),
+        "clg_digest_host": (C.c_int, [P, C.c_uint64, C.POINTER(Digest)]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),
         "clg_ifl_close": (C.c_int, [P, C.c_uint32]),

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/clonos_engine.h"
+#include "digest.h"
 #include "kernels.h"
 
 static_assert(sizeof(clg_delta_req) == 32, "clg_delta_req layout");
@@ -629,6 +630,9 @@ struct clg_engine {
   PinBuf h_rmeta;
   PinBuf h_rout;  // replay-prep: the subpartition results, read back in one place (pinned)
   DevBuf d_plan;
+  DevBuf d_dgtab, d_dgpart, d_dgout;  // log digest: the constant table (uploaded once), partials, results
+  PinBuf h_dgout;
+  bool dgtab_ready = false;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 
@@ -1270,6 +1274,70 @@ struct clg_engine {
     }));
     if (out_kind != CLG_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, total, hipMemcpyDeviceToHost, stream));
     return sync();
+  }
+
+  // getDeterminants(start_epoch[i]) of log[i] as runs for the device-side piece expansion
+  // (clg_get_determinants_batch, clg_digest_logs): run i's output offset is its place in the
+  // packed order, its pad the request index; len[i] / out_off[i] (optional) per request.
+  int plan_determinant_runs(const uint32_t* log, const int64_t* start_epoch, uint32_t n, uint32_t* len,
+                            uint64_t* out_off, std::vector<clg::SegSpan>& runs, std::vector<uint32_t>& segtab,
+                            uint32_t* n_pieces, uint64_t* total) {
+    runs.reserve(n);
+    // each log's segment indices once in segtab: the log's place there, by handle (a hash map
+    // took 0.1 ms for config 5's 2 064 logs)
+    if (tab_at.size() < logs.size()) tab_at.resize(logs.size(), UINT64_MAX);
+    std::vector<uint32_t> touched;
+    touched.reserve(n);
+    int st = CLG_OK;
+    uint64_t dst = 0;
+    for (uint32_t i = 0; i < n && st == CLG_OK; ++i) {
+      Log* l;
+      if ((st = get_log(log[i], &l)) != CLG_OK) break;
+      int32_t s = 0, nb = 0;
+      if (l->depth != 0 && (st = determinants_range(*l, start_epoch[i], &s, &nb)) != CLG_OK) break;
+      if (len) len[i] = uint32_t(nb);
+      if (out_off) out_off[i] = dst;
+      if (nb > 0) {
+        uint64_t& at = tab_at[log[i]];
+        if (at == UINT64_MAX) {
+          at = segtab.size();
+          touched.push_back(log[i]);
+          segtab.insert(segtab.end(), l->segs.begin(), l->segs.end());
+        }
+        runs.push_back(clg::SegSpan{at, uint32_t(s), uint32_t(nb), dst, *n_pieces, i});
+        *n_pieces += uint32_t(s + nb - 1) / C() - uint32_t(s) / C() + 1;
+      }
+      dst += uint64_t(nb);
+    }
+    for (uint32_t h : touched) tab_at[h] = UINT64_MAX;
+    *total = dst;
+    return st;
+  }
+
+  // The digest of every run (digest.hip), `n` results read back into out: out[run.pad] for a
+  // run, {0, 0} for a request without one.  d_runs / d_pc: the runs and their pieces on the
+  // device, queued on `stream`.
+  int run_digest(const clg::SegSpan* d_runs, uint32_t n_runs, const clg::GatherPiece* d_pc, uint32_t n_pieces,
+                 uint64_t bytes, uint32_t n, clg_digest* out) {
+    if (!dgtab_ready) {
+      uint64_t tab[clg::kDigestTabWords];
+      clg::digest_table(tab);
+      CHK(d_dgtab.ensure(sizeof(tab)));
+      HIPCHK(hipMemcpy(d_dgtab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
+      dgtab_ready = true;
+    }
+    CHK(d_dgpart.ensure(size_t(n_pieces) * 8 + 8));
+    CHK(d_dgout.ensure(size_t(n) * sizeof(clg_digest)));
+    CHK(h_dgout.ensure(size_t(n) * sizeof(clg_digest)));
+    HIPCHK(hipMemsetAsync(d_dgout.p, 0, size_t(n) * sizeof(clg_digest), stream));
+    CHK(timed("log_digest", bytes, [&] {
+      return clg::launch_digest(d_pc, n_pieces, d_runs, n_runs, d_dgtab.as<uint64_t>(), d_dgpart.as<uint64_t>(),
+                                d_dgout.as<clg_digest>(), stream);
+    }));
+    HIPCHK(hipMemcpyAsync(h_dgout.p, d_dgout.p, size_t(n) * sizeof(clg_digest), hipMemcpyDeviceToHost, stream));
+    CHK(sync());
+    memcpy(out, h_dgout.p, size_t(n) * sizeof(clg_digest));
+    return CLG_OK;
   }
 
   // Device-output slice gather on gstream, after everything already queued on `stream`
@@ -3502,7 +3570,6 @@ int clg_get_determinants_batch(clg_engine* e, const uint32_t* log, const int64_t
   std::vector<clg::SegSpan> runs;
   std::vector<uint32_t> segtab;
   uint32_t n_pieces = 0;
-  const uint32_t C = e->C();
   uint64_t dst = 0;
   if (!out) {  // sizes only (the merge measures every copy first): no gather plan
     for (uint32_t i = 0; i < n; ++i) {
@@ -3517,39 +3584,106 @@ int clg_get_determinants_batch(clg_engine* e, const uint32_t* log, const int64_t
     if (total) *total = dst;
     return CLG_OK;
   }
-  runs.reserve(n);
-  // each log's segment indices once in segtab: the log's place there, by handle (a hash map
-  // took 0.1 ms for config 5's 2 064 logs)
-  std::vector<uint64_t>& tab_at = e->tab_at;
-  if (tab_at.size() < e->logs.size()) tab_at.resize(e->logs.size(), UINT64_MAX);
-  std::vector<uint32_t> touched;
-  touched.reserve(n);
-  int st = CLG_OK;
-  for (uint32_t i = 0; i < n && st == CLG_OK; ++i) {
-    Log* l;
-    if ((st = e->get_log(log[i], &l)) != CLG_OK) break;
-    int32_t s = 0, nb = 0;
-    if (l->depth != 0 && (st = e->determinants_range(*l, start_epoch[i], &s, &nb)) != CLG_OK) break;
-    len[i] = uint32_t(nb);
-    if (out_off) out_off[i] = dst;
-    if (nb > 0) {
-      uint64_t& at = tab_at[log[i]];
-      if (at == UINT64_MAX) {
-        at = segtab.size();
-        touched.push_back(log[i]);
-        segtab.insert(segtab.end(), l->segs.begin(), l->segs.end());
-      }
-      runs.push_back(clg::SegSpan{at, uint32_t(s), uint32_t(nb), dst, n_pieces, 0});
-      n_pieces += uint32_t(s + nb - 1) / C - uint32_t(s) / C + 1;
-    }
-    dst += uint64_t(nb);
-  }
-  for (uint32_t h : touched) tab_at[h] = UINT64_MAX;
-  if (st != CLG_OK) return st;
+  CHK(e->plan_determinant_runs(log, start_epoch, n, len, out_off, runs, segtab, &n_pieces, &dst));
   if (total) *total = dst;
   if (dst > cap) return fail(CLG_E_CAPACITY, "getDeterminants batch needs %llu bytes", (unsigned long long)dst);
   CHK(e->flush());
   return e->run_gather_runs(runs, segtab, n_pieces, dst, out, out_kind);
+}
+
+// The digest of getDeterminants(start_epoch[i]) of log[i] (digest.h): the ranges, runs and
+// segment table as clg_get_determinants_batch builds them, then a read-only pass over the
+// pieces.  What LogReplayerImpl.checkFinished (LogReplayerImpl.java:126-128) asserts by length
+// alone, and only under -ea, a caller can assert by content.
+int clg_digest_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n, clg_digest* out) {
+  ENGINE_GUARD(e);
+  if (n && (!log || !start_epoch || !out)) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (!n) return CLG_OK;
+  std::vector<clg::SegSpan> runs;
+  std::vector<uint32_t> segtab;
+  uint32_t n_pieces = 0;
+  uint64_t total = 0;
+  CHK(e->plan_determinant_runs(log, start_epoch, n, nullptr, nullptr, runs, segtab, &n_pieces, &total));
+  if (runs.empty()) {
+    memset(out, 0, size_t(n) * sizeof(clg_digest));
+    return CLG_OK;
+  }
+  CHK(e->flush());
+  size_t o[2];
+  const size_t hb = clg_engine::gather_desc_layout(runs, segtab, o);
+  CHK(e->h_desc.ensure(hb));
+  CHK(e->d_desc.ensure(hb));
+  CHK(e->d_pieces.ensure(size_t(n_pieces) * sizeof(clg::GatherPiece)));
+  clg_engine::gather_desc_fill(e->h_desc.as<uint8_t>(), runs, segtab, o);
+  HIPCHK(hipMemcpyAsync(e->d_desc.p, e->h_desc.p, hb, hipMemcpyHostToDevice, e->stream));
+  CHK(e->gather_expand(e->d_desc.as<uint8_t>(), runs, o, n_pieces, e->d_pieces.as<clg::GatherPiece>(), e->stream));
+  return e->run_digest(e->d_desc.as<clg::SegSpan>(), uint32_t(runs.size()), e->d_pieces.as<clg::GatherPiece>(), n_pieces,
+                       total, n, out);
+}
+
+// The digest of spans of host or device memory: the same pieces, one per 16 KiB of span, built
+// on the host (a host input is staged as clg_decode_host stages its bytes).  What
+// DeterminantResponseEvent.merge (DeterminantResponseEvent.java:137-146) decides on lengths
+// alone, the receiver of a merged winner can check by content.
+int clg_digest_spans(clg_engine* e, const uint8_t* bytes, const uint64_t* off, const uint64_t* len, uint32_t n,
+                     uint32_t in_kind, clg_digest* out) {
+  ENGINE_GUARD(e);
+  if (n && (!off || !len || !out)) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (in_kind != CLG_MEM_HOST && in_kind != CLG_MEM_DEVICE) return fail(CLG_E_INVALID_ARG, "in_kind %u", in_kind);
+  if (!n) return CLG_OK;
+  constexpr uint64_t kPiece = 16384;
+  uint64_t lo = UINT64_MAX, hi = 0, total = 0, n_pieces = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (len[i] >> 32) return fail(CLG_E_INVALID_ARG, "span %u of %llu bytes", i, (unsigned long long)len[i]);
+    if (len[i] == 0) continue;
+    lo = std::min(lo, off[i]);
+    hi = std::max(hi, off[i] + len[i]);
+    total += len[i];
+    n_pieces += (len[i] + kPiece - 1) / kPiece;
+  }
+  if (!total) {
+    memset(out, 0, size_t(n) * sizeof(clg_digest));
+    return CLG_OK;
+  }
+  if (!bytes) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (n_pieces >> 32) return fail(CLG_E_INVALID_ARG, "spans of %llu bytes in one call", (unsigned long long)total);
+  const uint8_t* base = bytes;  // span i starts at base + (off[i] - base_off)
+  uint64_t base_off = 0;
+  if (in_kind == CLG_MEM_HOST) {
+    CHK(e->d_stage.ensure(hi - lo + 16));
+    CHK(e->h_stage.ensure(hi - lo + 16));
+    memcpy(e->h_stage.p, bytes + lo, hi - lo);
+    HIPCHK(hipMemcpyAsync(e->d_stage.p, e->h_stage.p, hi - lo, hipMemcpyHostToDevice, e->stream));
+    base = e->d_stage.as<uint8_t>();
+    base_off = lo;
+  }
+  std::vector<clg::SegSpan> runs;
+  std::vector<clg::GatherPiece> pieces;
+  runs.reserve(n);
+  pieces.reserve(n_pieces);
+  uint64_t dst = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (len[i] == 0) continue;
+    runs.push_back(clg::SegSpan{0, 0, uint32_t(len[i]), dst, uint32_t(pieces.size()), i});
+    for (uint64_t a = 0; a < len[i]; a += kPiece)
+      pieces.push_back(clg::GatherPiece{base + (off[i] - base_off) + a, dst + a, uint32_t(std::min(kPiece, len[i] - a)), 0});
+    dst += len[i];
+  }
+  const size_t rb = clg_engine::al16(runs.size() * sizeof(clg::SegSpan)), pb = pieces.size() * sizeof(clg::GatherPiece);
+  CHK(e->h_desc.ensure(rb + pb));
+  CHK(e->d_desc.ensure(rb + pb));
+  memcpy(e->h_desc.as<uint8_t>(), runs.data(), runs.size() * sizeof(clg::SegSpan));
+  memcpy(e->h_desc.as<uint8_t>() + rb, pieces.data(), pb);
+  HIPCHK(hipMemcpyAsync(e->d_desc.p, e->h_desc.p, rb + pb, hipMemcpyHostToDevice, e->stream));
+  return e->run_digest(e->d_desc.as<clg::SegSpan>(), uint32_t(runs.size()),
+                       reinterpret_cast<const clg::GatherPiece*>(e->d_desc.as<uint8_t>() + rb), uint32_t(pieces.size()),
+                       total, n, out);
+}
+
+int clg_digest_host(const uint8_t* bytes, uint64_t n, clg_digest* out) {
+  if (!out || (n && !bytes)) return fail(CLG_E_INVALID_ARG, "null argument");
+  *out = clg_digest{clg::dg_bytes(bytes, n), n};
+  return CLG_OK;
 }
 
 int clg_slice_batch(clg_engine* e, const clg_slice_req* reqs, uint32_t n, clg_slice_res* res, void* out, uint64_t cap,

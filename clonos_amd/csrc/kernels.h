@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct clg_digest;  // include/clonos_engine.h
+
 namespace clg {
 
 // ---- decode geometry ---------------------------------------------------------
@@ -501,6 +503,19 @@ struct GatherPiece {
   uint32_t len;
   uint32_t pad;
 };
+
+// ---- log digest (digest.h, digest.hip) ---------------------------------------------
+// The constant table the digest kernels read, in u64 words: the square ladder R^(2^j), then
+// R^(8 q) for q < 64 (a lane window is 8 words), R^k for k <= 8, and R^512 (a wave's words per
+// iteration).  digest_table fills kDigestTabWords host words.
+constexpr uint32_t kDigestTabWin = 32, kDigestTabOne = kDigestTabWin + 64, kDigestTabIter = kDigestTabOne + 9,
+                   kDigestTabWords = kDigestTabIter + 1;
+void digest_table(uint64_t* tab);
+// Digest of each run: pass 1 writes one partial per piece (pieces as k_expand_pieces produces
+// them: dst is the piece's offset in the packed order, runs[].dst its run's), pass 2 adds a
+// run's partials and writes {hash, len} to d_out[run.pad].
+int launch_digest(const GatherPiece* d_pieces, uint32_t n_pieces, const struct SegSpan* d_runs, uint32_t n_runs,
+                  const uint64_t* d_tab, uint64_t* d_partial, ::clg_digest* d_out, void* stream);
 
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {

@@ -34,6 +34,12 @@ the responses (WaitingDeterminantsState.java:97-109).  Across GPUs: every rank m
 copy of each log of the failed vertices, one all-reduce(MAX) over packed
 (len << 8 | rank) picks the winner per log, and one all-to-all moves each winner's bytes to
 the rank hosting the failed vertex's replacement (merge_responses).
+
+Verification.  A replica is trusted to equal its owner's log, and a merged winner the log its
+rank measured; the log digest (clg_digest_logs / clg_digest_spans: 16 bytes per log, computed
+where the bytes live) lets the product check both without moving the bytes: Replicator.verify
+compares every replica with its owner at a quiescent point, merge_responses(verify=True) the
+received winners with what their ranks hold.
 """
 from __future__ import annotations
 
@@ -66,6 +72,8 @@ DELTA_REQ = np.dtype([("log", "<u4"), ("offset_from_epoch", "<i4"), ("epoch", "<
                       ("len", "<u4"), ("status", "<i4")])
 assert SLICE_REQ.itemsize == C.sizeof(_lib.SliceReq) and SLICE_RES.itemsize == C.sizeof(_lib.SliceRes)
 assert DELTA_REQ.itemsize == C.sizeof(_lib.DeltaReq)
+# Replicator.verify's wire row, one per planned request: the owner's digest of the log
+VERIFY_ROW = np.dtype([("gid", "<i8"), ("len", "<u8"), ("hash", "<u8")])
 
 
 def _align(n: int) -> int:
@@ -86,6 +94,20 @@ class ExchangeStats:
     applied: int = 0        # deltas applied to replicas
     applied_bytes: int = 0  # delta bytes those deltas carried
     skipped: int = 0        # rows for logs this rank does not want
+
+
+@dataclass
+class VerifyReport:
+    """Replicator.verify on one rank: the gids whose replica here is shorter / longer than the
+    owner's log, or of its length with another hash; `checked` replicas were compared."""
+    short: List[int]
+    long: List[int]
+    differs: List[int]
+    checked: int = 0
+
+    @property
+    def clean(self) -> bool:
+        return not (self.short or self.long or self.differs)
 
 
 class ReplicationPlan:
@@ -148,6 +170,17 @@ class EngineIO:
     def apply(self, req: np.ndarray, recv) -> None:
         kind = _lib.CLG_MEM_DEVICE if recv.is_cuda else _lib.CLG_MEM_HOST
         check(lib.clg_upstream_delta_batch(self.engine.handle, req.ctypes.data, len(req), recv.data_ptr(), kind))
+
+    def digest(self, handles: np.ndarray, start_epochs: np.ndarray) -> np.ndarray:
+        """DIGEST rows of getDeterminants(start_epochs[i]) of handles[i] (clg_digest_logs)."""
+        return self.engine.digest_logs(handles, start_epochs)
+
+    def digest_spans(self, tensor, offs: np.ndarray, lens: np.ndarray) -> np.ndarray:
+        """DIGEST rows of tensor[offs[i] : offs[i] + lens[i]] (clg_digest_spans; device input
+        for a tensor in HBM)."""
+        if tensor.is_cuda:
+            return self.engine.digest_spans(tensor.data_ptr(), offs, lens, device=True)
+        return self.engine.digest_spans(tensor.numpy(), offs, lens)
 
     # replay-prep merge: a copy is getDeterminants(startEpoch) of a log (owned or replica);
     # both calls are one native call for all the copies (clg_get_determinants_batch)
@@ -303,6 +336,48 @@ class Replicator:
         return st
 
 
+    def verify(self, start_epoch: int) -> VerifyReport:
+        """Compare every replica with its owner's log from `start_epoch` by digest.  All ranks
+        call it together at a quiescent point (after exchange, before new appends).  Each
+        owner digests every log it sends, once; one all-to-all carries one row per planned
+        request (gid, len, hash) with the header rows' static splits (ReplicationPlan.n_to /
+        n_from); each receiver digests its replicas from the same epoch.  With one rank no
+        collective runs and the report is empty."""
+        import torch
+        import torch.distributed as dist
+        plan = self.plan
+        rep = VerifyReport([], [], [])
+        if plan.world == 1:
+            return rep
+        nq = len(plan.req_gid)
+        rows = np.zeros(nq, VERIFY_ROW)
+        if nq:
+            sent, inv = np.unique(plan.req_gid, return_inverse=True)  # each sent log digested once
+            dg = self.io.digest(self.handle[sent].astype(np.uint32), np.full(len(sent), start_epoch, np.int64))
+            rows["gid"] = plan.req_gid
+            rows["len"] = dg["len"][inv]
+            rows["hash"] = dg["hash"][inv]
+        backend = dist.get_backend(self.group)
+        dev = self.device if backend == "nccl" else "cpu"
+        vsend = torch.from_numpy(rows.view(np.uint8).copy()).to(dev)
+        vrecv = torch.empty(int(plan.n_from.sum()) * VERIFY_ROW.itemsize, dtype=torch.uint8, device=dev)
+        dist.all_to_all_single(vrecv, vsend, output_split_sizes=(plan.n_from * VERIFY_ROW.itemsize).tolist(),
+                               input_split_sizes=(plan.n_to * VERIFY_ROW.itemsize).tolist(), group=self.group)
+        rr = vrecv.cpu().numpy().view(VERIFY_ROW)
+        h = self.replica_handle[rr["gid"]]
+        have = np.nonzero(h >= 0)[0]
+        if not len(have):
+            return rep
+        mine = self.io.digest(h[have].astype(np.uint32), np.full(len(have), start_epoch, np.int64))
+        theirs = rr[have]
+        gid = theirs["gid"]
+        rep.short = gid[mine["len"] < theirs["len"]].tolist()
+        rep.long = gid[mine["len"] > theirs["len"]].tolist()
+        rep.differs = gid[(mine["len"] == theirs["len"]) & (mine["hash"] != theirs["hash"])].tolist()
+        rep.checked = len(have)
+        return rep
+
+
 def rows_sent(rows: np.ndarray) -> int:
     """Header rows that carry a delta (the rest are the static slots of requests with none)."""
     return int((rows["len"] > 0).sum())
@@ -377,7 +452,7 @@ def copy_arrays(copies) -> Tuple[np.ndarray, np.ndarray]:
 
 def merge_responses(io, table: LogTable, failed: Sequence[int], copies,
                     start_epochs: Dict[int, int], dest_of: Dict[int, int], device, group=None,
-                    timing: Optional[Dict[str, float]] = None) -> MergedCopies:
+                    timing: Optional[Dict[str, float]] = None, verify: bool = False) -> MergedCopies:
     """Cross-GPU DeterminantResponseEvent.merge for the logs of the failed vertices.
 
     copies: gid -> io handle of this rank's copy (owned log or replica) of a log of a failed
@@ -391,7 +466,12 @@ def merge_responses(io, table: LogTable, failed: Sequence[int], copies,
     rank tie-break picks identical content).  Step 2: the winners this rank holds are
     gathered in one call, grouped by destination, and one all-to-all carries them to the
     ranks hosting the replacements.  Returns this rank's MergedCopies (a log no rank holds
-    is absent, as in the merged map)."""
+    is absent, as in the merged map).
+
+    verify=True (off by default): each winning rank also digests its winners where they lie
+    (io.digest) and the digests travel beside the lengths, one 8-byte hash per winner in a
+    third collective; the destination digests the spans it received (io.digest_spans, device
+    input for a buffer in HBM) and raises RuntimeError on a mismatch."""
     import time as _time
     import torch
     import torch.distributed as dist
@@ -436,6 +516,9 @@ def merge_responses(io, table: LogTable, failed: Sequence[int], copies,
             timing["gather"] = timing.get("gather", 0.0) + t2 - t1
             timing["alloc"] = timing.get("alloc", 0.0) + t1 - t0
         offs = MERGE_GUARD + np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if len(mine) else lens
+        if verify and len(mine):
+            sel = np.searchsorted(held, mine)
+            _check_winners(io, buf, gids[mine], offs, lens, io.digest(handles[sel], epochs[sel])["hash"])
         res = MergedCopies(buf, gids=gids[mine], offs=offs, lens=lens, ranks=np.zeros(len(mine), np.int64))
         if timing is not None:
             timing["finish"] = timing.get("finish", 0.0) + _time.perf_counter() - t2
@@ -467,4 +550,25 @@ def merge_responses(io, table: LogTable, failed: Sequence[int], copies,
     recv = inbound[np.lexsort((inbound, win_rank[inbound]))]
     lens = win_len[recv]
     offs = MERGE_GUARD + np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if len(recv) else lens
+    if verify:  # the winners' hashes, in the order their bytes went
+        hsend = np.zeros(len(order), np.uint64)
+        if len(order):
+            sel = np.searchsorted(held, order)
+            hsend[:] = io.digest(handles[sel], epochs[sel])["hash"]
+        n_to = np.bincount(dest[mine], minlength=world).astype(np.int64)
+        n_from = np.bincount(win_rank[inbound], minlength=world).astype(np.int64)
+        ht = torch.from_numpy(hsend.view(np.int64).copy()).to(dev)
+        hr = torch.empty(len(recv), dtype=torch.int64, device=dev)
+        dist.all_to_all_single(hr, ht, output_split_sizes=n_from.tolist(), input_split_sizes=n_to.tolist(), group=group)
+        _check_winners(io, buf, gids[recv], offs, lens, hr.cpu().numpy().view(np.uint64))
     return MergedCopies(buf, gids=gids[recv], offs=offs, lens=lens, ranks=win_rank[recv])
+
+
+def _check_winners(io, buf, gids: np.ndarray, offs: np.ndarray, lens: np.ndarray, want_hash: np.ndarray) -> None:
+    """merge_responses(verify=True): the received winners' digests against their ranks'."""
+    if not len(gids):
+        return
+    got = io.digest_spans(buf, offs.astype(np.uint64), lens.astype(np.uint64))
+    bad = np.nonzero((got["hash"] != want_hash) | (got["len"] != lens.astype(np.uint64)))[0]
+    if len(bad):
+        raise RuntimeError(f"merged copies differ from the logs their ranks measured: gids {gids[bad][:8].tolist()}")

@@ -113,6 +113,20 @@ class DecodedBatch:
         return out
 
 
+# clg_digest rows: two spans are equal only when both fields are equal
+DIGEST = np.dtype([("hash", np.uint64), ("len", np.uint64)])
+
+
+def digest_host(data: Union[bytes, np.ndarray]) -> Tuple[int, int]:
+    """clg_digest_host: (hash, len) of host bytes on the CPU (no engine, no GPU) -- the same
+    digest Engine.digest_logs / digest_spans compute on the device."""
+    buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(
+        data, np.uint8)
+    d = _lib.Digest()
+    check(lib.clg_digest_host(buf.ctypes.data if buf.size else None, buf.size, C.byref(d)))
+    return int(d.hash), int(d.len)
+
+
 def _np_ptr(a: np.ndarray) -> int:
     return a.ctypes.data if a.size else 0
 
@@ -642,6 +656,40 @@ class Engine:
         k = nk.value
         win = winner[:k].copy()
         return win, self._finish(st, d, arrs, base, k, [np.frombuffer(blobs[i], np.uint8) for i in win])
+
+    # ---- log digests (clg_digest_*) -----------------------------------------------------------
+    def digest_logs(self, handles, start_epochs) -> np.ndarray:
+        """Digest of getDeterminants(start_epochs[i]) of log handles[i], computed where the bytes
+        live: a DIGEST row per request (16 bytes each come back).  Handles may repeat."""
+        h = np.ascontiguousarray(handles, np.uint32)
+        ep = np.ascontiguousarray(start_epochs, np.int64)
+        if h.shape != ep.shape or h.ndim != 1:
+            raise ValueError("handles and start_epochs must be 1-d and of equal length")
+        out = np.zeros(h.size, DIGEST)
+        if h.size:
+            check(lib.clg_digest_logs(self._h, _np_ptr(h), _np_ptr(ep), h.size, _np_ptr(out)))
+        return out
+
+    def digest_spans(self, data_or_ptr, offs, lens, device: bool = False) -> np.ndarray:
+        """Digest of span i = bytes[offs[i], offs[i] + lens[i]) of host bytes (bytes / uint8
+        array) or, with device=True, of device memory at the address data_or_ptr."""
+        so = np.ascontiguousarray(offs, np.uint64)
+        sl = np.ascontiguousarray(lens, np.uint64)
+        if so.shape != sl.shape or so.ndim != 1:
+            raise ValueError("offs and lens must be 1-d and of equal length")
+        out = np.zeros(so.size, DIGEST)
+        if not so.size:
+            return out
+        if device:
+            ptr, kind, keep = int(data_or_ptr), _lib.CLG_MEM_DEVICE, None
+        else:
+            keep = (np.ascontiguousarray(data_or_ptr, np.uint8) if isinstance(data_or_ptr, np.ndarray)
+                    else np.frombuffer(bytes(data_or_ptr), np.uint8))
+            if sl.size and int((so + sl).max()) > keep.size:
+                raise ValueError("span outside the data")
+            ptr, kind = (keep.ctypes.data if keep.size else None), _lib.CLG_MEM_HOST
+        check(lib.clg_digest_spans(self._h, ptr, _np_ptr(so), _np_ptr(sl), so.size, kind, _np_ptr(out)))
+        return out
 
     # ---- instrumentation ---------------------------------------------------------------------
     def kernel_stats(self):

@@ -347,3 +347,42 @@ def prepare_replay(engine: Engine, jobs: Sequence[Tuple[int, DeterminantResponse
             j += 1
         res.append(VertexReplay(vid, main, main.span_slice(i), sp))
     return main, res
+
+
+# ---- replay verification -----------------------------------------------------------------
+@dataclass
+class ReplayCheck:
+    """verify_replay's answer for one item: `matches` only when both fields of the two digests
+    (hash, len) are equal."""
+    matches: bool
+    regenerated: Tuple[int, int]  # digest of getDeterminants(start_epoch) of the regenerated log
+    recovered: Tuple[int, int]    # digest of the recovered copy
+
+
+def verify_replay(engine: Engine, items: Sequence[Tuple[int, int, bytes]]) -> List[ReplayCheck]:
+    """Does each regenerated log equal its recovered copy?  An item is (log handle,
+    start_epoch, recovered bytes): the log as the replay re-appended it, and the response bytes
+    the replay was fed from.  LogReplayerImpl.checkFinished (LogReplayerImpl.java:126-128)
+    asserts only that the two have the same length, and only under -ea: a replay that diverged
+    but logged as many bytes passes it.  Here both sides are digested on the device
+    (clg_digest_logs over the segment pool, clg_digest_spans over the recovered bytes) and
+    compared by content.
+
+    To find the first divergent epoch, digest the suffixes from each epoch in one batch:
+    items [(h, e, recovered[start_of(e):]) for e in epochs] -- the suffixes from the epochs
+    after the divergence match, so the last epoch whose suffix does not is where it diverged."""
+    n = len(items)
+    if not n:
+        return []
+    handles = np.array([it[0] for it in items], np.uint32)
+    epochs = np.array([it[1] for it in items], np.int64)
+    blobs = [bytes(it[2]) for it in items]
+    lens = np.array([len(b) for b in blobs], np.uint64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    regen = engine.digest_logs(handles, epochs)
+    recov = engine.digest_spans(b"".join(blobs), offs, lens)
+    out = []
+    for a, b in zip(regen, recov):
+        ra, rb = (int(a["hash"]), int(a["len"])), (int(b["hash"]), int(b["len"]))
+        out.append(ReplayCheck(ra == rb, ra, rb))
+    return out

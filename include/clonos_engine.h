@@ -477,6 +477,36 @@ int clg_get_determinants_batch(clg_engine* e, const uint32_t* log, const int64_t
                                void* out, uint64_t cap, uint32_t out_kind, uint64_t* out_off, uint32_t* len,
                                uint64_t* total);
 
+/* ---- log digests ------------------------------------------------------------------------------
+ * A way to say that two copies of a log hold the same bytes without moving those bytes: 16 bytes
+ * per log.  The digest of a span of n bytes b[0..n) is the pair {hash, len = n}, with
+ *   p = 2^61 - 1, R = 2654435761 (a primitive root mod p), m = ceil(n / 4),
+ *   w_k = the little-endian u32 of bytes 4k .. 4k+3, zero-padded past n,
+ *   hash = ( sum_{k<m} w_k * R^(m-1-k) ) mod p, always reduced to [0, p)
+ * (h = 0, then h = (h * R + w_k) mod p per word).  Two spans are taken as equal only when BOTH
+ * fields are equal.  Differing spans of equal length collide with probability at most m / p:
+ * this protects against accidents, not adversaries. */
+typedef struct clg_digest {
+  uint64_t hash;
+  uint64_t len;
+} clg_digest;
+/* Digest of getDeterminants(start_epoch[i]) of log[i], n logs, one read-only pass over HBM; only
+ * n * 16 bytes come back.  The range rules are clg_get_determinants_batch's (depth-0 log and
+ * empty range: {0, 0}; unknown handle: CLG_E_NO_LOG; absent epoch: from the earliest), staged
+ * appends are flushed first, requests may repeat a log and come in any order.  Strengthens
+ * LogReplayerImpl.checkFinished's length-only assertion (LogReplayerImpl.java:126-128): the
+ * regenerated log is compared with the recovered one by content. */
+int clg_digest_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n, clg_digest* out);
+/* Digest of span i = bytes[off[i], off[i]+len[i]) of host or device memory (in_kind CLG_MEM_HOST
+ * / CLG_MEM_DEVICE); a span of 2^32 bytes or more is CLG_E_INVALID_ARG.  Device input is read
+ * in aligned 16-byte words, only those that hold a byte of a span.  Strengthens
+ * DeterminantResponseEvent.merge (DeterminantResponseEvent.java:137-146), which keeps the longer
+ * copy on its length alone: the received winner is compared with the log its owner measured. */
+int clg_digest_spans(clg_engine* e, const uint8_t* bytes, const uint64_t* off, const uint64_t* len, uint32_t n,
+                     uint32_t in_kind, clg_digest* out);
+/* The same digest of host bytes on the CPU (no engine, no GPU). */
+int clg_digest_host(const uint8_t* bytes, uint64_t n, clg_digest* out);
+
 /* ---- in-flight (data) log (RT/inflightlogging/, I/ below) -------------------------------------
  * InFlightLog I/InFlightLog.java:32-55, two implementations (I/InFlightLogConfig.java:44 picks
  * one by taskmanager.inflight.type, default "spillable"):

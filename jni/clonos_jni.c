@@ -298,6 +298,42 @@ JNIEXPORT jint JNICALL FN(nDecodeHost)(JNIEnv* env, jclass cls, jlong e, jobject
   return s;
 }
 
+/* clg_digest_logs: out = {hash, len} per request (2 n longs). */
+JNIEXPORT jint JNICALL FN(nDigestLogs)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray starts,
+                                       jlongArray out) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  clg_digest* d = (clg_digest*)calloc((size_t)n + 1, sizeof(clg_digest));
+  if (!d) return CLG_E_INVALID_ARG;
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* st = (*env)->GetLongArrayElements(env, starts, NULL);
+  int s = clg_digest_logs(ENG(e), (const uint32_t*)lg, (const int64_t*)st, (uint32_t)n, d);
+  (*env)->ReleaseLongArrayElements(env, starts, st, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  if (s == CLG_OK) (*env)->SetLongArrayRegion(env, out, 0, 2 * n, (const jlong*)d);
+  free(d);
+  return s;
+}
+
+/* clg_digest_spans over a direct buffer: span i = bytes[offs[i], offs[i] + lens[i]); out as
+ * nDigestLogs. */
+JNIEXPORT jint JNICALL FN(nDigestSpans)(JNIEnv* env, jclass cls, jlong e, jobject bytes, jlongArray offs,
+                                        jlongArray lens, jlongArray out) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, offs);
+  clg_digest* d = (clg_digest*)calloc((size_t)n + 1, sizeof(clg_digest));
+  if (!d) return CLG_E_INVALID_ARG;
+  jlong* so = (*env)->GetLongArrayElements(env, offs, NULL);
+  jlong* sl = (*env)->GetLongArrayElements(env, lens, NULL);
+  int s = clg_digest_spans(ENG(e), addr(env, bytes, 0), (const uint64_t*)so, (const uint64_t*)sl, (uint32_t)n,
+                           CLG_MEM_HOST, d);
+  (*env)->ReleaseLongArrayElements(env, lens, sl, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, offs, so, JNI_ABORT);
+  if (s == CLG_OK) (*env)->SetLongArrayRegion(env, out, 0, 2 * n, (const jlong*)d);
+  free(d);
+  return s;
+}
+
 /* clg_log_get_id: out = {vertexId, isMain, irpLower, irpUpper, subpartition, job}. */
 JNIEXPORT jint JNICALL FN(nLogGetId)(JNIEnv* env, jclass cls, jlong e, jint log, jlongArray out) {
   (void)cls;

@@ -92,6 +92,21 @@ public final class ClonosEngine implements AutoCloseable {
 		return applied[0] != 0;
 	}
 
+	/** The digests {hash, len} of getDeterminants(startEpochs[i]) of logs[i], computed on the device
+	 *  (clg_digest_logs): 2 longs per log.  Two logs are equal only when both words are. */
+	public long[] digestLogs(int[] logs, long[] startEpochs) {
+		long[] out = new long[2 * logs.length];
+		check(nDigestLogs(handle, logs, startEpochs, out));
+		return out;
+	}
+
+	/** The same digests of spans of a direct buffer (clg_digest_spans). */
+	public long[] digestSpans(ByteBuffer direct, long[] offs, long[] lens) {
+		long[] out = new long[2 * offs.length];
+		check(nDigestSpans(handle, direct, offs, lens, out));
+		return out;
+	}
+
 	@Override
 	public void close() {
 		nDestroy(handle);
@@ -215,6 +230,10 @@ public final class ClonosEngine implements AutoCloseable {
 	static native int nDecodeHost(long engine, ByteBuffer bytes, int off, int len, ByteBuffer recOff, ByteBuffer tag,
 								  ByteBuffer v0, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff,
 								  ByteBuffer wVarLen, ByteBuffer wSub, long[] result);
+	/** clg_digest_logs: out = {hash, len} of getDeterminants(startEpochs[i]) of logs[i] (2 n longs). */
+	static native int nDigestLogs(long engine, int[] logs, long[] startEpochs, long[] out);
+	/** clg_digest_spans: span i = direct[offs[i], offs[i] + lens[i]); out as nDigestLogs. */
+	static native int nDigestSpans(long engine, ByteBuffer direct, long[] offs, long[] lens, long[] out);
 	/** out = {vertexId, isMain, irpLower, irpUpper, subpartition, job}. */
 	static native int nLogGetId(long engine, int log, long[] out);
 	static native int nEnrichBatch(long engine, int strategy, long[] requests, int[] logs, byte[] flags,

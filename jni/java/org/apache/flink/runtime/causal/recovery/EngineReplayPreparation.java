@@ -68,6 +68,7 @@ public final class EngineReplayPreparation {
 		}
 	}
 
+	private final ClonosEngine engine;
 	private final RecoveryManagerContext context;
 	private final ByteBuffer recOff;
 	private final ByteBuffer tag;
@@ -76,6 +77,7 @@ public final class EngineReplayPreparation {
 
 	public EngineReplayPreparation(ClonosEngine engine, RecoveryManagerContext context,
 								   DeterminantResponseEvent determinantAccumulator) {
+		this.engine = engine;
 		this.context = context;
 		final short vertex = context.getTaskVertexID().getVertexID();
 		final Map<CausalLogID, ByteBuf> dets = determinantAccumulator.getDeterminants();
@@ -142,6 +144,19 @@ public final class EngineReplayPreparation {
 		}
 		return new EngineDecodedLog(log, context.causalLog.getDeterminantEncoder(), recOff, tag, (int) mainResult[0],
 			(int) mainResult[2], (int) mainResult[4]);
+	}
+
+	/**
+	 * Does the main log the replay regenerated (engine log {@code logHandle}, from {@code startEpoch})
+	 * hold the bytes of the recovered one?  LogReplayerImpl.checkFinished (LogReplayerImpl.java:126-128)
+	 * asserts only that the two have the same length, and only under -ea; this compares content, by
+	 * the engine's digest of both (16 bytes each come back).
+	 */
+	public boolean regeneratedLogMatches(ByteBuf recovered, int logHandle, long startEpoch) {
+		final ByteBuffer bytes = direct(recovered);
+		final long[] regenerated = engine.digestLogs(new int[] {logHandle}, new long[] {startEpoch});
+		final long[] expected = engine.digestSpans(bytes, new long[] {0}, new long[] {recovered.readableBytes()});
+		return regenerated[0] == expected[0] && regenerated[1] == expected[1];
 	}
 
 	/** The sizes the recovery thread of (partition, index) builds buffers with. */
