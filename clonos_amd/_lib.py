@@ -63,6 +63,7 @@ EXPORTED = [
     "clg_ifl_replay_batch", "clg_replay_prepare_device", "clg_get_determinants_batch", "clg_response_put_batch",
     "clg_host_register", "clg_host_unregister",
     "clg_digest_logs", "clg_digest_spans", "clg_digest_host",
+    "clg_diff_logs", "clg_lcp_host",
 ]
 
 
@@ -237,6 +238,10 @@ class Digest(C.Structure):  # clg_digest: equal only when both fields are equal
     _fields_ = [("hash", C.c_uint64), ("len", C.c_uint64)]
 
 
+class Diff(C.Structure):  # clg_diff: equal when lcp == len_log == len_ref
+    _fields_ = [("lcp", C.c_uint64), ("len_log", C.c_uint64), ("len_ref", C.c_uint64)]
+
+
 def _load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -317,6 +322,8 @@ def _load() -> C.CDLL:
         "clg_digest_logs": (C.c_int, [P, P, P, C.c_uint32, P]),
         "clg_digest_spans": (C.c_int, [P, P, P, P, C.c_uint32, C.c_uint32, P]),
         "clg_digest_host": (C.c_int, [P, C.c_uint64, C.POINTER(Digest)]),
+        "clg_diff_logs": (C.c_int, [P, P, P, C.c_uint32, P, P, P, C.c_uint32, P]),
+        "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),
         "clg_ifl_close": (C.c_int, [P, C.c_uint32]),

@@ -16,7 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libclonos_engine.so")
 SOURCES = [os.path.join(CSRC, "engine.cpp"), os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "decode_fast.hip"),
            os.path.join(CSRC, "decode_fused.hip"), os.path.join(CSRC, "replay.hip"), os.path.join(CSRC, "encode.hip"),
-           os.path.join(CSRC, "response.cpp"), os.path.join(CSRC, "digest.hip")]
+           os.path.join(CSRC, "response.cpp"), os.path.join(CSRC, "digest.hip"),
+           os.path.join(CSRC, "diff.hip")]
 HEADERS = [
     os.path.join(CSRC, "kernels.h"),
     os.path.join(CSRC, "jser_device.h"),
@@ -25,6 +26,7 @@ HEADERS = [
     os.path.join(CSRC, "jser_flat.h"),
     os.path.join(CSRC, "handoff.h"),
     os.path.join(CSRC, "digest.h"),
+    os.path.join(CSRC, "diff.h"),
     os.path.join(ROOT, "include", "clonos_engine.h"),
 ]
 ARCH = os.environ.get("CLONOS_OFFLOAD_ARCH", "gfx950")

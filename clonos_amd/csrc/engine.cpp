@@ -31,10 +31,12 @@
 #include <vector>
 
 #include "../../include/clonos_engine.h"
+#include "diff.h"
 #include "digest.h"
 #include "kernels.h"
 
 static_assert(sizeof(clg_delta_req) == 32, "clg_delta_req layout");
+static_assert(sizeof(clg_diff) == 24, "clg_diff layout");
 
 namespace {
 
@@ -633,6 +635,8 @@ struct clg_engine {
   DevBuf d_dgtab, d_dgpart, d_dgout;  // log digest: the constant table (uploaded once), partials, results
   PinBuf h_dgout;
   bool dgtab_ready = false;
+  DevBuf d_dffirst, d_dfout;  // log comparison: a word per piece, results
+  PinBuf h_dfout;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 
@@ -3683,6 +3687,81 @@ int clg_digest_spans(clg_engine* e, const uint8_t* bytes, const uint64_t* off, c
 int clg_digest_host(const uint8_t* bytes, uint64_t n, clg_digest* out) {
   if (!out || (n && !bytes)) return fail(CLG_E_INVALID_ARG, "null argument");
   *out = clg_digest{clg::dg_bytes(bytes, n), n};
+  return CLG_OK;
+}
+
+// The longest common prefix of getDeterminants(start_epoch[i]) of log[i] and a reference span
+// (diff.h): the ranges, runs, segment table and pieces as clg_digest_logs builds them, each run
+// with the device address of its reference (host input staged as clg_digest_spans stages it),
+// then a read-only pass over both.  Where LogReplayerImpl.checkFinished
+// (LogReplayerImpl.java:126-128) and the digests say only that two copies part, this says where.
+int clg_diff_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n, const uint8_t* bytes,
+                  const uint64_t* off, const uint64_t* len, uint32_t in_kind, clg_diff* out) {
+  ENGINE_GUARD(e);
+  if (n && (!log || !start_epoch || !off || !len || !out)) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (in_kind != CLG_MEM_HOST && in_kind != CLG_MEM_DEVICE) return fail(CLG_E_INVALID_ARG, "in_kind %u", in_kind);
+  if (!n) return CLG_OK;
+  uint64_t lo = UINT64_MAX, hi = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (len[i] >> 32) return fail(CLG_E_INVALID_ARG, "span %u of %llu bytes", i, (unsigned long long)len[i]);
+    if (len[i] == 0) continue;
+    lo = std::min(lo, off[i]);
+    hi = std::max(hi, off[i] + len[i]);
+  }
+  if (hi && !bytes) return fail(CLG_E_INVALID_ARG, "null argument");
+  std::vector<clg::SegSpan> runs;
+  std::vector<uint32_t> segtab, len_log(n);
+  uint32_t n_pieces = 0;
+  uint64_t total = 0;
+  CHK(e->plan_determinant_runs(log, start_epoch, n, len_log.data(), nullptr, runs, segtab, &n_pieces, &total));
+  for (uint32_t i = 0; i < n; ++i) out[i] = clg_diff{0, len_log[i], len[i]};  // (a request without a run stays so)
+  if (runs.empty()) return CLG_OK;
+  CHK(e->flush());
+  const uint8_t* base = bytes;  // span i starts at base + (off[i] - base_off)
+  uint64_t base_off = 0;
+  if (in_kind == CLG_MEM_HOST && hi) {
+    CHK(e->d_stage.ensure(hi - lo + 16));
+    CHK(e->h_stage.ensure(hi - lo + 16));
+    memcpy(e->h_stage.p, bytes + lo, hi - lo);
+    HIPCHK(hipMemcpyAsync(e->d_stage.p, e->h_stage.p, hi - lo, hipMemcpyHostToDevice, e->stream));
+    base = e->d_stage.as<uint8_t>();
+    base_off = lo;
+  }
+  size_t o[2];
+  const size_t gb = clg_engine::al16(clg_engine::gather_desc_layout(runs, segtab, o));
+  const size_t hb = gb + runs.size() * sizeof(clg::DiffRef);  // runs | segment table | references
+  CHK(e->h_desc.ensure(hb));
+  CHK(e->d_desc.ensure(hb));
+  CHK(e->d_pieces.ensure(size_t(n_pieces) * sizeof(clg::GatherPiece)));
+  clg_engine::gather_desc_fill(e->h_desc.as<uint8_t>(), runs, segtab, o);
+  clg::DiffRef* refs = reinterpret_cast<clg::DiffRef*>(e->h_desc.as<uint8_t>() + gb);
+  uint64_t compared = 0;
+  for (size_t k = 0; k < runs.size(); ++k) {
+    const uint32_t i = runs[k].pad;
+    refs[k] = clg::DiffRef{len[i] ? base + (off[i] - base_off) : nullptr, uint32_t(len[i]), 0};
+    compared += 2 * std::min<uint64_t>(runs[k].len, len[i]);
+  }
+  HIPCHK(hipMemcpyAsync(e->d_desc.p, e->h_desc.p, hb, hipMemcpyHostToDevice, e->stream));
+  CHK(e->gather_expand(e->d_desc.as<uint8_t>(), runs, o, n_pieces, e->d_pieces.as<clg::GatherPiece>(), e->stream));
+  CHK(e->d_dffirst.ensure(size_t(n_pieces) * 4 + 4));
+  CHK(e->d_dfout.ensure(size_t(n) * sizeof(clg_diff)));
+  CHK(e->h_dfout.ensure(size_t(n) * sizeof(clg_diff)));
+  memcpy(e->h_dfout.p, out, size_t(n) * sizeof(clg_diff));
+  HIPCHK(hipMemcpyAsync(e->d_dfout.p, e->h_dfout.p, size_t(n) * sizeof(clg_diff), hipMemcpyHostToDevice, e->stream));
+  CHK(e->timed("log_diff", compared, [&] {
+    return clg::launch_diff(e->d_pieces.as<clg::GatherPiece>(), n_pieces, e->d_desc.as<clg::SegSpan>(),
+                            uint32_t(runs.size()), reinterpret_cast<const clg::DiffRef*>(e->d_desc.as<uint8_t>() + gb),
+                            e->d_dffirst.as<uint32_t>(), e->d_dfout.as<clg_diff>(), e->stream);
+  }));
+  HIPCHK(hipMemcpyAsync(e->h_dfout.p, e->d_dfout.p, size_t(n) * sizeof(clg_diff), hipMemcpyDeviceToHost, e->stream));
+  CHK(e->sync());
+  memcpy(out, e->h_dfout.p, size_t(n) * sizeof(clg_diff));
+  return CLG_OK;
+}
+
+int clg_lcp_host(const uint8_t* a, uint64_t na, const uint8_t* b, uint64_t nb, uint64_t* lcp) {
+  if (!lcp || (na && !a) || (nb && !b)) return fail(CLG_E_INVALID_ARG, "null argument");
+  *lcp = clg::df_lcp_bytes(a, na, b, nb);
   return CLG_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 struct clg_digest;  // include/clonos_engine.h
+struct clg_diff;
 
 namespace clg {
 
@@ -516,6 +517,20 @@ void digest_table(uint64_t* tab);
 // run's partials and writes {hash, len} to d_out[run.pad].
 int launch_digest(const GatherPiece* d_pieces, uint32_t n_pieces, const struct SegSpan* d_runs, uint32_t n_runs,
                   const uint64_t* d_tab, uint64_t* d_partial, ::clg_digest* d_out, void* stream);
+
+// ---- log comparison (diff.h, diff.hip) ---------------------------------------------
+// The reference span of a run (parallel to the runs): its device address and length.
+struct DiffRef {
+  const uint8_t* ref;
+  uint32_t len;
+  uint32_t pad;
+};
+// Longest common prefix of each run and its reference span: pass 1 writes one u32 per piece
+// (pieces as k_expand_pieces produces them), the offset in the piece of its first differing
+// byte inside min(run, reference) or kDiffNone; pass 2 takes a run's minimum and writes
+// {lcp, len_log, len_ref} to d_out[run.pad].
+int launch_diff(const GatherPiece* d_pieces, uint32_t n_pieces, const struct SegSpan* d_runs, uint32_t n_runs,
+                const DiffRef* d_refs, uint32_t* d_first, ::clg_diff* d_out, void* stream);
 
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {

@@ -39,7 +39,8 @@ Verification.  A replica is trusted to equal its owner's log, and a merged winne
 rank measured; the log digest (clg_digest_logs / clg_digest_spans: 16 bytes per log, computed
 where the bytes live) lets the product check both without moving the bytes: Replicator.verify
 compares every replica with its owner at a quiescent point, merge_responses(verify=True) the
-received winners with what their ranks hold.
+received winners with what their ranks hold.  Replicator.locate then says where a flagged
+replica leaves its owner's log (clg_diff_logs on the fetched copy): only the flagged logs move.
 """
 from __future__ import annotations
 
@@ -108,6 +109,34 @@ class VerifyReport:
     @property
     def clean(self) -> bool:
         return not (self.short or self.long or self.differs)
+
+
+@dataclass
+class ReplicaDivergence:
+    """Replicator.locate's answer for one flagged log: where this rank's replica leaves the
+    owner's copy.  Offsets are relative to getDeterminants(start_epoch).  The epoch and record
+    fields are filled where the io offers them (EngineIO does), following
+    replay.locate_divergence's record rule, from the replica's own epoch table."""
+    gid: int
+    offset: int        # bytes the two have in common
+    len_replica: int
+    len_owner: int
+    kind: str          # "differs" | "replica_is_prefix" | "owner_is_prefix" ("equal": flagged, yet no difference)
+    epoch: Optional[int] = None
+    epoch_offset: Optional[int] = None
+    record: Optional[int] = None
+    record_offset: Optional[int] = None
+    replica: object = None  # that record as the replica holds it (determinants.Determinant or None)
+    owner: object = None    # ... and as the owner does
+
+
+class LocateResult(list):
+    """Replicator.locate's list of ReplicaDivergence; `unlocated`: the flagged gids beyond
+    `limit` per owner rank, which were not fetched."""
+
+    def __init__(self, items=(), unlocated=()):
+        super().__init__(items)
+        self.unlocated: List[int] = list(unlocated)
 
 
 class ReplicationPlan:
@@ -181,6 +210,22 @@ class EngineIO:
         if tensor.is_cuda:
             return self.engine.digest_spans(tensor.data_ptr(), offs, lens, device=True)
         return self.engine.digest_spans(tensor.numpy(), offs, lens)
+
+    def diff(self, handles: np.ndarray, start_epochs: np.ndarray, tensor, offs: np.ndarray, lens: np.ndarray
+             ) -> np.ndarray:
+        """DIFF rows of getDeterminants(start_epochs[i]) of handles[i] against
+        tensor[offs[i] : offs[i] + lens[i]] (clg_diff_logs; device input for a tensor in HBM)."""
+        if tensor.is_cuda:
+            return self.engine.diff_logs(handles, start_epochs, tensor.data_ptr(), offs, lens, device=True)
+        return self.engine.diff_logs(handles, start_epochs, tensor.numpy(), offs, lens)
+
+    def locate_records(self, handles, start_epochs, tensor, offs, lens, offsets):
+        """replay.locate_records for logs that part from tensor[offs[i] : offs[i] + lens[i]] at
+        offsets[i]: (epoch, epoch_offset, record, record_offset, the log's determinant, the
+        tensor's) per item.  Only these spans are read back for the decode."""
+        from .replay import locate_records
+        blobs = [tensor[int(o):int(o) + int(n)].cpu().numpy().tobytes() for o, n in zip(offs, lens)]
+        return locate_records(self.engine, handles, start_epochs, blobs, offsets)
 
     # replay-prep merge: a copy is getDeterminants(startEpoch) of a log (owned or replica);
     # both calls are one native call for all the copies (clg_get_determinants_batch)
@@ -376,6 +421,88 @@ class Replicator:
         rep.differs = gid[(mine["len"] == theirs["len"]) & (mine["hash"] != theirs["hash"])].tolist()
         rep.checked = len(have)
         return rep
+
+
+    def locate(self, start_epoch: int, report: VerifyReport, limit: int = 8) -> "LocateResult":
+        """Where do the replicas that `report` (this rank's verify(start_epoch)) flags leave
+        their owners' logs?  Collective: every rank calls it after verify, at the same quiescent
+        point, with the same `limit`.  For up to `limit` flagged gids (short, long, differs) per
+        owner rank, this rank fetches the owner's copy and compares its replica with it where
+        the bytes arrive (io.diff: device input on the engine).  Three all-to-alls, as exchange
+        does it: the requests with static splits (`limit` gid slots per rank pair, padded with
+        -1), the copies' lengths with the same splits, and the payload with the splits the
+        lengths give (owners fill it with io.copy_lengths / io.copy_batch).  Only the flagged
+        logs' bytes move.  Returns a LocateResult: one ReplicaDivergence per fetched gid, and in
+        `unlocated` the flagged gids beyond `limit`, which are reported, never dropped.  With
+        one rank no collective runs."""
+        import torch
+        import torch.distributed as dist
+        plan = self.plan
+        world = plan.world
+        flagged = sorted({int(g) for g in list(report.short) + list(report.long) + list(report.differs)})
+        if world == 1:
+            return LocateResult([], flagged)
+        if limit < 1:
+            raise ValueError("limit must be at least 1")
+        owner = np.array([owner_rank(int(plan.table.vertex[g]), world) for g in flagged], np.int64)
+        ask = np.full((world, limit), -1, np.int64)
+        unlocated: List[int] = []
+        for r in range(world):
+            of_r = [g for g, o in zip(flagged, owner) if o == r]
+            ask[r, :len(of_r[:limit])] = of_r[:limit]
+            unlocated += of_r[limit:]
+        backend = dist.get_backend(self.group)
+        dev = self.device if backend == "nccl" else "cpu"
+        # 1. requests, static splits: asked[r] = the gids rank r wants from this rank
+        asked_t = torch.empty(world * limit, dtype=torch.int64, device=dev)
+        dist.all_to_all_single(asked_t, torch.from_numpy(ask.reshape(-1).copy()).to(dev), group=self.group)
+        asked = asked_t.cpu().numpy().reshape(world, limit)
+        live = asked >= 0
+        gids = asked[live]
+        h = self.handle[gids] if len(gids) else np.zeros(0, np.int64)
+        if len(gids) and (h < 0).any():
+            raise ValueError(f"asked for gids this rank does not send: {gids[h < 0][:8].tolist()}")
+        eps = np.full(len(gids), start_epoch, np.int64)
+        # 2. the copies' lengths, the same splits
+        lens_out = np.zeros((world, limit), np.int64)
+        if len(gids):
+            lens_out[live] = self.io.copy_lengths(h.astype(np.uint32), eps)
+        lens_t = torch.empty(world * limit, dtype=torch.int64, device=dev)
+        dist.all_to_all_single(lens_t, torch.from_numpy(lens_out.reshape(-1).copy()).to(dev), group=self.group)
+        lens_in = lens_t.cpu().numpy().reshape(world, limit)
+        # 3. the payload: the asked copies back to back, by destination then slot
+        bytes_to, bytes_from = lens_out.sum(axis=1), lens_in.sum(axis=1)
+        nsend, nrecv = int(bytes_to.sum()), int(bytes_from.sum())
+        send = torch.empty(nsend + BLOB_ALIGN, dtype=torch.uint8, device=self.device)
+        if len(gids) and self.io.copy_batch(h.astype(np.uint32), eps, send, 0) != nsend:
+            raise RuntimeError("the copies changed between measuring and gathering them (not quiescent)")
+        recv = torch.empty(max(nrecv, 1) + BLOB_ALIGN, dtype=torch.uint8, device=dev)
+        dist.all_to_all_single(recv[:nrecv], _to_comm(send[:nsend], backend), output_split_sizes=bytes_from.tolist(),
+                               input_split_sizes=bytes_to.tolist(), group=self.group)
+        filled = ask >= 0
+        got = ask[filled]
+        if not len(got):
+            return LocateResult([], unlocated)
+        if str(self.device).startswith("cuda") and not recv.is_cuda:  # gloo: into HBM once
+            recv = recv.to(self.device)
+        ln = lens_in[filled].astype(np.uint64)  # (row-major: by owner rank then slot, as the payload lies)
+        offs = np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.uint64)
+        rh = self.replica_handle[got].astype(np.uint32)
+        eps = np.full(len(got), start_epoch, np.int64)
+        rows = self.io.diff(rh, eps, recv, offs, ln)
+        out = LocateResult([], unlocated)
+        for g, r in zip(got.tolist(), rows):
+            lcp, ll, lr = int(r["lcp"]), int(r["len_log"]), int(r["len_ref"])
+            kind = ("differs" if lcp < min(ll, lr) else "replica_is_prefix" if ll < lr else
+                    "owner_is_prefix" if ll > lr else "equal")
+            out.append(ReplicaDivergence(g, lcp, ll, lr, kind))
+        part = [k for k, d in enumerate(out) if d.kind != "equal"]
+        if part and hasattr(self.io, "locate_records"):
+            recs = self.io.locate_records(rh[part], eps[part], recv, offs[part], ln[part], [out[k].offset for k in part])
+            for k, r in zip(part, recs):
+                d = out[k]
+                d.epoch, d.epoch_offset, d.record, d.record_offset, d.replica, d.owner = r
+        return out
 
 
 def rows_sent(rows: np.ndarray) -> int:

@@ -85,32 +85,45 @@ class DecodedBatch:
         raw = self.spans_bytes[s] if self.spans_bytes is not None else None
         sl = self.span_slice(s)
         widx = {int(i): k for k, i in enumerate(self.w_idx)}
-        out: List[D.Determinant] = []
-        for i in range(sl.start, sl.stop):
-            t = int(self.tag[i])
-            v0 = int(self.v0[i])
-            if t == D.ORDER:
-                out.append(D.OrderDeterminant(v0))
-            elif t == D.TIMESTAMP:
-                out.append(D.TimestampDeterminant(v0))
-            elif t == D.RNG:
-                out.append(D.RNGDeterminant(v0))
-            elif t == D.BUFFER_BUILT:
-                out.append(D.BufferBuiltDeterminant(v0))
-            else:
-                k = widx[i]
-                rc, v1, vo, vl, sub = (int(self.w_rc[k]), int(self.w_v1[k]), int(self.w_var_off[k]),
-                                       int(self.w_var_len[k]), int(self.w_sub[k]))
-                var = bytes(raw[vo:vo + vl]) if raw is not None and vo else None
-                if t == D.IGNORE_CHECKPOINT:
-                    out.append(D.IgnoreCheckpointDeterminant(rc, v0))
-                elif t == D.TIMER_TRIGGER:
-                    out.append(D.TimerTriggerDeterminant(rc, v0, sub, var if sub == D.INTERNAL else None))
-                elif t == D.SOURCE_CHECKPOINT:
-                    out.append(D.SourceCheckpointDeterminant(rc, v0, v1, sub & 0x7F, var if sub & 0x80 else None))
-                elif t == D.SERIALIZABLE:
-                    out.append(D.SerializableDeterminant(var if var is not None else b""))
-        return out
+        var = (lambda vo, vl: bytes(raw[vo:vo + vl])) if raw is not None else None
+        return [self._determinant(i, widx.get(i), var) for i in range(sl.start, sl.stop)]
+
+    def determinant_at(self, s: int, k: int, var=None) -> D.Determinant:
+        """Record k of span s alone.  var(off, len) returns span-relative bytes of the span (a
+        name, storage reference or java stream); None: from spans_bytes when the batch kept them."""
+        i = int(self.span_rec_base[s]) + k
+        if not 0 <= k < int(self.span_rec_base[s + 1]) - int(self.span_rec_base[s]):
+            raise IndexError("record index outside the span")
+        if var is None and self.spans_bytes is not None:
+            raw = self.spans_bytes[s]
+            var = lambda vo, vl: bytes(raw[vo:vo + vl])
+        w = int(np.searchsorted(self.w_idx, i))  # w_idx ascends: global record indices in record order
+        return self._determinant(i, w if w < len(self.w_idx) and int(self.w_idx[w]) == i else None, var)
+
+    def _determinant(self, i: int, k: Optional[int], var) -> D.Determinant:
+        """Record i (global index); k: its side-table row when it is wide."""
+        t = int(self.tag[i])
+        v0 = int(self.v0[i])
+        if t == D.ORDER:
+            return D.OrderDeterminant(v0)
+        if t == D.TIMESTAMP:
+            return D.TimestampDeterminant(v0)
+        if t == D.RNG:
+            return D.RNGDeterminant(v0)
+        if t == D.BUFFER_BUILT:
+            return D.BufferBuiltDeterminant(v0)
+        rc, v1, vo, vl, sub = (int(self.w_rc[k]), int(self.w_v1[k]), int(self.w_var_off[k]),
+                               int(self.w_var_len[k]), int(self.w_sub[k]))
+        b = var(vo, vl) if var is not None and vo else None
+        if t == D.IGNORE_CHECKPOINT:
+            return D.IgnoreCheckpointDeterminant(rc, v0)
+        if t == D.TIMER_TRIGGER:
+            return D.TimerTriggerDeterminant(rc, v0, sub, b if sub == D.INTERNAL else None)
+        if t == D.SOURCE_CHECKPOINT:
+            return D.SourceCheckpointDeterminant(rc, v0, v1, sub & 0x7F, b if sub & 0x80 else None)
+        if t == D.SERIALIZABLE:
+            return D.SerializableDeterminant(b if b is not None else b"")
+        raise ValueError(f"tag {t} in a decoded batch")
 
 
 # clg_digest rows: two spans are equal only when both fields are equal
@@ -125,6 +138,22 @@ def digest_host(data: Union[bytes, np.ndarray]) -> Tuple[int, int]:
     d = _lib.Digest()
     check(lib.clg_digest_host(buf.ctypes.data if buf.size else None, buf.size, C.byref(d)))
     return int(d.hash), int(d.len)
+
+
+# clg_diff rows: equal when lcp == len_log == len_ref; one a prefix of the other when
+# lcp == min(len_log, len_ref) and the lengths differ; otherwise lcp is the first differing byte
+DIFF = np.dtype([("lcp", np.uint64), ("len_log", np.uint64), ("len_ref", np.uint64)])
+
+
+def lcp_host(a: Union[bytes, np.ndarray], b: Union[bytes, np.ndarray]) -> int:
+    """clg_lcp_host: the number of leading bytes a and b have in common, on the CPU (no engine,
+    no GPU) -- what Engine.diff_logs computes on the device."""
+    ba, bb = (x if isinstance(x, np.ndarray) else np.frombuffer(bytes(x), np.uint8) for x in (a, b))
+    ba, bb = np.ascontiguousarray(ba, np.uint8), np.ascontiguousarray(bb, np.uint8)
+    out = C.c_uint64(0)
+    check(lib.clg_lcp_host(ba.ctypes.data if ba.size else None, ba.size, bb.ctypes.data if bb.size else None, bb.size,
+                           C.byref(out)))
+    return int(out.value)
 
 
 def _np_ptr(a: np.ndarray) -> int:
@@ -689,6 +718,33 @@ class Engine:
                 raise ValueError("span outside the data")
             ptr, kind = (keep.ctypes.data if keep.size else None), _lib.CLG_MEM_HOST
         check(lib.clg_digest_spans(self._h, ptr, _np_ptr(so), _np_ptr(sl), so.size, kind, _np_ptr(out)))
+        return out
+
+    # ---- log comparison (clg_diff_logs) -------------------------------------------------------
+    def diff_logs(self, handles, start_epochs, data_or_ptr, offs, lens, device: bool = False) -> np.ndarray:
+        """Longest common prefix of getDeterminants(start_epochs[i]) of log handles[i] and the
+        reference span i = bytes[offs[i], offs[i] + lens[i]) of host bytes (bytes / uint8 array)
+        or, with device=True, of device memory at the address data_or_ptr: a DIFF row
+        (lcp, len_log, len_ref) per request (24 bytes each come back).  Handles may repeat."""
+        h = np.ascontiguousarray(handles, np.uint32)
+        ep = np.ascontiguousarray(start_epochs, np.int64)
+        so = np.ascontiguousarray(offs, np.uint64)
+        sl = np.ascontiguousarray(lens, np.uint64)
+        if h.ndim != 1 or not (h.shape == ep.shape == so.shape == sl.shape):
+            raise ValueError("handles, start_epochs, offs and lens must be 1-d and of equal length")
+        out = np.zeros(h.size, DIFF)
+        if not h.size:
+            return out
+        if device:
+            ptr, kind, keep = int(data_or_ptr), _lib.CLG_MEM_DEVICE, None
+        else:
+            keep = (np.ascontiguousarray(data_or_ptr, np.uint8) if isinstance(data_or_ptr, np.ndarray)
+                    else np.frombuffer(bytes(data_or_ptr), np.uint8))
+            if int((so + sl).max()) > keep.size:
+                raise ValueError("span outside the data")
+            ptr, kind = (keep.ctypes.data if keep.size else None), _lib.CLG_MEM_HOST
+        check(lib.clg_diff_logs(self._h, _np_ptr(h), _np_ptr(ep), h.size, ptr, _np_ptr(so), _np_ptr(sl), kind,
+                                _np_ptr(out)))
         return out
 
     # ---- instrumentation ---------------------------------------------------------------------

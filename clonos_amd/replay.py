@@ -26,7 +26,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .engine import CausalLogID, DecodedBatch, Engine, _np_ptr
+from . import determinants as D
+from .engine import CausalLogID, DecodedBatch, Engine, ThreadCausalLog, _np_ptr
 
 
 # numpy views of the C structs (include/clonos_engine.h)
@@ -351,15 +352,160 @@ def prepare_replay(engine: Engine, jobs: Sequence[Tuple[int, DeterminantResponse
 
 # ---- replay verification -----------------------------------------------------------------
 @dataclass
+class Divergence:
+    """Where a regenerated log leaves its recovered copy (locate_divergence).  Offsets are
+    relative to the start of the compared range, getDeterminants(start_epoch) of the log."""
+    offset: int                   # bytes the two have in common (clg_diff.lcp)
+    kind: str                     # "differs" | "log_is_prefix" | "recovered_is_prefix"
+    epoch: Optional[int]          # the last epoch of the log's range that starts at or before `offset`
+    epoch_offset: Optional[int]   # ... and the offset inside it (None: the log has no epoch)
+    record: Optional[int]         # index of the record that holds the byte (None: no record on either side)
+    record_offset: Optional[int]  # ... and where it starts in the range
+    regenerated: Optional[D.Determinant]  # that record as the log holds it; None: the log ended
+    recovered: Optional[D.Determinant]    # before it, or its decode stopped at or before it
+
+
+@dataclass
 class ReplayCheck:
     """verify_replay's answer for one item: `matches` only when both fields of the two digests
     (hash, len) are equal."""
     matches: bool
     regenerated: Tuple[int, int]  # digest of getDeterminants(start_epoch) of the regenerated log
     recovered: Tuple[int, int]    # digest of the recovered copy
+    divergence: Optional[Divergence] = None  # verify_replay(locate=True), when the two do not match
 
 
-def verify_replay(engine: Engine, items: Sequence[Tuple[int, int, bytes]]) -> List[ReplayCheck]:
+# the statuses with which a decode stops at a record (clg_decoded.err_off names it)
+_DECODE_STOPS = (_lib.CLG_E_CORRUPT_TAG, _lib.CLG_E_TRUNCATED, _lib.CLG_E_BAD_ENUM, _lib.CLG_E_NEG_LEN,
+                 _lib.CLG_E_BAD_SERIAL)
+
+
+def range_epochs(log: ThreadCausalLog, start_epoch: int) -> Tuple[int, List[Tuple[int, int]]]:
+    """The physical start of getDeterminants(start_epoch) of `log` and the epochs of that range
+    as (epoch id, offset in the range), from the log's own epoch table (an absent epoch starts
+    the range at the earliest one, as clg_get_determinants does)."""
+    eps = log.state()["epochs"]
+    if not eps:
+        return 0, []
+    at = [k for k, (e, _) in enumerate(eps) if e == start_epoch]
+    k0 = at[0] if at else 0
+    s = eps[k0][1]
+    return s, [(int(e), int(o) - s) for e, o in eps[k0:]]
+
+
+def _decode_clipped(decode, n: int):
+    """decode(clip) with clip[i] = None (the whole of item i) or a length; an item at which the
+    decode stops is clipped to the bytes before its failing record and the batch decoded again
+    (one more call per such item, none for clean input).  Returns (batch, clip)."""
+    clip: List[Optional[int]] = [None] * n
+    while True:
+        try:
+            return decode(clip), clip
+        except _lib.ClonosError as x:
+            if x.status not in _DECODE_STOPS or not hasattr(x, "err_span"):
+                raise
+            clip[x.err_span] = int(x.err_off)
+
+
+def locate_records(engine: Engine, handles, start_epochs, blobs: Sequence[bytes], offsets: Sequence[int]):
+    """The record rule of locate_divergence for items that are known to diverge at range offset
+    offsets[i]: per item (epoch, epoch_offset, record, record_offset, log's determinant, the
+    bytes' determinant).  Both sides go through the batched decode, one call each for all items
+    (decode_logs over the pool, decode_host over the given bytes).  k_side = that side's decoded
+    records with off <= offset; record = max(k_log, k_bytes) - 1; a side's determinant is its
+    record at that index when it has one.  The records before it are byte-identical on both
+    sides, so both agree on its start."""
+    n = len(handles)
+    if not n:
+        return []
+    logs = [ThreadCausalLog(engine, int(h), None) for h in handles]
+    epochs = [int(e) for e in start_epochs]
+    ranges = [range_epochs(l, e) for l, e in zip(logs, epochs)]
+    blobs = [bytes(b) for b in blobs]
+
+    # a log whose decode stops is decoded from the host, from its bytes before the failing record
+    moved: Dict[int, bytes] = {}
+
+    keep, dec_l = list(range(n)), None
+    while keep:
+        try:
+            dec_l = engine.decode_logs([logs[i] for i in keep], [epochs[i] for i in keep])
+            break
+        except _lib.ClonosError as x:
+            if x.status not in _DECODE_STOPS or not hasattr(x, "err_span"):
+                raise
+            i = keep.pop(x.err_span)  # (one more call per such log, none for clean input)
+            moved[i] = logs[i].read_phys(ranges[i][0], int(x.err_off)) if x.err_off else b""
+    span_l = {i: k for k, i in enumerate(keep)}
+    extra = sorted(moved)
+    host = blobs + [moved[i] for i in extra]
+    lens = [len(b) for b in host]
+    starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if host else []
+    joined = b"".join(host)
+
+    def decode_h(clip):
+        return engine.decode_host(joined, [(int(o), ln if c is None else c) for o, ln, c in zip(starts, lens, clip)])
+
+    dec_h, _ = _decode_clipped(decode_h, len(host))
+    span_m = {i: n + k for k, i in enumerate(extra)}
+
+    out = []
+    for i in range(n):
+        off = int(offsets[i])
+        s_phys, eps = ranges[i]
+        # the log's side: its own span of the pool decode, or of the host decode when it was moved
+        if i in span_l:
+            bl, sl = dec_l, span_l[i]
+            var_l = (lambda vo, vl, i=i, s=s_phys: logs[i].read_phys(s + vo, vl))
+        else:
+            bl, sl = dec_h, span_m[i]
+            var_l = (lambda vo, vl, b=moved[i]: b[vo:vo + vl])
+        off_l = np.asarray(bl.off[bl.span_slice(sl)])
+        off_r = np.asarray(dec_h.off[dec_h.span_slice(i)])
+        k_l = int(np.searchsorted(off_l, off, side="right"))
+        k_r = int(np.searchsorted(off_r, off, side="right"))
+        rec = max(k_l, k_r) - 1
+        ep = [(e, o) for e, o in eps if o <= off]
+        epoch, epoch_off = (ep[-1][0], off - ep[-1][1]) if ep else (None, None)
+        if rec < 0:
+            out.append((epoch, epoch_off, None, None, None, None))
+            continue
+        d_l = bl.determinant_at(sl, rec, var_l) if rec < len(off_l) else None
+        d_r = dec_h.determinant_at(i, rec, lambda vo, vl, b=blobs[i]: b[vo:vo + vl]) if rec < len(off_r) else None
+        rec_off = int(off_l[rec]) if rec < len(off_l) else int(off_r[rec])
+        out.append((epoch, epoch_off, rec, rec_off, d_l, d_r))
+    return out
+
+
+def locate_divergence(engine: Engine, items: Sequence[Tuple[int, int, bytes]]) -> List[Optional[Divergence]]:
+    """Where does each regenerated log leave its recovered copy?  Items as verify_replay's:
+    (log handle, start_epoch, recovered bytes).  None for an item whose two sides are equal,
+    else a Divergence: the first differing byte (clg_diff_logs compares the log where it lies
+    with the recovered bytes, 24 bytes per item come back), whether one side is a prefix of the
+    other, the epoch (from the log's own epoch table: the recovered bytes carry none), and the
+    record that holds the byte, decoded on each side.  Only divergent items are decoded: the
+    logs with one decode_logs and the recovered bytes with one decode_host for all of them.  A
+    replay that diverged logged some nondeterminism differently: the two determinants say which."""
+    n = len(items)
+    if not n:
+        return []
+    handles = np.array([it[0] for it in items], np.uint32)
+    epochs = np.array([it[1] for it in items], np.int64)
+    blobs = [bytes(it[2]) for it in items]
+    lens = np.array([len(b) for b in blobs], np.uint64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    rows = engine.diff_logs(handles, epochs, b"".join(blobs), offs, lens)
+    out: List[Optional[Divergence]] = [None] * n
+    bad = [i for i in range(n) if not int(rows[i]["lcp"]) == int(rows[i]["len_log"]) == int(rows[i]["len_ref"])]
+    recs = locate_records(engine, handles[bad], epochs[bad], [blobs[i] for i in bad], [int(rows[i]["lcp"]) for i in bad])
+    for i, r in zip(bad, recs):
+        lcp, ll, lr = (int(rows[i][f]) for f in ("lcp", "len_log", "len_ref"))
+        kind = "differs" if lcp < min(ll, lr) else ("log_is_prefix" if ll < lr else "recovered_is_prefix")
+        out[i] = Divergence(lcp, kind, *r)
+    return out
+
+
+def verify_replay(engine: Engine, items: Sequence[Tuple[int, int, bytes]], locate: bool = False) -> List[ReplayCheck]:
     """Does each regenerated log equal its recovered copy?  An item is (log handle,
     start_epoch, recovered bytes): the log as the replay re-appended it, and the response bytes
     the replay was fed from.  LogReplayerImpl.checkFinished (LogReplayerImpl.java:126-128)
@@ -368,7 +514,10 @@ def verify_replay(engine: Engine, items: Sequence[Tuple[int, int, bytes]]) -> Li
     (clg_digest_logs over the segment pool, clg_digest_spans over the recovered bytes) and
     compared by content.
 
-    To find the first divergent epoch, digest the suffixes from each epoch in one batch:
+    locate=True: each item that does not match also carries where the two part
+    (ReplayCheck.divergence, from locate_divergence over those items alone).
+
+    To find the first divergent epoch without it, digest the suffixes from each epoch in one batch:
     items [(h, e, recovered[start_of(e):]) for e in epochs] -- the suffixes from the epochs
     after the divergence match, so the last epoch whose suffix does not is where it diverged."""
     n = len(items)
@@ -385,4 +534,8 @@ def verify_replay(engine: Engine, items: Sequence[Tuple[int, int, bytes]]) -> Li
     for a, b in zip(regen, recov):
         ra, rb = (int(a["hash"]), int(a["len"])), (int(b["hash"]), int(b["len"]))
         out.append(ReplayCheck(ra == rb, ra, rb))
+    if locate:
+        bad = [i for i, c in enumerate(out) if not c.matches]
+        for i, d in zip(bad, locate_divergence(engine, [items[i] for i in bad])):
+            out[i].divergence = d
     return out

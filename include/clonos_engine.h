@@ -507,6 +507,36 @@ int clg_digest_spans(clg_engine* e, const uint8_t* bytes, const uint64_t* off, c
 /* The same digest of host bytes on the CPU (no engine, no GPU). */
 int clg_digest_host(const uint8_t* bytes, uint64_t n, clg_digest* out);
 
+/* ---- log comparison ---------------------------------------------------------------------------
+ * Where two copies of a log part, not only whether they do.  lcp is the number of leading bytes
+ * the log range and the reference span have in common, lcp <= min(len_log, len_ref):
+ *   equal                         lcp == len_log == len_ref
+ *   one is a prefix of the other  lcp == min(len_log, len_ref) and the lengths differ
+ *   differ                        lcp is the offset of the first differing byte in the range */
+typedef struct clg_diff {
+  uint64_t lcp;
+  uint64_t len_log;
+  uint64_t len_ref;
+} clg_diff;
+/* For each i < n: compare getDeterminants(start_epoch[i]) of log[i] with the reference span
+ * bytes[off[i], off[i] + len[i]) of host or device memory (in_kind CLG_MEM_HOST /
+ * CLG_MEM_DEVICE), one read-only pass over both where they lie; only n * 24 bytes come back.
+ * The range rules are clg_digest_logs' (depth-0 log and empty range: len_log 0; unknown handle:
+ * CLG_E_NO_LOG; absent epoch: from the earliest), staged appends are flushed first, requests
+ * may repeat a log and come in any order.  A reference span of 2^32 bytes or more is
+ * CLG_E_INVALID_ARG.  Host input is staged as clg_digest_spans stages it.  Device input is read
+ * in aligned 16-byte words, only those that hold a byte of a span (and of a span only the
+ * first min(len_log, len_ref) bytes): the caller's buffer need not be padded or aligned.
+ * After a failed length check (LogReplayerImpl.checkFinished, LogReplayerImpl.java:126-128) or
+ * a failed digest comparison this names the byte at which the regenerated log left the
+ * recovered one; and where DeterminantResponseEvent.merge (DeterminantResponseEvent.java:137-146)
+ * keeps the longer copy on its length alone, it says whether the shorter one is a prefix of it
+ * (a copy that lags) or not (a corrupt one). */
+int clg_diff_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n, const uint8_t* bytes,
+                  const uint64_t* off, const uint64_t* len, uint32_t in_kind, clg_diff* out);
+/* The same of two host byte strings on the CPU (no engine, no GPU). */
+int clg_lcp_host(const uint8_t* a, uint64_t na, const uint8_t* b, uint64_t nb, uint64_t* lcp);
+
 /* ---- in-flight (data) log (RT/inflightlogging/, I/ below) -------------------------------------
  * InFlightLog I/InFlightLog.java:32-55, two implementations (I/InFlightLogConfig.java:44 picks
  * one by taskmanager.inflight.type, default "spillable"):

@@ -334,6 +334,32 @@ JNIEXPORT jint JNICALL FN(nDigestSpans)(JNIEnv* env, jclass cls, jlong e, jobjec
   return s;
 }
 
+/* clg_diff_logs over a direct buffer: getDeterminants(starts[i]) of logs[i] against
+ * bytes[offs[i], offs[i] + lens[i]); out = {lcp, lenLog, lenRef} per request (3 n longs). */
+JNIEXPORT jint JNICALL FN(nDiffLogs)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray starts, jobject bytes,
+                                     jlongArray offs, jlongArray lens, jlongArray out) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  if ((*env)->GetArrayLength(env, starts) < n || (*env)->GetArrayLength(env, offs) < n ||
+      (*env)->GetArrayLength(env, lens) < n || (*env)->GetArrayLength(env, out) < 3 * n)
+    return CLG_E_INVALID_ARG;
+  clg_diff* d = (clg_diff*)calloc((size_t)n + 1, sizeof(clg_diff));
+  if (!d) return CLG_E_INVALID_ARG;
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* st = (*env)->GetLongArrayElements(env, starts, NULL);
+  jlong* so = (*env)->GetLongArrayElements(env, offs, NULL);
+  jlong* sl = (*env)->GetLongArrayElements(env, lens, NULL);
+  int s = clg_diff_logs(ENG(e), (const uint32_t*)lg, (const int64_t*)st, (uint32_t)n, addr(env, bytes, 0),
+                        (const uint64_t*)so, (const uint64_t*)sl, CLG_MEM_HOST, d);
+  (*env)->ReleaseLongArrayElements(env, lens, sl, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, offs, so, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, starts, st, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  if (s == CLG_OK) (*env)->SetLongArrayRegion(env, out, 0, 3 * n, (const jlong*)d);
+  free(d);
+  return s;
+}
+
 /* clg_log_get_id: out = {vertexId, isMain, irpLower, irpUpper, subpartition, job}. */
 JNIEXPORT jint JNICALL FN(nLogGetId)(JNIEnv* env, jclass cls, jlong e, jint log, jlongArray out) {
   (void)cls;

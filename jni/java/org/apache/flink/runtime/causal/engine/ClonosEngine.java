@@ -107,6 +107,15 @@ public final class ClonosEngine implements AutoCloseable {
 		return out;
 	}
 
+	/** Where getDeterminants(startEpochs[i]) of logs[i] leaves span i = direct[offs[i], offs[i] + lens[i])
+	 *  (clg_diff_logs): 3 longs per log, {lcp, lenLog, lenRef}.  lcp is the number of leading bytes the
+	 *  two have in common; they are equal when all three words are. */
+	public long[] diffLogs(int[] logs, long[] startEpochs, ByteBuffer direct, long[] offs, long[] lens) {
+		long[] out = new long[3 * logs.length];
+		check(nDiffLogs(handle, logs, startEpochs, direct, offs, lens, out));
+		return out;
+	}
+
 	@Override
 	public void close() {
 		nDestroy(handle);
@@ -234,6 +243,10 @@ public final class ClonosEngine implements AutoCloseable {
 	static native int nDigestLogs(long engine, int[] logs, long[] startEpochs, long[] out);
 	/** clg_digest_spans: span i = direct[offs[i], offs[i] + lens[i]); out as nDigestLogs. */
 	static native int nDigestSpans(long engine, ByteBuffer direct, long[] offs, long[] lens, long[] out);
+	/** clg_diff_logs: out = {lcp, lenLog, lenRef} of logs[i] from startEpochs[i] against
+	 *  direct[offs[i], offs[i] + lens[i]) (3 n longs). */
+	static native int nDiffLogs(long engine, int[] logs, long[] startEpochs, ByteBuffer direct, long[] offs, long[] lens,
+								long[] out);
 	/** out = {vertexId, isMain, irpLower, irpUpper, subpartition, job}. */
 	static native int nLogGetId(long engine, int log, long[] out);
 	static native int nEnrichBatch(long engine, int strategy, long[] requests, int[] logs, byte[] flags,

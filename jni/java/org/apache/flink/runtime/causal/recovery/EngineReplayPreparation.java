@@ -159,6 +159,22 @@ public final class EngineReplayPreparation {
 		return regenerated[0] == expected[0] && regenerated[1] == expected[1];
 	}
 
+	/**
+	 * Where does the regenerated main log (engine log {@code logHandle}, from {@code startEpoch}) leave
+	 * the recovered one?  The offset of the first byte in which the two differ, counted from the start
+	 * of that range; when one is a prefix of the other, the shorter one's length; -1 when they are equal.
+	 * After {@link #regeneratedLogMatches} (or checkFinished's length assertion,
+	 * LogReplayerImpl.java:126-128) has failed this is the next question: the determinant at that offset
+	 * is the nondeterminism that was not logged.  The log is compared where it lies in HBM
+	 * (clg_diff_logs); 24 bytes come back.
+	 */
+	public long firstDivergence(int logHandle, long startEpoch, ByteBuf recovered) {
+		final ByteBuffer bytes = direct(recovered);
+		final long[] d = engine.diffLogs(new int[] {logHandle}, new long[] {startEpoch}, bytes, new long[] {0},
+			new long[] {recovered.readableBytes()});
+		return d[0] == d[1] && d[1] == d[2] ? -1 : d[0];
+	}
+
 	/** The sizes the recovery thread of (partition, index) builds buffers with. */
 	public SubpartitionSizes sizes(IntermediateResultPartitionID partition, int index) {
 		final Map<Integer, SubpartitionSizes> m = bySubpartition.get(partition);
