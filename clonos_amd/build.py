@@ -25,6 +25,7 @@ HEADERS = [
     os.path.join(CSRC, "dev_slow.h"),
     os.path.join(CSRC, "jser_flat.h"),
     os.path.join(CSRC, "handoff.h"),
+    os.path.join(CSRC, "slice_order.h"),
     os.path.join(CSRC, "digest.h"),
     os.path.join(CSRC, "diff.h"),
     os.path.join(ROOT, "include", "clonos_engine.h"),

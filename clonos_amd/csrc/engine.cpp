@@ -34,6 +34,7 @@
 #include "diff.h"
 #include "digest.h"
 #include "kernels.h"
+#include "slice_order.h"
 
 static_assert(sizeof(clg_delta_req) == 32, "clg_delta_req layout");
 static_assert(sizeof(clg_diff) == 24, "clg_diff layout");
@@ -543,6 +544,8 @@ struct DevSwitches {
   // initial spill arena bytes (tests: force its growth); 0: the default
   size_t jser_arena = getenv("CLONOS_JSER_ARENA") ? std::max<size_t>(256, size_t(env_num("CLONOS_JSER_ARENA", 0, 0))) : 0;
   int gather_prio = int(env_num("CLONOS_GATHER_PRIO", 1));     // the streams' priorities (clg_engine_create)
+  // the batched slice's dispatch window in segments (slice_order.h; 0: request order, -1: the default)
+  long long gather_window = env_num("CLONOS_GATHER_WINDOW", -1);
   int host_threads = int(env_num("CLONOS_HOST_THREADS", 16));  // host threads for the per-log loops
   int lean = int(env_num("CLONOS_LEAN", -1));  // 0/1: the count pass's lean walk forced off / on (-1: by the hint)
   int warm = int(env_num("CLONOS_WARM", -1));  // speculative warm-up bytes (-1: the default, spec_warm)
@@ -1233,7 +1236,13 @@ struct clg_engine {
   // log segment copying it for every consumer of that log (each segment read from HBM once):
   // in the config-2 step the gather fell from 0.68 to 0.54 ms but the decode beside it rose
   // from 0.62 to 0.75 and the step from 0.732 to 0.786 ms; isolated 0.46 against 0.39 ms.
-  // The re-reads are not what bounds the step.)
+  // Kept: the same pieces with a log's consumers ordered window by window (slice_order.h),
+  // k_gather as it is.  At 128 segments per window the gather fetches 0.32 GB per launch
+  // instead of 0.84, the 0.31 GB minimum nearly, with the writes unchanged; alone it still
+  // takes 0.39 ms, so the re-reads are not what bounds the gather itself, which writes 1.4 GB
+  // in that time whatever it reads; in the step, beside the decode's traffic, they cost about
+  // 2 % (0.723 against 0.737 ms).  Windows of 16 segments and fewer fetch as little and are
+  // slower alone (0.41, 0.43 ms): DESIGN.md section 7, "A windowed order".)
   static size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
   static size_t gather_desc_layout(const std::vector<clg::SegSpan>& runs, const std::vector<uint32_t>& segtab,
                                    size_t o[2]) {
@@ -3821,6 +3830,9 @@ int clg_slice_batch(clg_engine* e, const clg_slice_req* reqs, uint32_t n, clg_sl
     dst += uint64_t(nb);
   }
   if (total) *total = dst;
+  // dispatch order only: the same pieces, n_pieces as it was
+  const long long gw = e->sw.gather_window;
+  clg::window_order(runs, C, gw < 0 ? clg::default_window(C) : uint32_t(std::min<long long>(gw, UINT32_MAX)));
   return e->run_gather_runs(runs, segtab, n_pieces, dst, out, out_kind);
 }
 

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "slice_order.h"
+
 struct clg_digest;  // include/clonos_engine.h
 struct clg_diff;
 
@@ -545,15 +547,8 @@ struct ScatterChunk {
 // A run of a log's physical bytes.  Its gather pieces (one per segment it touches) or
 // decode tiles (one per min(segment, kTile) window) are generated on the device from the
 // log's segment-index table, uploaded once per call as one concatenated array, so host
-// work per call is O(requests + logs), not O(segments).
-struct SegSpan {
-  uint64_t segtab_off;  // first entry of the log's segment indices in the call's table
-  uint32_t phys;        // first physical byte of the run
-  uint32_t len;
-  uint64_t dst;         // gather: output offset of the run; decode: span index
-  uint32_t first;       // first piece / tile generated for the run
-  uint32_t pad;
-};
+// work per call is O(requests + logs), not O(segments).  (struct SegSpan: slice_order.h,
+// with the order of a batched slice's runs.)
 // Launch helpers' status: CLG_OK, or CLG_E_DEVICE with the HIP error kept (thread-local)
 // for the engine's error text (take_launch_error, nullptr when none).
 int launch_status(hipError_t e);

@@ -13,7 +13,7 @@ else
   git -C "$root" archive "$rev" clonos_amd include | tar -x -C "$src"
 fi
 objs=()
-for f in engine.cpp kernels.hip decode_fast.hip decode_fused.hip replay.hip encode.hip response.cpp; do
+for f in engine.cpp kernels.hip decode_fast.hip decode_fused.hip replay.hip encode.hip response.cpp digest.hip diff.hip; do
   o=/tmp/ab_${name}_$f.o
   /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w ${AB_DEFS:-} -I "$src/include" -c "$src/clonos_amd/csrc/$f" -o "$o" &
   objs+=("$o")
