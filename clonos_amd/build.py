@@ -1,8 +1,9 @@
 """Build libclonos_engine.so (gfx950) in-tree with hipcc.
 
 The shared library is the product: the C-ABI in include/clonos_engine.h plus the HIP
-kernels.  It is built in-tree so that it travels with the repository snapshot to the GPU
-box (git-ignored, not gpurun-ignored).
+kernels.  Every *.cpp and *.hip in csrc/ is compiled, one compile per source, and every *.h
+there is a dependency of all of them.  The library is built in-tree (git-ignored), so that it
+travels with a snapshot of the repository.
 """
 from __future__ import annotations
 
@@ -14,22 +15,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libclonos_engine.so")
-SOURCES = [os.path.join(CSRC, "engine.cpp"), os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "decode_fast.hip"),
-           os.path.join(CSRC, "decode_fused.hip"), os.path.join(CSRC, "replay.hip"), os.path.join(CSRC, "encode.hip"),
-           os.path.join(CSRC, "response.cpp"), os.path.join(CSRC, "digest.hip"),
-           os.path.join(CSRC, "diff.hip")]
-HEADERS = [
-    os.path.join(CSRC, "kernels.h"),
-    os.path.join(CSRC, "jser_device.h"),
-    os.path.join(CSRC, "dev_common.h"),
-    os.path.join(CSRC, "dev_slow.h"),
-    os.path.join(CSRC, "jser_flat.h"),
-    os.path.join(CSRC, "handoff.h"),
-    os.path.join(CSRC, "slice_order.h"),
-    os.path.join(CSRC, "digest.h"),
-    os.path.join(CSRC, "diff.h"),
-    os.path.join(ROOT, "include", "clonos_engine.h"),
-]
+# every source and header in csrc/ (sorted), so a new file cannot be forgotten
+SOURCES = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".cpp", ".hip")))
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
+    os.path.join(ROOT, "include", "clonos_engine.h")]
 ARCH = os.environ.get("CLONOS_OFFLOAD_ARCH", "gfx950")
 
 

@@ -4,7 +4,7 @@
 // metadata with exactly the reference's semantics, host staging of appends, and the
 // batching of all byte work into gfx950 kernels (kernels.hip) on one HIP stream.
 //
-// R/ = /root/reference/flink-runtime/src/main/java/org/apache/flink/runtime/causal/.
+// R/ = flink-runtime/src/main/java/org/apache/flink/runtime/causal/ of the reference.
 // The log metadata mirrors R/log/thread/ThreadCausalLogImpl.java:51-527 line for line in
 // behaviour (EpochStartOffset objects shared by reference with ConsumerOffset, Netty
 // component-granular discardReadComponents), but the bytes never leave HBM.
@@ -33,11 +33,14 @@
 #include "../../include/clonos_engine.h"
 #include "diff.h"
 #include "digest.h"
+#include "engine_host.h"
 #include "kernels.h"
 #include "slice_order.h"
 
 static_assert(sizeof(clg_delta_req) == 32, "clg_delta_req layout");
 static_assert(sizeof(clg_diff) == 24, "clg_diff layout");
+
+using namespace clg_internal;  // the host-only types (engine_host.h)
 
 namespace {
 
@@ -71,261 +74,6 @@ void note_launch_error(const char* what) {
       return r_;                                        \
     }                                                   \
   } while (0)
-
-struct EpochStart {
-  int64_t id;
-  int32_t offset;
-};
-struct Consumer {
-  std::shared_ptr<EpochStart> es;  // ConsumerOffset.epochStart (a reference, may go stale)
-  int32_t offset;
-};
-
-// EpochStart objects (with their shared_ptr control blocks) come from a per-thread free
-// list: a config-4 step opens an epoch in, and truncates one out of, each of 66 k logs.
-template <class T>
-struct EpochAlloc {
-  using value_type = T;
-  EpochAlloc() = default;
-  template <class U>
-  EpochAlloc(const EpochAlloc<U>&) {}
-  struct FreeList : std::vector<void*> {  // a thread's pooled blocks go back at its exit
-    ~FreeList() {
-      for (void* p : *this) ::operator delete(p);
-    }
-  };
-  static FreeList& free_list() {
-    static thread_local FreeList f;
-    return f;
-  }
-  T* allocate(size_t n) {
-    auto& f = free_list();
-    if (n == 1 && !f.empty()) {
-      void* p = f.back();
-      f.pop_back();
-      return static_cast<T*>(p);
-    }
-    return static_cast<T*>(::operator new(n * sizeof(T)));
-  }
-  void deallocate(T* p, size_t n) {
-    auto& f = free_list();
-    if (n == 1 && f.size() < (1u << 20)) f.push_back(p);
-    else ::operator delete(p);
-  }
-  template <class U>
-  bool operator==(const EpochAlloc<U>&) const { return true; }
-  template <class U>
-  bool operator!=(const EpochAlloc<U>&) const { return false; }
-};
-
-// A log's epochs: epoch id -> its start offset, in id order (the reference's
-// epochStartOffsets map).  A log holds few epochs between checkpoints, appended in
-// increasing order, so they live in a small sorted array, the first kInline inside the Log
-// itself: a config-4 step opens an epoch in, and truncates one out of, each of 66 k logs,
-// and per-log work is bound by cache misses.  The offset is kept inline; the shared
-// EpochStart object (Java's EpochStartOffset, which a ConsumerOffset references) exists
-// only once a consumer refers to the epoch (ref()), and rebase() keeps both in step.
-struct EpochEnt {
-  int64_t id = 0;
-  int32_t offset = 0;
-  std::shared_ptr<EpochStart> shared;  // null until a ConsumerOffset refers to the epoch
-};
-class EpochMap {
- public:
-  EpochEnt* begin() { return data(); }
-  EpochEnt* end() { return data() + n_; }
-  const EpochEnt* begin() const { return data(); }
-  const EpochEnt* end() const { return data() + n_; }
-  size_t size() const { return n_; }
-  bool empty() const { return n_ == 0; }
-  EpochEnt* find(int64_t k) {
-    EpochEnt* it = lower(k);
-    return it != end() && it->id == k ? it : end();
-  }
-  const EpochEnt* find(int64_t k) const { return const_cast<EpochMap*>(this)->find(k); }
-  // computeIfAbsent(k -> offset); the entry stays valid until the next insert or erase
-  EpochEnt* emplace(int64_t k, int32_t offset) {
-    EpochEnt* it = lower(k);
-    if (it != end() && it->id == k) return it;
-    const size_t i = size_t(it - begin());
-    if (big_.empty() && n_ < kInline) {
-      for (size_t j = n_; j > i; --j) inl_[j] = std::move(inl_[j - 1]);
-      inl_[i] = EpochEnt{k, offset, nullptr};
-    } else {
-      if (big_.empty()) {  // spill the inline entries
-        big_.reserve(2 * kInline);
-        for (uint32_t j = 0; j < n_; ++j) big_.push_back(std::move(inl_[j]));
-        for (auto& x : inl_) x.shared.reset();
-      }
-      big_.insert(big_.begin() + long(i), EpochEnt{k, offset, nullptr});
-    }
-    ++n_;
-    return begin() + i;
-  }
-  // drop every epoch with id < k (checkpoint completion)
-  void erase_below(int64_t k) {
-    const size_t d = size_t(lower(k) - begin());
-    if (!d) return;
-    if (big_.empty()) {
-      for (size_t j = d; j < n_; ++j) inl_[j - d] = std::move(inl_[j]);
-      for (size_t j = n_ - d; j < n_; ++j) inl_[j].shared.reset();
-    } else {
-      big_.erase(big_.begin(), big_.begin() + long(d));
-    }
-    n_ -= uint32_t(d);
-  }
-  // every offset -= move (the shared objects too: consumers see the rebased offset)
-  void rebase(int32_t move) {
-    for (EpochEnt& x : *this) {
-      x.offset -= move;
-      if (x.shared) x.shared->offset = x.offset;
-    }
-  }
-  // the EpochStart object a ConsumerOffset holds (created on first reference)
-  static std::shared_ptr<EpochStart> ref(EpochEnt& x) {
-    if (!x.shared) x.shared = std::allocate_shared<EpochStart>(EpochAlloc<EpochStart>(), EpochStart{x.id, x.offset});
-    return x.shared;
-  }
-
- private:
-  static constexpr uint32_t kInline = 2;
-  EpochEnt* data() { return big_.empty() ? inl_ : big_.data(); }
-  const EpochEnt* data() const { return big_.empty() ? inl_ : big_.data(); }
-  EpochEnt* lower(int64_t k) {
-    if (n_ == 0 || end()[-1].id < k) return end();  // the common case: a new epoch
-    return std::lower_bound(begin(), end(), k, [](const EpochEnt& a, int64_t b) { return a.id < b; });
-  }
-  uint32_t n_ = 0;
-  EpochEnt inl_[kInline];
-  std::vector<EpochEnt> big_;  // all entries once more than kInline were held
-};
-
-// A log's segments (Netty components), the first kInline inside the Log itself.
-class SegList {
- public:
-  size_t size() const { return n_; }
-  bool empty() const { return n_ == 0; }
-  uint32_t operator[](size_t i) const { return data()[i]; }
-  const uint32_t* begin() const { return data(); }
-  const uint32_t* end() const { return data() + n_; }
-  void push_back(uint32_t v) {
-    if (big_.empty() && n_ < kInline) {
-      inl_[n_++] = v;
-      return;
-    }
-    if (big_.empty()) big_.assign(inl_, inl_ + n_);
-    big_.push_back(v);
-    ++n_;
-  }
-  // drop the first k (discardReadComponents)
-  void erase_front(size_t k) {
-    if (!k) return;
-    if (big_.empty()) {
-      for (size_t j = k; j < n_; ++j) inl_[j - k] = inl_[j];
-    } else {
-      big_.erase(big_.begin(), big_.begin() + long(k));
-      if (big_.size() <= kInline) {  // back inline
-        std::copy(big_.begin(), big_.end(), inl_);
-        big_.clear();
-        big_.shrink_to_fit();
-      }
-    }
-    n_ -= uint32_t(k);
-  }
-
- private:
-  static constexpr uint32_t kInline = 6;
-  const uint32_t* data() const { return big_.empty() ? inl_ : big_.data(); }
-  uint32_t n_ = 0;
-  uint32_t inl_[kInline] = {};
-  std::vector<uint32_t> big_;  // all segments once more than kInline were held
-};
-struct ChKey {
-  uint64_t lo, hi;
-  bool operator==(const ChKey& o) const { return lo == o.lo && hi == o.hi; }
-};
-struct ChKeyHash {
-  size_t operator()(const ChKey& k) const { return std::hash<uint64_t>()(k.lo * 0x9E3779B97F4A7C15ull ^ k.hi); }
-};
-
-// JobCausalLogImpl (one per job per TaskManager, JobCausalLogFactory.java:56-67): the
-// job's sharing depth (ExecutionConfig.determinantSharingDepth) and its
-// latestCompletedCheckpoint, whose CAS gates the fan-out of truncation (:230-246).
-struct Job {
-  bool open = false;
-  uint64_t lo = 0, hi = 0;  // JobID (an AbstractID)
-  int32_t depth = CLG_FULL_SHARING;
-  int64_t latest_cp = 0;  // JobCausalLogImpl.latestCompletedCheckpoint (:92, :117)
-};
-
-struct Log {
-  clg_causal_log_id id{};
-  uint32_t job = 0;
-  int32_t depth = CLG_FULL_SHARING;  // the owning job's sharing depth
-  bool open = false;
-  SegList segs;                // composite components
-  int32_t writer = 0;          // visibleWriterIndex (== composite writerIndex)
-  int32_t flushed = 0;         // physical bytes [0, flushed) are resident in HBM
-  // Host copy of physical bytes [tail_start, writer): the staged bytes [flushed, writer)
-  // plus the most recent flushed ones (clg_config.host_tail_bytes), so a slice of the log's
-  // tail -- a consumer keeping up with its producer -- is served without a GPU round trip.
-  // tail_start <= flushed <= writer.
-  std::vector<uint8_t> tail;
-  int32_t tail_start = 0;
-  uint32_t pending_bytes() const { return uint32_t(writer - flushed); }
-  const uint8_t* pending_data() const { return tail.data() + (flushed - tail_start); }
-  EpochMap epochs;
-  std::unordered_map<ChKey, Consumer, ChKeyHash> consumers;
-};
-
-// In-flight (data) log of one subpartition (InMemorySubpartitionInFlightLogger.java:28-207):
-// SortedMap<epoch, List<Buffer>>; each buffer's bytes occupy whole pool segments.
-struct IflBuf {
-  std::vector<uint32_t> segs;
-  uint32_t len;
-};
-// The spillable logger's replay iterator (SpilledReplayIterator.java:60-401): a consumer and a
-// prefetch EpochCursor (:306-394) over the live view tailMap(view) of the epochs.
-struct IflCursor {
-  int64_t ne = 0;    // nextEpoch
-  int64_t off = 0;   // nextEpochOffset
-  int64_t last = 0;  // lastEpoch
-  int64_t rem = 0;   // remaining
-};
-struct IflIter {
-  bool exists = false;  // currentIterator != null
-  int64_t view = 0;     // the tailMap's lower bound (getInFlightIterator's epochID)
-  IflCursor con, pre;
-};
-struct InFlight {
-  bool open = false;
-  uint32_t type = CLG_IFL_IN_MEMORY;
-  bool replaying = false;  // spillable: isReplaying (:58)
-  IflIter it;              // spillable: currentIterator (:60)
-  std::map<int64_t, std::vector<IflBuf>> epochs;
-};
-
-struct IdKey {  // (job, CausalLogID): logs of different jobs never alias
-  uint32_t job;
-  int16_t v;
-  uint8_t main;
-  int8_t sub;
-  int64_t lo, hi;
-  bool operator<(const IdKey& o) const {
-    if (job != o.job) return job < o.job;
-    if (v != o.v) return v < o.v;
-    if (main != o.main) return main < o.main;
-    if (main) return false;  // CausalLogID.equals: main logs compare by vertex only
-    if (lo != o.lo) return lo < o.lo;
-    if (hi != o.hi) return hi < o.hi;
-    return sub < o.sub;
-  }
-};
-IdKey key_of(uint32_t job, const clg_causal_log_id& id) {
-  IdKey k{job, id.vertex_id, uint8_t(id.is_main ? 1 : 0), id.is_main ? int8_t(0) : id.subpartition,
-          id.is_main ? 0 : id.irp_lower, id.is_main ? 0 : id.irp_upper};
-  return k;
-}
 
 struct DevBuf {
   void* p = nullptr;
@@ -387,117 +135,6 @@ struct PendingTiming {
   uint64_t bytes;
 };
 
-// Guard bytes either side of the segment pool: the gather and decode kernels issue aligned
-// 16-B loads that may start before a piece's first byte or end past its last.
-constexpr size_t kPoolGuard = 256;
-
-// Two-level engine lock.  The per-call ThreadCausalLog operations of the drop-in (append,
-// hasDelta, offset, slices the host tail holds, logLength, a host-input upstream delta) take
-// only the stripe of their log, so task threads appending and Netty threads slicing
-// different logs run in parallel -- as on the reference's per-log objects -- without
-// touching a shared cache line.  Everything that touches the GPU, the log table or several
-// logs at once takes the engine mutex and then every stripe (EXCLUSIVE).  Exclusive is
-// re-entrant (clg_job_close -> clg_log_close), and a per-log request from the exclusive
-// holder passes through.
-constexpr uint32_t kLogStripes = 64;
-struct alignas(64) Stripe {
-  std::mutex m;
-};
-struct EngineLock {
-  std::mutex m;
-  std::atomic<std::thread::id> owner{};
-  int depth = 0;
-  Stripe stripe[kLogStripes];
-  bool owned() const { return owner.load(std::memory_order_relaxed) == std::this_thread::get_id(); }
-  void lock() {
-    if (owned()) {
-      ++depth;
-      return;
-    }
-    m.lock();
-    for (auto& s : stripe) s.m.lock();
-    owner.store(std::this_thread::get_id(), std::memory_order_relaxed);
-    depth = 1;
-  }
-  void unlock() {
-    if (--depth == 0) {
-      owner.store(std::thread::id(), std::memory_order_relaxed);
-      for (uint32_t i = kLogStripes; i-- > 0;) stripe[i].m.unlock();
-      m.unlock();
-    }
-  }
-};
-struct XGuard {
-  EngineLock& l;
-  explicit XGuard(EngineLock& l_) : l(l_) { l.lock(); }
-  ~XGuard() { l.unlock(); }
-};
-
-// A few host threads for the per-log loops of very large batches (config 4: 66 k logs per
-// decode, truncation): run(fn) calls fn(part, parts) once per part, the calling thread taking
-// part 0; workers spin briefly for the next job, then sleep.  Jobs only ever come from the
-// holder of the engine lock, one at a time.
-class WorkPool {
- public:
-  explicit WorkPool(unsigned n) : n_(n ? n : 1) {
-    for (unsigned i = 1; i < n_; ++i) th_.emplace_back([this, i] { loop(i); });
-  }
-  ~WorkPool() {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto& t : th_) t.join();
-  }
-  unsigned size() const { return n_; }
-  void run(const std::function<void(unsigned, unsigned)>& fn) {
-    if (n_ == 1) {
-      fn(0, 1);
-      return;
-    }
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      job_ = &fn;
-      left_.store(n_ - 1, std::memory_order_relaxed);
-      gen_.fetch_add(1, std::memory_order_release);
-    }
-    cv_.notify_all();
-    fn(0, n_);
-    while (left_.load(std::memory_order_acquire) != 0) std::this_thread::yield();
-  }
-
- private:
-  void loop(unsigned i) {
-    uint64_t seen = 0;
-    for (;;) {
-      // a short spin (the next job of a batch comes within microseconds), then sleep: a longer
-      // one burns the box's CPU quota between batches
-      const auto t0 = std::chrono::steady_clock::now();
-      while (gen_.load(std::memory_order_acquire) == seen &&
-             std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(50))
-        std::this_thread::yield();
-      const std::function<void(unsigned, unsigned)>* job;
-      {
-        std::unique_lock<std::mutex> g(mu_);
-        cv_.wait(g, [&] { return stop_ || gen_.load(std::memory_order_acquire) != seen; });
-        if (stop_) return;
-        seen = gen_.load(std::memory_order_acquire);
-        job = job_;
-      }
-      (*job)(i, n_);
-      left_.fetch_sub(1, std::memory_order_acq_rel);
-    }
-  }
-  unsigned n_;
-  std::vector<std::thread> th_;
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::atomic<uint64_t> gen_{0};
-  std::atomic<unsigned> left_{0};
-  const std::function<void(unsigned, unsigned)>* job_ = nullptr;
-  bool stop_ = false;
-};
 
 }  // namespace
 
@@ -598,7 +235,7 @@ struct clg_engine {
   hipEvent_t zdone[kSlots] = {};
   uint32_t plan_slot = 0;  // the slot stage_plan / enqueue_plan use (launch_fused sets it)
   DevBuf d_stage, d_desc, d_pieces, d_tiles, d_spans, d_agg, d_conv, d_tres, d_sres, d_totals, d_out;
-  std::vector<uint64_t> tab_at;  // clg_get_determinants_batch: a log's place in the segment table (UINT64_MAX: none)
+  std::vector<uint64_t> tab_at;  // RunPlan: a log's place in the segment table (UINT64_MAX: none)
   DevBuf d_fconv, d_lanes, d_sums, d_fres, d_flags, d_dbg, d_prof, d_rprof, d_prof2, d_jpos, d_jlen, d_jn, d_defer;
   DevBuf d_o_off, d_o_tag, d_o_v0, d_o_widx, d_o_wrc, d_o_wv1, d_o_wvo, d_o_wvl, d_o_wsub;
   DevBuf d_zctl, d_ztiles, d_zbits;  // fast decode: control words, tiles, record-start bitmaps
@@ -1207,6 +844,23 @@ struct clg_engine {
     }
   }
 
+  // A gather's output: the launch writes to the caller's device buffer, or to d_out, which is
+  // then copied to the caller's host buffer.  launch(dout) queues the kernel on `stream`;
+  // wait = false returns without a sync when the output stays on the device.
+  template <class L>
+  int gather_out(void* out, uint32_t out_kind, uint64_t total, const char* stat, bool wait, L&& launch) {
+    uint8_t* dout;
+    if (out_kind == CLG_MEM_DEVICE) {
+      dout = static_cast<uint8_t*>(out);
+    } else {
+      CHK(d_out.ensure(total));
+      dout = d_out.as<uint8_t>();
+    }
+    CHK(timed(stat, 2 * total, [&] { return launch(dout); }));
+    if (out_kind != CLG_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, total, hipMemcpyDeviceToHost, stream));
+    return wait || out_kind != CLG_MEM_DEVICE ? sync() : CLG_OK;
+  }
+
   int run_gather(const std::vector<clg::GatherPiece>& pieces, uint64_t total, void* out, uint32_t out_kind,
                  const char* stat = "slice_gather", bool wait = true) {
     if (pieces.empty()) return CLG_OK;
@@ -1215,21 +869,61 @@ struct clg_engine {
     CHK(d_desc.ensure(db));
     memcpy(h_desc.p, pieces.data(), db);
     HIPCHK(hipMemcpyAsync(d_desc.p, h_desc.p, db, hipMemcpyHostToDevice, stream));
-    uint8_t* dout;
-    if (out_kind == CLG_MEM_DEVICE) {
-      dout = static_cast<uint8_t*>(out);
-    } else {
-      CHK(d_out.ensure(total));
-      dout = d_out.as<uint8_t>();
-    }
-    CHK(timed(stat, 2 * total, [&] {
+    return gather_out(out, out_kind, total, stat, wait, [&](uint8_t* dout) {
       return clg::launch_gather(d_desc.as<clg::GatherPiece>(), uint32_t(pieces.size()), dout, stream);
-    }));
-    if (out_kind != CLG_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, total, hipMemcpyDeviceToHost, stream));
-    return wait || out_kind != CLG_MEM_DEVICE ? sync() : CLG_OK;
+    });
   }
 
-  // The gather's descriptors, staged: runs | segment table; *o: where each part starts.
+  // A gather's run plan: byte ranges of logs as runs for the device-side piece expansion
+  // (k_expand_pieces), packed back to back in the output, with each log's segment indices once
+  // in segtab: the log's place there is kept by handle in tab_at (a hash map took 0.1 ms for
+  // config 5's 2 064 logs), whose touched entries are reset when the plan goes.
+  struct RunPlan {
+    clg_engine& e;
+    std::vector<clg::SegSpan> runs;
+    std::vector<uint32_t> segtab;
+    uint32_t n_pieces = 0;
+    uint64_t total = 0;  // bytes planned: the next run's place in the output
+    std::vector<uint32_t> touched;
+    RunPlan(clg_engine& en, uint32_t n) : e(en) {
+      runs.reserve(n);
+      touched.reserve(n);
+      if (e.tab_at.size() < e.logs.size()) e.tab_at.resize(e.logs.size(), UINT64_MAX);
+    }
+    RunPlan(const RunPlan&) = delete;
+    ~RunPlan() {
+      for (uint32_t h : touched) e.tab_at[h] = UINT64_MAX;
+    }
+    // [phys, phys + nb) of log h for request `req` (the run's pad), at `total` in the output
+    void add(uint32_t h, int32_t phys, int32_t nb, uint32_t req) {
+      if (nb > 0) {
+        uint64_t& at = e.tab_at[h];
+        if (at == UINT64_MAX) {
+          const SegList& segs = e.logs[h].segs;
+          at = segtab.size();
+          touched.push_back(h);
+          segtab.insert(segtab.end(), segs.begin(), segs.end());
+        }
+        runs.push_back(clg::SegSpan{at, uint32_t(phys), uint32_t(nb), total, n_pieces, req});
+        n_pieces += uint32_t(phys + nb - 1) / e.C() - uint32_t(phys) / e.C() + 1;
+      }
+      total += uint64_t(nb);
+    }
+  };
+
+  struct DescSet {
+    PinBuf& h;
+    DevBuf &d, &pieces;
+  };
+  struct StagedPlan {
+    const clg::SegSpan* runs;
+    const clg::GatherPiece* pieces;
+    const uint8_t* extra;
+  };
+  static size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
+  // A run plan on the device.  The descriptors, staged through s.h into s.d on `on`:
+  // runs | segment table | `extra_bytes` of the caller's at the next 16-byte boundary; then the
+  // pieces, expanded on the device into s.pieces.
   // (Tried and removed: pieces in source order -- every consumer's piece of one segment back
   // to back on one XCD, for L2 hits -- took the isolated config-2 gather from 0.39 to 0.43 ms
   // and cost 0.1 ms of host grouping per step.  Round 5: a segment-major gather, one block per
@@ -1243,88 +937,76 @@ struct clg_engine {
   // in that time whatever it reads; in the step, beside the decode's traffic, they cost about
   // 2 % (0.723 against 0.737 ms).  Windows of 16 segments and fewer fetch as little and are
   // slower alone (0.41, 0.43 ms): DESIGN.md section 7, "A windowed order".)
-  static size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
-  static size_t gather_desc_layout(const std::vector<clg::SegSpan>& runs, const std::vector<uint32_t>& segtab,
-                                   size_t o[2]) {
-    o[0] = 0;
-    o[1] = al16(runs.size() * sizeof(clg::SegSpan));
-    return o[1] + segtab.size() * 4;
-  }
-  static void gather_desc_fill(uint8_t* h, const std::vector<clg::SegSpan>& runs, const std::vector<uint32_t>& segtab,
-                               const size_t o[2]) {
-    memcpy(h + o[0], runs.data(), runs.size() * sizeof(clg::SegSpan));
-    memcpy(h + o[1], segtab.data(), segtab.size() * 4);
-  }
-  int gather_expand(const uint8_t* d, const std::vector<clg::SegSpan>& runs, const size_t o[2], uint32_t n_pieces,
-                    clg::GatherPiece* pieces, hipStream_t on) {
-    return clg::launch_expand_pieces(reinterpret_cast<const clg::SegSpan*>(d), uint32_t(runs.size()), n_pieces,
-                                     reinterpret_cast<const uint32_t*>(d + o[1]), pool, C(), pieces, on);
+  int stage_run_plan(const RunPlan& p, DescSet s, hipStream_t on, StagedPlan* sp, const void* extra = nullptr,
+                     size_t extra_bytes = 0) {
+    const size_t rb = p.runs.size() * sizeof(clg::SegSpan), o_tab = al16(rb), tb = p.segtab.size() * 4;
+    const size_t o_extra = extra_bytes ? al16(o_tab + tb) : o_tab + tb, hb = o_extra + extra_bytes;
+    CHK(s.h.ensure(hb));
+    CHK(s.d.ensure(hb));
+    CHK(s.pieces.ensure(size_t(p.n_pieces) * sizeof(clg::GatherPiece)));
+    uint8_t* h = s.h.as<uint8_t>();
+    memcpy(h, p.runs.data(), rb);
+    memcpy(h + o_tab, p.segtab.data(), tb);
+    if (extra_bytes) memcpy(h + o_extra, extra, extra_bytes);
+    HIPCHK(hipMemcpyAsync(s.d.p, h, hb, hipMemcpyHostToDevice, on));
+    const uint8_t* d = s.d.as<uint8_t>();
+    *sp = StagedPlan{s.d.as<clg::SegSpan>(), s.pieces.as<clg::GatherPiece>(), d + o_extra};
+    return clg::launch_expand_pieces(sp->runs, uint32_t(p.runs.size()), p.n_pieces,
+                                     reinterpret_cast<const uint32_t*>(d + o_tab), pool, C(), s.pieces.as<clg::GatherPiece>(), on);
   }
 
   // Batched gather from runs: pieces are generated on the device (k_expand_pieces).
-  int run_gather_runs(const std::vector<clg::SegSpan>& runs, const std::vector<uint32_t>& segtab, uint32_t n_pieces,
-                      uint64_t total, void* out, uint32_t out_kind) {
-    if (runs.empty() || !n_pieces) return CLG_OK;
-    if (out_kind == CLG_MEM_DEVICE && (cfg.flags & CLG_F_ASYNC_SLICE))
-      return gather_runs_async(runs, segtab, n_pieces, total, out);
-    size_t o[2];
-    const size_t hb = gather_desc_layout(runs, segtab, o);
-    CHK(h_desc.ensure(hb));
-    CHK(d_desc.ensure(hb));
-    CHK(d_pieces.ensure(size_t(n_pieces) * sizeof(clg::GatherPiece)));
-    gather_desc_fill(h_desc.as<uint8_t>(), runs, segtab, o);
-    HIPCHK(hipMemcpyAsync(d_desc.p, h_desc.p, hb, hipMemcpyHostToDevice, stream));
-    CHK(gather_expand(d_desc.as<uint8_t>(), runs, o, n_pieces, d_pieces.as<clg::GatherPiece>(), stream));
-    uint8_t* dout;
-    if (out_kind == CLG_MEM_DEVICE) {
-      dout = static_cast<uint8_t*>(out);
-    } else {
-      CHK(d_out.ensure(total));
-      dout = d_out.as<uint8_t>();
-    }
-    CHK(timed("slice_gather", 2 * total, [&] {
-      return clg::launch_gather(d_pieces.as<clg::GatherPiece>(), n_pieces, dout, stream);
-    }));
-    if (out_kind != CLG_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, total, hipMemcpyDeviceToHost, stream));
-    return sync();
+  int run_gather_runs(const RunPlan& p, void* out, uint32_t out_kind) {
+    if (p.runs.empty() || !p.n_pieces) return CLG_OK;
+    if (out_kind == CLG_MEM_DEVICE && (cfg.flags & CLG_F_ASYNC_SLICE)) return gather_runs_async(p, out);
+    StagedPlan sp;
+    CHK(stage_run_plan(p, DescSet{h_desc, d_desc, d_pieces}, stream, &sp));
+    return gather_out(out, out_kind, p.total, "slice_gather", true,
+                      [&](uint8_t* dout) { return clg::launch_gather(sp.pieces, p.n_pieces, dout, stream); });
   }
 
-  // getDeterminants(start_epoch[i]) of log[i] as runs for the device-side piece expansion
-  // (clg_get_determinants_batch, clg_digest_logs): run i's output offset is its place in the
-  // packed order, its pad the request index; len[i] / out_off[i] (optional) per request.
+  // getDeterminants(start_epoch[i]) of log[i] as runs (clg_get_determinants_batch,
+  // clg_digest_logs, clg_diff_logs): run i's output offset is its place in the packed order,
+  // its pad the request index; len[i] / out_off[i] (optional) per request.
   int plan_determinant_runs(const uint32_t* log, const int64_t* start_epoch, uint32_t n, uint32_t* len,
-                            uint64_t* out_off, std::vector<clg::SegSpan>& runs, std::vector<uint32_t>& segtab,
-                            uint32_t* n_pieces, uint64_t* total) {
-    runs.reserve(n);
-    // each log's segment indices once in segtab: the log's place there, by handle (a hash map
-    // took 0.1 ms for config 5's 2 064 logs)
-    if (tab_at.size() < logs.size()) tab_at.resize(logs.size(), UINT64_MAX);
-    std::vector<uint32_t> touched;
-    touched.reserve(n);
-    int st = CLG_OK;
-    uint64_t dst = 0;
-    for (uint32_t i = 0; i < n && st == CLG_OK; ++i) {
+                            uint64_t* out_off, RunPlan& p) {
+    for (uint32_t i = 0; i < n; ++i) {
       Log* l;
-      if ((st = get_log(log[i], &l)) != CLG_OK) break;
+      CHK(get_log(log[i], &l));
       int32_t s = 0, nb = 0;
-      if (l->depth != 0 && (st = determinants_range(*l, start_epoch[i], &s, &nb)) != CLG_OK) break;
+      if (l->depth != 0) CHK(determinants_range(*l, start_epoch[i], &s, &nb));
       if (len) len[i] = uint32_t(nb);
-      if (out_off) out_off[i] = dst;
-      if (nb > 0) {
-        uint64_t& at = tab_at[log[i]];
-        if (at == UINT64_MAX) {
-          at = segtab.size();
-          touched.push_back(log[i]);
-          segtab.insert(segtab.end(), l->segs.begin(), l->segs.end());
-        }
-        runs.push_back(clg::SegSpan{at, uint32_t(s), uint32_t(nb), dst, *n_pieces, i});
-        *n_pieces += uint32_t(s + nb - 1) / C() - uint32_t(s) / C() + 1;
-      }
-      dst += uint64_t(nb);
+      if (out_off) out_off[i] = p.total;
+      p.add(log[i], s, nb, i);
     }
-    for (uint32_t h : touched) tab_at[h] = UINT64_MAX;
-    *total = dst;
-    return st;
+    return CLG_OK;
+  }
+
+  // Spans [off[i], off[i] + len[i]) of `bytes` for a kernel: span i starts at
+  // *base + (off[i] - *base_off).  Device memory is read in place; of host memory the range
+  // [lo, hi) that covers the non-empty spans is staged through h_stage into d_stage (queued on
+  // `stream`), with 16 guard bytes for the kernels' aligned loads.
+  int stage_spans(const uint8_t* bytes, const uint64_t* off, const uint64_t* len, uint32_t n, uint32_t in_kind,
+                  const uint8_t** base, uint64_t* base_off) {
+    *base = bytes;
+    *base_off = 0;
+    if (in_kind != CLG_MEM_HOST) return CLG_OK;
+    uint64_t lo = UINT64_MAX, hi = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (len[i] == 0) continue;
+      lo = std::min(lo, off[i]);
+      hi = std::max(hi, off[i] + len[i]);
+    }
+    if (lo == UINT64_MAX) lo = hi = 0;
+    CHK(d_stage.ensure(hi - lo + 16));
+    CHK(h_stage.ensure(hi - lo + 16));
+    if (hi > lo) {
+      memcpy(h_stage.p, bytes + lo, hi - lo);
+      HIPCHK(hipMemcpyAsync(d_stage.p, h_stage.p, hi - lo, hipMemcpyHostToDevice, stream));
+    }
+    *base = d_stage.as<uint8_t>();
+    *base_off = lo;
+    return CLG_OK;
   }
 
   // The digest of every run (digest.hip), `n` results read back into out: out[run.pad] for a
@@ -1356,26 +1038,16 @@ struct clg_engine {
   // Device-output slice gather on gstream, after everything already queued on `stream`
   // (appends); returns without waiting.  Its own descriptor buffers, so the next decode
   // on `stream` does not touch them; the next gather waits for this one first.
-  int gather_runs_async(const std::vector<clg::SegSpan>& runs, const std::vector<uint32_t>& segtab, uint32_t n_pieces,
-                        uint64_t total, void* out) {
+  int gather_runs_async(const RunPlan& p, void* out) {
     const uint32_t set = gseq++ & 1u;
     if (gdone[set]) HIPCHK(hipEventSynchronize(gdone[set]));  // the gather two calls ago released this set
     else HIPCHK(hipEventCreateWithFlags(&gdone[set], hipEventDisableTiming));
-    size_t o[2];
-    const size_t hb = gather_desc_layout(runs, segtab, o);
-    PinBuf& hd = h_gdesc[set];
-    DevBuf& dd = d_gdesc[set];
-    DevBuf& dp = d_gpieces[set];
-    CHK(hd.ensure(hb));
-    CHK(dd.ensure(hb));
-    CHK(dp.ensure(size_t(n_pieces) * sizeof(clg::GatherPiece)));
-    gather_desc_fill(hd.as<uint8_t>(), runs, segtab, o);
     // no wait on `stream`: every pool write (flush, upstream scatter) has completed when
     // its call returned, and decodes only read the pool
-    HIPCHK(hipMemcpyAsync(dd.p, hd.p, hb, hipMemcpyHostToDevice, gstream));
-    CHK(gather_expand(dd.as<uint8_t>(), runs, o, n_pieces, dp.as<clg::GatherPiece>(), gstream));
-    CHK(timed("slice_gather", 2 * total, [&] {
-      return clg::launch_gather(dp.as<clg::GatherPiece>(), n_pieces, static_cast<uint8_t*>(out), gstream);
+    StagedPlan sp;
+    CHK(stage_run_plan(p, DescSet{h_gdesc[set], d_gdesc[set], d_gpieces[set]}, gstream, &sp));
+    CHK(timed("slice_gather", 2 * p.total, [&] {
+      return clg::launch_gather(sp.pieces, p.n_pieces, static_cast<uint8_t*>(out), gstream);
     }, gstream));
     HIPCHK(hipEventRecord(gdone[set], gstream));
     g_pending = true;
@@ -3580,11 +3252,8 @@ int clg_get_determinants_batch(clg_engine* e, const uint32_t* log, const int64_t
                                uint64_t cap, uint32_t out_kind, uint64_t* out_off, uint32_t* len, uint64_t* total) {
   ENGINE_GUARD(e);
   if (n && (!log || !start_epoch || !len)) return fail(CLG_E_INVALID_ARG, "null argument");
-  std::vector<clg::SegSpan> runs;
-  std::vector<uint32_t> segtab;
-  uint32_t n_pieces = 0;
-  uint64_t dst = 0;
   if (!out) {  // sizes only (the merge measures every copy first): no gather plan
+    uint64_t dst = 0;
     for (uint32_t i = 0; i < n; ++i) {
       Log* l;
       CHK(e->get_log(log[i], &l));
@@ -3597,11 +3266,12 @@ int clg_get_determinants_batch(clg_engine* e, const uint32_t* log, const int64_t
     if (total) *total = dst;
     return CLG_OK;
   }
-  CHK(e->plan_determinant_runs(log, start_epoch, n, len, out_off, runs, segtab, &n_pieces, &dst));
-  if (total) *total = dst;
-  if (dst > cap) return fail(CLG_E_CAPACITY, "getDeterminants batch needs %llu bytes", (unsigned long long)dst);
+  clg_engine::RunPlan p(*e, n);
+  CHK(e->plan_determinant_runs(log, start_epoch, n, len, out_off, p));
+  if (total) *total = p.total;
+  if (p.total > cap) return fail(CLG_E_CAPACITY, "getDeterminants batch needs %llu bytes", (unsigned long long)p.total);
   CHK(e->flush());
-  return e->run_gather_runs(runs, segtab, n_pieces, dst, out, out_kind);
+  return e->run_gather_runs(p, out, out_kind);
 }
 
 // The digest of getDeterminants(start_epoch[i]) of log[i] (digest.h): the ranges, runs and
@@ -3612,26 +3282,16 @@ int clg_digest_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epo
   ENGINE_GUARD(e);
   if (n && (!log || !start_epoch || !out)) return fail(CLG_E_INVALID_ARG, "null argument");
   if (!n) return CLG_OK;
-  std::vector<clg::SegSpan> runs;
-  std::vector<uint32_t> segtab;
-  uint32_t n_pieces = 0;
-  uint64_t total = 0;
-  CHK(e->plan_determinant_runs(log, start_epoch, n, nullptr, nullptr, runs, segtab, &n_pieces, &total));
-  if (runs.empty()) {
+  clg_engine::RunPlan p(*e, n);
+  CHK(e->plan_determinant_runs(log, start_epoch, n, nullptr, nullptr, p));
+  if (p.runs.empty()) {
     memset(out, 0, size_t(n) * sizeof(clg_digest));
     return CLG_OK;
   }
   CHK(e->flush());
-  size_t o[2];
-  const size_t hb = clg_engine::gather_desc_layout(runs, segtab, o);
-  CHK(e->h_desc.ensure(hb));
-  CHK(e->d_desc.ensure(hb));
-  CHK(e->d_pieces.ensure(size_t(n_pieces) * sizeof(clg::GatherPiece)));
-  clg_engine::gather_desc_fill(e->h_desc.as<uint8_t>(), runs, segtab, o);
-  HIPCHK(hipMemcpyAsync(e->d_desc.p, e->h_desc.p, hb, hipMemcpyHostToDevice, e->stream));
-  CHK(e->gather_expand(e->d_desc.as<uint8_t>(), runs, o, n_pieces, e->d_pieces.as<clg::GatherPiece>(), e->stream));
-  return e->run_digest(e->d_desc.as<clg::SegSpan>(), uint32_t(runs.size()), e->d_pieces.as<clg::GatherPiece>(), n_pieces,
-                       total, n, out);
+  clg_engine::StagedPlan sp;
+  CHK(e->stage_run_plan(p, clg_engine::DescSet{e->h_desc, e->d_desc, e->d_pieces}, e->stream, &sp));
+  return e->run_digest(sp.runs, uint32_t(p.runs.size()), sp.pieces, p.n_pieces, p.total, n, out);
 }
 
 // The digest of spans of host or device memory: the same pieces, one per 16 KiB of span, built
@@ -3645,12 +3305,9 @@ int clg_digest_spans(clg_engine* e, const uint8_t* bytes, const uint64_t* off, c
   if (in_kind != CLG_MEM_HOST && in_kind != CLG_MEM_DEVICE) return fail(CLG_E_INVALID_ARG, "in_kind %u", in_kind);
   if (!n) return CLG_OK;
   constexpr uint64_t kPiece = 16384;
-  uint64_t lo = UINT64_MAX, hi = 0, total = 0, n_pieces = 0;
+  uint64_t total = 0, n_pieces = 0;
   for (uint32_t i = 0; i < n; ++i) {
     if (len[i] >> 32) return fail(CLG_E_INVALID_ARG, "span %u of %llu bytes", i, (unsigned long long)len[i]);
-    if (len[i] == 0) continue;
-    lo = std::min(lo, off[i]);
-    hi = std::max(hi, off[i] + len[i]);
     total += len[i];
     n_pieces += (len[i] + kPiece - 1) / kPiece;
   }
@@ -3660,16 +3317,9 @@ int clg_digest_spans(clg_engine* e, const uint8_t* bytes, const uint64_t* off, c
   }
   if (!bytes) return fail(CLG_E_INVALID_ARG, "null argument");
   if (n_pieces >> 32) return fail(CLG_E_INVALID_ARG, "spans of %llu bytes in one call", (unsigned long long)total);
-  const uint8_t* base = bytes;  // span i starts at base + (off[i] - base_off)
-  uint64_t base_off = 0;
-  if (in_kind == CLG_MEM_HOST) {
-    CHK(e->d_stage.ensure(hi - lo + 16));
-    CHK(e->h_stage.ensure(hi - lo + 16));
-    memcpy(e->h_stage.p, bytes + lo, hi - lo);
-    HIPCHK(hipMemcpyAsync(e->d_stage.p, e->h_stage.p, hi - lo, hipMemcpyHostToDevice, e->stream));
-    base = e->d_stage.as<uint8_t>();
-    base_off = lo;
-  }
+  const uint8_t* base;  // span i starts at base + (off[i] - base_off)
+  uint64_t base_off;
+  CHK(e->stage_spans(bytes, off, len, n, in_kind, &base, &base_off));
   std::vector<clg::SegSpan> runs;
   std::vector<clg::GatherPiece> pieces;
   runs.reserve(n);
@@ -3710,57 +3360,41 @@ int clg_diff_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch
   if (n && (!log || !start_epoch || !off || !len || !out)) return fail(CLG_E_INVALID_ARG, "null argument");
   if (in_kind != CLG_MEM_HOST && in_kind != CLG_MEM_DEVICE) return fail(CLG_E_INVALID_ARG, "in_kind %u", in_kind);
   if (!n) return CLG_OK;
-  uint64_t lo = UINT64_MAX, hi = 0;
+  bool any = false;
   for (uint32_t i = 0; i < n; ++i) {
     if (len[i] >> 32) return fail(CLG_E_INVALID_ARG, "span %u of %llu bytes", i, (unsigned long long)len[i]);
-    if (len[i] == 0) continue;
-    lo = std::min(lo, off[i]);
-    hi = std::max(hi, off[i] + len[i]);
+    any |= len[i] != 0;
   }
-  if (hi && !bytes) return fail(CLG_E_INVALID_ARG, "null argument");
-  std::vector<clg::SegSpan> runs;
-  std::vector<uint32_t> segtab, len_log(n);
-  uint32_t n_pieces = 0;
-  uint64_t total = 0;
-  CHK(e->plan_determinant_runs(log, start_epoch, n, len_log.data(), nullptr, runs, segtab, &n_pieces, &total));
+  if (any && !bytes) return fail(CLG_E_INVALID_ARG, "null argument");
+  std::vector<uint32_t> len_log(n);
+  clg_engine::RunPlan p(*e, n);
+  CHK(e->plan_determinant_runs(log, start_epoch, n, len_log.data(), nullptr, p));
   for (uint32_t i = 0; i < n; ++i) out[i] = clg_diff{0, len_log[i], len[i]};  // (a request without a run stays so)
-  if (runs.empty()) return CLG_OK;
+  if (p.runs.empty()) return CLG_OK;
   CHK(e->flush());
-  const uint8_t* base = bytes;  // span i starts at base + (off[i] - base_off)
-  uint64_t base_off = 0;
-  if (in_kind == CLG_MEM_HOST && hi) {
-    CHK(e->d_stage.ensure(hi - lo + 16));
-    CHK(e->h_stage.ensure(hi - lo + 16));
-    memcpy(e->h_stage.p, bytes + lo, hi - lo);
-    HIPCHK(hipMemcpyAsync(e->d_stage.p, e->h_stage.p, hi - lo, hipMemcpyHostToDevice, e->stream));
-    base = e->d_stage.as<uint8_t>();
-    base_off = lo;
-  }
-  size_t o[2];
-  const size_t gb = clg_engine::al16(clg_engine::gather_desc_layout(runs, segtab, o));
-  const size_t hb = gb + runs.size() * sizeof(clg::DiffRef);  // runs | segment table | references
-  CHK(e->h_desc.ensure(hb));
-  CHK(e->d_desc.ensure(hb));
-  CHK(e->d_pieces.ensure(size_t(n_pieces) * sizeof(clg::GatherPiece)));
-  clg_engine::gather_desc_fill(e->h_desc.as<uint8_t>(), runs, segtab, o);
-  clg::DiffRef* refs = reinterpret_cast<clg::DiffRef*>(e->h_desc.as<uint8_t>() + gb);
+  const uint8_t* base;  // span i starts at base + (off[i] - base_off)
+  uint64_t base_off;
+  CHK(e->stage_spans(bytes, off, len, n, in_kind, &base, &base_off));
+  std::vector<clg::DiffRef> refs(p.runs.size());  // staged behind the plan: runs | segment table | references
   uint64_t compared = 0;
-  for (size_t k = 0; k < runs.size(); ++k) {
-    const uint32_t i = runs[k].pad;
+  for (size_t k = 0; k < p.runs.size(); ++k) {
+    const uint32_t i = p.runs[k].pad;
     refs[k] = clg::DiffRef{len[i] ? base + (off[i] - base_off) : nullptr, uint32_t(len[i]), 0};
-    compared += 2 * std::min<uint64_t>(runs[k].len, len[i]);
+    compared += 2 * std::min<uint64_t>(p.runs[k].len, len[i]);
   }
-  HIPCHK(hipMemcpyAsync(e->d_desc.p, e->h_desc.p, hb, hipMemcpyHostToDevice, e->stream));
-  CHK(e->gather_expand(e->d_desc.as<uint8_t>(), runs, o, n_pieces, e->d_pieces.as<clg::GatherPiece>(), e->stream));
+  clg_engine::StagedPlan sp;
+  CHK(e->stage_run_plan(p, clg_engine::DescSet{e->h_desc, e->d_desc, e->d_pieces}, e->stream, &sp, refs.data(),
+                        refs.size() * sizeof(clg::DiffRef)));
+  const uint32_t n_pieces = p.n_pieces;
   CHK(e->d_dffirst.ensure(size_t(n_pieces) * 4 + 4));
   CHK(e->d_dfout.ensure(size_t(n) * sizeof(clg_diff)));
   CHK(e->h_dfout.ensure(size_t(n) * sizeof(clg_diff)));
   memcpy(e->h_dfout.p, out, size_t(n) * sizeof(clg_diff));
   HIPCHK(hipMemcpyAsync(e->d_dfout.p, e->h_dfout.p, size_t(n) * sizeof(clg_diff), hipMemcpyHostToDevice, e->stream));
   CHK(e->timed("log_diff", compared, [&] {
-    return clg::launch_diff(e->d_pieces.as<clg::GatherPiece>(), n_pieces, e->d_desc.as<clg::SegSpan>(),
-                            uint32_t(runs.size()), reinterpret_cast<const clg::DiffRef*>(e->d_desc.as<uint8_t>() + gb),
-                            e->d_dffirst.as<uint32_t>(), e->d_dfout.as<clg_diff>(), e->stream);
+    return clg::launch_diff(sp.pieces, n_pieces, sp.runs, uint32_t(p.runs.size()),
+                            reinterpret_cast<const clg::DiffRef*>(sp.extra), e->d_dffirst.as<uint32_t>(),
+                            e->d_dfout.as<clg_diff>(), e->stream);
   }));
   HIPCHK(hipMemcpyAsync(e->h_dfout.p, e->d_dfout.p, size_t(n) * sizeof(clg_diff), hipMemcpyDeviceToHost, e->stream));
   CHK(e->sync());
@@ -3780,16 +3414,11 @@ int clg_slice_batch(clg_engine* e, const clg_slice_req* reqs, uint32_t n, clg_sl
   if (!(out_kind == CLG_MEM_DEVICE && (e->cfg.flags & CLG_F_ASYNC_SLICE))) e->settle();
   if (n && (!reqs || !res)) return fail(CLG_E_INVALID_ARG, "null argument");
   CHK(e->flush());
-  std::vector<clg::SegSpan> runs;
-  std::vector<uint32_t> segtab;
-  std::unordered_map<uint32_t, uint64_t> tab_of;  // log -> its segment indices in segtab
-  runs.reserve(n);
-  uint32_t n_pieces = 0;
+  clg_engine::RunPlan p(*e, n);
   const uint32_t C = e->C();
-  uint64_t dst = 0;
   for (uint32_t i = 0; i < n; ++i) {
     clg_slice_res& r = res[i];
-    r = clg_slice_res{CLG_OK, 0, 0, 0, dst};
+    r = clg_slice_res{CLG_OK, 0, 0, 0, p.total};
     const ChKey k{reqs[i].consumer.lo, reqs[i].consumer.hi};
     int32_t has = 0;
     int st = e->has_delta(reqs[i].log, k, reqs[i].epoch, &has);
@@ -3810,30 +3439,20 @@ int clg_slice_batch(clg_engine* e, const clg_slice_req* reqs, uint32_t n, clg_sl
       r.status = st;
       continue;
     }
-    if (dst + uint64_t(nb) > cap) {
+    if (p.total + uint64_t(nb) > cap) {
       // undo the consumer advance so the request can be retried with a bigger buffer
       e->logs[reqs[i].log].consumers[k].offset -= nb;
       r.status = CLG_E_CAPACITY;
       continue;
     }
     r.len = nb;
-    if (nb > 0) {
-      auto ti = tab_of.find(reqs[i].log);
-      if (ti == tab_of.end()) {
-        const auto& segs = e->logs[reqs[i].log].segs;
-        ti = tab_of.emplace(reqs[i].log, segtab.size()).first;
-        segtab.insert(segtab.end(), segs.begin(), segs.end());
-      }
-      runs.push_back(clg::SegSpan{ti->second, uint32_t(phys), uint32_t(nb), dst, n_pieces, 0});
-      n_pieces += uint32_t(phys + nb - 1) / C - uint32_t(phys) / C + 1;
-    }
-    dst += uint64_t(nb);
+    p.add(reqs[i].log, phys, nb, i);
   }
-  if (total) *total = dst;
+  if (total) *total = p.total;
   // dispatch order only: the same pieces, n_pieces as it was
   const long long gw = e->sw.gather_window;
-  clg::window_order(runs, C, gw < 0 ? clg::default_window(C) : uint32_t(std::min<long long>(gw, UINT32_MAX)));
-  return e->run_gather_runs(runs, segtab, n_pieces, dst, out, out_kind);
+  clg::window_order(p.runs, C, gw < 0 ? clg::default_window(C) : uint32_t(std::min<long long>(gw, UINT32_MAX)));
+  return e->run_gather_runs(p, out, out_kind);
 }
 
 int clg_consumer_seek(clg_engine* e, uint32_t h, clg_channel_id c, int64_t epoch, int32_t offset) {
@@ -3947,23 +3566,14 @@ int clg_decode_host(clg_engine* e, const uint8_t* bytes, const uint64_t* span_of
                     clg_decoded* out, uint64_t* span_rec_base) {
   ENGINE_GUARD(e);
   if (!out || (n && (!span_off || !span_len))) return fail(CLG_E_INVALID_ARG, "null argument");
-  uint64_t lo = UINT64_MAX, hi = 0, total = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (span_len[i] == 0) continue;
-    lo = std::min(lo, span_off[i]);
-    hi = std::max(hi, span_off[i] + span_len[i]);
-    total += span_len[i];
-  }
-  if (lo == UINT64_MAX) lo = hi = 0;
-  CHK(e->d_stage.ensure(hi - lo + 16));
-  CHK(e->h_stage.ensure(hi - lo + 16));
-  if (hi > lo) {
-    memcpy(e->h_stage.p, bytes + lo, hi - lo);
-    HIPCHK(hipMemcpyAsync(e->d_stage.p, e->h_stage.p, hi - lo, hipMemcpyHostToDevice, e->stream));
-  }
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; ++i) total += span_len[i];
+  const uint8_t* base;  // span i starts at base + (span_off[i] - base_off)
+  uint64_t base_off;
+  CHK(e->stage_spans(bytes, span_off, span_len, n, CLG_MEM_HOST, &base, &base_off));
   auto build = [&](clg_engine::DecodePlan& p, uint32_t T) {
     for (uint32_t i = 0; i < n; ++i)
-      e->plan_host_span(p, e->d_stage.as<uint8_t>() + (span_len[i] ? span_off[i] - lo : 0), span_len[i], i, T);
+      e->plan_host_span(p, base + (span_len[i] ? span_off[i] - base_off : 0), span_len[i], i, T);
   };
   return e->decode(build, total, out, span_rec_base);
 }

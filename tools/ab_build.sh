@@ -1,5 +1,7 @@
 # Build the engine library of a git revision (or the working tree, "wt") into ab/lib<name>.so
 # for A/B timing on one GPU box (tools/ab.sh).  usage: [AB_DEFS=-DX=1] tools/ab_build.sh <name> [rev | wt | dir]
+# The sources are whatever *.cpp and *.hip the tree being built holds in clonos_amd/csrc/, as in
+# clonos_amd/build.py, so one script builds revisions with different file layouts.
 set -euo pipefail
 root=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; rev=${2:-wt}
@@ -12,12 +14,12 @@ else
   src=/tmp/ab_wt_$name; rm -rf "$src"; mkdir -p "$src"
   git -C "$root" archive "$rev" clonos_amd include | tar -x -C "$src"
 fi
-objs=()
-for f in engine.cpp kernels.hip decode_fast.hip decode_fused.hip replay.hip encode.hip response.cpp digest.hip diff.hip; do
-  o=/tmp/ab_${name}_$f.o
-  /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w ${AB_DEFS:-} -I "$src/include" -c "$src/clonos_amd/csrc/$f" -o "$o" &
-  objs+=("$o")
+objs=(); pids=()
+for p in $(ls "$src"/clonos_amd/csrc/*.cpp "$src"/clonos_amd/csrc/*.hip | LC_ALL=C sort); do
+  o=/tmp/ab_${name}_$(basename "$p").o
+  /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w ${AB_DEFS:-} -I "$src/include" -c "$p" -o "$o" &
+  pids+=($!); objs+=("$o")
 done
-wait
+for pid in "${pids[@]}"; do wait "$pid"; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/ab/lib$name.so" "${objs[@]}"
 echo "$root/ab/lib$name.so"
