@@ -64,6 +64,7 @@ EXPORTED = [
     "clg_host_register", "clg_host_unregister",
     "clg_digest_logs", "clg_digest_spans", "clg_digest_host",
     "clg_diff_logs", "clg_lcp_host",
+    "clg_digest_prefixes", "clg_digest_epochs", "clg_digest_prefixes_host",
 ]
 
 
@@ -322,6 +323,9 @@ def _load() -> C.CDLL:
         "clg_digest_logs": (C.c_int, [P, P, P, C.c_uint32, P]),
         "clg_digest_spans": (C.c_int, [P, P, P, P, C.c_uint32, C.c_uint32, P]),
         "clg_digest_host": (C.c_int, [P, C.c_uint64, C.POINTER(Digest)]),
+        "clg_digest_prefixes": (C.c_int, [P, P, P, C.c_uint32, P, P, P]),
+        "clg_digest_epochs": (C.c_int, [P, P, P, C.c_uint32, C.c_uint64, P, P, P, u64p]),
+        "clg_digest_prefixes_host": (C.c_int, [P, C.c_uint64, P, C.c_uint32, P]),
         "clg_diff_logs": (C.c_int, [P, P, P, C.c_uint32, P, P, P, C.c_uint32, P]),
         "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),

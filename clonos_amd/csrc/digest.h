@@ -16,7 +16,8 @@
 // depend on the data.  This protects against accidents, not adversaries.
 //
 // Plain C++: compiles under hipcc (host and device) and under g++ without HIP
-// (tests/digest_host.cpp, where the power ladder's high bits are checked).
+// (tests/digest_host.cpp, where the power ladder's high bits are checked, and
+// tests/digest_prefix_host.cpp for the prefix digests at the end of this file).
 #pragma once
 #include <stdint.h>
 
@@ -104,6 +105,51 @@ CLG_DG_HD uint64_t dg_bytes(const uint8_t* b, uint64_t n) {
     h = dg_step(h, w);
   }
   return h;
+}
+
+// ---- prefix digests: the digest of b[0..c) at many cuts c_1 <= ... <= c_K in one pass ----------
+// With m(c) = ceil(c / 4), c_0 = 0 and D_0 = 0:
+//   D_j = D_{j-1} * R^(m(c_j) - m(c_{j-1})) + S_j  (mod p),
+//   S_j = sum_{c_{j-1} <= i < c_j} b_i * 2^(8 (i mod 4)) * R^(m(c_j) - 1 - floor(i / 4)),
+// the digest of the stretch [c_{j-1}, c_j) with c_{j-1} mod 4 zero bytes in front of it: the
+// stretch in the span's own word frame.  A word that a cut splits gives its low bytes to one
+// stretch and its high bytes to the next, with the same weight (the byte-linear form above).
+CLG_DG_HD uint32_t dg_words(uint64_t c) { return uint32_t((c + 3) >> 2); }
+
+// S of the stretch [c0, c1) of b (c0 <= c1; b is the span, not the stretch): word by word, the
+// bytes of a word outside the stretch taken as zero.
+CLG_DG_HD uint64_t dg_stretch(const uint8_t* b, uint64_t c0, uint64_t c1) {
+  uint64_t h = 0;
+  for (uint64_t k = c0 >> 2; 4 * k < c1; ++k) {
+    const uint64_t lo = 4 * k < c0 ? c0 : 4 * k, hi = 4 * k + 4 < c1 ? 4 * k + 4 : c1;
+    uint32_t w = 0;
+    for (uint64_t i = lo; i < hi; ++i) w |= uint32_t(b[i]) << (8 * (i & 3));
+    h = dg_step(h, w);
+  }
+  return h;
+}
+
+// The map x -> x * mul + add (mod p) that one cut applies to the digest before it; the maps of
+// consecutive cuts compose associatively, which is what lets a wave scan them.
+struct DgMap {
+  uint64_t mul, add;  // in [0, p)
+};
+CLG_DG_HD uint64_t dg_apply(DgMap f, uint64_t x) { return dg_add(dg_mul(x, f.mul), f.add); }
+// f first, then g
+CLG_DG_HD DgMap dg_then(DgMap f, DgMap g) { return DgMap{dg_mul(f.mul, g.mul), dg_add(dg_mul(f.add, g.mul), g.add)}; }
+
+// hash[j] / len[j] = the digest of the first min(cuts[j], n) bytes of b, cuts non-decreasing:
+// the recurrence, one pass over b.  (Cuts are 32 bits, so exponents stay inside the ladder.)
+CLG_DG_HD void dg_prefixes(const uint8_t* b, uint64_t n, const uint32_t* cuts, uint32_t n_cuts, uint64_t* hash,
+                           uint64_t* len) {
+  uint64_t d = 0, prev = 0;
+  for (uint32_t j = 0; j < n_cuts; ++j) {
+    const uint64_t c = cuts[j] < n ? cuts[j] : n;
+    if (c > prev) d = dg_apply(DgMap{dg_pow(dg_words(c) - dg_words(prev)), dg_stretch(b, prev, c)}, d);
+    hash[j] = d;
+    len[j] = c;
+    if (c > prev) prev = c;
+  }
 }
 
 }  // namespace clg

@@ -7,8 +7,17 @@
 //  * k_digest_runs     pass 2: a wave per run adds its pieces' partials (contiguous) mod p and
 //                      writes {hash, len}
 //
+// Prefix digests (digest.h, "prefix digests": a range's digest at many cuts) run the same two
+// passes over stretches -- a run per non-empty stretch between two cuts, digested in the range's
+// word frame: kLead instantiations, where a run has a lead-in of (previous cut) mod 4 zero
+// bytes and pass 2 writes the stretch's sum S to a scratch word -- and then
+//  * k_digest_chain    pass 3: a wave per request evaluates D_j = D_{j-1} R^dm_j + S_j over its
+//                      cuts, 64 cuts per round by a scan of (multiplier, addend) maps, and writes
+//                      {D_j, min(cut, len)} per cut; k_digest_chain_short, a thread per request
+//                      walking its cuts in turn, serves calls whose requests all have few cuts
+//
 // No atomics, no spin waits and no word taken from another running workgroup: the kernel
-// boundary orders the two passes, and the result is deterministic.
+// boundaries order the passes, and the result is deterministic.
 //
 // Pass 1 reads aligned 16-byte words and only those that hold a byte of the piece (as the
 // gather's copy_range does), so it never leaves the pages the piece lies on.  A lane's window is
@@ -65,8 +74,12 @@ __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
 
 }  // namespace
 
+// kLead: the runs are stretches of prefix digests, run k with lead[k] zero bytes in front of it
+// (the whole-log digest runs the instantiation without: no load, no add).
+template <bool kLead>
 __global__ __launch_bounds__(256) void k_digest_pieces(const GatherPiece* __restrict__ pieces, uint32_t n_pieces,
                                                        const SegSpan* __restrict__ runs, uint32_t n_runs,
+                                                       const uint32_t* __restrict__ lead,
                                                        const uint64_t* __restrict__ tab,
                                                        uint64_t* __restrict__ partial) {
   const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
@@ -76,9 +89,11 @@ __global__ __launch_bounds__(256) void k_digest_pieces(const GatherPiece* __rest
     if (lane == 0) partial[g] = 0;
     return;
   }
-  const SegSpan r = runs[dg_find_run(runs, n_runs, g)];
-  const uint32_t a = (uint32_t)(pc.dst - r.dst);  // the piece's first byte in its span
-  const uint32_t m = (r.len + 3u) >> 2;           // the span's words
+  const uint32_t ri = dg_find_run(runs, n_runs, g);
+  const SegSpan r = runs[ri];
+  const uint32_t ld = kLead ? lead[ri] : 0u;
+  const uint32_t a = (uint32_t)(pc.dst - r.dst) + ld;  // the piece's first byte in its span (its frame)
+  const uint32_t m = (r.len + ld + 3u) >> 2;           // the span's (the frame's) words
   const uint32_t k1 = (a + pc.len - 1u) >> 2;     // the piece's last logical word
   const uintptr_t src = (uintptr_t)pc.src, end = src + pc.len;
   const uintptr_t vbase = src - (a & 3u);         // where the piece's first logical word starts
@@ -139,9 +154,11 @@ __global__ __launch_bounds__(256) void k_digest_pieces(const GatherPiece* __rest
   if (lane == 0) partial[g] = dg_mul(acc, f);
 }
 
+// kSum: write the run's sum to sums[run index] (a stretch's S) instead of a row to out[run.pad]
+template <bool kSum>
 __global__ __launch_bounds__(256) void k_digest_runs(const SegSpan* __restrict__ runs, uint32_t n_runs,
                                                      uint32_t n_pieces, const uint64_t* __restrict__ partial,
-                                                     clg_digest* __restrict__ out) {
+                                                     clg_digest* __restrict__ out, uint64_t* __restrict__ sums) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (w >= n_runs) return;
   const SegSpan r = runs[w];
@@ -150,7 +167,66 @@ __global__ __launch_bounds__(256) void k_digest_runs(const SegSpan* __restrict__
   for (uint32_t i = r.first + lane; i < p1; i += 64u) acc = dg_add(acc, partial[i]);
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) acc = dg_add(acc, shfl_xor64(acc, o));
-  if (lane == 0) out[r.pad] = clg_digest{acc, r.len};
+  if (lane == 0) {
+    if (kSum) sums[w] = acc;
+    else out[r.pad] = clg_digest{acc, r.len};
+  }
+}
+
+namespace {
+
+__device__ __forceinline__ DgMap cut_map(const PrefixCut c, const uint64_t* __restrict__ tab,
+                                         const uint64_t* __restrict__ sums) {
+  return DgMap{dg_pow_lad(tab, c.dm), c.slot != kPrefixNoSlot ? sums[c.slot] : 0u};
+}
+
+}  // namespace
+
+// Pass 3, a wave per request: lane t of a round takes cut t's map x -> x R^dm + S, an inclusive
+// scan by shuffles composes the maps of the cuts up to it, and applying that to the carry (the
+// digest before the round) gives D at the cut; lane 63's goes into the next round.
+__global__ __launch_bounds__(256) void k_digest_chain(const uint64_t* __restrict__ first, uint32_t n_req,
+                                                      const PrefixCut* __restrict__ cuts,
+                                                      const uint64_t* __restrict__ tab,
+                                                      const uint64_t* __restrict__ sums,
+                                                      clg_digest* __restrict__ out) {
+  const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (w >= n_req) return;  // (wave-uniform)
+  const uint64_t k0 = first[w], k1 = first[w + 1u];
+  uint64_t carry = 0;
+  for (uint64_t base = k0; base < k1; base += 64u) {  // (wave-uniform trip count)
+    const uint64_t k = base + lane;
+    const bool live = k < k1;
+    PrefixCut c{0u, 0u, kPrefixNoSlot, 0u};
+    if (live) c = cuts[k];
+    DgMap f = live ? cut_map(c, tab, sums) : DgMap{1u, 0u};
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const DgMap g{(uint64_t)__shfl_up((unsigned long long)f.mul, o, 64),
+                    (uint64_t)__shfl_up((unsigned long long)f.add, o, 64)};
+      if (lane >= (uint32_t)o) f = dg_then(g, f);
+    }
+    const uint64_t d = dg_apply(f, carry);
+    if (live) out[k] = clg_digest{d, c.len};
+    carry = (uint64_t)__shfl((unsigned long long)d, 63, 64);  // (dead lanes hold the identity: d passes through)
+  }
+}
+
+// Pass 3 for a call whose requests all have few cuts (tens of thousands of logs with an epoch
+// or two each): a thread per request walks its cuts in turn.
+__global__ __launch_bounds__(256) void k_digest_chain_short(const uint64_t* __restrict__ first, uint32_t n_req,
+                                                            const PrefixCut* __restrict__ cuts,
+                                                            const uint64_t* __restrict__ tab,
+                                                            const uint64_t* __restrict__ sums,
+                                                            clg_digest* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_req) return;
+  uint64_t d = 0;
+  for (uint64_t k = first[i], k1 = first[i + 1u]; k < k1; ++k) {
+    const PrefixCut c = cuts[k];
+    d = dg_apply(cut_map(c, tab, sums), d);
+    out[k] = clg_digest{d, c.len};
+  }
 }
 
 void digest_table(uint64_t* tab) {
@@ -163,10 +239,30 @@ void digest_table(uint64_t* tab) {
 int launch_digest(const GatherPiece* d_pieces, uint32_t n_pieces, const SegSpan* d_runs, uint32_t n_runs,
                   const uint64_t* d_tab, uint64_t* d_partial, clg_digest* d_out, void* stream) {
   if (!n_pieces || !n_runs) return CLG_OK;
-  hipLaunchKernelGGL(k_digest_pieces, dim3((n_pieces + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_pieces, n_pieces,
-                     d_runs, n_runs, d_tab, d_partial);
-  hipLaunchKernelGGL(k_digest_runs, dim3((n_runs + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_runs, n_runs, n_pieces,
-                     d_partial, d_out);
+  hipLaunchKernelGGL(k_digest_pieces<false>, dim3((n_pieces + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_pieces,
+                     n_pieces, d_runs, n_runs, (const uint32_t*)nullptr, d_tab, d_partial);
+  hipLaunchKernelGGL(k_digest_runs<false>, dim3((n_runs + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_runs, n_runs,
+                     n_pieces, d_partial, d_out, (uint64_t*)nullptr);
+  return launch_status(hipGetLastError());
+}
+
+int launch_digest_prefixes(const GatherPiece* d_pieces, uint32_t n_pieces, const SegSpan* d_runs, uint32_t n_runs,
+                           const uint32_t* d_lead, const uint64_t* d_first, uint32_t n_req, const PrefixCut* d_cuts,
+                           bool few_cuts, const uint64_t* d_tab, uint64_t* d_partial, uint64_t* d_sums,
+                           clg_digest* d_out, void* stream) {
+  if (!n_req) return CLG_OK;
+  if (n_pieces && n_runs) {
+    hipLaunchKernelGGL(k_digest_pieces<true>, dim3((n_pieces + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_pieces,
+                       n_pieces, d_runs, n_runs, d_lead, d_tab, d_partial);
+    hipLaunchKernelGGL(k_digest_runs<true>, dim3((n_runs + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_runs, n_runs,
+                       n_pieces, d_partial, (clg_digest*)nullptr, d_sums);
+  }
+  if (few_cuts)
+    hipLaunchKernelGGL(k_digest_chain_short, dim3((n_req + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_first,
+                       n_req, d_cuts, d_tab, d_sums, d_out);
+  else
+    hipLaunchKernelGGL(k_digest_chain, dim3((n_req + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_first, n_req,
+                       d_cuts, d_tab, d_sums, d_out);
   return launch_status(hipGetLastError());
 }
 

@@ -273,6 +273,7 @@ struct clg_engine {
   PinBuf h_rout;  // replay-prep: the subpartition results, read back in one place (pinned)
   DevBuf d_plan;
   DevBuf d_dgtab, d_dgpart, d_dgout;  // log digest: the constant table (uploaded once), partials, results
+  DevBuf d_dgsum;                     // prefix digests: a sum per stretch
   PinBuf h_dgout;
   bool dgtab_ready = false;
   DevBuf d_dffirst, d_dfout;  // log comparison: a word per piece, results
@@ -1009,18 +1010,87 @@ struct clg_engine {
     return CLG_OK;
   }
 
+  // The digest kernels' constant table, uploaded once.
+  int ensure_dgtab() {
+    if (dgtab_ready) return CLG_OK;
+    uint64_t tab[clg::kDigestTabWords];
+    clg::digest_table(tab);
+    CHK(d_dgtab.ensure(sizeof(tab)));
+    HIPCHK(hipMemcpy(d_dgtab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
+    dgtab_ready = true;
+    return CLG_OK;
+  }
+
+  // Prefix digests (clg_digest_prefixes, clg_digest_epochs; digest.h): request i's cuts are
+  // cuts[first[i] .. first[i + 1]), first[0] = 0, already checked not to decrease; a row per cut
+  // into out.  Each non-empty stretch between two clamped cuts is one run (pad: its cut), so a
+  // request's bytes up to its largest cut are read once; empty stretches live only in the
+  // chain's per-cut table.  Staged behind the plan: first | cut table | lead-ins.
+  int digest_prefixes(const uint32_t* log, const int64_t* start_epoch, uint32_t n, const uint64_t* first,
+                      const uint32_t* cuts, clg_digest* out) {
+    const uint64_t K = first[n];
+    if (!K) return CLG_OK;
+    if (K >> 32) return fail(CLG_E_INVALID_ARG, "%llu cuts in one call", (unsigned long long)K);
+    RunPlan p(*this, uint32_t(K));
+    std::vector<clg::PrefixCut> tab(K);
+    std::vector<uint32_t> lead;
+    lead.reserve(K);
+    uint64_t most = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      Log* l;
+      CHK(get_log(log[i], &l));
+      int32_t s = 0, nb = 0;
+      if (l->depth != 0) CHK(determinants_range(*l, start_epoch[i], &s, &nb));
+      most = std::max(most, first[i + 1] - first[i]);
+      uint32_t prev = 0;
+      for (uint64_t k = first[i]; k < first[i + 1]; ++k) {
+        const uint32_t c = std::min(cuts[k], uint32_t(nb));
+        tab[k] = clg::PrefixCut{clg::dg_words(c) - clg::dg_words(prev), c, clg::kPrefixNoSlot, 0};
+        if (c > prev) {
+          tab[k].slot = uint32_t(p.runs.size());
+          lead.push_back(prev & 3u);
+          p.add(log[i], s + int32_t(prev), int32_t(c - prev), uint32_t(k));
+          prev = c;
+        }
+      }
+    }
+    if (p.runs.empty()) {  // every clamped cut is 0
+      memset(out, 0, size_t(K) * sizeof(clg_digest));
+      return CLG_OK;
+    }
+    CHK(flush());
+    const size_t fb = size_t(n + 1) * 8, cb = size_t(K) * sizeof(clg::PrefixCut), lb = lead.size() * 4;
+    std::vector<uint8_t> extra(fb + cb + lb);
+    memcpy(extra.data(), first, fb);
+    memcpy(extra.data() + fb, tab.data(), cb);
+    memcpy(extra.data() + fb + cb, lead.data(), lb);
+    StagedPlan sp;
+    CHK(stage_run_plan(p, DescSet{h_desc, d_desc, d_pieces}, stream, &sp, extra.data(), extra.size()));
+    CHK(ensure_dgtab());
+    const uint32_t n_runs = uint32_t(p.runs.size());
+    CHK(d_dgpart.ensure(size_t(p.n_pieces) * 8 + 8));
+    CHK(d_dgsum.ensure(size_t(n_runs) * 8));
+    CHK(d_dgout.ensure(size_t(K) * sizeof(clg_digest)));
+    CHK(h_dgout.ensure(size_t(K) * sizeof(clg_digest)));
+    CHK(timed("log_digest_prefix", p.total, [&] {
+      return clg::launch_digest_prefixes(
+          sp.pieces, p.n_pieces, sp.runs, n_runs, reinterpret_cast<const uint32_t*>(sp.extra + fb + cb),
+          reinterpret_cast<const uint64_t*>(sp.extra), n, reinterpret_cast<const clg::PrefixCut*>(sp.extra + fb),
+          most <= clg::kPrefixFewCuts, d_dgtab.as<uint64_t>(), d_dgpart.as<uint64_t>(), d_dgsum.as<uint64_t>(),
+          d_dgout.as<clg_digest>(), stream);
+    }));
+    HIPCHK(hipMemcpyAsync(h_dgout.p, d_dgout.p, size_t(K) * sizeof(clg_digest), hipMemcpyDeviceToHost, stream));
+    CHK(sync());
+    memcpy(out, h_dgout.p, size_t(K) * sizeof(clg_digest));
+    return CLG_OK;
+  }
+
   // The digest of every run (digest.hip), `n` results read back into out: out[run.pad] for a
   // run, {0, 0} for a request without one.  d_runs / d_pc: the runs and their pieces on the
   // device, queued on `stream`.
   int run_digest(const clg::SegSpan* d_runs, uint32_t n_runs, const clg::GatherPiece* d_pc, uint32_t n_pieces,
                  uint64_t bytes, uint32_t n, clg_digest* out) {
-    if (!dgtab_ready) {
-      uint64_t tab[clg::kDigestTabWords];
-      clg::digest_table(tab);
-      CHK(d_dgtab.ensure(sizeof(tab)));
-      HIPCHK(hipMemcpy(d_dgtab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
-      dgtab_ready = true;
-    }
+    CHK(ensure_dgtab());
     CHK(d_dgpart.ensure(size_t(n_pieces) * 8 + 8));
     CHK(d_dgout.ensure(size_t(n) * sizeof(clg_digest)));
     CHK(h_dgout.ensure(size_t(n) * sizeof(clg_digest)));
@@ -3346,6 +3416,77 @@ int clg_digest_spans(clg_engine* e, const uint8_t* bytes, const uint64_t* off, c
 int clg_digest_host(const uint8_t* bytes, uint64_t n, clg_digest* out) {
   if (!out || (n && !bytes)) return fail(CLG_E_INVALID_ARG, "null argument");
   *out = clg_digest{clg::dg_bytes(bytes, n), n};
+  return CLG_OK;
+}
+
+// The digest of getDeterminants(start_epoch[i]) of log[i] at each of the request's cuts
+// (digest.h, "prefix digests"), the range read once.  DeterminantResponseEvent.merge
+// (DeterminantResponseEvent.java:137-146) keeps the longest copy on its length alone and
+// ThreadCausalLogImpl.processUpstreamDelta drops what lies below its own offset unread: both
+// take the shorter copy for a prefix of the longer.  The holder of the longer copy can check
+// that with the other side's 16 bytes: its own digest at the other side's length.
+int clg_digest_prefixes(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                        const uint64_t* cut_first, const uint32_t* cuts, clg_digest* out) {
+  ENGINE_GUARD(e);
+  if (!cut_first || (n && (!log || !start_epoch))) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (cut_first[0] != 0) return fail(CLG_E_INVALID_ARG, "cut_first[0] is %llu", (unsigned long long)cut_first[0]);
+  for (uint32_t i = 0; i < n; ++i)
+    if (cut_first[i + 1] < cut_first[i]) return fail(CLG_E_INVALID_ARG, "cut_first decreases at request %u", i);
+  if (cut_first[n] && (!cuts || !out)) return fail(CLG_E_INVALID_ARG, "null argument");
+  for (uint32_t i = 0; i < n; ++i)
+    for (uint64_t k = cut_first[i] + 1; k < cut_first[i + 1]; ++k)
+      if (cuts[k] < cuts[k - 1]) return fail(CLG_E_INVALID_ARG, "cuts of request %u decrease", i);
+  return e->digest_prefixes(log, start_epoch, n, cut_first, cuts, out);
+}
+
+// Cuts at the range's own epoch ends: a row per epoch of the range, so two holders of a log can
+// name the first epoch in which their copies part without moving a log byte -- the check behind
+// the same merge by length (DeterminantResponseEvent.java:137-146) and offset dedup
+// (ThreadCausalLogImpl.processUpstreamDelta), epoch by epoch.  A depth-0 log and a log without
+// epochs have no rows.
+int clg_digest_epochs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n, uint64_t cap,
+                      uint64_t* first, int64_t* epoch_id, clg_digest* out, uint64_t* total) {
+  ENGINE_GUARD(e);
+  if (!first || (n && (!log || !start_epoch))) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (out && !epoch_id) return fail(CLG_E_INVALID_ARG, "null argument");
+  std::vector<uint32_t> cuts;
+  first[0] = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    Log* l;
+    CHK(e->get_log(log[i], &l));
+    uint64_t rows = 0;
+    if (l->depth != 0 && !l->epochs.empty()) {
+      int32_t s = 0, nb = 0;
+      CHK(e->determinants_range(*l, start_epoch[i], &s, &nb));
+      const auto* ep = l->epochs.find(start_epoch[i]);
+      if (ep == l->epochs.end()) ep = l->epochs.begin();
+      rows = uint64_t(l->epochs.end() - ep);
+      if (out && first[i] + rows <= cap) {
+        for (int32_t prev = s; ep != l->epochs.end(); ++ep) {
+          // an epoch ends where the next one starts, the last at the writer
+          const int32_t end = ep + 1 != l->epochs.end() ? (ep + 1)->offset : l->writer;
+          if (end < prev) return fail(CLG_E_STATE, "epoch %lld of log %u ends before it starts", (long long)ep->id, log[i]);
+          epoch_id[cuts.size()] = ep->id;
+          cuts.push_back(uint32_t(end - s));
+          prev = end;
+        }
+      }
+    }
+    first[i + 1] = first[i] + rows;
+  }
+  if (total) *total = first[n];
+  if (!out) return CLG_OK;
+  if (first[n] > cap) return fail(CLG_E_CAPACITY, "epoch digests need %llu rows", (unsigned long long)first[n]);
+  return e->digest_prefixes(log, start_epoch, n, first, cuts.data(), out);
+}
+
+int clg_digest_prefixes_host(const uint8_t* bytes, uint64_t n, const uint32_t* cuts, uint32_t n_cuts, clg_digest* out) {
+  if ((n_cuts && (!cuts || !out)) || (n && !bytes)) return fail(CLG_E_INVALID_ARG, "null argument");
+  for (uint32_t j = 1; j < n_cuts; ++j)
+    if (cuts[j] < cuts[j - 1]) return fail(CLG_E_INVALID_ARG, "cuts decrease at %u", j);
+  std::vector<uint64_t> hash(n_cuts), len(n_cuts);
+  clg::dg_prefixes(bytes, n, cuts, n_cuts, hash.data(), len.data());
+  for (uint32_t j = 0; j < n_cuts; ++j) out[j] = clg_digest{hash[j], len[j]};
   return CLG_OK;
 }
 

@@ -519,6 +519,25 @@ void digest_table(uint64_t* tab);
 // run's partials and writes {hash, len} to d_out[run.pad].
 int launch_digest(const GatherPiece* d_pieces, uint32_t n_pieces, const struct SegSpan* d_runs, uint32_t n_runs,
                   const uint64_t* d_tab, uint64_t* d_partial, ::clg_digest* d_out, void* stream);
+// Prefix digests (digest.h): one cut of a request, in the order of the cuts.  dm: words the
+// frame grows by from the cut before, m(cut) - m(previous cut); len: the cut clamped to the
+// range; slot: the run (the non-empty stretch from the previous cut) whose sum S the cut adds,
+// or kPrefixNoSlot for an empty stretch (S = 0).
+struct PrefixCut {
+  uint32_t dm, len, slot, pad;
+};
+constexpr uint32_t kPrefixNoSlot = 0xFFFFFFFFu;
+// A chain of at most this many cuts per request everywhere in a call is walked by one thread.
+constexpr uint32_t kPrefixFewCuts = 8;
+// Digest of a range at each of its cuts: the runs are the non-empty stretches between cuts
+// (d_lead[k]: run k's lead-in, its start in the range mod 4); pass 1 as launch_digest's in the
+// range's word frame, pass 2 writes run k's sum to d_sums[k], pass 3 chains request i's cuts
+// d_cuts[d_first[i] .. d_first[i + 1]) and writes a row per cut to d_out (few_cuts: every
+// request has at most kPrefixFewCuts).
+int launch_digest_prefixes(const GatherPiece* d_pieces, uint32_t n_pieces, const struct SegSpan* d_runs,
+                           uint32_t n_runs, const uint32_t* d_lead, const uint64_t* d_first, uint32_t n_req,
+                           const PrefixCut* d_cuts, bool few_cuts, const uint64_t* d_tab, uint64_t* d_partial,
+                           uint64_t* d_sums, ::clg_digest* d_out, void* stream);
 
 // ---- log comparison (diff.h, diff.hip) ---------------------------------------------
 // The reference span of a run (parallel to the runs): its device address and length.

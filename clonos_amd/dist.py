@@ -41,11 +41,19 @@ where the bytes live) lets the product check both without moving the bytes: Repl
 compares every replica with its owner at a quiescent point, merge_responses(verify=True) the
 received winners with what their ranks hold.  Replicator.locate then says where a flagged
 replica leaves its owner's log (clg_diff_logs on the fetched copy): only the flagged logs move.
+
+Prefixes.  The merge by length and the offset dedup both take the shorter copy of a log for a
+prefix of the longer one.  Prefix digests (clg_digest_prefixes: a log's digest at many cut
+lengths in one read) let the holder of the longer copy check that with the other side's 16
+bytes: Replicator.verify(prefixes=True) tells a lagging replica from a diverged one,
+Replicator.first_bad_epoch names the epoch in which two copies part from per-epoch rows
+(clg_digest_epochs), and merge_responses(verify="prefixes") checks every losing copy against
+the winner.  No log bytes move in any of them.
 """
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import itertools
@@ -75,6 +83,8 @@ assert SLICE_REQ.itemsize == C.sizeof(_lib.SliceReq) and SLICE_RES.itemsize == C
 assert DELTA_REQ.itemsize == C.sizeof(_lib.DeltaReq)
 # Replicator.verify's wire row, one per planned request: the owner's digest of the log
 VERIFY_ROW = np.dtype([("gid", "<i8"), ("len", "<u8"), ("hash", "<u8")])
+# Replicator.first_bad_epoch's wire row, one per epoch of an asked log: the digest up to its end
+EPOCH_ROW = np.dtype([("epoch", "<i8"), ("len", "<u8"), ("hash", "<u8")])
 
 
 def _align(n: int) -> int:
@@ -100,15 +110,40 @@ class ExchangeStats:
 @dataclass
 class VerifyReport:
     """Replicator.verify on one rank: the gids whose replica here is shorter / longer than the
-    owner's log, or of its length with another hash; `checked` replicas were compared."""
+    owner's log, or of its length with another hash; `checked` replicas were compared.
+    verify(prefixes=True) also fills short_diverged / long_diverged: the subsets of short / long
+    whose shorter copy is NOT a prefix of the longer one (the rest of `short` merely lag)."""
     short: List[int]
     long: List[int]
     differs: List[int]
     checked: int = 0
+    short_diverged: List[int] = field(default_factory=list)
+    long_diverged: List[int] = field(default_factory=list)
 
     @property
     def clean(self) -> bool:
         return not (self.short or self.long or self.differs)
+
+    @property
+    def diverged(self) -> List[int]:
+        """The gids whose copies hold different bytes somewhere in their common part."""
+        return sorted(set(self.differs) | set(self.short_diverged) | set(self.long_diverged))
+
+    def only_diverged(self) -> "VerifyReport":
+        """A report of the diverged gids alone, for Replicator.locate: lagging true prefixes
+        move no bytes."""
+        return VerifyReport(list(self.short_diverged), list(self.long_diverged), list(self.differs), self.checked,
+                            list(self.short_diverged), list(self.long_diverged))
+
+
+class EpochResult(dict):
+    """Replicator.first_bad_epoch's answer: gid -> the first epoch id in which the replica here
+    and the owner's log differ (None: every epoch row is equal); `unlocated`: the gids beyond
+    `limit` per owner rank, which were not compared."""
+
+    def __init__(self, items=(), unlocated=()):
+        super().__init__(items)
+        self.unlocated: List[int] = list(unlocated)
 
 
 @dataclass
@@ -210,6 +245,16 @@ class EngineIO:
         if tensor.is_cuda:
             return self.engine.digest_spans(tensor.data_ptr(), offs, lens, device=True)
         return self.engine.digest_spans(tensor.numpy(), offs, lens)
+
+    def digest_prefixes(self, handles: np.ndarray, start_epochs: np.ndarray, first: np.ndarray, cuts: np.ndarray
+                        ) -> np.ndarray:
+        """DIGEST rows of getDeterminants(start_epochs[i]) of handles[i] at its cut lengths
+        cuts[first[i] : first[i + 1]], not decreasing (clg_digest_prefixes)."""
+        return self.engine.digest_prefixes(handles, start_epochs, (first, cuts))[0]
+
+    def digest_epochs(self, handles: np.ndarray, start_epochs: np.ndarray):
+        """(first, epoch ids, DIGEST rows): a row per epoch of each range (clg_digest_epochs)."""
+        return self.engine.digest_epochs(handles, start_epochs)
 
     def diff(self, handles: np.ndarray, start_epochs: np.ndarray, tensor, offs: np.ndarray, lens: np.ndarray
              ) -> np.ndarray:
@@ -381,13 +426,23 @@ class Replicator:
         return st
 
 
-    def verify(self, start_epoch: int) -> VerifyReport:
+    def verify(self, start_epoch: int, prefixes: bool = False) -> VerifyReport:
         """Compare every replica with its owner's log from `start_epoch` by digest.  All ranks
         call it together at a quiescent point (after exchange, before new appends).  Each
         owner digests every log it sends, once; one all-to-all carries one row per planned
         request (gid, len, hash) with the header rows' static splits (ReplicationPlan.n_to /
         n_from); each receiver digests its replicas from the same epoch.  With one rank no
-        collective runs and the report is empty."""
+        collective runs and the report is empty.
+
+        prefixes=True (every rank passes the same value) also says whether the shorter copy
+        of a short / long pair is a prefix of the longer one -- a lagging replica, the benign
+        case, or a diverged one.  Whichever side holds the longer copy digests it at the other
+        side's length (io.digest_prefixes) and compares: the replica does so for `long` with
+        the row it already has; for `short` a second all-to-all carries the replicas'
+        (gid, len, hash) back to the owners (the same static splits, swapped), each owner
+        digests every sent log once at the distinct lengths its replicas reported, and a
+        third all-to-all returns one verdict byte per planned request.  short, long and
+        differs are what verify(start_epoch) gives."""
         import torch
         import torch.distributed as dist
         plan = self.plan
@@ -411,7 +466,7 @@ class Replicator:
         rr = vrecv.cpu().numpy().view(VERIFY_ROW)
         h = self.replica_handle[rr["gid"]]
         have = np.nonzero(h >= 0)[0]
-        if not len(have):
+        if not len(have) and not prefixes:
             return rep
         mine = self.io.digest(h[have].astype(np.uint32), np.full(len(have), start_epoch, np.int64))
         theirs = rr[have]
@@ -420,7 +475,121 @@ class Replicator:
         rep.long = gid[mine["len"] > theirs["len"]].tolist()
         rep.differs = gid[(mine["len"] == theirs["len"]) & (mine["hash"] != theirs["hash"])].tolist()
         rep.checked = len(have)
+        if not prefixes:
+            return rep
+        # long: this rank holds the longer copy -- its digest at the owner's length
+        lg = np.nonzero(mine["len"] > theirs["len"])[0]
+        if len(lg):
+            at = self.io.digest_prefixes(h[have][lg].astype(np.uint32), np.full(len(lg), start_epoch, np.int64),
+                                         np.arange(len(lg) + 1, dtype=np.uint64), theirs["len"][lg].astype(np.uint32))
+            rep.long_diverged = gid[lg[(at["hash"] != theirs["hash"][lg]) | (at["len"] != theirs["len"][lg])]].tolist()
+        # short: the owner holds the longer copy -- the replicas' rows go back, splits swapped
+        back = np.zeros(len(rr), VERIFY_ROW)
+        back["gid"] = -1  # (a log this rank keeps no replica of)
+        back["gid"][have] = gid
+        back["len"][have] = mine["len"]
+        back["hash"][have] = mine["hash"]
+        bsend = torch.from_numpy(back.view(np.uint8).copy()).to(dev)
+        brecv = torch.empty(nq * VERIFY_ROW.itemsize, dtype=torch.uint8, device=dev)
+        dist.all_to_all_single(brecv, bsend, output_split_sizes=(plan.n_to * VERIFY_ROW.itemsize).tolist(),
+                               input_split_sizes=(plan.n_from * VERIFY_ROW.itemsize).tolist(), group=self.group)
+        br = brecv.cpu().numpy().view(VERIFY_ROW)  # row k answers planned request k
+        verdict = np.zeros(nq, np.uint8)
+        ask = np.nonzero((br["gid"] >= 0) & (br["len"] < rows["len"]))[0] if nq else np.zeros(0, np.int64)
+        if len(ask):
+            if not np.array_equal(br["gid"][ask], plan.req_gid[ask]):
+                raise RuntimeError("verify: the replicas' rows do not follow the plan's requests")
+            # each sent log once, at the distinct lengths its replicas reported
+            pairs = np.unique(np.stack([plan.req_gid[ask], br["len"][ask].astype(np.int64)], axis=1), axis=0)
+            logs, first = np.unique(pairs[:, 0], return_index=True)
+            first = np.concatenate([first, [len(pairs)]]).astype(np.uint64)
+            at = self.io.digest_prefixes(self.handle[logs].astype(np.uint32), np.full(len(logs), start_epoch, np.int64),
+                                         first, pairs[:, 1].astype(np.uint32))
+            key = pairs[:, 0] * (1 << 32) + pairs[:, 1]  # (sorted: np.unique orders the rows)
+            row = np.searchsorted(key, plan.req_gid[ask] * (1 << 32) + br["len"][ask].astype(np.int64))
+            verdict[ask] = (at["hash"][row] != br["hash"][ask]) | (at["len"][row] != br["len"][ask])
+        vt = torch.empty(int(plan.n_from.sum()), dtype=torch.uint8, device=dev)
+        dist.all_to_all_single(vt, torch.from_numpy(verdict).to(dev), output_split_sizes=plan.n_from.tolist(),
+                               input_split_sizes=plan.n_to.tolist(), group=self.group)
+        bad = vt.cpu().numpy()[have] != 0
+        rep.short_diverged = gid[bad & (mine["len"] < theirs["len"])].tolist()
         return rep
+
+    def first_bad_epoch(self, start_epoch: int, gids: Sequence[int], limit: int = 8) -> "EpochResult":
+        """In which epoch does this rank's replica of each of `gids` part from its owner's log?
+        Collective: every rank calls it at the same quiescent point with the same `limit` and
+        its own gids (flagged by verify, say).  Owner and replica each digest the log at its
+        own epoch ends (io.digest_epochs: one row per epoch of getDeterminants(start_epoch),
+        the digest of the range up to that epoch's end) and the owner's rows come here:
+        three all-to-alls as locate does them -- the requests with static splits (`limit` gid
+        slots per rank pair, padded with -1), the row counts with the same splits, then the
+        rows with the splits the counts give.  The answer per gid is the first epoch id whose
+        rows (id, len, hash) differ -- a copy that merely lags differs in its last epoch --
+        or None when all are equal.  No log bytes move: 24 bytes per epoch and log.  Gids
+        beyond `limit` per owner rank are returned in `unlocated`.  With one rank no
+        collective runs."""
+        import torch
+        import torch.distributed as dist
+        plan = self.plan
+        world = plan.world
+        want = sorted({int(g) for g in gids})
+        if world == 1:
+            return EpochResult({}, want)
+        if limit < 1:
+            raise ValueError("limit must be at least 1")
+        if any(self.replica_handle[g] < 0 for g in want):
+            raise ValueError("first_bad_epoch: a gid this rank keeps no replica of")
+        owner = np.array([owner_rank(int(plan.table.vertex[g]), world) for g in want], np.int64)
+        ask = np.full((world, limit), -1, np.int64)
+        unlocated: List[int] = []
+        for r in range(world):
+            of_r = [g for g, o in zip(want, owner) if o == r]
+            ask[r, :len(of_r[:limit])] = of_r[:limit]
+            unlocated += of_r[limit:]
+        backend = dist.get_backend(self.group)
+        dev = self.device if backend == "nccl" else "cpu"
+        # 1. requests, static splits: asked[r] = the gids rank r wants from this rank
+        asked_t = torch.empty(world * limit, dtype=torch.int64, device=dev)
+        dist.all_to_all_single(asked_t, torch.from_numpy(ask.reshape(-1).copy()).to(dev), group=self.group)
+        asked = asked_t.cpu().numpy().reshape(world, limit)
+        live = asked >= 0
+        og = asked[live]
+        oh = self.handle[og] if len(og) else np.zeros(0, np.int64)
+        if len(og) and (oh < 0).any():
+            raise ValueError(f"asked for gids this rank does not send: {og[oh < 0][:8].tolist()}")
+        # 2. rows per slot, the same splits
+        n_out = np.zeros((world, limit), np.int64)
+        orow = np.zeros(0, EPOCH_ROW)
+        if len(og):
+            f, ids, dg = self.io.digest_epochs(oh.astype(np.uint32), np.full(len(og), start_epoch, np.int64))
+            n_out[live] = np.diff(np.asarray(f, np.int64))
+            orow = np.zeros(len(ids), EPOCH_ROW)
+            orow["epoch"], orow["len"], orow["hash"] = ids, dg["len"], dg["hash"]
+        n_t = torch.empty(world * limit, dtype=torch.int64, device=dev)
+        dist.all_to_all_single(n_t, torch.from_numpy(n_out.reshape(-1).copy()).to(dev), group=self.group)
+        n_in = n_t.cpu().numpy().reshape(world, limit)
+        # 3. the rows: by destination then slot, as digest_epochs returned them
+        to_b, from_b = n_out.sum(axis=1) * EPOCH_ROW.itemsize, n_in.sum(axis=1) * EPOCH_ROW.itemsize
+        rt = torch.empty(int(from_b.sum()), dtype=torch.uint8, device=dev)
+        dist.all_to_all_single(rt, torch.from_numpy(orow.view(np.uint8).copy()).to(dev),
+                               output_split_sizes=from_b.tolist(), input_split_sizes=to_b.tolist(), group=self.group)
+        theirs = rt.cpu().numpy().view(EPOCH_ROW)
+        filled = ask >= 0
+        got = ask[filled]
+        out = EpochResult({}, unlocated)
+        if not len(got):
+            return out
+        f, ids, dg = self.io.digest_epochs(self.replica_handle[got].astype(np.uint32),
+                                           np.full(len(got), start_epoch, np.int64))
+        f = np.asarray(f, np.int64)
+        tf = np.concatenate([[0], np.cumsum(n_in[filled])]).astype(np.int64)  # (row-major: owner rank then slot)
+        for k, g in enumerate(got.tolist()):
+            a = [(int(i), int(d["len"]), int(d["hash"])) for i, d in zip(ids[f[k]:f[k + 1]], dg[f[k]:f[k + 1]])]
+            b = [(int(r["epoch"]), int(r["len"]), int(r["hash"])) for r in theirs[tf[k]:tf[k + 1]]]
+            same = next((j for j, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+            rest = [x[0] for x in (a[same:same + 1] + b[same:same + 1])]
+            out[g] = min(rest) if rest else None
+        return out
 
 
     def locate(self, start_epoch: int, report: VerifyReport, limit: int = 8) -> "LocateResult":
@@ -579,7 +748,7 @@ def copy_arrays(copies) -> Tuple[np.ndarray, np.ndarray]:
 
 def merge_responses(io, table: LogTable, failed: Sequence[int], copies,
                     start_epochs: Dict[int, int], dest_of: Dict[int, int], device, group=None,
-                    timing: Optional[Dict[str, float]] = None, verify: bool = False) -> MergedCopies:
+                    timing: Optional[Dict[str, float]] = None, verify=False) -> MergedCopies:
     """Cross-GPU DeterminantResponseEvent.merge for the logs of the failed vertices.
 
     copies: gid -> io handle of this rank's copy (owned log or replica) of a log of a failed
@@ -598,7 +767,13 @@ def merge_responses(io, table: LogTable, failed: Sequence[int], copies,
     verify=True (off by default): each winning rank also digests its winners where they lie
     (io.digest) and the digests travel beside the lengths, one 8-byte hash per winner in a
     third collective; the destination digests the spans it received (io.digest_spans, device
-    input for a buffer in HBM) and raises RuntimeError on a mismatch."""
+    input for a buffer in HBM) and raises RuntimeError on a mismatch.
+
+    verify="prefixes" does all of that and checks the assumption of step 1 itself, that every
+    losing copy is a prefix of the winner: one all-gather carries each rank's (len, hash) per
+    log (len -1: not held), each winning rank digests its winners once at the distinct losing
+    lengths (io.digest_prefixes) and, after the last collective, raises RuntimeError naming
+    the gids and ranks whose copy is not a prefix of the winner this rank holds."""
     import time as _time
     import torch
     import torch.distributed as dist
@@ -657,6 +832,33 @@ def merge_responses(io, table: LogTable, failed: Sequence[int], copies,
     win_rank = np.where(win >= 0, win & 0xFF, -1)
     win_len = np.where(win >= 0, win >> 8, 0)
     mine = np.nonzero(win_rank == rank)[0]
+    not_prefix: List[Tuple[int, int]] = []  # (gid, rank) of losing copies that are no prefix of this rank's winner
+    if verify == "prefixes":
+        said = np.full((max(n, 1), 2), -1, np.int64)
+        if len(held):
+            dg = io.digest(handles, epochs)
+            said[held, 0] = dg["len"].astype(np.int64)
+            said[held, 1] = np.ascontiguousarray(dg["hash"]).view(np.int64)
+        st = torch.from_numpy(said).to(dev)
+        every = [torch.empty_like(st) for _ in range(world)]
+        dist.all_gather(every, st, group=group)
+        every = np.stack([t.cpu().numpy() for t in every])[:, :n]  # [rank, log, (len, hash)]
+        if len(mine):
+            sel = np.searchsorted(held, mine)
+            lens_l = every[:, mine, 0]  # [rank, winner]
+            lose = (lens_l >= 0) & (np.arange(world)[:, None] != rank)
+            cuts = [np.unique(lens_l[lose[:, j], j]) for j in range(len(mine))]
+            first = np.concatenate([[0], np.cumsum([len(c) for c in cuts])]).astype(np.uint64)
+            flat = np.concatenate(cuts).astype(np.uint32) if len(cuts) else np.zeros(0, np.uint32)
+            if len(flat):
+                at = io.digest_prefixes(handles[sel], epochs[sel], first, flat)
+                for j in range(len(mine)):
+                    c = cuts[j]
+                    for r in np.nonzero(lose[:, j])[0]:
+                        k = int(first[j]) + int(np.searchsorted(c, lens_l[r, j]))
+                        if (int(at["len"][k]) != int(lens_l[r, j])
+                                or int(at["hash"][k]) != int(every[r, mine[j], 1].view(np.uint64))):
+                            not_prefix.append((int(gids[mine[j]]), int(r)))
     order = mine[np.argsort(dest[mine], kind="stable")]  # by destination, then log order
     send_split = np.bincount(dest[mine], weights=win_len[mine], minlength=world).astype(np.int64)
     inbound = np.nonzero((win_rank >= 0) & (dest == rank))[0]
@@ -688,6 +890,9 @@ def merge_responses(io, table: LogTable, failed: Sequence[int], copies,
         hr = torch.empty(len(recv), dtype=torch.int64, device=dev)
         dist.all_to_all_single(hr, ht, output_split_sizes=n_from.tolist(), input_split_sizes=n_to.tolist(), group=group)
         _check_winners(io, buf, gids[recv], offs, lens, hr.cpu().numpy().view(np.uint64))
+    if not_prefix:
+        raise RuntimeError("merged winners are not extensions of every other copy: (gid, rank) "
+                           f"{not_prefix[:8]} hold bytes that are no prefix of the winner")
     return MergedCopies(buf, gids=gids[recv], offs=offs, lens=lens, ranks=win_rank[recv])
 
 

@@ -160,6 +160,39 @@ def _np_ptr(a: np.ndarray) -> int:
     return a.ctypes.data if a.size else 0
 
 
+def _flat_cuts(cuts, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """cuts as a list of n arrays, or a (first, flat) pair -> (first uint64[n + 1], flat uint32)."""
+    if isinstance(cuts, tuple) and len(cuts) == 2 and np.ndim(cuts[0]) == 1 and len(cuts[0]) == n + 1:
+        first = np.ascontiguousarray(cuts[0], np.uint64)
+        wide = np.asarray(cuts[1])
+    else:
+        per = [np.asarray(c).reshape(-1) for c in cuts]
+        if len(per) != n:
+            raise ValueError("one array of cuts per request")
+        first = np.zeros(n + 1, np.uint64)
+        np.cumsum([c.size for c in per], out=first[1:])
+        wide = np.concatenate(per) if per else np.zeros(0, np.uint32)
+    wide = wide.reshape(-1)
+    if wide.size and (int(wide.min()) < 0 or int(wide.max()) >> 32):
+        raise ValueError("cuts must fit 32 bits")
+    if first[0] != 0 or int(first[-1]) != wide.size or (np.diff(first.astype(np.int64)) < 0).any():
+        raise ValueError("first must start at 0, not decrease and end at the number of cuts")
+    return first, np.ascontiguousarray(wide, np.uint32)
+
+
+def digest_prefixes_host(data: Union[bytes, np.ndarray], cuts) -> np.ndarray:
+    """clg_digest_prefixes_host: a DIGEST row per cut, the digest of the first min(cut, len) bytes
+    of host bytes, on the CPU in one pass (no engine, no GPU) -- what Engine.digest_prefixes
+    computes on the device.  Cuts must not decrease."""
+    buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(
+        data, np.uint8)
+    _, c = _flat_cuts([cuts], 1)
+    out = np.zeros(c.size, DIGEST)
+    check(lib.clg_digest_prefixes_host(buf.ctypes.data if buf.size else None, buf.size, _np_ptr(c), c.size,
+                                       _np_ptr(out)))
+    return out
+
+
 class Engine:
     """One engine per GPU (one process per GPU).  Owns the HBM segment pool."""
 
@@ -719,6 +752,43 @@ class Engine:
             ptr, kind = (keep.ctypes.data if keep.size else None), _lib.CLG_MEM_HOST
         check(lib.clg_digest_spans(self._h, ptr, _np_ptr(so), _np_ptr(sl), so.size, kind, _np_ptr(out)))
         return out
+
+    def digest_prefixes(self, handles, start_epochs, cuts) -> Tuple[np.ndarray, np.ndarray]:
+        """Digest of getDeterminants(start_epochs[i]) of log handles[i] at each of its cuts, the
+        range read once: cuts is a list of arrays (one per request, not decreasing) or a
+        (first, flat) tuple.  Returns (rows, first): DIGEST row k, first[i] <= k < first[i + 1],
+        is the digest of the first min(cut, len) bytes of request i's range.  The holder of a
+        longer copy checks with it that a shorter copy is a prefix: its own row at the other
+        side's length must equal the other side's whole digest."""
+        h = np.ascontiguousarray(handles, np.uint32)
+        ep = np.ascontiguousarray(start_epochs, np.int64)
+        if h.shape != ep.shape or h.ndim != 1:
+            raise ValueError("handles and start_epochs must be 1-d and of equal length")
+        first, flat = _flat_cuts(cuts, h.size)
+        out = np.zeros(flat.size, DIGEST)
+        check(lib.clg_digest_prefixes(self._h, _np_ptr(h), _np_ptr(ep), h.size, _np_ptr(first), _np_ptr(flat),
+                                      _np_ptr(out)))
+        return out, first
+
+    def digest_epochs(self, handles, start_epochs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Digests at the range's own epoch ends: (first, epoch_ids, rows); rows first[i] ..
+        first[i + 1] are request i's, one per epoch of its range in order, each the digest of the
+        range up to that epoch's end (the last is digest_logs' row).  Two copies of a log part
+        in the first epoch whose rows differ."""
+        h = np.ascontiguousarray(handles, np.uint32)
+        ep = np.ascontiguousarray(start_epochs, np.int64)
+        if h.shape != ep.shape or h.ndim != 1:
+            raise ValueError("handles and start_epochs must be 1-d and of equal length")
+        first = np.zeros(h.size + 1, np.uint64)
+        total = C.c_uint64(0)
+        check(lib.clg_digest_epochs(self._h, _np_ptr(h), _np_ptr(ep), h.size, 0, _np_ptr(first), None, None,
+                                    C.byref(total)))
+        ids = np.zeros(total.value, np.int64)
+        out = np.zeros(total.value, DIGEST)
+        if total.value:
+            check(lib.clg_digest_epochs(self._h, _np_ptr(h), _np_ptr(ep), h.size, total.value, _np_ptr(first),
+                                        _np_ptr(ids), _np_ptr(out), C.byref(total)))
+        return first, ids, out
 
     # ---- log comparison (clg_diff_logs) -------------------------------------------------------
     def diff_logs(self, handles, start_epochs, data_or_ptr, offs, lens, device: bool = False) -> np.ndarray:

@@ -506,6 +506,32 @@ int clg_digest_spans(clg_engine* e, const uint8_t* bytes, const uint64_t* off, c
                      uint32_t in_kind, clg_digest* out);
 /* The same digest of host bytes on the CPU (no engine, no GPU). */
 int clg_digest_host(const uint8_t* bytes, uint64_t n, clg_digest* out);
+/* Prefix digests: a range's digest at many cut lengths, the range read once (the hash is a
+ * polynomial in R, so the digest of a prefix falls out of the same pass).
+ * out[k], cut_first[i] <= k < cut_first[i+1] (cut_first[0] = 0): the digest of the first
+ * min(cuts[k], len_i) bytes of getDeterminants(start_epoch[i]) of log[i].  A cut past the end
+ * clamps (the row's len then says so), a cut at the end gives clg_digest_logs' row, a cut of 0
+ * gives {0, 0}.  Range rules and errors are clg_digest_logs'; cuts of one request must not
+ * decrease (CLG_E_INVALID_ARG names the request; nothing is written).  What this lets a caller
+ * check: DeterminantResponseEvent.merge (DeterminantResponseEvent.java:137-146) keeps the
+ * longest copy of a log and ThreadCausalLogImpl.processUpstreamDelta skips what lies below its
+ * own offset, both on the assumption that the shorter copy is a prefix of the longer one; the
+ * holder of the longer copy compares its digest at the other side's length with the 16 bytes
+ * the other side sent. */
+int clg_digest_prefixes(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                        const uint64_t* cut_first, const uint32_t* cuts, clg_digest* out);
+/* Cuts at the range's own epoch ends: one row per epoch of the range, in order:
+ * epoch_id[k], out[k] = the digest of the range up to the end of that epoch (the last row of a
+ * request is clg_digest_logs' row; an empty epoch repeats the row before it; a depth-0 log and
+ * a log without epochs have no rows).  first[i]..first[i+1] are request i's rows (n + 1
+ * entries); *total rows in all; more than cap: CLG_E_CAPACITY with *total set; out == NULL:
+ * sizes only.  Two holders of a log whose rows differ first at epoch E parted in epoch E: the
+ * same prefix assumption (DeterminantResponseEvent.java:137-146, ThreadCausalLogImpl's offset
+ * dedup) checked epoch by epoch with no log bytes moved. */
+int clg_digest_epochs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n, uint64_t cap,
+                      uint64_t* first, int64_t* epoch_id, clg_digest* out, uint64_t* total);
+/* CPU: the same rows for one span of host bytes, in one pass over it (no engine, no GPU). */
+int clg_digest_prefixes_host(const uint8_t* bytes, uint64_t n, const uint32_t* cuts, uint32_t n_cuts, clg_digest* out);
 
 /* ---- log comparison ---------------------------------------------------------------------------
  * Where two copies of a log part, not only whether they do.  lcp is the number of leading bytes

@@ -360,6 +360,75 @@ JNIEXPORT jint JNICALL FN(nDiffLogs)(JNIEnv* env, jclass cls, jlong e, jintArray
   return s;
 }
 
+/* clg_digest_prefixes: request i's cuts are cuts[cutFirst[i] .. cutFirst[i + 1]) (n + 1 longs);
+ * out = {hash, len} per cut (2 longs each). */
+JNIEXPORT jint JNICALL FN(nDigestPrefixes)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray starts,
+                                           jlongArray cutFirst, jintArray cuts, jlongArray out) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs), k = (*env)->GetArrayLength(env, cuts);
+  if ((*env)->GetArrayLength(env, starts) < n || (*env)->GetArrayLength(env, cutFirst) < n + 1 ||
+      (*env)->GetArrayLength(env, out) < 2 * k)
+    return CLG_E_INVALID_ARG;
+  clg_digest* d = (clg_digest*)calloc((size_t)k + 1, sizeof(clg_digest));
+  if (!d) return CLG_E_INVALID_ARG;
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* st = (*env)->GetLongArrayElements(env, starts, NULL);
+  jlong* cf = (*env)->GetLongArrayElements(env, cutFirst, NULL);
+  jint* ct = (*env)->GetIntArrayElements(env, cuts, NULL);
+  int s = cf[n] == (jlong)k ? clg_digest_prefixes(ENG(e), (const uint32_t*)lg, (const int64_t*)st, (uint32_t)n,
+                                                  (const uint64_t*)cf, (const uint32_t*)ct, d)
+                            : CLG_E_INVALID_ARG;
+  (*env)->ReleaseIntArrayElements(env, cuts, ct, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, cutFirst, cf, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, starts, st, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  if (s == CLG_OK) (*env)->SetLongArrayRegion(env, out, 0, 2 * k, (const jlong*)d);
+  free(d);
+  return s;
+}
+
+/* clg_digest_epochs: first = n + 1 longs, total = 1 long; epochIds / out null: sizes only,
+ * otherwise room for epochIds.length rows: ids and {hash, len} (2 longs) per row. */
+JNIEXPORT jint JNICALL FN(nDigestEpochs)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray starts,
+                                         jlongArray first, jlongArray epochIds, jlongArray out, jlongArray total) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  const jsize cap = epochIds && out ? (*env)->GetArrayLength(env, epochIds) : 0;
+  if ((*env)->GetArrayLength(env, starts) < n || (*env)->GetArrayLength(env, first) < n + 1 ||
+      (*env)->GetArrayLength(env, total) < 1 || (cap && (*env)->GetArrayLength(env, out) < 2 * cap))
+    return CLG_E_INVALID_ARG;
+  const int sizes_only = !(epochIds && out);
+  clg_digest* d = (clg_digest*)calloc((size_t)cap + 1, sizeof(clg_digest));
+  int64_t* ids = (int64_t*)calloc((size_t)cap + 1, sizeof(int64_t));
+  uint64_t* fs = (uint64_t*)calloc((size_t)n + 1, sizeof(uint64_t));
+  if (!d || !ids || !fs) {
+    free(d);
+    free(ids);
+    free(fs);
+    return CLG_E_INVALID_ARG;
+  }
+  uint64_t tot = 0;
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* st = (*env)->GetLongArrayElements(env, starts, NULL);
+  int s = clg_digest_epochs(ENG(e), (const uint32_t*)lg, (const int64_t*)st, (uint32_t)n, (uint64_t)cap, fs,
+                            sizes_only ? NULL : ids, sizes_only ? NULL : d, &tot);
+  (*env)->ReleaseLongArrayElements(env, starts, st, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  const jlong t = (jlong)tot;
+  (*env)->SetLongArrayRegion(env, total, 0, 1, &t);
+  if (s == CLG_OK) {
+    (*env)->SetLongArrayRegion(env, first, 0, n + 1, (const jlong*)fs);
+    if (!sizes_only) {
+      (*env)->SetLongArrayRegion(env, epochIds, 0, (jsize)tot, (const jlong*)ids);
+      (*env)->SetLongArrayRegion(env, out, 0, 2 * (jsize)tot, (const jlong*)d);
+    }
+  }
+  free(d);
+  free(ids);
+  free(fs);
+  return s;
+}
+
 /* clg_log_get_id: out = {vertexId, isMain, irpLower, irpUpper, subpartition, job}. */
 JNIEXPORT jint JNICALL FN(nLogGetId)(JNIEnv* env, jclass cls, jlong e, jint log, jlongArray out) {
   (void)cls;

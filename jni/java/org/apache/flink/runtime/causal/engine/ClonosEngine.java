@@ -116,6 +116,33 @@ public final class ClonosEngine implements AutoCloseable {
 		return out;
 	}
 
+	/** The digests of getDeterminants(startEpochs[i]) of logs[i] at each of its cut lengths
+	 *  cuts[cutFirst[i] .. cutFirst[i + 1]) (not decreasing; unsigned), the range read once
+	 *  (clg_digest_prefixes): 2 longs per cut, {hash, min(cut, length)}.  The holder of the longer copy of
+	 *  a log checks with it that the shorter copy is a prefix: its row at the other side's length must
+	 *  equal the other side's digest -- what the merge by length (DeterminantResponseEvent.java:137-146)
+	 *  and processUpstreamDelta's offset dedup take for granted. */
+	public long[] digestPrefixes(int[] logs, long[] startEpochs, long[] cutFirst, int[] cuts) {
+		long[] out = new long[2 * cuts.length];
+		check(nDigestPrefixes(handle, logs, startEpochs, cutFirst, cuts, out));
+		return out;
+	}
+
+	/** One row per epoch of getDeterminants(startEpochs[i]) of logs[i], the digest of the range up to that
+	 *  epoch's end (clg_digest_epochs).  Returns {first (n + 1 longs), epochIds, rows (2 longs each)}:
+	 *  request i's rows are first[i] .. first[i + 1].  Two copies part in the first epoch whose rows differ. */
+	public long[][] digestEpochs(int[] logs, long[] startEpochs) {
+		long[] first = new long[logs.length + 1];
+		long[] total = new long[1];
+		check(nDigestEpochs(handle, logs, startEpochs, first, null, null, total));
+		long[] ids = new long[(int) total[0]];
+		long[] out = new long[2 * ids.length];
+		if (ids.length > 0) {
+			check(nDigestEpochs(handle, logs, startEpochs, first, ids, out, total));
+		}
+		return new long[][] {first, ids, out};
+	}
+
 	@Override
 	public void close() {
 		nDestroy(handle);
@@ -247,6 +274,13 @@ public final class ClonosEngine implements AutoCloseable {
 	 *  direct[offs[i], offs[i] + lens[i]) (3 n longs). */
 	static native int nDiffLogs(long engine, int[] logs, long[] startEpochs, ByteBuffer direct, long[] offs, long[] lens,
 								long[] out);
+	/** clg_digest_prefixes: out = {hash, len} per cut (2 longs each), cuts[cutFirst[i] .. cutFirst[i + 1]) request i's. */
+	static native int nDigestPrefixes(long engine, int[] logs, long[] startEpochs, long[] cutFirst, int[] cuts,
+									  long[] out);
+	/** clg_digest_epochs: first = n + 1 longs, total = 1 long; epochIds and out null: sizes only, otherwise room
+	 *  for epochIds.length rows (out: 2 longs per row). */
+	static native int nDigestEpochs(long engine, int[] logs, long[] startEpochs, long[] first, long[] epochIds,
+									long[] out, long[] total);
 	/** out = {vertexId, isMain, irpLower, irpUpper, subpartition, job}. */
 	static native int nLogGetId(long engine, int log, long[] out);
 	static native int nEnrichBatch(long engine, int strategy, long[] requests, int[] logs, byte[] flags,
