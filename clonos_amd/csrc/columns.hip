@@ -1,0 +1,303 @@
+// columns.hip -- typed replay columns (columns.h): the stable partition of a decoded batch by
+// determinant class, computed where the records already are.
+//
+//  * k_col_count     pass 1: a workgroup per tile of kColTile records reads the tags only (one
+//                    16-byte load per thread) and writes the tile's count per class and its
+//                    number of tags above 7
+//  * k_col_scan      pass 2: ONE workgroup loops over all tiles' counts (config 2's 64 M records
+//                    are 16 K tiles: 16 rounds, no look-back) and writes the exclusive per-class
+//                    base of every tile; the totals and the first tile with a tag above 7 go to
+//                    pinned memory, which the host reads before anything is written to the caller
+//  * k_col_write     pass 3: a workgroup per tile reads the tags again and v0, ranks each record
+//                    within its class (ballot and mbcnt in the wave, the waves' totals through
+//                    LDS) and stores the narrowed value at tile base + rank
+//  * k_col_span_base a wave per span boundary: the base of the tile that holds the boundary's
+//                    record plus the class counts of the tags before it inside the tile
+//  * k_col_wide_v0   a thread per side row: w_v0[k] = v0[w_idx[k]]
+//  * k_col_find_bad  one wave: the lowest record of a tile whose tag is above 7
+//
+// No atomics, no spin waits and no word taken from another running workgroup: kernel boundaries
+// order the passes, and the result is deterministic.
+//
+// In k_col_write a thread's 16 records are kColThreads apart (record k * 256 + thread), so a
+// wave's tag and v0 loads are contiguous and, in every round, its lanes of one class store to
+// adjacent addresses.  The order column is written with per-lane byte stores.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/clonos_engine.h"
+#include "columns.h"
+#include "kernels.h"
+
+namespace clg {
+
+namespace {
+
+constexpr uint32_t kColWaves = kColThreads / 64;
+constexpr uint32_t kColChunks = kColPerThread * kColWaves;  // a tile's (round, wave) chunks, in record order
+static_assert(kColChunks == 64, "the chunk counts are scanned by one wave");
+
+__device__ __forceinline__ uint32_t col_lane_rank(uint64_t m) {  // set bits of m below this lane
+  return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
+}
+
+__device__ __forceinline__ uint32_t col_wave_sum(uint32_t x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o, 64);
+  return x;
+}
+
+__device__ __forceinline__ uint32_t col_wave_incl(uint32_t x, uint32_t lane) {
+#pragma unroll
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
+    if (lane >= o) x += y;
+  }
+  return x;
+}
+
+}  // namespace
+
+// counts[tile * kColCountWords + c]: records of class c (c < 5), tags above 7 (c == 5).
+__global__ __launch_bounds__(kColThreads) void k_col_count(const uint8_t* __restrict__ tag, uint64_t n,
+                                                          uint32_t* __restrict__ counts) {
+  __shared__ uint32_t ws[kColWaves][6];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint64_t i0 = uint64_t(blockIdx.x) * kColTile + uint64_t(tid) * kColPerThread;
+  // a count per class in 8-bit fields (at most 16 each)
+  uint64_t acc = 0;
+  if (i0 + kColPerThread <= n && ((uintptr_t)(tag + i0) & 15) == 0) {
+    const uint4 v = *reinterpret_cast<const uint4*>(tag + i0);
+    const uint32_t q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc += 1ull << (8u * col_class((q[j] >> (8 * b)) & 0xFFu));
+  } else {  // the batch's last records, or a tag array that is not 16-byte aligned
+    for (uint32_t j = 0; j < kColPerThread; ++j)
+      if (i0 + j < n) acc += 1ull << (8u * col_class(tag[i0 + j]));
+  }
+#pragma unroll
+  for (uint32_t c = 0; c < 6; ++c) {
+    const uint32_t s = col_wave_sum(uint32_t(acc >> (8u * c)) & 0xFFu);
+    if (lane == 0) ws[w][c] = s;
+  }
+  __syncthreads();
+  if (tid < kColCountWords) {
+    uint32_t s = 0;
+    if (tid < 6)
+      for (uint32_t k = 0; k < kColWaves; ++k) s += ws[k][tid];
+    counts[size_t(blockIdx.x) * kColCountWords + tid] = s;
+  }
+}
+
+__global__ __launch_bounds__(kColScanThreads) void k_col_scan(const uint32_t* __restrict__ counts, uint32_t n_tiles,
+                                                             uint64_t* __restrict__ base, ColRes* __restrict__ res) {
+  constexpr uint32_t kW = kColScanThreads / 64;
+  __shared__ uint32_t ws[kW][kColClasses];
+  __shared__ uint32_t wtot[kColClasses];
+  __shared__ uint32_t wbad[kW];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  uint64_t carry[kColClasses] = {0, 0, 0, 0, 0};
+  uint32_t bad = ~0u;  // this thread's first tile with a tag above 7
+  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kColScanThreads) {
+    const uint32_t t = t0 + tid;
+    uint32_t c[kColClasses], inc[kColClasses];
+#pragma unroll
+    for (uint32_t k = 0; k < kColClasses; ++k) c[k] = 0;
+    if (t < n_tiles) {
+      const uint4 lo = *reinterpret_cast<const uint4*>(counts + size_t(t) * kColCountWords);
+      const uint2 hi = *reinterpret_cast<const uint2*>(counts + size_t(t) * kColCountWords + 4);
+      c[0] = lo.x, c[1] = lo.y, c[2] = lo.z, c[3] = lo.w, c[4] = hi.x;
+      if (hi.y && t < bad) bad = t;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kColClasses; ++k) {
+      inc[k] = col_wave_incl(c[k], lane);
+      if (lane == 63) ws[w][k] = inc[k];
+    }
+    __syncthreads();
+    if (tid < 64) {  // the waves' totals -> their exclusive prefix, and the round's total
+#pragma unroll
+      for (uint32_t k = 0; k < kColClasses; ++k) {
+        const uint32_t x = lane < kW ? ws[lane][k] : 0u;
+        const uint32_t s = col_wave_incl(x, lane);
+        if (lane < kW) ws[lane][k] = s - x;
+        if (lane == kW - 1) wtot[k] = s;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < kColClasses; ++k) {
+      if (t < n_tiles) base[size_t(t) * kColClasses + k] = carry[k] + ws[w][k] + (inc[k] - c[k]);
+      carry[k] += wtot[k];  // (a round holds at most kColScanThreads * kColTile records: 32 bits)
+    }
+    __syncthreads();  // (ws is written again in the next round)
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint32_t x = (uint32_t)__shfl_xor((int)bad, o, 64);
+    bad = x < bad ? x : bad;
+  }
+  if (lane == 0) wbad[w] = bad;
+  __syncthreads();
+  if (tid == 0) {
+    for (uint32_t j = 1; j < kW; ++j) bad = wbad[j] < bad ? wbad[j] : bad;
+    for (uint32_t k = 0; k < kColClasses; ++k) res->total[k] = carry[k];
+    res->bad_tile = bad == ~0u ? kColNoTile : uint64_t(bad);
+  }
+}
+
+struct ColLimits {
+  uint64_t n[4];  // the class totals the host checked against the capacities: no store at or past them
+};
+
+__global__ __launch_bounds__(kColThreads) void k_col_write(const uint8_t* __restrict__ tag, const int64_t* __restrict__ v0,
+                                                          uint64_t n, const uint64_t* __restrict__ base, ColOut out,
+                                                          ColLimits lim) {
+  __shared__ uint32_t cnt[kColChunks][4];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint64_t i0 = uint64_t(blockIdx.x) * kColTile;
+  uint32_t cls[kColPerThread];
+  int64_t v[kColPerThread];
+#pragma unroll
+  for (uint32_t k = 0; k < kColPerThread; ++k) {
+    const uint64_t i = i0 + k * kColThreads + tid;
+    cls[k] = i < n ? col_class(tag[i]) : kColBad;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < kColPerThread; ++k) {
+    const uint64_t i = i0 + k * kColThreads + tid;
+    v[k] = cls[k] < kColWide ? v0[i] : 0;  // (wide records' v0 goes to w_v0: k_col_wide_v0)
+  }
+  // the chunks' counts, then their exclusive prefix in record order (round-major, then wave)
+#pragma unroll
+  for (uint32_t k = 0; k < kColPerThread; ++k) {
+#pragma unroll
+    for (uint32_t c = 0; c < 4; ++c) {
+      const uint64_t m = __ballot(cls[k] == c);
+      if (lane == 0) cnt[k * kColWaves + w][c] = (uint32_t)__popcll(m);
+    }
+  }
+  __syncthreads();
+  if (tid < kColChunks) {
+#pragma unroll
+    for (uint32_t c = 0; c < 4; ++c) {
+      const uint32_t x = cnt[tid][c];
+      cnt[tid][c] = col_wave_incl(x, lane) - x;
+    }
+  }
+  __syncthreads();
+  uint64_t tb[4];
+#pragma unroll
+  for (uint32_t c = 0; c < 4; ++c) tb[c] = base[size_t(blockIdx.x) * kColClasses + c];
+#pragma unroll
+  for (uint32_t k = 0; k < kColPerThread; ++k) {
+    uint32_t rank = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < 4; ++c) {
+      const uint64_t m = __ballot(cls[k] == c);
+      if (cls[k] == c) rank = col_lane_rank(m);
+    }
+    const uint32_t c = cls[k];
+    if (c < 4) {
+      const uint64_t at = tb[c] + cnt[k * kColWaves + w][c] + rank;
+      if (at < lim.n[c]) {
+        if (c == kColOrder) out.order[at] = col_i8(v[k]);
+        else if (c == kColTimestamp) out.timestamp[at] = v[k];
+        else if (c == kColRng) out.rng[at] = col_i32(v[k]);
+        else out.buffer_built[at] = col_i32(v[k]);
+      }
+    }
+  }
+}
+
+// span_base[s * 5 + c], s <= n_spans: the class-c records before record span_rec_base[s].
+__global__ __launch_bounds__(256) void k_col_span_base(const uint8_t* __restrict__ tag, uint64_t n,
+                                                      const uint64_t* __restrict__ base, const ColRes* __restrict__ res,
+                                                      const uint64_t* __restrict__ span_rec_base, uint32_t n_spans,
+                                                      uint64_t* __restrict__ span_base) {
+  const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (s > n_spans) return;  // (wave-uniform)
+  const uint64_t r = span_rec_base[s];
+  uint64_t b[kColClasses];
+  uint32_t c[kColClasses] = {0, 0, 0, 0, 0};
+  if (r >= n) {  // the end of the batch: the totals
+#pragma unroll
+    for (uint32_t k = 0; k < kColClasses; ++k) b[k] = res->total[k];
+  } else {
+    const uint64_t tile = r / kColTile, t0 = tile * kColTile;
+#pragma unroll
+    for (uint32_t k = 0; k < kColClasses; ++k) b[k] = base[tile * kColClasses + k];
+    for (uint64_t i = t0 + lane; i < r; i += 64) {
+      const uint32_t k = col_class(tag[i]);
+#pragma unroll
+      for (uint32_t q = 0; q < kColClasses; ++q) c[q] += k == q;
+    }
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < kColClasses; ++k) {
+    const uint32_t t = col_wave_sum(c[k]);
+    if (lane == k) span_base[uint64_t(s) * kColClasses + k] = b[k] + t;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_col_wide_v0(const uint32_t* __restrict__ w_idx, uint64_t n_wide,
+                                                    const int64_t* __restrict__ v0, uint64_t n,
+                                                    int64_t* __restrict__ w_v0) {
+  const uint64_t k = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (k >= n_wide) return;
+  const uint32_t i = w_idx[k];
+  w_v0[k] = i < n ? v0[i] : 0;
+}
+
+__global__ __launch_bounds__(64) void k_col_find_bad(const uint8_t* __restrict__ tag, uint64_t n, uint64_t tile,
+                                                    ColRes* __restrict__ res) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t t0 = tile * kColTile, t1 = t0 + kColTile < n ? t0 + kColTile : n;
+  uint64_t best = ~0ull;
+  for (uint64_t i = t0 + lane; i < t1; i += 64)
+    if (col_class(tag[i]) == kColBad && i < best) best = i;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint64_t x = (uint64_t)__shfl_xor((unsigned long long)best, o, 64);
+    best = x < best ? x : best;
+  }
+  if (lane == 0) {
+    res->bad_index = best;
+    res->bad_tag = best != ~0ull ? tag[best] : 0;
+  }
+}
+
+int launch_col_count_scan(const ColIn& in, uint32_t n_tiles, uint32_t* d_counts, uint64_t* d_base, ColRes* res,
+                          void* stream) {
+  if (n_tiles)
+    hipLaunchKernelGGL(k_col_count, dim3(n_tiles), dim3(kColThreads), 0, (hipStream_t)stream, in.tag, in.n, d_counts);
+  hipLaunchKernelGGL(k_col_scan, dim3(1), dim3(kColScanThreads), 0, (hipStream_t)stream, d_counts, n_tiles, d_base, res);
+  return launch_status(hipGetLastError());
+}
+
+int launch_col_find_bad(const ColIn& in, uint64_t tile, ColRes* res, void* stream) {
+  hipLaunchKernelGGL(k_col_find_bad, dim3(1), dim3(64), 0, (hipStream_t)stream, in.tag, in.n, tile, res);
+  return launch_status(hipGetLastError());
+}
+
+int launch_col_write(const ColIn& in, uint32_t n_tiles, const uint64_t* d_base, const ColRes* res, bool write,
+                     const ColOut& out, const uint64_t* d_span_rec_base, uint32_t n_spans, uint64_t* span_base,
+                     void* stream) {
+  if (write && n_tiles) {
+    ColLimits lim;
+    for (int c = 0; c < 4; ++c) lim.n[c] = res->total[c];
+    hipLaunchKernelGGL(k_col_write, dim3(n_tiles), dim3(kColThreads), 0, (hipStream_t)stream, in.tag, in.v0, in.n,
+                       d_base, out, lim);
+  }
+  if (write && out.w_v0 && in.n_wide)
+    hipLaunchKernelGGL(k_col_wide_v0, dim3((uint32_t)((in.n_wide + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       in.w_idx, in.n_wide, in.v0, in.n, out.w_v0);
+  if (span_base && d_span_rec_base)
+    hipLaunchKernelGGL(k_col_span_base, dim3((n_spans + 1 + 3) / 4), dim3(256), 0, (hipStream_t)stream, in.tag, in.n,
+                       d_base, res, d_span_rec_base, n_spans, span_base);
+  return launch_status(hipGetLastError());
+}
+
+}  // namespace clg

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/clonos_engine.h"
+#include "columns.h"
 #include "diff.h"
 #include "digest.h"
 #include "engine_host.h"
@@ -39,6 +40,7 @@
 
 static_assert(sizeof(clg_delta_req) == 32, "clg_delta_req layout");
 static_assert(sizeof(clg_diff) == 24, "clg_diff layout");
+static_assert(sizeof(clg_columns) == 232, "clg_columns layout");
 
 using namespace clg_internal;  // the host-only types (engine_host.h)
 
@@ -278,6 +280,10 @@ struct clg_engine {
   bool dgtab_ready = false;
   DevBuf d_dffirst, d_dfout;  // log comparison: a word per piece, results
   PinBuf h_dfout;
+  // typed columns: per-tile counts and bases, span boundaries and bases, the scan's results
+  // (pinned: the kernel writes them), host-output staging
+  DevBuf d_colcnt, d_colbase, d_colsrb, d_colsb, d_colout;
+  PinBuf h_colres, h_colsb;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 
@@ -3836,6 +3842,229 @@ int clg_decode_wait(clg_engine* e) {
   std::string err;
   const int st = e->wait_oldest(&err);
   return st == CLG_OK ? CLG_OK : fail(st, "%s", err.c_str());
+}
+
+// ---- typed replay columns (columns.h) -------------------------------------------------------
+// The stable partition of a decoded batch by determinant class, from the decode's output where
+// it lies: count and scan, the host's capacity check on the scan's totals, then the write, the
+// span bases and the wide rows' v0.  LogReplayerImpl (LogReplayerImpl.java:61-119) asks for one
+// typed value at a time and never for a record's offset: the columns are what it consumes.
+namespace {
+
+struct ColPtrs {  // a clg_columns' arrays, for copies and checks
+  void* p[12];
+  uint32_t width[12];
+  bool wide[12];
+};
+ColPtrs col_ptrs(const clg_columns& c) {
+  return ColPtrs{{c.tag, c.order, c.timestamp, c.rng, c.buffer_built, c.w_idx, c.w_rc, c.w_v1, c.w_var_off,
+                  c.w_var_len, c.w_sub, c.w_v0},
+                 {1, 1, 8, 4, 4, 4, 4, 8, 4, 4, 1, 8},
+                 {false, false, false, false, false, true, true, true, true, true, true, true}};
+}
+
+// `in`: device addresses (the caller's device arrays, engine scratch, or the device side of
+// registered host memory).
+int columnize_device(clg_engine* e, const clg_decoded& in, const uint64_t* span_rec_base, uint32_t n_spans,
+                     clg_columns* out) {
+  clg::col_reset_result(out);
+  const uint64_t n = in.n_rec, nw = in.n_wide;
+  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  if ((n && (!in.tag || !in.v0)) || (nw && (!in.w_idx || !in.w_rc || !in.w_v1 || !in.w_var_off || !in.w_var_len || !in.w_sub)))
+    return fail(CLG_E_INVALID_ARG, "null input array");
+  if (!clg::col_spans_ok(span_rec_base, n_spans, n))
+    return fail(CLG_E_INVALID_ARG, "span_rec_base decreases or passes n_rec");
+  if ((n + clg::kColTile - 1) / clg::kColTile >> 31) return fail(CLG_E_INVALID_ARG, "%llu records in one call", (unsigned long long)n);
+  const ColPtrs cp = col_ptrs(*out);
+  if (out->out_kind != CLG_MEM_HOST)
+    for (int i = 0; i < 12; ++i)
+      if (uintptr_t(cp.p[i]) % cp.width[i]) return fail(CLG_E_INVALID_ARG, "column %d is not aligned to its element", i);
+  const uint32_t n_tiles = uint32_t((n + clg::kColTile - 1) / clg::kColTile);
+  const clg::ColIn cin{in.tag, in.v0, in.w_idx, n, nw};
+
+  // count and scan; the totals come back before anything is written to the caller
+  CHK(e->d_colcnt.ensure(size_t(n_tiles) * clg::kColCountWords * 4 + 64));
+  CHK(e->d_colbase.ensure(size_t(n_tiles) * clg::kColClasses * 8 + 64));
+  CHK(e->h_colres.ensure(sizeof(clg::ColRes)));
+  clg::ColRes* res = e->h_colres.as<clg::ColRes>();
+  CHK(e->timed("decode_columns", n, [&] {
+    return clg::launch_col_count_scan(cin, n_tiles, e->d_colcnt.as<uint32_t>(), e->d_colbase.as<uint64_t>(), res, e->stream);
+  }));
+  CHK(e->sync());
+  out->n_rec = n;
+  if (res->bad_tile != clg::kColNoTile) {  // a tag above 7: one wave finds the record
+    CHK(clg::launch_col_find_bad(cin, res->bad_tile, res, e->stream));
+    CHK(e->sync());
+    out->err_status = CLG_E_INVALID_ARG;
+    out->err_span = clg::col_span_of(span_rec_base, n_spans, res->bad_index);
+    out->err_off = int64_t(res->bad_index);
+    out->err_tag = int32_t(res->bad_tag);
+    return fail(CLG_E_INVALID_ARG, "record %llu has tag %llu", (unsigned long long)res->bad_index,
+                (unsigned long long)res->bad_tag);
+  }
+  uint64_t tot[clg::kColClasses];
+  for (uint32_t c = 0; c < clg::kColClasses; ++c) out->n_class[c] = tot[c] = res->total[c];
+  if (tot[clg::kColWide] != nw)
+    return fail(CLG_E_INVALID_ARG, "n_wide is %llu, the tags hold %llu wide records", (unsigned long long)nw,
+                (unsigned long long)tot[clg::kColWide]);
+  const bool sizes_only = clg::col_sizes_only(*out);
+  const char* short_col = sizes_only ? nullptr : clg::col_short_column(*out, n, tot);
+  const bool write = !sizes_only && !short_col;
+
+  // where the kernels write: the caller's device arrays, the device side of registered host
+  // arrays, or engine staging (plain host memory, and registered memory that is not wholly
+  // inside one registered range)
+  const uint64_t cnt[5] = {tot[0], tot[1], tot[2], tot[3], nw};  // order, timestamp, rng, buffer_built, w_v0
+  void* const host_dst[5] = {out->order, out->timestamp, out->rng, out->buffer_built, out->w_v0};
+  const uint32_t wd[5] = {1, 8, 4, 4, 8};
+  bool staged = out->out_kind == CLG_MEM_HOST;
+  void* dev_dst[5] = {host_dst[0], host_dst[1], host_dst[2], host_dst[3], host_dst[4]};
+  if (write && out->out_kind == CLG_MEM_MAPPED) {
+    for (int i = 0; i < 5 && !staged; ++i)
+      if (cnt[i] && !(dev_dst[i] = reinterpret_cast<void*>(clg_mapped_device_address(host_dst[i], cnt[i] * wd[i])))) staged = true;
+  }
+  uint64_t at[6] = {0};
+  if (write && staged) {
+    for (int i = 0; i < 5; ++i) at[i + 1] = (at[i] + cnt[i] * wd[i] + 15) & ~uint64_t(15);
+    CHK(e->d_colout.ensure(at[5] + 16));
+    for (int i = 0; i < 5; ++i) dev_dst[i] = e->d_colout.as<uint8_t>() + at[i];
+  }
+  const clg::ColOut cout_{static_cast<int8_t*>(dev_dst[0]), static_cast<int64_t*>(dev_dst[1]), static_cast<int32_t*>(dev_dst[2]),
+                          static_cast<int32_t*>(dev_dst[3]), static_cast<int64_t*>(dev_dst[4])};
+  const bool want_sb = out->span_base && n_spans;
+  if (want_sb) {
+    const size_t sb = size_t(n_spans + 1) * 8;
+    CHK(e->h_colsb.ensure(sb * clg::kColClasses));
+    CHK(e->d_colsrb.ensure(sb));
+    CHK(e->d_colsb.ensure(sb * clg::kColClasses));
+    memcpy(e->h_colsb.p, span_rec_base, sb);
+    HIPCHK(hipMemcpyAsync(e->d_colsrb.p, e->h_colsb.p, sb, hipMemcpyHostToDevice, e->stream));
+  }
+  uint64_t moved = n_tiles * uint64_t(clg::kColClasses) * 8 + (want_sb ? uint64_t(n_spans + 1) * 48 : 0);
+  if (write) moved += n + 8 * (n - nw) + tot[0] + 8 * tot[1] + 4 * tot[2] + 4 * tot[3] + 20 * nw;
+  CHK(e->timed("decode_columns", moved, [&] {
+    return clg::launch_col_write(cin, n_tiles, e->d_colbase.as<uint64_t>(), res, write, cout_,
+                                 want_sb ? e->d_colsrb.as<uint64_t>() : nullptr, n_spans, e->d_colsb.as<uint64_t>(), e->stream);
+  }));
+  if (want_sb)  // (h_colsb's copy of span_rec_base was uploaded by the copy queued before the kernels)
+    HIPCHK(hipMemcpyAsync(e->h_colsb.p, e->d_colsb.p, size_t(n_spans + 1) * 8 * clg::kColClasses, hipMemcpyDeviceToHost, e->stream));
+  if (write) {
+    // the arrays that stay as they are: the tags and the side rows
+    const void* src[6] = {in.tag, in.w_idx, in.w_rc, in.w_v1, in.w_var_off, in.w_var_len};
+    void* dst[6] = {out->tag, out->w_idx, out->w_rc, out->w_v1, out->w_var_off, out->w_var_len};
+    const uint64_t nb[6] = {n, nw * 4, nw * 4, nw * 8, nw * 4, nw * 4};
+    for (int i = 0; i < 6; ++i)
+      if (nb[i] && dst[i] != src[i]) HIPCHK(hipMemcpyAsync(dst[i], src[i], nb[i], hipMemcpyDefault, e->stream));
+    if (nw && out->w_sub != in.w_sub) HIPCHK(hipMemcpyAsync(out->w_sub, in.w_sub, nw, hipMemcpyDefault, e->stream));
+    if (staged)
+      for (int i = 0; i < 5; ++i)
+        if (cnt[i]) HIPCHK(hipMemcpyAsync(host_dst[i], dev_dst[i], cnt[i] * wd[i], hipMemcpyDeviceToHost, e->stream));
+  }
+  CHK(e->sync());
+  if (out->span_base) {
+    if (n_spans) memcpy(out->span_base, e->h_colsb.p, size_t(n_spans + 1) * 8 * clg::kColClasses);
+    else memcpy(out->span_base, tot, sizeof tot);
+  }
+  if (short_col)
+    return fail(CLG_E_CAPACITY, "column %s is too small (records %llu; totals %llu %llu %llu %llu %llu)", short_col,
+                (unsigned long long)n, (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2],
+                (unsigned long long)tot[3], (unsigned long long)tot[4]);
+  return CLG_OK;
+}
+
+// The decode into engine scratch (the host-output staging arrays, kept between calls), grown
+// and run again on the decode's own CLG_E_CAPACITY, then the columns of what it produced.
+int decode_columns(clg_engine* e, const std::function<int(clg_decoded*, uint64_t*)>& run, uint32_t n_spans,
+                   clg_columns* out) {
+  clg::col_reset_result(out);
+  std::vector<uint64_t> base(size_t(n_spans) + 1, 0);
+  clg_decoded d{};
+  uint64_t need = 1u << 16, wneed = 1u << 12;
+  int st = CLG_OK;
+  for (int round = 0;; ++round) {
+    CHK(e->d_o_off.ensure(need * 4));
+    CHK(e->d_o_tag.ensure(need));
+    CHK(e->d_o_v0.ensure(need * 8));
+    CHK(e->d_o_widx.ensure(wneed * 4));
+    CHK(e->d_o_wrc.ensure(wneed * 4));
+    CHK(e->d_o_wv1.ensure(wneed * 8));
+    CHK(e->d_o_wvo.ensure(wneed * 4));
+    CHK(e->d_o_wvl.ensure(wneed * 4));
+    CHK(e->d_o_wsub.ensure(wneed));
+    d = clg_decoded{};
+    d.off = e->d_o_off.as<uint32_t>(), d.tag = e->d_o_tag.as<uint8_t>(), d.v0 = e->d_o_v0.as<int64_t>();
+    d.w_idx = e->d_o_widx.as<uint32_t>(), d.w_rc = e->d_o_wrc.as<int32_t>(), d.w_v1 = e->d_o_wv1.as<int64_t>();
+    d.w_var_off = e->d_o_wvo.as<uint32_t>(), d.w_var_len = e->d_o_wvl.as<uint32_t>(), d.w_sub = e->d_o_wsub.as<uint8_t>();
+    d.cap = std::min({uint64_t(e->d_o_off.cap / 4), uint64_t(e->d_o_tag.cap), uint64_t(e->d_o_v0.cap / 8)});
+    d.wcap = std::min({uint64_t(e->d_o_widx.cap / 4), uint64_t(e->d_o_wrc.cap / 4), uint64_t(e->d_o_wv1.cap / 8),
+                       uint64_t(e->d_o_wvo.cap / 4), uint64_t(e->d_o_wvl.cap / 4), uint64_t(e->d_o_wsub.cap)});
+    d.out_kind = CLG_MEM_DEVICE;
+    st = run(&d, base.data());
+    if (st != CLG_E_CAPACITY || round == 2) break;
+    need = std::max<uint64_t>(d.n_rec, d.cap);  // (the decode reported what it produced)
+    wneed = std::max<uint64_t>(d.n_wide, d.wcap);
+  }
+  if (st == CLG_E_CAPACITY) return st;
+  if (st != CLG_OK && d.err_status == CLG_OK) return st;  // an engine failure, not a decode result
+  const std::string decode_err = st != CLG_OK ? g_err : std::string();
+  CHK(columnize_device(e, d, base.data(), n_spans, out));
+  out->err_status = d.err_status;
+  out->err_span = d.err_span;
+  out->err_off = d.err_off;
+  out->err_tag = d.err_tag;
+  if (st != CLG_OK) g_err = decode_err;
+  return st;
+}
+
+}  // namespace
+
+int clg_columnize(clg_engine* e, const clg_decoded* in, const uint64_t* span_rec_base, uint32_t n_spans,
+                  clg_columns* out) {
+  ENGINE_GUARD(e);
+  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg_decoded d = *in;
+  if (in->out_kind == CLG_MEM_MAPPED) {  // registered host memory: its device side
+    const uint64_t n = in->n_rec, w = in->n_wide;
+    const auto dev = [](void* p, uint64_t bytes, uintptr_t* a) {
+      *a = p && bytes ? clg_mapped_device_address(p, bytes) : uintptr_t(p);
+      return *a != 0 || !p;
+    };
+    uintptr_t a[8];
+    if (!(dev(d.tag, n, &a[0]) && dev(d.v0, n * 8, &a[1]) && dev(d.w_idx, w * 4, &a[2]) && dev(d.w_rc, w * 4, &a[3]) &&
+          dev(d.w_v1, w * 8, &a[4]) && dev(d.w_var_off, w * 4, &a[5]) && dev(d.w_var_len, w * 4, &a[6]) &&
+          dev(d.w_sub, w, &a[7])))
+      return fail(CLG_E_INVALID_ARG, "an input array is not inside memory registered with clg_host_register");
+    d.tag = reinterpret_cast<uint8_t*>(a[0]), d.v0 = reinterpret_cast<int64_t*>(a[1]);
+    d.w_idx = reinterpret_cast<uint32_t*>(a[2]), d.w_rc = reinterpret_cast<int32_t*>(a[3]);
+    d.w_v1 = reinterpret_cast<int64_t*>(a[4]), d.w_var_off = reinterpret_cast<uint32_t*>(a[5]);
+    d.w_var_len = reinterpret_cast<uint32_t*>(a[6]), d.w_sub = reinterpret_cast<uint8_t*>(a[7]);
+  } else if (in->out_kind != CLG_MEM_DEVICE) {
+    return fail(CLG_E_INVALID_ARG, "the decoded batch must be device or registered memory (out_kind %u)", in->out_kind);
+  }
+  return columnize_device(e, d, span_rec_base, n_spans, out);
+}
+
+int clg_decode_logs_columns(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                            clg_columns* out) {
+  ENGINE_GUARD(e);
+  if (!out || (n && (!log || !start_epoch))) return fail(CLG_E_INVALID_ARG, "null argument");
+  return decode_columns(e, [&](clg_decoded* d, uint64_t* base) { return clg_decode_logs(e, log, start_epoch, n, d, base); },
+                        n, out);
+}
+
+int clg_decode_host_columns(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
+                            uint32_t n, clg_columns* out) {
+  ENGINE_GUARD(e);
+  if (!out || (n && (!span_off || !span_len))) return fail(CLG_E_INVALID_ARG, "null argument");
+  return decode_columns(
+      e, [&](clg_decoded* d, uint64_t* base) { return clg_decode_host(e, bytes, span_off, span_len, n, d, base); }, n, out);
+}
+
+int clg_columnize_host(const clg_decoded* in, const uint64_t* span_rec_base, uint32_t n_spans, clg_columns* out) {
+  const char* what = "";
+  const int st = clg::col_build_host(in, span_rec_base, n_spans, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "columns: %s", what);
 }
 
 int clg_replay_prep(clg_engine* e, const uint64_t* key, const uint8_t* bytes, const uint64_t* off, const uint64_t* len,

@@ -553,6 +553,43 @@ struct DiffRef {
 int launch_diff(const GatherPiece* d_pieces, uint32_t n_pieces, const struct SegSpan* d_runs, uint32_t n_runs,
                 const DiffRef* d_refs, uint32_t* d_first, ::clg_diff* d_out, void* stream);
 
+// ---- typed replay columns (columns.h, columns.hip) ---------------------------------
+// Device addresses of a decoded batch's arrays and of the columns the kernels write.
+struct ColIn {
+  const uint8_t* tag;
+  const int64_t* v0;
+  const uint32_t* w_idx;
+  uint64_t n, n_wide;
+};
+struct ColOut {
+  int8_t* order;
+  int64_t* timestamp;
+  int32_t* rng;
+  int32_t* buffer_built;
+  int64_t* w_v0;
+};
+// The scan's results, in pinned memory the host reads: class totals, the first tile with a tag
+// above 7 (kColNoTile: none); k_col_find_bad adds that tile's lowest such record and its tag.
+constexpr uint64_t kColNoTile = ~0ull;
+struct ColRes {
+  uint64_t total[5];
+  uint64_t bad_tile;
+  uint64_t bad_index;
+  uint64_t bad_tag;
+};
+// Count (a workgroup per tile -> d_counts[tile * kColCountWords]) and scan (one workgroup ->
+// d_base[tile * 5], the exclusive per-class base of every tile; *res).
+int launch_col_count_scan(const ColIn& in, uint32_t n_tiles, uint32_t* d_counts, uint64_t* d_base, ColRes* res,
+                          void* stream);
+// The lowest record of tile `tile` whose tag is above 7 -> res->bad_index / bad_tag (one wave).
+int launch_col_find_bad(const ColIn& in, uint64_t tile, ColRes* res, void* stream);
+// Write (a workgroup per tile; none without `write`), span bases (a wave per boundary:
+// span_base[s * 5 + c] for s <= n_spans, from d_span_rec_base) and wide v0 (a thread per side
+// row; none without out.w_v0).
+int launch_col_write(const ColIn& in, uint32_t n_tiles, const uint64_t* d_base, const ColRes* res, bool write,
+                     const ColOut& out, const uint64_t* d_span_rec_base, uint32_t n_spans, uint64_t* span_base,
+                     void* stream);
+
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {
   uint8_t* dst;        // inside one segment

@@ -126,8 +126,184 @@ class DecodedBatch:
         raise ValueError(f"tag {t} in a decoded batch")
 
 
+def _wide_determinant(t: int, v0: int, rc: int, v1: int, vo: int, vl: int, sub: int, var) -> D.Determinant:
+    """A wide record from its side row (DecodedBatch._determinant's rules)."""
+    b = var(vo, vl) if var is not None and vo else None
+    if t == D.IGNORE_CHECKPOINT:
+        return D.IgnoreCheckpointDeterminant(rc, v0)
+    if t == D.TIMER_TRIGGER:
+        return D.TimerTriggerDeterminant(rc, v0, sub, b if sub == D.INTERNAL else None)
+    if t == D.SOURCE_CHECKPOINT:
+        return D.SourceCheckpointDeterminant(rc, v0, v1, sub & 0x7F, b if sub & 0x80 else None)
+    if t == D.SERIALIZABLE:
+        return D.SerializableDeterminant(b if b is not None else b"")
+    raise ValueError(f"tag {t} in a decoded batch")
+
+
+# tag -> column class (clg_columns): ORDER, TIMESTAMP, RNG, BUFFER_BUILT, WIDE; 5: no class
+COL_CLASS_OF_TAG = np.array([0, 1, 2, 4, 4, 4, 4, 3] + [5] * 248, np.uint8)
+_COL_FIELDS = (("tag", np.uint8), ("order", np.int8), ("timestamp", np.int64), ("rng", np.int32),
+               ("buffer_built", np.int32), ("w_idx", np.uint32), ("w_rc", np.int32), ("w_v1", np.int64),
+               ("w_var_off", np.uint32), ("w_var_len", np.uint32), ("w_sub", np.uint8), ("w_v0", np.int64))
+_SOA_IN_FIELDS = (("tag", np.uint8), ("v0", np.int64), ("w_idx", np.uint32), ("w_rc", np.int32), ("w_v1", np.int64),
+                  ("w_var_off", np.uint32), ("w_var_len", np.uint32), ("w_sub", np.uint8))  # (off is not read)
+_COL_WIDE = ("w_idx", "w_rc", "w_v1", "w_var_off", "w_var_len", "w_sub", "w_v0")
+_COL_CAP = {"tag": "cap_tag", "order": "cap_order", "timestamp": "cap_timestamp", "rng": "cap_rng",
+            "buffer_built": "cap_buffer_built"}
+
+
+@dataclass
+class SpanColumns:
+    """One span's view of the columns: its tags (the interleaving) and its slice of each column;
+    w0 is the span's first row in the batch's wide columns."""
+    tag: np.ndarray
+    order: np.ndarray
+    timestamp: np.ndarray
+    rng: np.ndarray
+    buffer_built: np.ndarray
+    w0: int
+    n_wide: int
+
+
+class DecodedColumns:
+    """Typed replay columns (layout: include/clonos_engine.h clg_columns): tag in record order,
+    one array per determinant class holding that class's values in record order, the wide rows,
+    and span_base[(n_spans + 1), 5], the class counts before each span.  Record offsets are not
+    part of the columns (use decode_logs for those)."""
+
+    def __init__(self, tag, order, timestamp, rng, buffer_built, w_idx, w_rc, w_v1, w_var_off, w_var_len, w_sub, w_v0,
+                 span_base, spans_bytes=None):
+        self.tag, self.order, self.timestamp, self.rng, self.buffer_built = tag, order, timestamp, rng, buffer_built
+        self.w_idx, self.w_rc, self.w_v1, self.w_v0 = w_idx, w_rc, w_v1, w_v0
+        self.w_var_off, self.w_var_len, self.w_sub = w_var_off, w_var_len, w_sub
+        self.span_base = np.asarray(span_base, np.uint64).reshape(-1, _lib.COL_CLASSES)
+        self.spans_bytes = spans_bytes
+        # a decode error the columns stop at (decode_logs_columns(..., partial=True)): a ClonosError, or None
+        self.error: Optional[ClonosError] = None
+
+    @property
+    def n_rec(self) -> int:
+        return int(self.tag.shape[0])
+
+    @property
+    def n_spans(self) -> int:
+        return int(self.span_base.shape[0]) - 1
+
+    @property
+    def span_rec_base(self) -> np.ndarray:
+        """Each span's first record index (the decode's span_rec_base): the row sums."""
+        return self.span_base.sum(axis=1, dtype=np.uint64)
+
+    def span(self, s: int) -> SpanColumns:
+        if not 0 <= s < self.n_spans:
+            raise IndexError("span index")
+        a, b = self.span_base[s].astype(np.int64), self.span_base[s + 1].astype(np.int64)
+        r0, r1 = int(a.sum()), int(b.sum())
+        return SpanColumns(self.tag[r0:r1], self.order[a[0]:b[0]], self.timestamp[a[1]:b[1]], self.rng[a[2]:b[2]],
+                           self.buffer_built[a[3]:b[3]], int(a[4]), int(b[4] - a[4]))
+
+    def to_soa(self) -> DecodedBatch:
+        """The inverse: tag, v0 and the side table as the decode gives them (off is None)."""
+        tag = np.asarray(self.tag)
+        cls = COL_CLASS_OF_TAG[tag]
+        v0 = np.zeros(tag.shape[0], np.int64)
+        for c, col in enumerate((self.order, self.timestamp, self.rng, self.buffer_built, self.w_v0)):
+            m = cls == c
+            if int(m.sum()) != len(col):
+                raise ValueError(f"class {c}: the tags ask for {int(m.sum())} values, the column holds {len(col)}")
+            v0[m] = col
+        if (cls == 5).any():
+            raise ValueError("a tag above 7 in the columns")
+        return DecodedBatch(None, tag.copy(), v0, self.w_idx, self.w_rc, self.w_v1, self.w_var_off, self.w_var_len,
+                            self.w_sub, self.span_rec_base, self.spans_bytes)
+
+    def determinants(self, s: int, var=None) -> List[D.Determinant]:
+        """The Determinant objects of span s, as DecodedBatch.determinants builds them.
+        var(off, len): span-relative bytes (names, references, java streams); None: from
+        spans_bytes when the columns kept them."""
+        if var is None and self.spans_bytes is not None:
+            raw = self.spans_bytes[s]
+            var = lambda vo, vl: bytes(raw[vo:vo + vl])
+        sp = self.span(s)
+        at = [0, 0, 0, 0, sp.w0]
+        out = []
+        for t in sp.tag.tolist():
+            c = int(COL_CLASS_OF_TAG[t])
+            k = at[c]
+            at[c] += 1
+            if c == 0:
+                out.append(D.OrderDeterminant(int(sp.order[k])))
+            elif c == 1:
+                out.append(D.TimestampDeterminant(int(sp.timestamp[k])))
+            elif c == 2:
+                out.append(D.RNGDeterminant(int(sp.rng[k])))
+            elif c == 3:
+                out.append(D.BufferBuiltDeterminant(int(sp.buffer_built[k])))
+            else:
+                out.append(_wide_determinant(t, int(self.w_v0[k]), int(self.w_rc[k]), int(self.w_v1[k]),
+                                             int(self.w_var_off[k]), int(self.w_var_len[k]), int(self.w_sub[k]), var))
+        return out
+
+
+def _columns_struct(arrs: dict, base: Optional[np.ndarray], kind: int) -> _lib.Columns:
+    """clg_columns over host arrays (arrs: name -> array, capacity = its length)."""
+    c = _lib.Columns()
+    for name, _ in _COL_FIELDS:
+        setattr(c, name, _np_ptr(arrs[name]) or None)
+    for name, cap in _COL_CAP.items():
+        setattr(c, cap, arrs[name].size)
+    c.cap_wide = min(arrs[k].size for k in _COL_WIDE)
+    c.span_base = _np_ptr(base) if base is not None else None
+    c.out_kind = kind
+    return c
+
+
+def _columns_result(c: _lib.Columns, arrs: dict, base: np.ndarray, spans_bytes=None) -> DecodedColumns:
+    n = [int(x) for x in c.n_class]
+    cnt = {"tag": int(c.n_rec), "order": n[0], "timestamp": n[1], "rng": n[2], "buffer_built": n[3]}
+    return DecodedColumns(*[arrs[k][:cnt.get(k, n[4])] for k, _ in _COL_FIELDS], base, spans_bytes)
+
+
+def _columns_error(st: int, c: _lib.Columns) -> ClonosError:
+    err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
+    err.err_span, err.err_off, err.err_tag, err.n_rec = c.err_span, c.err_off, c.err_tag, c.n_rec
+    err.n_class = [int(x) for x in c.n_class]
+    return err
+
+
+def _host_columns(n: int, n_class: Sequence[int]) -> dict:
+    cnt = {"tag": n, "order": n_class[0], "timestamp": n_class[1], "rng": n_class[2], "buffer_built": n_class[3]}
+    return {k: np.zeros(cnt.get(k, n_class[4]), dt) for k, dt in _COL_FIELDS}
+
+
+def columnize_host(batch: DecodedBatch) -> DecodedColumns:
+    """clg_columnize_host: the typed columns of a decoded batch on the CPU in one pass (no engine,
+    no GPU) -- what Engine.columnize computes on the device."""
+    d = _lib.Decoded()
+    keep = []
+    for name, dt in _SOA_IN_FIELDS:
+        a =np.ascontiguousarray(getattr(batch, name), dt)
+        keep.append(a)
+        setattr(d, name, _np_ptr(a) or None)
+    d.n_rec, d.n_wide = batch.n_rec, len(batch.w_idx)
+    srb = np.ascontiguousarray(batch.span_rec_base, np.uint64)
+    n_spans = max(len(srb) - 1, 0)
+    base = np.zeros((n_spans + 1) * _lib.COL_CLASSES, np.uint64)
+    c = _lib.Columns()  # every column pointer null: sizes only
+    c.span_base = _np_ptr(base)
+    st = lib.clg_columnize_host(C.byref(d), _np_ptr(srb), n_spans, C.byref(c))
+    if st != _lib.CLG_OK:
+        raise _columns_error(st, c)
+    arrs = _host_columns(int(c.n_rec), [int(x) for x in c.n_class])
+    c = _columns_struct(arrs, base, _lib.CLG_MEM_HOST)
+    st = lib.clg_columnize_host(C.byref(d), _np_ptr(srb), n_spans, C.byref(c))
+    if st != _lib.CLG_OK:
+        raise _columns_error(st, c)
+    return _columns_result(c, arrs, base, batch.spans_bytes)
+
+
 # clg_digest rows: two spans are equal only when both fields are equal
-DIGEST = np.dtype([("hash", np.uint64), ("len", np.uint64)])
+DIGEST =np.dtype([("hash", np.uint64), ("len", np.uint64)])
 
 
 def digest_host(data: Union[bytes, np.ndarray]) -> Tuple[int, int]:
@@ -623,6 +799,87 @@ class Engine:
         check(lib.clg_decode_logs_async(self._h, _np_ptr(handles), _np_ptr(start_epochs), len(handles),
                                         C.byref(dec), _np_ptr(base)))
         self._queued.append(keep)
+
+    # ---- typed replay columns (clg_columns)
+    @staticmethod
+    def _column_bounds(total: int, n_spans: int) -> dict:
+        """Capacities no batch of `total` encoded bytes can exceed (the shortest record of each
+        class: ORDER 2 B, TIMESTAMP 9, RNG and BUFFER_BUILT 5, wide 6), untouched pages of
+        np.empty arrays cost nothing."""
+        cap = {"tag": total // 2, "order": total // 2, "timestamp": total // 9, "rng": total // 5,
+               "buffer_built": total // 5}
+        return {k: np.empty(cap.get(k, total // 6) + n_spans + 1, dt) for k, dt in _COL_FIELDS}
+
+    def _columns_finish(self, st: int, c: _lib.Columns, arrs, base, spans_bytes, partial: bool) -> DecodedColumns:
+        if st != _lib.CLG_OK and not (partial and c.err_status == st):
+            raise _columns_error(st, c)
+        cols = _columns_result(c, arrs, base, spans_bytes)
+        if st != _lib.CLG_OK:
+            cols.error = _columns_error(st, c)
+        return cols
+
+    def columnize(self, dec: _lib.Decoded, base: np.ndarray, cols: Optional[_lib.Columns] = None
+                  ) -> Optional[DecodedColumns]:
+        """clg_columnize: the typed columns of a decoded batch that lies in device memory (or in
+        registered host memory, dec.out_kind CLG_MEM_MAPPED); dec.n_rec / n_wide are the decode's
+        results, base its span_rec_base.  cols: a clg_columns the caller set up (any out_kind, or
+        all pointers null for sizes only) -- filled in place, its status raised; None: host arrays
+        of exactly the batch's sizes (a sizes-only call first), returned as DecodedColumns."""
+        base = np.ascontiguousarray(base, np.uint64)
+        n_spans = max(base.size - 1, 0)
+        if cols is not None:
+            st = lib.clg_columnize(self._h, C.byref(dec), _np_ptr(base), n_spans, C.byref(cols))
+            if st != _lib.CLG_OK:
+                raise _columns_error(st, cols)
+            return None
+        sb = np.zeros((n_spans + 1) * _lib.COL_CLASSES, np.uint64)
+        c = _lib.Columns()
+        c.span_base = _np_ptr(sb)
+        st = lib.clg_columnize(self._h, C.byref(dec), _np_ptr(base), n_spans, C.byref(c))
+        if st != _lib.CLG_OK:
+            raise _columns_error(st, c)
+        arrs = _host_columns(int(c.n_rec), [int(x) for x in c.n_class])
+        c = _columns_struct(arrs, sb, _lib.CLG_MEM_HOST)
+        st = lib.clg_columnize(self._h, C.byref(dec), _np_ptr(base), n_spans, C.byref(c))
+        if st != _lib.CLG_OK:
+            raise _columns_error(st, c)
+        return _columns_result(c, arrs, sb)
+
+    def decode_logs_columns(self, logs: Sequence["ThreadCausalLog"], start_epochs: Sequence[int],
+                            keep_bytes: bool = False, partial: bool = False) -> DecodedColumns:
+        """clg_decode_logs_columns: decode_logs' ranges decoded on the GPU and delivered as typed
+        columns.  A decode error raises as decode_logs' does; partial=True returns the columns of
+        each span's records up to its first error instead, the error in .error."""
+        n = len(logs)
+        h = np.array([l.handle for l in logs], np.uint32)
+        ep = np.array(start_epochs, np.int64)
+        arrs = self._column_bounds(self.log_lengths(h)[1] if n else 0, n)
+        base = np.zeros((n + 1) * _lib.COL_CLASSES, np.uint64)
+        c = _columns_struct(arrs, base, _lib.CLG_MEM_HOST)
+        st = lib.clg_decode_logs_columns(self._h, _np_ptr(h), _np_ptr(ep), n, C.byref(c))
+        sb = [np.frombuffer(l.getDeterminants(e), np.uint8) for l, e in zip(logs, start_epochs)] if keep_bytes else None
+        return self._columns_finish(st, c, arrs, base, sb, partial)
+
+    def decode_logs_columns_raw(self, handles: np.ndarray, start_epochs: np.ndarray, cols: _lib.Columns) -> int:
+        """clg_decode_logs_columns into a clg_columns the caller set up (any out_kind; all pointers
+        null: sizes only).  Returns the status; the results are in cols."""
+        return lib.clg_decode_logs_columns(self._h, _np_ptr(handles), _np_ptr(start_epochs), len(handles), C.byref(cols))
+
+    def decode_host_columns(self, data: Union[bytes, np.ndarray], spans: Optional[Sequence[Tuple[int, int]]] = None,
+                            partial: bool = False) -> DecodedColumns:
+        """clg_decode_host_columns: decode_host's spans decoded on the GPU and delivered as typed
+        columns (errors as decode_logs_columns)."""
+        buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(
+            data, np.uint8)
+        if spans is None:
+            spans = [(0, buf.size)]
+        so = np.array([s[0] for s in spans], np.uint64)
+        sl = np.array([s[1] for s in spans], np.uint64)
+        arrs = self._column_bounds(int(sl.sum()), len(spans))
+        base = np.zeros((len(spans) + 1) * _lib.COL_CLASSES, np.uint64)
+        c = _columns_struct(arrs, base, _lib.CLG_MEM_HOST)
+        st = lib.clg_decode_host_columns(self._h, _np_ptr(buf), _np_ptr(so), _np_ptr(sl), len(spans), C.byref(c))
+        return self._columns_finish(st, c, arrs, base, [buf[int(o):int(o) + int(k)] for o, k in zip(so, sl)], partial)
 
     def decode_wait(self) -> None:
         """clg_decode_wait: completes the oldest queued asynchronous decode and raises its error."""

@@ -27,7 +27,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from . import determinants as D
-from .engine import CausalLogID, DecodedBatch, Engine, ThreadCausalLog, _np_ptr
+from .engine import CausalLogID, DecodedBatch, Engine, ThreadCausalLog, _np_ptr, _wide_determinant
 
 
 # numpy views of the C structs (include/clonos_engine.h)
@@ -539,3 +539,100 @@ def verify_replay(engine: Engine, items: Sequence[Tuple[int, int, bytes]], locat
         for i, d in zip(bad, locate_divergence(engine, [items[i] for i in bad])):
             out[i].divergence = d
     return out
+
+
+# ---- LogReplayerImpl over typed columns ---------------------------------------------------------
+class ReplayOrderError(AssertionError):
+    """A replay call whose type is not the next determinant's (the reference's `assert
+    nextDeterminant instanceof ...`, LogReplayerImpl.java:62, :72, :82, :92, :103)."""
+
+    def __init__(self, position: int, asked: str, found: str):
+        super().__init__(f"record {position} of the span: asked for {asked}, the next determinant is {found}")
+        self.position, self.asked, self.found = position, asked, found
+
+
+_ASYNC_TAGS = (D.TIMER_TRIGGER, D.SOURCE_CHECKPOINT, D.IGNORE_CHECKPOINT)  # AsyncDeterminant's subclasses
+
+
+class ColumnReplayer:
+    """LogReplayerImpl's cursor (LogReplayerImpl.java:51-158) over one span of DecodedColumns:
+    the next determinant is the next tag; every method reads that tag and bumps one index into
+    one column.  var(off, len): the span's bytes for names, references and java streams (None:
+    from the columns' spans_bytes when they kept them)."""
+
+    def __init__(self, columns, s: int, var=None):
+        sp = columns.span(s)
+        self._c = columns
+        self._tag = sp.tag
+        self._order, self._ts, self._rng, self._bb = sp.order, sp.timestamp, sp.rng, sp.buffer_built
+        self._pos = 0                      # records consumed
+        self._at = [0, 0, 0, 0, sp.w0]     # the next index into each class's column
+        if var is None and columns.spans_bytes is not None:
+            raw = columns.spans_bytes[s]
+            var = lambda vo, vl: bytes(raw[vo:vo + vl])
+        self._var = var
+
+    def _next(self, asked: str, *tags) -> int:
+        """The next tag, which must be one of `tags`; the record is consumed."""
+        t = int(self._tag[self._pos]) if self._pos < len(self._tag) else None
+        if t not in tags:
+            raise ReplayOrderError(self._pos, asked, "nothing (the log is finished)" if t is None else D.TAG_NAMES[t])
+        self._pos += 1
+        return t
+
+    def _bump(self, cls: int) -> int:
+        k = self._at[cls]
+        self._at[cls] = k + 1
+        return k
+
+    def _wide(self, t: int) -> D.Determinant:
+        c, k = self._c, self._bump(4)
+        return _wide_determinant(t, int(c.w_v0[k]), int(c.w_rc[k]), int(c.w_v1[k]), int(c.w_var_off[k]),
+                                 int(c.w_var_len[k]), int(c.w_sub[k]), self._var)
+
+    def replayNextChannel(self) -> int:  # :71-78, a Java byte
+        self._next("ORDER", D.ORDER)
+        return int(self._order[self._bump(0)])
+
+    def replayNextTimestamp(self) -> int:  # :81-88
+        self._next("TIMESTAMP", D.TIMESTAMP)
+        return int(self._ts[self._bump(1)])
+
+    def replayRandomInt(self) -> int:  # :61-68
+        self._next("RNG", D.RNG)
+        return int(self._rng[self._bump(2)])
+
+    def replayNextBufferSize(self) -> int:
+        """The next BufferBuilt size (SubpartitionRecoveryThread.run, ReplayingState.java:161-188)."""
+        self._next("BUFFER_BUILT", D.BUFFER_BUILT)
+        return int(self._bb[self._bump(3)])
+
+    def replaySerializableDeterminant(self) -> bytes:  # :91-98; the java stream (Python does not deserialize it)
+        return self._wide(self._next("SERIALIZABLE", D.SERIALIZABLE)).stream
+
+    def triggerAsyncEvent(self, current_record_count: int) -> D.Determinant:
+        """:102-119: the async determinant, consumed; raises when the epoch tracker's record
+        count is not the determinant's (:110-111), with the determinant left in place."""
+        t = int(self._tag[self._pos]) if self._pos < len(self._tag) else None
+        if t not in _ASYNC_TAGS:
+            raise ReplayOrderError(self._pos, "an async determinant",
+                                   "nothing (the log is finished)" if t is None else D.TAG_NAMES[t])
+        rc = int(self._c.w_rc[self._at[4]])
+        if current_record_count != rc:
+            raise RuntimeError("Current record count is not the determinants record count. "
+                               f"Current: {current_record_count}, determinant: {rc}")
+        self._pos += 1
+        return self._wide(t)
+
+    def record_count_target(self) -> Optional[int]:
+        """What postHook hands the epoch tracker (:147-152): the next determinant's record count
+        when that determinant is async, else None."""
+        if self._pos < len(self._tag) and int(self._tag[self._pos]) in _ASYNC_TAGS:
+            return int(self._c.w_rc[self._at[4]])
+        return None
+
+    def next_tag(self) -> Optional[int]:
+        return int(self._tag[self._pos]) if self._pos < len(self._tag) else None
+
+    def isFinished(self) -> bool:  # :154-156
+        return self._pos >= len(self._tag)

@@ -61,7 +61,9 @@ enum {
 
 /* CLG_MEM_MAPPED: host memory registered with clg_host_register.  For decode outputs
  * (clg_decoded.out_kind) the single-launch small decode writes it straight from the GPU (no
- * staging copy); every other path treats it as CLG_MEM_HOST. */
+ * staging copy), and so do the column kernels for clg_columns.out_kind; clg_columnize also reads
+ * a decoded batch from it (clg_decoded.out_kind of its input).  Every other path treats it as
+ * CLG_MEM_HOST. */
 enum { CLG_MEM_HOST = 0, CLG_MEM_DEVICE = 1, CLG_MEM_MAPPED = 2 };
 
 /* Pin and map [p, p + bytes) of host memory for the device (hipHostRegister, mapped); a
@@ -310,6 +312,84 @@ int clg_decode_logs_async(clg_engine* e, const uint32_t* log, const int64_t* sta
  * returns ITS status (FIFO: one wait per queued decode, in queue order).  A later decode
  * still running on the GPU is not waited for.  With nothing queued: CLG_OK. */
 int clg_decode_wait(clg_engine* e);
+
+/* ---- typed replay columns -----------------------------------------------------------------
+ * The stable partition of a decoded batch by determinant class: what LogReplayerImpl
+ * (LogReplayerImpl.java:61-119) consumes one typed value at a time -- replayNextChannel a byte,
+ * replayRandomInt an int, replayNextTimestamp a long -- and SubpartitionRecoveryThread as int
+ * sizes, without the 13-byte rows around them.
+ *   class 0 ORDER (tag 0)         order        i8[n_class[0]]
+ *   class 1 TIMESTAMP (tag 1)     timestamp    i64[n_class[1]]
+ *   class 2 RNG (tag 2)           rng          i32[n_class[2]]
+ *   class 3 BUFFER_BUILT (tag 7)  buffer_built i32[n_class[3]]
+ *   class 4 WIDE (tags 3,4,5,6)   clg_decoded's side rows (w_idx the global record index), and
+ *                                 w_v0[k] = v0[w_idx[k]]
+ * Each column holds v0 of its class's records in record order, narrowed to the field's own
+ * width (lossless: the decode sign-extends those fields into v0).  tag[n_rec] is the decode's,
+ * in record order: it is the interleaving.  span_base[(n_spans + 1) * 5], always host memory
+ * (may be NULL): span_base[s * 5 + c] = class-c records before span s, so span s's channels are
+ * order[span_base[s*5] .. span_base[(s+1)*5]); an empty span has equal rows; the last row holds
+ * the totals.  `off` is not part of the columns: a caller that needs offsets keeps using the
+ * decode.  Nothing else is lost: walking tag and popping each class's next value gives back
+ * tag, v0 and the side table. */
+#define CLG_COL_CLASSES 5
+enum { CLG_COL_ORDER = 0, CLG_COL_TIMESTAMP = 1, CLG_COL_RNG = 2, CLG_COL_BUFFER_BUILT = 3, CLG_COL_WIDE = 4 };
+typedef struct clg_columns {
+  uint8_t* tag;
+  int8_t* order;
+  int64_t* timestamp;
+  int32_t* rng;
+  int32_t* buffer_built;
+  uint32_t* w_idx;
+  int32_t* w_rc;
+  int64_t* w_v1;
+  uint32_t* w_var_off;
+  uint32_t* w_var_len;
+  uint8_t* w_sub;
+  int64_t* w_v0;
+  uint64_t* span_base;        /* host memory, (n_spans + 1) * 5 entries, or NULL */
+  uint64_t cap_tag;           /* capacities in elements; a NULL column holds nothing */
+  uint64_t cap_order;
+  uint64_t cap_timestamp;
+  uint64_t cap_rng;
+  uint64_t cap_buffer_built;
+  uint64_t cap_wide;          /* of each w_* array */
+  uint32_t out_kind;          /* CLG_MEM_HOST / CLG_MEM_DEVICE / CLG_MEM_MAPPED (all columns) */
+  uint32_t reserved;
+  /* results */
+  uint64_t n_rec;
+  uint64_t n_class[CLG_COL_CLASSES]; /* the class totals */
+  int32_t err_status;         /* as clg_decoded: the decode's first error, CLG_OK if none */
+  uint32_t err_span;
+  int64_t err_off;
+  int32_t err_tag;
+  uint32_t reserved2;
+} clg_columns;
+
+/* Columns of a decoded batch: in->tag, v0, w_* (n_rec records, n_wide side rows; in->off is
+ * not read) are device memory, or registered host memory with in->out_kind CLG_MEM_MAPPED;
+ * span_rec_base (host, n_spans + 1 entries, not decreasing, the last at most n_rec) is the
+ * decode's.  Every column pointer NULL: sizes only (the totals and span_base are filled, no
+ * column is written).  A column whose capacity is below its total: CLG_E_CAPACITY with the
+ * totals and span_base filled and no column written.  A tag above 7: CLG_E_INVALID_ARG with the
+ * lowest such record index in err_off (err_tag the tag, err_span its span), nothing written.
+ * Side rows that do not match the wide tags (n_wide): CLG_E_INVALID_ARG.  CLG_MEM_DEVICE and
+ * CLG_MEM_MAPPED columns are written by the kernels; CLG_MEM_HOST ones through engine staging
+ * and a copy.  Synchronous. */
+int clg_columnize(clg_engine* e, const clg_decoded* in, const uint64_t* span_rec_base, uint32_t n_spans,
+                  clg_columns* out);
+/* clg_decode_logs / clg_decode_host into engine-owned device scratch (kept between calls; grown
+ * and decoded again on the decode's own CLG_E_CAPACITY), then clg_columnize.  Ranges, flush rules
+ * and decode errors are the decodes': with a decode error each span's records up to its first
+ * error are columnized, the error fields are passed through and the decode's status is
+ * returned.  Synchronous; pending asynchronous decodes are completed first. */
+int clg_decode_logs_columns(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                            clg_columns* out);
+int clg_decode_host_columns(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
+                            uint32_t n, clg_columns* out);
+/* The same columns on the CPU (no engine, no GPU): every array of `in` and `out` is host memory;
+ * results and error rules are clg_columnize's. */
+int clg_columnize_host(const clg_decoded* in, const uint64_t* span_rec_base, uint32_t n_spans, clg_columns* out);
 
 /* ---- replay-prep (DeterminantResponseEvent.merge + LogReplayer decode) ----------------
  * `n` candidate copies of logs (e.g. one per responding GPU / downstream):

@@ -143,6 +143,30 @@ public final class ClonosEngine implements AutoCloseable {
 		return new long[][] {first, ids, out};
 	}
 
+	/** getDeterminants(startEpochs[i]) of logs[i] decoded on the device and delivered as typed columns
+	 *  (clg_decode_logs_columns): the channels as bytes, the timestamps as longs, the random numbers and
+	 *  buffer sizes as ints, each in record order, plus the tag stream that interleaves them -- what
+	 *  LogReplayerImpl (LogReplayerImpl.java:61-119) consumes one value at a time.  Two native calls: sizes,
+	 *  then the columns into direct buffers of exactly those sizes.  A decode error keeps each span's
+	 *  records up to its first error; EngineDecodedColumns.errStatus() then says so. */
+	public EngineDecodedColumns decodeLogsColumns(int[] logs, long[] startEpochs) {
+		long[] res = new long[10];
+		long[] spanBase = new long[5 * (logs.length + 1)];
+		int st = nDecodeLogsColumns(handle, logs, startEpochs, null, null, null, null, null, null, null, null, null,
+			null, null, null, res, spanBase);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st); // engine failure, not a decode error
+		}
+		EngineDecodedColumns c = new EngineDecodedColumns(res, logs.length);
+		st = nDecodeLogsColumns(handle, logs, startEpochs, c.tag, c.order, c.timestamp, c.rng, c.bufferBuilt, c.wIdx,
+			c.wRc, c.wV1, c.wVarOff, c.wVarLen, c.wSub, c.wV0, res, c.spanBase);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st);
+		}
+		c.setResult(res);
+		return c;
+	}
+
 	@Override
 	public void close() {
 		nDestroy(handle);
@@ -256,6 +280,12 @@ public final class ClonosEngine implements AutoCloseable {
 	static native int nDecodeLogs(long engine, int[] logs, long[] startEpochs, ByteBuffer off, ByteBuffer tag,
 								  ByteBuffer v0, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff,
 								  ByteBuffer wVarLen, ByteBuffer wSub, long[] result, long[] spanRecBase);
+	/** clg_decode_logs_columns: typed columns into direct buffers (all null: sizes only); result = {nRec, nOrder,
+	 *  nTimestamp, nRng, nBufferBuilt, nWide, errStatus, errSpan, errOff, errTag}; spanBase = 5 (n + 1) longs. */
+	static native int nDecodeLogsColumns(long engine, int[] logs, long[] startEpochs, ByteBuffer tag, ByteBuffer order,
+										 ByteBuffer timestamp, ByteBuffer rng, ByteBuffer bufferBuilt, ByteBuffer wIdx,
+										 ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff, ByteBuffer wVarLen,
+										 ByteBuffer wSub, ByteBuffer wV0, long[] result, long[] spanBase);
 	/** clg_decode_logs_async: ctx[0] = a handle for nDecodeWait (the buffers stay reachable until then). */
 	static native int nDecodeLogsAsync(long engine, int[] logs, long[] startEpochs, ByteBuffer off, ByteBuffer tag,
 									   ByteBuffer v0, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff,
