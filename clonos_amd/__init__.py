@@ -3,8 +3,8 @@ replay-prep on gfx950).  The compute path is libclonos_engine.so (HIP); this pac
 the host-side mirror of the reference Java interfaces."""
 from . import determinants
 from ._lib import ClonosError
-from .engine import (DIFF, DIGEST, CausalLogID, DecodedBatch, DecodedColumns, Engine, ThreadCausalLog, columnize_host,
+from .engine import (DIFF, DIGEST, CausalLogID, DecodedBatch, DecodedColumns, Engine, ThreadCausalLog, columnize_host, gather_payloads_host,
                      digest_host, digest_prefixes_host, lcp_host)
 
 __all__ = ["Engine", "ThreadCausalLog", "CausalLogID", "DecodedBatch", "ClonosError", "determinants", "DIGEST",
-           "digest_host", "DIFF", "lcp_host", "digest_prefixes_host", "DecodedColumns", "columnize_host"]
+           "digest_host", "DIFF", "lcp_host", "digest_prefixes_host", "DecodedColumns", "columnize_host", "gather_payloads_host"]

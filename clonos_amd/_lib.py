@@ -66,6 +66,8 @@ EXPORTED = [
     "clg_diff_logs", "clg_lcp_host",
     "clg_digest_prefixes", "clg_digest_epochs", "clg_digest_prefixes_host",
     "clg_columnize", "clg_decode_logs_columns", "clg_decode_host_columns", "clg_columnize_host",
+    "clg_gather_payloads", "clg_gather_payloads_logs", "clg_decode_logs_columns_var", "clg_decode_host_columns_var",
+    "clg_gather_payloads_host",
 ]
 
 
@@ -174,6 +176,15 @@ class Columns(C.Structure):  # clg_columns
         ("n_rec", C.c_uint64), ("n_class", C.c_uint64 * COL_CLASSES),
         ("err_status", C.c_int32), ("err_span", C.c_uint32), ("err_off", C.c_int64), ("err_tag", C.c_int32),
         ("reserved2", C.c_uint32),
+    ]
+
+
+class Payloads(C.Structure):  # clg_payloads
+    _fields_ = [
+        ("var", C.c_void_p), ("pos", C.c_void_p),
+        ("cap_var", C.c_uint64), ("cap_pos", C.c_uint64),
+        ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
+        ("n_rows", C.c_uint64), ("n_var", C.c_uint64), ("bad_row", C.c_uint64),
     ]
 
 
@@ -352,6 +363,11 @@ def _load() -> C.CDLL:
         "clg_decode_logs_columns": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Columns)]),
         "clg_decode_host_columns": (C.c_int, [P, P, P, P, C.c_uint32, C.POINTER(Columns)]),
         "clg_columnize_host": (C.c_int, [C.POINTER(Decoded), P, C.c_uint32, C.POINTER(Columns)]),
+        "clg_gather_payloads": (C.c_int, [P, P, P, P, C.c_uint32, P, P, P, C.c_uint32, C.POINTER(Payloads)]),
+        "clg_gather_payloads_logs": (C.c_int, [P, P, P, C.c_uint32, P, P, P, C.c_uint32, C.POINTER(Payloads)]),
+        "clg_decode_logs_columns_var": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads)]),
+        "clg_decode_host_columns_var": (C.c_int, [P, P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads)]),
+        "clg_gather_payloads_host": (C.c_int, [P, P, P, C.c_uint32, P, P, P, C.POINTER(Payloads)]),
         "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),

@@ -36,11 +36,13 @@
 #include "digest.h"
 #include "engine_host.h"
 #include "kernels.h"
+#include "payload.h"
 #include "slice_order.h"
 
 static_assert(sizeof(clg_delta_req) == 32, "clg_delta_req layout");
 static_assert(sizeof(clg_diff) == 24, "clg_diff layout");
 static_assert(sizeof(clg_columns) == 232, "clg_columns layout");
+static_assert(sizeof(clg_payloads) == 64, "clg_payloads layout");
 
 using namespace clg_internal;  // the host-only types (engine_host.h)
 
@@ -284,6 +286,10 @@ struct clg_engine {
   // (pinned: the kernel writes them), host-output staging
   DevBuf d_colcnt, d_colbase, d_colsrb, d_colsb, d_colout;
   PinBuf h_colres, h_colsb;
+  // the payload column: span table | segment table | row_base (pinned, then device), the rows of
+  // a host caller, per-tile sums / bad rows / bases, the scan's results, host-output staging
+  DevBuf d_paydesc, d_payrows, d_paytile, d_payout;
+  PinBuf h_paydesc, h_payres;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 
@@ -3975,8 +3981,15 @@ int columnize_device(clg_engine* e, const clg_decoded& in, const uint64_t* span_
 
 // The decode into engine scratch (the host-output staging arrays, kept between calls), grown
 // and run again on the decode's own CLG_E_CAPACITY, then the columns of what it produced.
+// keep (optional): the decoded batch in engine scratch and columnize_device's own status, for
+// the payload column of the same rows (decode_columns_var).
+struct ColKeep {
+  clg_decoded d{};
+  bool valid = false;        // the decode produced a batch and columnize_device ran
+  int col_status = CLG_OK;   // columnize_device's
+};
 int decode_columns(clg_engine* e, const std::function<int(clg_decoded*, uint64_t*)>& run, uint32_t n_spans,
-                   clg_columns* out) {
+                   clg_columns* out, ColKeep* keep = nullptr) {
   clg::col_reset_result(out);
   std::vector<uint64_t> base(size_t(n_spans) + 1, 0);
   clg_decoded d{};
@@ -4008,7 +4021,9 @@ int decode_columns(clg_engine* e, const std::function<int(clg_decoded*, uint64_t
   if (st == CLG_E_CAPACITY) return st;
   if (st != CLG_OK && d.err_status == CLG_OK) return st;  // an engine failure, not a decode result
   const std::string decode_err = st != CLG_OK ? g_err : std::string();
-  CHK(columnize_device(e, d, base.data(), n_spans, out));
+  const int col_status = columnize_device(e, d, base.data(), n_spans, out);
+  if (keep) keep->d = d, keep->valid = true, keep->col_status = col_status;
+  CHK(col_status);
   out->err_status = d.err_status;
   out->err_span = d.err_span;
   out->err_off = d.err_off;
@@ -4017,7 +4032,241 @@ int decode_columns(clg_engine* e, const std::function<int(clg_decoded*, uint64_t
   return st;
 }
 
+// ---- the payload column (payload.h) ---------------------------------------------------------
+// The wide rows' payload bytes packed in row order: size and scan, the host's check of the
+// scan's totals, then pos and the copy.  Host work is O(spans + segments covered): a PaySpan per
+// span and the segment table; the rows stay on the device.
+//
+// d_off / d_len: device addresses of the rows.  sizes_forced: fill the results, write nothing.
+int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans, const std::vector<uint32_t>& segtab,
+                           const uint32_t* d_off, const uint32_t* d_len, const uint64_t* row_base, clg_payloads* out,
+                           bool sizes_forced = false) {
+  const uint32_t ns = uint32_t(spans.size());
+  clg::pay_reset_result(out);
+  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  if (!clg::pay_row_base_ok(row_base, ns)) return fail(CLG_E_INVALID_ARG, "row_base does not start at 0 or decreases");
+  const uint64_t n = ns ? row_base[ns] : 0;
+  if (n > 0xFFFFFFFFull) return fail(CLG_E_INVALID_ARG, "%llu rows in one call", (unsigned long long)n);
+  out->n_rows = n;
+  const bool sizes_only = sizes_forced || clg::pay_sizes_only(*out);
+  const bool direct = out->out_kind == CLG_MEM_DEVICE;
+  if (!sizes_only && direct && uintptr_t(out->pos) % 8) return fail(CLG_E_INVALID_ARG, "pos is not aligned to its element");
+  if (!n) {  // no rows: only pos[0]
+    if (sizes_only) return CLG_OK;
+    if (const char* name = clg::pay_short(*out, 0, 0)) return fail(CLG_E_CAPACITY, "%s is too small (rows 0)", name);
+    const uint64_t zero = 0;
+    if (direct) HIPCHK(hipMemcpy(out->pos, &zero, 8, hipMemcpyHostToDevice));
+    else out->pos[0] = 0;
+    return CLG_OK;
+  }
+  if (!d_off || !d_len) return fail(CLG_E_INVALID_ARG, "null row array");
+  const uint32_t n_tiles = uint32_t((n + clg::kPayTile - 1) / clg::kPayTile);
+
+  // span table | row_base | segment table, in one upload
+  const size_t sb = size_t(ns) * sizeof(clg::PaySpan), rb = size_t(ns + 1) * 8, tb = segtab.size() * 4;
+  CHK(e->h_paydesc.ensure(sb + rb + tb + 16));
+  CHK(e->d_paydesc.ensure(sb + rb + tb + 16));
+  uint8_t* h = e->h_paydesc.as<uint8_t>();
+  memcpy(h, spans.data(), sb);
+  memcpy(h + sb, row_base, rb);
+  if (tb) memcpy(h + sb + rb, segtab.data(), tb);
+  HIPCHK(hipMemcpyAsync(e->d_paydesc.p, h, sb + rb + tb, hipMemcpyHostToDevice, e->stream));
+  const uint8_t* dd = e->d_paydesc.as<uint8_t>();
+  const clg::PayIn in{d_off, d_len, reinterpret_cast<const uint64_t*>(dd + sb), reinterpret_cast<const clg::PaySpan*>(dd),
+                      reinterpret_cast<const uint32_t*>(dd + sb + rb), e->pool, n, ns, e->C()};
+  CHK(e->d_paytile.ensure(size_t(n_tiles) * 24 + 64));
+  uint64_t* d_sum = e->d_paytile.as<uint64_t>();
+  uint64_t* d_bad = d_sum + n_tiles;
+  uint64_t* d_base = d_bad + n_tiles;
+  CHK(e->h_payres.ensure(sizeof(clg::PayRes)));
+  clg::PayRes* res = e->h_payres.as<clg::PayRes>();
+
+  // size and scan; the totals come back before anything is written to the caller
+  CHK(e->timed("decode_payloads", n * 8 + uint64_t(n_tiles) * 40 + sb + rb, [&] {
+    return clg::launch_pay_size_scan(in, n_tiles, d_sum, d_bad, d_base, res, e->stream);
+  }));
+  CHK(e->sync());
+  out->n_var = res->n_var;
+  if (res->bad_row != clg::kPayNoRow) {
+    out->bad_row = res->bad_row;
+    return fail(CLG_E_INVALID_ARG, "row %llu passes its span's end", (unsigned long long)res->bad_row);
+  }
+  if (sizes_only) return CLG_OK;
+  const uint64_t nv = res->n_var;
+  if (const char* name = clg::pay_short(*out, n, nv))
+    return fail(CLG_E_CAPACITY, "%s is too small (rows %llu, payload bytes %llu)", name, (unsigned long long)n,
+                (unsigned long long)nv);
+
+  // where the kernels write: the caller's device arrays, or engine staging and one copy each
+  // (host and registered memory alike: the short rows' byte stores stay off the link)
+  uint64_t* dpos = out->pos;
+  uint8_t* dvar = out->var;
+  if (!direct) {
+    const size_t pb = clg_engine::al16((n + 1) * 8);
+    CHK(e->d_payout.ensure(pb + nv + 16));
+    dpos = e->d_payout.as<uint64_t>();
+    dvar = e->d_payout.as<uint8_t>() + pb;
+  }
+  CHK(e->timed("decode_payloads", n * 12 + (n + 1) * 8 + uint64_t(n_tiles) * 8 + 2 * nv, [&] {
+    return clg::launch_pay_write(in, n_tiles, d_base, nv, dpos, dvar, e->stream);
+  }));
+  if (!direct) {
+    HIPCHK(hipMemcpyAsync(out->pos, dpos, (n + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+    if (nv) HIPCHK(hipMemcpyAsync(out->var, dvar, nv, hipMemcpyDeviceToHost, e->stream));
+  }
+  return e->sync();
+}
+
+// The rows of a caller: device arrays as they are, host arrays staged.
+int stage_payload_rows(clg_engine* e, const uint32_t* off, const uint32_t* len, uint64_t n, uint32_t in_kind,
+                       const uint32_t** d_off, const uint32_t** d_len) {
+  *d_off = off;
+  *d_len = len;
+  if (in_kind != CLG_MEM_HOST || !n) return CLG_OK;
+  if (!off || !len) return fail(CLG_E_INVALID_ARG, "null row array");
+  const size_t b = clg_engine::al16(n * 4);
+  CHK(e->d_payrows.ensure(2 * b + 16));
+  uint8_t* d = e->d_payrows.as<uint8_t>();
+  HIPCHK(hipMemcpyAsync(d, off, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d + b, len, n * 4, hipMemcpyHostToDevice, e->stream));
+  *d_off = reinterpret_cast<const uint32_t*>(d);
+  *d_len = reinterpret_cast<const uint32_t*>(d + b);
+  return CLG_OK;
+}
+
+// Spans of one buffer (host input staged as clg_decode_host stages it) as contiguous PaySpans.
+int payload_spans_bytes(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
+                        uint32_t n, uint32_t in_kind, std::vector<clg::PaySpan>& spans) {
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; ++i) total += span_len[i];
+  if (total && !bytes) return fail(CLG_E_INVALID_ARG, "null argument");
+  const uint8_t* base = bytes;
+  uint64_t base_off = 0;
+  if (total) CHK(e->stage_spans(bytes, span_off, span_len, n, in_kind, &base, &base_off));
+  spans.resize(n);
+  for (uint32_t i = 0; i < n; ++i)
+    spans[i] = clg::PaySpan{span_len[i] ? base + (span_off[i] - base_off) : nullptr, 0, span_len[i], 0, 0};
+  return CLG_OK;
+}
+
+// getDeterminants(start_epoch[i]) of log[i], in place: plan_log_span's run and table entries.
+int payload_spans_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                       std::vector<clg::PaySpan>& spans, std::vector<uint32_t>& segtab) {
+  CHK(e->flush());
+  spans.resize(n);
+  const uint32_t C = e->C();
+  for (uint32_t i = 0; i < n; ++i) {
+    Log* l;
+    CHK(e->get_log(log[i], &l));
+    int32_t s = 0, nb = 0;
+    if (l->depth != 0) CHK(e->determinants_range(*l, start_epoch[i], &s, &nb));
+    spans[i] = clg::PaySpan{nullptr, segtab.size(), uint64_t(nb), 0, 0};
+    if (nb > 0) {  // only the segments the span covers go into the table (phys rebased on them)
+      const uint32_t s0 = uint32_t(s) / C, s1 = uint32_t(s + nb - 1) / C + 1;
+      spans[i].phys = uint32_t(s) - s0 * C;
+      segtab.insert(segtab.end(), l->segs.begin() + s0, l->segs.begin() + s1);
+    }
+  }
+  return CLG_OK;
+}
+
+// decode_columns, then the payloads of the wide rows it produced (row_base: the columns' wide
+// span bases).  The columns' status wins when it is not CLG_OK.
+int decode_columns_var(clg_engine* e, const std::function<int(clg_decoded*, uint64_t*)>& run, uint32_t n,
+                       clg_columns* out, clg_payloads* var,
+                       const std::function<int(std::vector<clg::PaySpan>&, std::vector<uint32_t>&)>& spans_of) {
+  clg::pay_reset_result(var);
+  std::vector<uint64_t> own_sb;
+  uint64_t* const caller_sb = out->span_base;
+  if (!caller_sb) {  // (the wide bases are needed whether or not the caller asked for them)
+    own_sb.assign(size_t(n + 1) * clg::kColClasses, 0);
+    out->span_base = own_sb.data();
+  }
+  ColKeep keep;
+  const int cs = decode_columns(e, run, n, out, &keep);
+  const std::string col_err = g_err;
+  std::vector<uint64_t> row_base(size_t(n) + 1);
+  for (uint32_t s = 0; s <= n; ++s) row_base[s] = out->span_base[size_t(s) * clg::kColClasses + clg::kColWide];
+  out->span_base = caller_sb;
+  if (!keep.valid || (keep.col_status != CLG_OK && keep.col_status != CLG_E_CAPACITY)) return cs;
+  std::vector<clg::PaySpan> spans;
+  std::vector<uint32_t> segtab;
+  int ps = spans_of(spans, segtab);
+  if (ps == CLG_OK)
+    ps = gather_payloads_device(e, spans, segtab, keep.d.w_var_off, keep.d.w_var_len, row_base.data(), var,
+                                keep.col_status == CLG_E_CAPACITY);
+  if (cs != CLG_OK) {
+    g_err = col_err;
+    return cs;
+  }
+  return ps;
+}
+
 }  // namespace
+
+int clg_gather_payloads(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
+                        uint32_t n_spans, const uint32_t* w_var_off, const uint32_t* w_var_len,
+                        const uint64_t* row_base, uint32_t in_kind, clg_payloads* out) {
+  ENGINE_GUARD(e);
+  if (!out || (n_spans && (!span_off || !span_len || !row_base))) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::pay_reset_result(out);
+  if (in_kind != CLG_MEM_HOST && in_kind != CLG_MEM_DEVICE) return fail(CLG_E_INVALID_ARG, "in_kind %u", in_kind);
+  if (!clg::pay_row_base_ok(row_base, n_spans)) return fail(CLG_E_INVALID_ARG, "row_base does not start at 0 or decreases");
+  std::vector<clg::PaySpan> spans;
+  CHK(payload_spans_bytes(e, bytes, span_off, span_len, n_spans, in_kind, spans));
+  const uint32_t *d_off, *d_len;
+  CHK(stage_payload_rows(e, w_var_off, w_var_len, n_spans ? row_base[n_spans] : 0, in_kind, &d_off, &d_len));
+  return gather_payloads_device(e, spans, {}, d_off, d_len, row_base, out);
+}
+
+int clg_gather_payloads_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                             const uint32_t* w_var_off, const uint32_t* w_var_len, const uint64_t* row_base,
+                             uint32_t in_kind, clg_payloads* out) {
+  ENGINE_GUARD(e);
+  if (!out || (n && (!log || !start_epoch || !row_base))) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::pay_reset_result(out);
+  if (in_kind != CLG_MEM_HOST && in_kind != CLG_MEM_DEVICE) return fail(CLG_E_INVALID_ARG, "in_kind %u", in_kind);
+  if (!clg::pay_row_base_ok(row_base, n)) return fail(CLG_E_INVALID_ARG, "row_base does not start at 0 or decreases");
+  std::vector<clg::PaySpan> spans;
+  std::vector<uint32_t> segtab;
+  CHK(payload_spans_logs(e, log, start_epoch, n, spans, segtab));
+  const uint32_t *d_off, *d_len;
+  CHK(stage_payload_rows(e, w_var_off, w_var_len, n ? row_base[n] : 0, in_kind, &d_off, &d_len));
+  return gather_payloads_device(e, spans, segtab, d_off, d_len, row_base, out);
+}
+
+int clg_decode_logs_columns_var(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                                clg_columns* out, clg_payloads* var) {
+  ENGINE_GUARD(e);
+  if (!out || !var || (n && (!log || !start_epoch))) return fail(CLG_E_INVALID_ARG, "null argument");
+  return decode_columns_var(
+      e, [&](clg_decoded* d, uint64_t* base) { return clg_decode_logs(e, log, start_epoch, n, d, base); }, n, out, var,
+      [&](std::vector<clg::PaySpan>& spans, std::vector<uint32_t>& segtab) {
+        return payload_spans_logs(e, log, start_epoch, n, spans, segtab);
+      });
+}
+
+int clg_decode_host_columns_var(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off,
+                                const uint64_t* span_len, uint32_t n, clg_columns* out, clg_payloads* var) {
+  ENGINE_GUARD(e);
+  if (!out || !var || (n && (!span_off || !span_len))) return fail(CLG_E_INVALID_ARG, "null argument");
+  // The bytes are staged again: the decode's staged copy shares d_stage with its fallbacks'
+  // re-plans, so whether it is intact when the decode returns depends on the path the decode took.
+  return decode_columns_var(
+      e, [&](clg_decoded* d, uint64_t* base) { return clg_decode_host(e, bytes, span_off, span_len, n, d, base); }, n, out,
+      var, [&](std::vector<clg::PaySpan>& spans, std::vector<uint32_t>&) {
+        return payload_spans_bytes(e, bytes, span_off, span_len, n, CLG_MEM_HOST, spans);
+      });
+}
+
+int clg_gather_payloads_host(const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
+                             uint32_t n_spans, const uint32_t* w_var_off, const uint32_t* w_var_len,
+                             const uint64_t* row_base, clg_payloads* out) {
+  const char* what = "";
+  const int st = clg::pay_build_host(bytes, span_off, span_len, n_spans, w_var_off, w_var_len, row_base, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "payloads: %s", what);
+}
 
 int clg_columnize(clg_engine* e, const clg_decoded* in, const uint64_t* span_rec_base, uint32_t n_spans,
                   clg_columns* out) {

@@ -590,6 +590,44 @@ int launch_col_write(const ColIn& in, uint32_t n_tiles, const uint64_t* d_base, 
                      const ColOut& out, const uint64_t* d_span_rec_base, uint32_t n_spans, uint64_t* span_base,
                      void* stream);
 
+// ---- the payload column (payload.h, payload.hip) -----------------------------------
+// Where a span's bytes lie, one entry per span (empty spans included, so a row's span index is
+// the entry's index).  base set: contiguous memory (a caller's device buffer, staged host
+// input), span byte o at base[o].  base null: a range of a log in the segment pool, span byte o
+// is physical byte p = phys + o, in segment segtab[segtab_off + p / C] at offset p % C
+// (plan_log_span's rule: the table holds only the segments the span covers, phys rebased).
+struct PaySpan {
+  const uint8_t* base;
+  uint64_t segtab_off;
+  uint64_t len;
+  uint32_t phys;
+  uint32_t pad;
+};
+struct PayIn {  // device addresses
+  const uint32_t* off;       // w_var_off[n_rows]
+  const uint32_t* len;       // w_var_len[n_rows]
+  const uint64_t* row_base;  // [n_spans + 1]
+  const PaySpan* spans;      // [n_spans]
+  const uint32_t* segtab;
+  const uint8_t* pool;
+  uint64_t n_rows;
+  uint32_t n_spans;
+  uint32_t seg_bytes;
+};
+// The scan's results, in pinned memory the host reads before anything is written to the caller.
+struct PayRes {
+  uint64_t n_var;
+  uint64_t bad_row;  // kPayNoRow: none
+};
+// Size (a workgroup per tile of kPayTile rows -> d_sum[tile], d_bad[tile]) and scan (one
+// workgroup -> d_base[tile], the bytes before the tile; *res).
+int launch_pay_size_scan(const PayIn& in, uint32_t n_tiles, uint64_t* d_sum, uint64_t* d_bad, uint64_t* d_base,
+                         PayRes* res, void* stream);
+// Pos (pos[k] for k <= n_rows; none when pos is null) and copy (var; none when n_var is 0).  The
+// copy scans its tile's lengths again and does not read pos, which may lie across the link.
+int launch_pay_write(const PayIn& in, uint32_t n_tiles, const uint64_t* d_base, uint64_t n_var, uint64_t* pos,
+                     uint8_t* var, void* stream);
+
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {
   uint8_t* dst;        // inside one segment

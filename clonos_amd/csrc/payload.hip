@@ -1,0 +1,298 @@
+// payload.hip -- the payload column (payload.h): the wide rows' payload bytes packed back to
+// back in row order, gathered from wherever the spans lie (pool segments, a caller's device
+// buffer, staged host input).
+//
+//  * k_pay_size   pass 1: a workgroup per tile of kPayTile rows loads the rows' offsets and
+//                 lengths (a 16-byte load each per thread), finds each row's span (one search
+//                 for the tile's ends, one per thread inside them, then steps), checks
+//                 off + len <= span length and writes the tile's byte sum (u64) and its lowest
+//                 bad row; a bad row counts as length 0 and none of its bytes is loaded
+//  * k_pay_scan   pass 2: ONE workgroup loops over the tiles' sums (a carry between rounds, no
+//                 look-back) and writes every tile's base; n_var and the lowest bad row go to
+//                 pinned memory, which the host reads before anything is written to the caller
+//  * k_pay_pos    pass 3: pos[k] = tile base + the scan inside the tile; pos[n_rows] = n_var
+//  * k_pay_copy   pass 4: the tile's scan again (pos may lie across the link and is not read
+//                 back), then a row of under kPayWaveRow bytes is copied by its own lane, byte
+//                 by byte inside the row's range, and a longer row by one wave, a per-segment
+//                 piece at a time, through copy_range<64>
+//
+// No atomics between workgroups, no spin waits and no word taken from another running
+// workgroup: kernel boundaries order the passes, and the result is deterministic (the order in
+// which a tile's long rows are handed to its waves is not, the bytes are).
+//
+// Source address: a span is either contiguous (PaySpan::base set) or a run of a log's physical
+// bytes behind the call's segment table; the kernels branch on base.  A degenerate table would
+// have to express a caller's buffer as pool segments, which it is not.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/clonos_engine.h"
+#include "copy_range.h"
+#include "kernels.h"
+#include "payload.h"
+
+namespace clg {
+
+namespace {
+
+constexpr uint32_t kPayWaves = kPayThreads / 64;
+static_assert(kPayPerThread == 4, "a thread's offsets and lengths are one 16-byte load each");
+static_assert(kPayTile <= 65536, "a tile's long rows are listed as u16");
+
+__device__ __forceinline__ uint64_t pay_wave_sum(uint64_t x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x += (uint64_t)__shfl_xor((unsigned long long)x, o, 64);
+  return x;
+}
+__device__ __forceinline__ uint64_t pay_wave_min(uint64_t x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint64_t y = (uint64_t)__shfl_xor((unsigned long long)x, o, 64);
+    x = y < x ? y : x;
+  }
+  return x;
+}
+__device__ __forceinline__ uint64_t pay_wave_incl(uint64_t x, uint32_t lane) {
+#pragma unroll
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o, 64);
+    if (lane >= o) x += y;
+  }
+  return x;
+}
+
+// Rows k0 .. k0 + 3 of a[] (n entries): zero at and past n.
+__device__ __forceinline__ void pay_load4(const uint32_t* __restrict__ a, uint64_t k0, uint64_t n, uint32_t v[4]) {
+  if (k0 + kPayPerThread <= n && ((uintptr_t)(a + k0) & 15) == 0) {
+    const uint4 q = *reinterpret_cast<const uint4*>(a + k0);
+    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+  } else {  // the last rows, or an array that is not 16-byte aligned
+#pragma unroll
+    for (uint32_t j = 0; j < kPayPerThread; ++j) v[j] = k0 + j < n ? a[k0 + j] : 0u;
+  }
+}
+
+// The spans of the tile's first and last row (thread 0 -> rng[0], rng[1]); the caller syncs.
+__device__ __forceinline__ void pay_tile_spans(const PayIn& in, uint64_t tile0, uint32_t* rng) {
+  const uint64_t last = (tile0 + kPayTile < in.n_rows ? tile0 + kPayTile : in.n_rows) - 1;
+  rng[0] = pay_span_of(in.row_base, 0, in.n_spans, tile0);
+  rng[1] = pay_span_of(in.row_base, rng[0], in.n_spans, last);
+}
+
+// This thread's rows k0 .. k0 + 3: offsets, lengths (0 past n_rows) and spans.
+struct PayRows {
+  uint32_t off[kPayPerThread], len[kPayPerThread], span[kPayPerThread];
+};
+__device__ __forceinline__ void pay_rows(const PayIn& in, uint64_t k0, const uint32_t* rng, PayRows& r) {
+  pay_load4(in.off, k0, in.n_rows, r.off);
+  pay_load4(in.len, k0, in.n_rows, r.len);
+#pragma unroll
+  for (uint32_t j = 0; j < kPayPerThread; ++j) r.span[j] = 0;
+  if (k0 >= in.n_rows) return;
+  uint32_t s = pay_span_of(in.row_base, rng[0], rng[1] + 1, k0);
+#pragma unroll
+  for (uint32_t j = 0; j < kPayPerThread; ++j) {
+    const uint64_t k = k0 + j;
+    if (k < in.n_rows) {
+      while (in.row_base[s + 1] <= k) ++s;  // (k < n_rows = row_base[n_spans]: ends at s < n_spans)
+      r.span[j] = s;
+    }
+  }
+}
+
+// The bytes before this thread's rows inside the tile (exclusive scan of the threads' sums).
+__device__ __forceinline__ uint64_t pay_tile_excl(uint64_t tsum, uint32_t tid, uint64_t* ws) {
+  const uint32_t lane = tid & 63, w = tid >> 6;
+  const uint64_t inc = pay_wave_incl(tsum, lane);
+  if (lane == 63) ws[w] = inc;
+  __syncthreads();
+  uint64_t before = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kPayWaves; ++k) before += k < w ? ws[k] : 0;
+  return before + inc - tsum;
+}
+
+// One lane copies a short row: loads and stores stay inside the row's own bytes, across a
+// segment boundary too.
+__device__ __forceinline__ void pay_copy_lane(const PayIn& in, const PaySpan& sp, uint32_t off, uint32_t len,
+                                              uint8_t* __restrict__ dst) {
+  if (sp.base) {
+    const uint8_t* src = sp.base + off;
+    for (uint32_t i = 0; i < len; ++i) dst[i] = src[i];
+    return;
+  }
+  const uint32_t C = in.seg_bytes;
+  uint64_t p = uint64_t(sp.phys) + off;
+  uint32_t done = 0;
+  while (done < len) {
+    const uint32_t so = uint32_t(p % C), take = len - done < C - so ? len - done : C - so;
+    const uint8_t* src = in.pool + size_t(in.segtab[sp.segtab_off + p / C]) * C + so;
+    for (uint32_t i = 0; i < take; ++i) dst[done + i] = src[i];
+    done += take;
+    p += take;
+  }
+}
+
+// One wave copies a long row, a per-segment piece at a time (arguments wave-uniform).
+__device__ __forceinline__ void pay_copy_wave(const PayIn& in, const PaySpan& sp, uint32_t off, uint32_t len,
+                                              uint8_t* dst, uint32_t lane) {
+  if (sp.base) {
+    copy_range<64>(sp.base + off, dst, len, lane);
+    return;
+  }
+  const uint32_t C = in.seg_bytes;
+  uint64_t p = uint64_t(sp.phys) + off;
+  uint32_t done = 0;
+  while (done < len) {
+    const uint32_t so = uint32_t(p % C), take = len - done < C - so ? len - done : C - so;
+    copy_range<64>(in.pool + size_t(in.segtab[sp.segtab_off + p / C]) * C + so, dst + done, take, lane);
+    done += take;
+    p += take;
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kPayThreads) void k_pay_size(const PayIn in, uint64_t* __restrict__ sum,
+                                                         uint64_t* __restrict__ bad) {
+  __shared__ uint32_t rng[2];
+  __shared__ uint64_t ws[kPayWaves], wb[kPayWaves];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint64_t tile0 = uint64_t(blockIdx.x) * kPayTile, k0 = tile0 + uint64_t(tid) * kPayPerThread;
+  if (tid == 0) pay_tile_spans(in, tile0, rng);
+  __syncthreads();
+  PayRows r;
+  pay_rows(in, k0, rng, r);
+  uint64_t acc = 0, b = kPayNoRow;
+#pragma unroll
+  for (uint32_t j = 0; j < kPayPerThread; ++j) {
+    if (k0 + j >= in.n_rows) continue;
+    if (pay_row_ok(r.off[j], r.len[j], in.spans[r.span[j]].len)) acc += r.len[j];
+    else if (b == kPayNoRow) b = k0 + j;
+  }
+  acc = pay_wave_sum(acc);
+  b = pay_wave_min(b);
+  if (lane == 0) ws[w] = acc, wb[w] = b;
+  __syncthreads();
+  if (tid == 0) {
+    for (uint32_t k = 1; k < kPayWaves; ++k) acc += ws[k], b = wb[k] < b ? wb[k] : b;
+    sum[blockIdx.x] = acc;
+    bad[blockIdx.x] = b;
+  }
+}
+
+__global__ __launch_bounds__(kPayScanThreads) void k_pay_scan(const uint64_t* __restrict__ sum,
+                                                             const uint64_t* __restrict__ bad, uint32_t n_tiles,
+                                                             uint64_t* __restrict__ base, PayRes* __restrict__ res) {
+  constexpr uint32_t kW = kPayScanThreads / 64;
+  __shared__ uint64_t ws[kW], wb[kW];
+  __shared__ uint64_t wtot;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  uint64_t carry = 0, b = kPayNoRow;
+  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kPayScanThreads) {
+    const uint32_t t = t0 + tid;
+    uint64_t c = 0;
+    if (t < n_tiles) {
+      c = sum[t];
+      const uint64_t x = bad[t];
+      b = x < b ? x : b;
+    }
+    const uint64_t inc = pay_wave_incl(c, lane);
+    if (lane == 63) ws[w] = inc;
+    __syncthreads();
+    if (tid < 64) {  // the waves' totals -> their exclusive prefix, and the round's total
+      const uint64_t x = lane < kW ? ws[lane] : 0;
+      const uint64_t s = pay_wave_incl(x, lane);
+      if (lane < kW) ws[lane] = s - x;
+      if (lane == kW - 1) wtot = s;
+    }
+    __syncthreads();
+    if (t < n_tiles) base[t] = carry + ws[w] + (inc - c);
+    carry += wtot;
+    __syncthreads();  // (ws is written again in the next round)
+  }
+  b = pay_wave_min(b);
+  if (lane == 0) wb[w] = b;
+  __syncthreads();
+  if (tid == 0) {
+    for (uint32_t j = 1; j < kW; ++j) b = wb[j] < b ? wb[j] : b;
+    res->n_var = carry;
+    res->bad_row = b;
+  }
+}
+
+__global__ __launch_bounds__(kPayThreads) void k_pay_pos(const PayIn in, const uint64_t* __restrict__ base,
+                                                        uint64_t n_var, uint64_t* __restrict__ pos) {
+  __shared__ uint64_t ws[kPayWaves];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t k0 = uint64_t(blockIdx.x) * kPayTile + uint64_t(tid) * kPayPerThread;
+  uint32_t len[kPayPerThread];
+  pay_load4(in.len, k0, in.n_rows, len);
+  uint64_t at = base[blockIdx.x] + pay_tile_excl(uint64_t(len[0]) + len[1] + len[2] + len[3], tid, ws);
+#pragma unroll
+  for (uint32_t j = 0; j < kPayPerThread; ++j) {
+    if (k0 + j < in.n_rows) pos[k0 + j] = at;
+    at += len[j];
+  }
+  if (blockIdx.x == gridDim.x - 1 && tid == 0) pos[in.n_rows] = n_var;
+}
+
+__global__ __launch_bounds__(kPayThreads) void k_pay_copy(const PayIn in, const uint64_t* __restrict__ base,
+                                                         uint64_t n_var, uint8_t* __restrict__ var) {
+  __shared__ uint32_t rng[2];
+  __shared__ uint64_t ws[kPayWaves];
+  __shared__ uint64_t s_pos[kPayTile];   // the long rows' destinations
+  __shared__ uint32_t s_span[kPayTile];  // ... and spans
+  __shared__ uint16_t s_long[kPayTile];  // the tile's long rows, in any order
+  __shared__ uint32_t s_nlong;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint64_t tile0 = uint64_t(blockIdx.x) * kPayTile, k0 = tile0 + uint64_t(tid) * kPayPerThread;
+  if (tid == 0) {
+    pay_tile_spans(in, tile0, rng);
+    s_nlong = 0;
+  }
+  __syncthreads();
+  PayRows r;
+  pay_rows(in, k0, rng, r);
+  uint64_t at = base[blockIdx.x] + pay_tile_excl(uint64_t(r.len[0]) + r.len[1] + r.len[2] + r.len[3], tid, ws);
+#pragma unroll
+  for (uint32_t j = 0; j < kPayPerThread; ++j) {
+    const uint32_t L = r.len[j];
+    if (L && at + L <= n_var) {  // (n_var: the total the host checked against the capacity)
+      if (L < kPayWaveRow) {
+        pay_copy_lane(in, in.spans[r.span[j]], r.off[j], L, var + at);
+      } else {
+        const uint32_t q = tid * kPayPerThread + j, i = atomicAdd(&s_nlong, 1u);  // (LDS, this workgroup's own)
+        s_long[i] = uint16_t(q);
+        s_pos[q] = at;
+        s_span[q] = r.span[j];
+      }
+    }
+    at += L;
+  }
+  __syncthreads();
+  const uint32_t n_long = s_nlong;
+  for (uint32_t i = w; i < n_long; i += kPayWaves) {
+    const uint32_t q = s_long[i];
+    const uint64_t k = tile0 + q;
+    pay_copy_wave(in, in.spans[s_span[q]], in.off[k], in.len[k], var + s_pos[q], lane);
+  }
+}
+
+int launch_pay_size_scan(const PayIn& in, uint32_t n_tiles, uint64_t* d_sum, uint64_t* d_bad, uint64_t* d_base,
+                         PayRes* res, void* stream) {
+  if (n_tiles) hipLaunchKernelGGL(k_pay_size, dim3(n_tiles), dim3(kPayThreads), 0, (hipStream_t)stream, in, d_sum, d_bad);
+  hipLaunchKernelGGL(k_pay_scan, dim3(1), dim3(kPayScanThreads), 0, (hipStream_t)stream, d_sum, d_bad, n_tiles, d_base, res);
+  return launch_status(hipGetLastError());
+}
+
+int launch_pay_write(const PayIn& in, uint32_t n_tiles, const uint64_t* d_base, uint64_t n_var, uint64_t* pos,
+                     uint8_t* var, void* stream) {
+  if (!n_tiles) return CLG_OK;
+  if (pos) hipLaunchKernelGGL(k_pay_pos, dim3(n_tiles), dim3(kPayThreads), 0, (hipStream_t)stream, in, d_base, n_var, pos);
+  if (var && n_var)
+    hipLaunchKernelGGL(k_pay_copy, dim3(n_tiles), dim3(kPayThreads), 0, (hipStream_t)stream, in, d_base, n_var, var);
+  return launch_status(hipGetLastError());
+}
+
+}  // namespace clg

@@ -72,6 +72,8 @@ class DecodedBatch:
         self.w_var_off, self.w_var_len, self.w_sub = w_var_off, w_var_len, w_sub
         self.span_rec_base = span_rec_base
         self.spans_bytes = spans_bytes  # optional: the raw span bytes, to materialise var fields
+        # optional: the packed payload column (clg_payloads.var); w_var_off then indexes it (DecodedColumns.to_soa)
+        self.var = None
 
     @property
     def n_rec(self) -> int:
@@ -82,7 +84,7 @@ class DecodedBatch:
 
     def determinants(self, s: int) -> List[D.Determinant]:
         """Rebuild Determinant objects for span s (LogReplayer consumption order)."""
-        raw = self.spans_bytes[s] if self.spans_bytes is not None else None
+        raw = self.var if self.var is not None else self.spans_bytes[s] if self.spans_bytes is not None else None
         sl = self.span_slice(s)
         widx = {int(i): k for k, i in enumerate(self.w_idx)}
         var = (lambda vo, vl: bytes(raw[vo:vo + vl])) if raw is not None else None
@@ -94,8 +96,8 @@ class DecodedBatch:
         i = int(self.span_rec_base[s]) + k
         if not 0 <= k < int(self.span_rec_base[s + 1]) - int(self.span_rec_base[s]):
             raise IndexError("record index outside the span")
-        if var is None and self.spans_bytes is not None:
-            raw = self.spans_bytes[s]
+        if var is None and (self.var is not None or self.spans_bytes is not None):
+            raw = self.var if self.var is not None else self.spans_bytes[s]
             var = lambda vo, vl: bytes(raw[vo:vo + vl])
         w = int(np.searchsorted(self.w_idx, i))  # w_idx ascends: global record indices in record order
         return self._determinant(i, w if w < len(self.w_idx) and int(self.w_idx[w]) == i else None, var)
@@ -114,7 +116,9 @@ class DecodedBatch:
             return D.BufferBuiltDeterminant(v0)
         rc, v1, vo, vl, sub = (int(self.w_rc[k]), int(self.w_v1[k]), int(self.w_var_off[k]),
                                int(self.w_var_len[k]), int(self.w_sub[k]))
-        b = var(vo, vl) if var is not None and vo else None
+        # (span-relative offset 0 is the record's tag, never a payload; an offset into the packed
+        # payload column may be 0)
+        b = var(vo, vl) if var is not None and (vo or self.var is not None) else None
         if t == D.IGNORE_CHECKPOINT:
             return D.IgnoreCheckpointDeterminant(rc, v0)
         if t == D.TIMER_TRIGGER:
@@ -178,6 +182,11 @@ class DecodedColumns:
         self.w_var_off, self.w_var_len, self.w_sub = w_var_off, w_var_len, w_sub
         self.span_base = np.asarray(span_base, np.uint64).reshape(-1, _lib.COL_CLASSES)
         self.spans_bytes = spans_bytes
+        # the payload column (clg_payloads; decode_logs_columns(..., payloads=True)): the wide rows'
+        # payload bytes packed in row order and var_pos[n_wide + 1], row k's bytes at
+        # var[var_pos[k]:var_pos[k + 1]]; None when not asked for
+        self.var: Optional[np.ndarray] = None
+        self.var_pos: Optional[np.ndarray] = None
         # a decode error the columns stop at (decode_logs_columns(..., partial=True)): a ClonosError, or None
         self.error: Optional[ClonosError] = None
 
@@ -202,8 +211,18 @@ class DecodedColumns:
         return SpanColumns(self.tag[r0:r1], self.order[a[0]:b[0]], self.timestamp[a[1]:b[1]], self.rng[a[2]:b[2]],
                            self.buffer_built[a[3]:b[3]], int(a[4]), int(b[4] - a[4]))
 
+    def payload(self, k: int) -> bytes:
+        """Wide row k's payload bytes (a name, a storage reference, a java stream; b"" for a row
+        without one), from the payload column."""
+        if self.var is None or self.var_pos is None:
+            raise ValueError("the columns carry no payload column (payloads=True)")
+        if not 0 <= k < len(self.var_pos) - 1:
+            raise IndexError("wide row index")
+        return self.var[int(self.var_pos[k]):int(self.var_pos[k + 1])].tobytes()
+
     def to_soa(self) -> DecodedBatch:
-        """The inverse: tag, v0 and the side table as the decode gives them (off is None)."""
+        """The inverse: tag, v0 and the side table as the decode gives them (off is None).  With
+        a payload column the batch carries it (DecodedBatch.var) and its w_var_off index it."""
         tag = np.asarray(self.tag)
         cls = COL_CLASS_OF_TAG[tag]
         v0 = np.zeros(tag.shape[0], np.int64)
@@ -214,14 +233,23 @@ class DecodedColumns:
             v0[m] = col
         if (cls == 5).any():
             raise ValueError("a tag above 7 in the columns")
+        if self.var is not None:
+            if len(self.var) >> 32:
+                raise ValueError("the payload column does not fit u32 offsets")
+            batch = DecodedBatch(None, tag.copy(), v0, self.w_idx, self.w_rc, self.w_v1,
+                                 self.var_pos[:-1].astype(np.uint32), self.w_var_len, self.w_sub, self.span_rec_base,
+                                 self.spans_bytes)
+            batch.var = self.var
+            return batch
         return DecodedBatch(None, tag.copy(), v0, self.w_idx, self.w_rc, self.w_v1, self.w_var_off, self.w_var_len,
                             self.w_sub, self.span_rec_base, self.spans_bytes)
 
     def determinants(self, s: int, var=None) -> List[D.Determinant]:
         """The Determinant objects of span s, as DecodedBatch.determinants builds them.
         var(off, len): span-relative bytes (names, references, java streams); None: from
-        spans_bytes when the columns kept them."""
-        if var is None and self.spans_bytes is not None:
+        spans_bytes when the columns kept them.  The payload column, when present, comes first."""
+        packed = var is None and self.var is not None
+        if var is None and not packed and self.spans_bytes is not None:
             raw = self.spans_bytes[s]
             var = lambda vo, vl: bytes(raw[vo:vo + vl])
         sp = self.span(s)
@@ -240,8 +268,9 @@ class DecodedColumns:
             elif c == 3:
                 out.append(D.BufferBuiltDeterminant(int(sp.buffer_built[k])))
             else:
+                v = (lambda vo, vl, _k=k: self.payload(_k)) if packed else var
                 out.append(_wide_determinant(t, int(self.w_v0[k]), int(self.w_rc[k]), int(self.w_v1[k]),
-                                             int(self.w_var_off[k]), int(self.w_var_len[k]), int(self.w_sub[k]), var))
+                                             int(self.w_var_off[k]), int(self.w_var_len[k]), int(self.w_sub[k]), v))
         return out
 
 
@@ -300,6 +329,50 @@ def columnize_host(batch: DecodedBatch) -> DecodedColumns:
     if st != _lib.CLG_OK:
         raise _columns_error(st, c)
     return _columns_result(c, arrs, base, batch.spans_bytes)
+
+
+def _payloads_struct(var: Optional[np.ndarray], pos: Optional[np.ndarray], kind: int = _lib.CLG_MEM_HOST) -> _lib.Payloads:
+    """clg_payloads over host arrays (capacity = their lengths); both None: sizes only."""
+    p = _lib.Payloads()
+    p.var = (_np_ptr(var) or None) if var is not None else None
+    p.pos = (_np_ptr(pos) or None) if pos is not None else None
+    p.cap_var = var.size if var is not None else 0
+    p.cap_pos = pos.size if pos is not None else 0
+    p.out_kind = kind
+    return p
+
+
+def _payloads_error(st: int, p: _lib.Payloads) -> ClonosError:
+    err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
+    err.n_rows, err.n_var, err.bad_row = int(p.n_rows), int(p.n_var), int(p.bad_row)
+    return err
+
+
+def _payloads_twice(call) -> Tuple[np.ndarray, np.ndarray]:
+    """call(clg_payloads) -> status, first for the sizes, then into host arrays of exactly those."""
+    p = _lib.Payloads()
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _payloads_error(st, p)
+    var, pos = np.zeros(int(p.n_var), np.uint8), np.zeros(int(p.n_rows) + 1, np.uint64)
+    p = _payloads_struct(var, pos)
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _payloads_error(st, p)
+    return var, pos
+
+
+def gather_payloads_host(data: Union[bytes, np.ndarray], span_off, span_len, w_var_off, w_var_len, row_base
+                         ) -> Tuple[np.ndarray, np.ndarray]:
+    """clg_gather_payloads_host: the payload column of spans data[span_off[s] : + span_len[s]] on
+    the CPU (no engine, no GPU).  Rows w_var_off / w_var_len are span-relative; row k belongs to
+    span s when row_base[s] <= k < row_base[s + 1].  Returns (var u8[n_var], pos u64[n_rows + 1])."""
+    buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    so, sl = np.ascontiguousarray(span_off, np.uint64), np.ascontiguousarray(span_len, np.uint64)
+    wo, wl = np.ascontiguousarray(w_var_off, np.uint32), np.ascontiguousarray(w_var_len, np.uint32)
+    rb = np.ascontiguousarray(row_base, np.uint64)
+    return _payloads_twice(lambda p: lib.clg_gather_payloads_host(_np_ptr(buf), _np_ptr(so), _np_ptr(sl), so.size,
+                                                                  _np_ptr(wo), _np_ptr(wl), _np_ptr(rb), C.byref(p)))
 
 
 # clg_digest rows: two spans are equal only when both fields are equal
@@ -845,20 +918,39 @@ class Engine:
             raise _columns_error(st, c)
         return _columns_result(c, arrs, sb)
 
+    @staticmethod
+    def _payload_bounds(total: int, n_spans: int) -> Tuple[np.ndarray, np.ndarray]:
+        """var / pos no batch of `total` encoded bytes can exceed (a wide record is at least 6 B)."""
+        return np.empty(total + 1, np.uint8), np.empty(total // 6 + n_spans + 2, np.uint64)
+
+    @staticmethod
+    def _payloads_attach(cols: DecodedColumns, p: _lib.Payloads, var: np.ndarray, pos: np.ndarray) -> DecodedColumns:
+        cols.var, cols.var_pos = var[:int(p.n_var)], pos[:int(p.n_rows) + 1]
+        return cols
+
     def decode_logs_columns(self, logs: Sequence["ThreadCausalLog"], start_epochs: Sequence[int],
-                            keep_bytes: bool = False, partial: bool = False) -> DecodedColumns:
+                            keep_bytes: bool = False, partial: bool = False, payloads: bool = False) -> DecodedColumns:
         """clg_decode_logs_columns: decode_logs' ranges decoded on the GPU and delivered as typed
         columns.  A decode error raises as decode_logs' does; partial=True returns the columns of
-        each span's records up to its first error instead, the error in .error."""
+        each span's records up to its first error instead, the error in .error.  payloads=True
+        (clg_decode_logs_columns_var): the wide rows' payload bytes come with the columns, gathered
+        on the device (.var, .var_pos, .payload(k)); the logs' bytes do not cross the link."""
         n = len(logs)
         h = np.array([l.handle for l in logs], np.uint32)
         ep = np.array(start_epochs, np.int64)
-        arrs = self._column_bounds(self.log_lengths(h)[1] if n else 0, n)
+        total = self.log_lengths(h)[1] if n else 0
+        arrs = self._column_bounds(total, n)
         base = np.zeros((n + 1) * _lib.COL_CLASSES, np.uint64)
         c = _columns_struct(arrs, base, _lib.CLG_MEM_HOST)
-        st = lib.clg_decode_logs_columns(self._h, _np_ptr(h), _np_ptr(ep), n, C.byref(c))
+        if payloads:
+            var, pos = self._payload_bounds(total, n)
+            p = _payloads_struct(var, pos)
+            st = lib.clg_decode_logs_columns_var(self._h, _np_ptr(h), _np_ptr(ep), n, C.byref(c), C.byref(p))
+        else:
+            st = lib.clg_decode_logs_columns(self._h, _np_ptr(h), _np_ptr(ep), n, C.byref(c))
         sb = [np.frombuffer(l.getDeterminants(e), np.uint8) for l, e in zip(logs, start_epochs)] if keep_bytes else None
-        return self._columns_finish(st, c, arrs, base, sb, partial)
+        cols = self._columns_finish(st, c, arrs, base, sb, partial)
+        return self._payloads_attach(cols, p, var, pos) if payloads else cols
 
     def decode_logs_columns_raw(self, handles: np.ndarray, start_epochs: np.ndarray, cols: _lib.Columns) -> int:
         """clg_decode_logs_columns into a clg_columns the caller set up (any out_kind; all pointers
@@ -866,9 +958,9 @@ class Engine:
         return lib.clg_decode_logs_columns(self._h, _np_ptr(handles), _np_ptr(start_epochs), len(handles), C.byref(cols))
 
     def decode_host_columns(self, data: Union[bytes, np.ndarray], spans: Optional[Sequence[Tuple[int, int]]] = None,
-                            partial: bool = False) -> DecodedColumns:
+                            partial: bool = False, payloads: bool = False) -> DecodedColumns:
         """clg_decode_host_columns: decode_host's spans decoded on the GPU and delivered as typed
-        columns (errors as decode_logs_columns)."""
+        columns (errors and payloads as decode_logs_columns)."""
         buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(
             data, np.uint8)
         if spans is None:
@@ -878,8 +970,51 @@ class Engine:
         arrs = self._column_bounds(int(sl.sum()), len(spans))
         base = np.zeros((len(spans) + 1) * _lib.COL_CLASSES, np.uint64)
         c = _columns_struct(arrs, base, _lib.CLG_MEM_HOST)
-        st = lib.clg_decode_host_columns(self._h, _np_ptr(buf), _np_ptr(so), _np_ptr(sl), len(spans), C.byref(c))
-        return self._columns_finish(st, c, arrs, base, [buf[int(o):int(o) + int(k)] for o, k in zip(so, sl)], partial)
+        if payloads:
+            var, pos = self._payload_bounds(int(sl.sum()), len(spans))
+            p = _payloads_struct(var, pos)
+            st = lib.clg_decode_host_columns_var(self._h, _np_ptr(buf), _np_ptr(so), _np_ptr(sl), len(spans), C.byref(c),
+                                                 C.byref(p))
+        else:
+            st = lib.clg_decode_host_columns(self._h, _np_ptr(buf), _np_ptr(so), _np_ptr(sl), len(spans), C.byref(c))
+        cols = self._columns_finish(st, c, arrs, base, [buf[int(o):int(o) + int(k)] for o, k in zip(so, sl)], partial)
+        return self._payloads_attach(cols, p, var, pos) if payloads else cols
+
+    # ---- the payload column (clg_payloads)
+    def gather_payloads(self, data, span_off, span_len, w_var_off, w_var_len, row_base, device: bool = False,
+                        out: Optional[_lib.Payloads] = None):
+        """clg_gather_payloads: the payload column of spans data[span_off[s] : + span_len[s]].
+        device=False: data, w_var_off and w_var_len are host arrays (staged); device=True: they
+        are device addresses (ints).  span_off, span_len and row_base are host arrays.  out: a
+        clg_payloads the caller set up (any out_kind; var and pos null: sizes only), filled in
+        place, the status returned; None: (var, pos) as host arrays of exactly the batch's sizes."""
+        so, sl = np.ascontiguousarray(span_off, np.uint64), np.ascontiguousarray(span_len, np.uint64)
+        rb = np.ascontiguousarray(row_base, np.uint64)
+        if device:
+            dp, wo, wl, kind, keep = int(data or 0), int(w_var_off or 0), int(w_var_len or 0), _lib.CLG_MEM_DEVICE, None
+        else:
+            buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(
+                data, np.uint8)
+            keep = (buf, np.ascontiguousarray(w_var_off, np.uint32), np.ascontiguousarray(w_var_len, np.uint32))
+            dp, wo, wl, kind = _np_ptr(keep[0]), _np_ptr(keep[1]), _np_ptr(keep[2]), _lib.CLG_MEM_HOST
+        call = lambda p: lib.clg_gather_payloads(self._h, dp or None, _np_ptr(so), _np_ptr(sl), so.size, wo or None,  # noqa: E731
+                                                 wl or None, _np_ptr(rb), kind, C.byref(p))
+        return call(out) if out is not None else _payloads_twice(call)
+
+    def gather_payloads_logs(self, handles, start_epochs, w_var_off, w_var_len, row_base, device: bool = False,
+                             out: Optional[_lib.Payloads] = None):
+        """clg_gather_payloads_logs: span i is getDeterminants(start_epochs[i]) of log handles[i],
+        read in place from the pool (rows, row_base, device and out as gather_payloads)."""
+        h, ep = np.ascontiguousarray(handles, np.uint32), np.ascontiguousarray(start_epochs, np.int64)
+        rb = np.ascontiguousarray(row_base, np.uint64)
+        if device:
+            wo, wl, kind, keep = int(w_var_off or 0), int(w_var_len or 0), _lib.CLG_MEM_DEVICE, None
+        else:
+            keep = (np.ascontiguousarray(w_var_off, np.uint32), np.ascontiguousarray(w_var_len, np.uint32))
+            wo, wl, kind = _np_ptr(keep[0]), _np_ptr(keep[1]), _lib.CLG_MEM_HOST
+        call = lambda p: lib.clg_gather_payloads_logs(self._h, _np_ptr(h), _np_ptr(ep), h.size, wo or None, wl or None,  # noqa: E731
+                                                      _np_ptr(rb), kind, C.byref(p))
+        return call(out) if out is not None else _payloads_twice(call)
 
     def decode_wait(self) -> None:
         """clg_decode_wait: completes the oldest queued asynchronous decode and raises its error."""
@@ -948,6 +1083,18 @@ class Engine:
         check(lib.clg_encode_batch(self._h, C.byref(ein), _np_ptr(out), out.size, _lib.CLG_MEM_HOST, C.byref(n_out),
                                    C.byref(bad)))
         return out[:n_out.value].tobytes()
+
+    def encode_columns(self, cols: "DecodedColumns") -> bytes:
+        """Re-encode columns that carry their payload column: encode_batch over to_soa()'s arrays
+        with w_var_off = var_pos[:-1] and var = cols.var -- the batch's bytes, without the log
+        crossing the link."""
+        if cols.var is None or cols.var_pos is None:
+            raise ValueError("the columns carry no payload column (payloads=True)")
+        if len(cols.var) >> 32:
+            raise ValueError(f"{len(cols.var)} payload bytes do not fit clg_encode_in's u32 offsets")
+        b = cols.to_soa()
+        return self.encode_batch(b.tag, b.v0, b.w_idx, b.w_rc, b.w_v1, cols.var_pos[:-1].astype(np.uint32), b.w_var_len,
+                                 b.w_sub, cols.var.tobytes())
 
     def encode_decoded(self, dec: "DecodedBatch", span_bytes: bytes) -> bytes:
         """Round trip: re-encode a decoded span (its var fields index the span bytes)."""

@@ -558,7 +558,8 @@ class ColumnReplayer:
     """LogReplayerImpl's cursor (LogReplayerImpl.java:51-158) over one span of DecodedColumns:
     the next determinant is the next tag; every method reads that tag and bumps one index into
     one column.  var(off, len): the span's bytes for names, references and java streams (None:
-    from the columns' spans_bytes when they kept them)."""
+    from the columns' payload column when they carry one -- the offsets are then var_pos, not
+    w_var_off -- else from their spans_bytes when they kept them)."""
 
     def __init__(self, columns, s: int, var=None):
         sp = columns.span(s)
@@ -567,7 +568,8 @@ class ColumnReplayer:
         self._order, self._ts, self._rng, self._bb = sp.order, sp.timestamp, sp.rng, sp.buffer_built
         self._pos = 0                      # records consumed
         self._at = [0, 0, 0, 0, sp.w0]     # the next index into each class's column
-        if var is None and columns.spans_bytes is not None:
+        self._packed = var is None and getattr(columns, "var", None) is not None
+        if var is None and not self._packed and columns.spans_bytes is not None:
             raw = columns.spans_bytes[s]
             var = lambda vo, vl: bytes(raw[vo:vo + vl])
         self._var = var
@@ -587,6 +589,9 @@ class ColumnReplayer:
 
     def _wide(self, t: int) -> D.Determinant:
         c, k = self._c, self._bump(4)
+        if self._packed:  # (w_var_off still says whether the row has a payload: nonzero)
+            return _wide_determinant(t, int(c.w_v0[k]), int(c.w_rc[k]), int(c.w_v1[k]), int(c.w_var_off[k]),
+                                     int(c.w_var_len[k]), int(c.w_sub[k]), lambda vo, vl: c.payload(k))
         return _wide_determinant(t, int(c.w_v0[k]), int(c.w_rc[k]), int(c.w_v1[k]), int(c.w_var_off[k]),
                                  int(c.w_var_len[k]), int(c.w_sub[k]), self._var)
 

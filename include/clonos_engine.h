@@ -391,6 +391,58 @@ int clg_decode_host_columns(clg_engine* e, const uint8_t* bytes, const uint64_t*
  * results and error rules are clg_columnize's. */
 int clg_columnize_host(const clg_decoded* in, const uint64_t* span_rec_base, uint32_t n_spans, clg_columns* out);
 
+/* ---- the payload column ---------------------------------------------------
+ * The columns carry a wide record's payload (a TimerTrigger's name, a SourceCheckpoint's storage
+ * reference, a Serializable record's stream) as w_var_off / w_var_len, offsets into its span's
+ * bytes.  The payload column carries the bytes: wide rows 0 .. n_rows, row k of span s when
+ * row_base[s] <= k < row_base[s + 1] (row_base: host memory, n_spans + 1 entries from 0, not
+ * decreasing, the last n_rows; for columns span_base[s * 5 + 4]), give
+ *   pos u64[n_rows + 1]  the exclusive prefix sum of w_var_len, pos[n_rows] = n_var
+ *   var u8[n_var]        var[pos[k] : pos[k + 1]] = span_s[w_var_off[k] : w_var_off[k] + w_var_len[k]]
+ * the shape of clg_encode_in's `var` (w_var_off = pos).  A row of length 0 occupies nothing.  A
+ * row whose range passes its span's end: CLG_E_INVALID_ARG, the lowest such row in bad_row,
+ * nothing written (no byte of such a row is loaded).  var and pos both NULL: sizes only (n_rows
+ * and n_var filled).  cap_var < n_var or cap_pos < n_rows + 1: CLG_E_CAPACITY, the results
+ * filled, nothing written. */
+typedef struct clg_payloads {
+  uint8_t* var;
+  uint64_t* pos;
+  uint64_t cap_var;           /* bytes */
+  uint64_t cap_pos;           /* entries */
+  uint32_t out_kind;          /* CLG_MEM_HOST / CLG_MEM_DEVICE / CLG_MEM_MAPPED (both arrays) */
+  uint32_t reserved;
+  /* results */
+  uint64_t n_rows;
+  uint64_t n_var;
+  uint64_t bad_row;           /* ~0 when none */
+} clg_payloads;
+
+/* Payloads of spans bytes[span_off[s], span_off[s] + span_len[s]) of one buffer.  in_kind
+ * (CLG_MEM_HOST / CLG_MEM_DEVICE) holds for bytes, w_var_off and w_var_len alike; host input is
+ * staged.  span_off, span_len and row_base are host memory.  Synchronous. */
+int clg_gather_payloads(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
+                        uint32_t n_spans, const uint32_t* w_var_off, const uint32_t* w_var_len,
+                        const uint64_t* row_base, uint32_t in_kind, clg_payloads* out);
+/* Span i is getDeterminants(start_epoch[i]) of log[i], read in place from the segment pool;
+ * ranges and flush rules are clg_decode_logs'.  in_kind holds for w_var_off and w_var_len. */
+int clg_gather_payloads_logs(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                             const uint32_t* w_var_off, const uint32_t* w_var_len, const uint64_t* row_base,
+                             uint32_t in_kind, clg_payloads* out);
+/* clg_decode_logs_columns / clg_decode_host_columns, then the payloads of the wide rows they
+ * produced, under one engine guard: the columns and the payloads describe the same bytes.  The
+ * columns' results, errors and statuses are the existing calls'; that status is returned when it
+ * is not CLG_OK, else the payloads'.  With a decode error the payloads are those of the rows
+ * kept (each span up to its first error).  When the columns report CLG_E_CAPACITY the payloads'
+ * n_rows and n_var are still filled (nothing is written), so one failed call sizes both. */
+int clg_decode_logs_columns_var(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                                clg_columns* out, clg_payloads* var);
+int clg_decode_host_columns_var(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off,
+                                const uint64_t* span_len, uint32_t n, clg_columns* out, clg_payloads* var);
+/* The same payloads on the CPU (no engine, no GPU): every array is host memory. */
+int clg_gather_payloads_host(const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
+                             uint32_t n_spans, const uint32_t* w_var_off, const uint32_t* w_var_len,
+                             const uint64_t* row_base, clg_payloads* out);
+
 /* ---- replay-prep (DeterminantResponseEvent.merge + LogReplayer decode) ----------------
  * `n` candidate copies of logs (e.g. one per responding GPU / downstream):
  * copy i is (key[i], bytes[off[i], off[i]+len[i])).  For every distinct key the LONGEST

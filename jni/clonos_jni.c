@@ -257,6 +257,60 @@ JNIEXPORT jint JNICALL FN(nDecodeLogsColumns)(JNIEnv* env, jclass cls, jlong e, 
   return s;
 }
 
+/* clg_decode_logs_columns_var: nDecodeLogsColumns' columns plus the payload column (var: the wide
+ * rows' payload bytes packed in row order; pos: (n_wide + 1) longs, row k's bytes at
+ * var[pos[k], pos[k + 1])); var and pos null with every column null: sizes only.  res is
+ * nDecodeLogsColumns' ten entries, then {n_rows, n_var, bad_row}. */
+JNIEXPORT jint JNICALL FN(nDecodeLogsColumnsVar)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray starts,
+                                                 jobject tag, jobject order, jobject timestamp, jobject rng,
+                                                 jobject buffer_built, jobject w_idx, jobject w_rc, jobject w_v1,
+                                                 jobject w_var_off, jobject w_var_len, jobject w_sub, jobject w_v0,
+                                                 jobject var, jobject pos, jlongArray res, jlongArray span_base) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* st = (*env)->GetLongArrayElements(env, starts, NULL);
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  clg_columns c;
+  memset(&c, 0, sizeof c);
+  c.tag = addr(env, tag, 0);
+  c.order = (int8_t*)addr(env, order, 0);
+  c.timestamp = (int64_t*)addr(env, timestamp, 0);
+  c.rng = (int32_t*)addr(env, rng, 0);
+  c.buffer_built = (int32_t*)addr(env, buffer_built, 0);
+  c.w_idx = (uint32_t*)addr(env, w_idx, 0);
+  c.w_rc = (int32_t*)addr(env, w_rc, 0);
+  c.w_v1 = (int64_t*)addr(env, w_v1, 0);
+  c.w_var_off = (uint32_t*)addr(env, w_var_off, 0);
+  c.w_var_len = (uint32_t*)addr(env, w_var_len, 0);
+  c.w_sub = addr(env, w_sub, 0);
+  c.w_v0 = (int64_t*)addr(env, w_v0, 0);
+  c.span_base = (uint64_t*)base;
+  c.cap_tag = cap(env, tag);
+  c.cap_order = cap(env, order);
+  c.cap_timestamp = cap(env, timestamp) / 8;
+  c.cap_rng = cap(env, rng) / 4;
+  c.cap_buffer_built = cap(env, buffer_built) / 4;
+  c.cap_wide = cap(env, w_sub);
+  c.out_kind = CLG_MEM_HOST;
+  clg_payloads p;
+  memset(&p, 0, sizeof p);
+  p.var = addr(env, var, 0);
+  p.pos = (uint64_t*)addr(env, pos, 0);
+  p.cap_var = cap(env, var);
+  p.cap_pos = cap(env, pos) / 8;
+  p.out_kind = CLG_MEM_HOST;
+  int s = clg_decode_logs_columns_var(ENG(e), (const uint32_t*)lg, (const int64_t*)st, (uint32_t)n, &c, &p);
+  jlong r[13] = {(jlong)c.n_rec,      (jlong)c.n_class[0], (jlong)c.n_class[1], (jlong)c.n_class[2], (jlong)c.n_class[3],
+                 (jlong)c.n_class[4], c.err_status,        c.err_span,          c.err_off,           c.err_tag,
+                 (jlong)p.n_rows,     (jlong)p.n_var,      (jlong)p.bad_row};
+  (*env)->SetLongArrayRegion(env, res, 0, 13, r);
+  (*env)->ReleaseLongArrayElements(env, span_base, base, 0);
+  (*env)->ReleaseLongArrayElements(env, starts, st, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  return s;
+}
+
 /* clg_decode_logs_async: the decode is queued; ctx[0] receives a handle that nDecodeWait
  * completes and frees (the output ByteBuffers must stay reachable until then). */
 typedef struct {

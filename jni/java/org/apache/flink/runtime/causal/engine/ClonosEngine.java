@@ -167,6 +167,32 @@ public final class ClonosEngine implements AutoCloseable {
 		return c;
 	}
 
+	/** decodeLogsColumns, and with withPayloads the payload column too (clg_decode_logs_columns_var): the
+	 *  names, storage references and java streams of the wide rows packed in row order, gathered on the
+	 *  device from the logs' segments -- EngineDecodedColumns.payload(k) is row k's bytes, and no log is
+	 *  copied to the host for them.  Two native calls: sizes (of the columns and the payloads), then both. */
+	public EngineDecodedColumns decodeLogsColumns(int[] logs, long[] startEpochs, boolean withPayloads) {
+		if (!withPayloads) {
+			return decodeLogsColumns(logs, startEpochs);
+		}
+		long[] res = new long[13];
+		long[] spanBase = new long[5 * (logs.length + 1)];
+		int st = nDecodeLogsColumnsVar(handle, logs, startEpochs, null, null, null, null, null, null, null, null, null,
+			null, null, null, null, null, res, spanBase);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st); // engine failure, not a decode error
+		}
+		EngineDecodedColumns c = new EngineDecodedColumns(res, logs.length);
+		c.allocatePayloads(res[10], res[11]);
+		st = nDecodeLogsColumnsVar(handle, logs, startEpochs, c.tag, c.order, c.timestamp, c.rng, c.bufferBuilt, c.wIdx,
+			c.wRc, c.wV1, c.wVarOff, c.wVarLen, c.wSub, c.wV0, c.var, c.varPos, res, c.spanBase);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st);
+		}
+		c.setResult(res);
+		return c;
+	}
+
 	@Override
 	public void close() {
 		nDestroy(handle);
@@ -286,6 +312,13 @@ public final class ClonosEngine implements AutoCloseable {
 										 ByteBuffer timestamp, ByteBuffer rng, ByteBuffer bufferBuilt, ByteBuffer wIdx,
 										 ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff, ByteBuffer wVarLen,
 										 ByteBuffer wSub, ByteBuffer wV0, long[] result, long[] spanBase);
+	/** clg_decode_logs_columns_var: nDecodeLogsColumns plus the payload column (var, and pos = nWide + 1 longs);
+	 *  result = nDecodeLogsColumns' ten entries, then {nRows, nVar, badRow}. */
+	static native int nDecodeLogsColumnsVar(long engine, int[] logs, long[] startEpochs, ByteBuffer tag, ByteBuffer order,
+											ByteBuffer timestamp, ByteBuffer rng, ByteBuffer bufferBuilt, ByteBuffer wIdx,
+											ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff, ByteBuffer wVarLen,
+											ByteBuffer wSub, ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos,
+											long[] result, long[] spanBase);
 	/** clg_decode_logs_async: ctx[0] = a handle for nDecodeWait (the buffers stay reachable until then). */
 	static native int nDecodeLogsAsync(long engine, int[] logs, long[] startEpochs, ByteBuffer off, ByteBuffer tag,
 									   ByteBuffer v0, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff,

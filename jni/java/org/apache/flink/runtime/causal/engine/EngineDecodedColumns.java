@@ -30,6 +30,9 @@ public final class EngineDecodedColumns {
 
 	final ByteBuffer tag, order, timestamp, rng, bufferBuilt;
 	final ByteBuffer wIdx, wRc, wV1, wVarOff, wVarLen, wSub, wV0;
+	/** The payload column (decodeLogsColumns(..., true)), else null: the wide rows' payload bytes packed in
+	 *  row order, and nWide + 1 longs, row k's bytes at var[varPos[k], varPos[k + 1]). */
+	ByteBuffer var, varPos;
 	final long[] spanBase;
 	private final int nSpans;
 	private long nRec;
@@ -58,6 +61,26 @@ public final class EngineDecodedColumns {
 
 	private static ByteBuffer direct(long bytes) {
 		return ByteBuffer.allocateDirect((int) Math.max(1, bytes)).order(ByteOrder.nativeOrder());
+	}
+
+	void allocatePayloads(long nRows, long nVar) {
+		this.var = direct(nVar);
+		this.varPos = direct(8 * (nRows + 1));
+	}
+
+	public boolean hasPayloads() {
+		return var != null;
+	}
+
+	/** Wide row k's payload (a TimerTrigger's name, a SourceCheckpoint's storage reference, a Serializable
+	 *  record's java stream; empty for a row without one): a slice of the payload column, not a copy.  k counts
+	 *  the batch's wide rows; span s's first is base(s, WIDE). */
+	public ByteBuffer payload(int k) {
+		if (var == null) {
+			throw new IllegalStateException("decoded without payloads");
+		}
+		final long a = varPos.getLong(8 * k), b = varPos.getLong(8 * (k + 1));
+		return slice(var, a, b - a, 1);
 	}
 
 	void setResult(long[] res) {
