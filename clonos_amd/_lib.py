@@ -68,6 +68,7 @@ EXPORTED = [
     "clg_columnize", "clg_decode_logs_columns", "clg_decode_host_columns", "clg_columnize_host",
     "clg_gather_payloads", "clg_gather_payloads_logs", "clg_decode_logs_columns_var", "clg_decode_host_columns_var",
     "clg_gather_payloads_host",
+    "clg_replay_prepare_columns", "clg_replay_prepare_columns_device",
 ]
 
 
@@ -230,6 +231,20 @@ class ReplayOut(C.Structure):
     ]
 
 
+class ReplayColumnsOut(C.Structure):  # clg_replay_columns_out
+    _fields_ = [
+        ("main", C.POINTER(Columns)),
+        ("var", C.POINTER(Payloads)),
+        ("buffer_sizes", C.c_void_p),
+        ("sizes_cap", C.c_uint64),
+        ("sizes_base", C.c_void_p),
+        ("sub_count", C.c_void_p),
+        ("sub_status", C.c_void_p),
+        ("sub_err_off", C.c_void_p),
+        ("sub_err_tag", C.c_void_p),
+    ]
+
+
 class EncodeIn(C.Structure):
     _fields_ = [
         ("tag", C.c_void_p), ("v0", C.c_void_p), ("n", C.c_uint64),
@@ -346,6 +361,9 @@ def _load() -> C.CDLL:
         "clg_causal_log_id_hash": (C.c_int32, [C.POINTER(CausalLogIdC)]),
         "clg_replay_prepare": (C.c_int, [P, C.POINTER(ReplayVertex), C.c_uint32, C.POINTER(ReplayOut)]),
         "clg_replay_prepare_device": (C.c_int, [P, C.POINTER(ReplayVertex), C.c_uint32, C.POINTER(ReplayOut)]),
+        "clg_replay_prepare_columns": (C.c_int, [P, C.POINTER(ReplayVertex), C.c_uint32, C.POINTER(ReplayColumnsOut)]),
+        "clg_replay_prepare_columns_device": (C.c_int, [P, C.POINTER(ReplayVertex), C.c_uint32,
+                                                        C.POINTER(ReplayColumnsOut)]),
         "clg_get_determinants_batch": (C.c_int, [P, P, P, C.c_uint32, P, C.c_uint64, C.c_uint32, P, P, u64p]),
         "clg_encode_batch": (C.c_int, [P, C.POINTER(EncodeIn), P, C.c_uint64, C.c_uint32, u64p, u64p]),
         "clg_enrich_batch": (C.c_int, [P, C.c_uint32, C.POINTER(EnrichReq), C.c_uint32, P, P, P, C.c_uint64,

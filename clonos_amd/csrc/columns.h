@@ -51,7 +51,16 @@ constexpr uint32_t kColScanThreads = 1024;
 // A tile's counts: a u32 per class, then the number of tags above 7, padded to 32 bytes.
 constexpr uint32_t kColCountWords = 8;
 
+// The one-launch form (k_col_small: one workgroup of kColScanThreads threads, four tiles a
+// round) takes batches of at most this many records and spans; larger ones take the
+// multi-kernel form.  kColSmallRecords is its floor, 8 tiles plus one (two rounds and a record, so
+// that a test reaches the carry between rounds): the measured crossover is 16384 records, and
+// between the two the one-launch form loses up to about 0.01 ms a call.
+constexpr uint32_t kColSmallRecords = 32769;
+constexpr uint32_t kColSmallSpans = 256;
+
 static_assert(kColPerThread == 16, "a thread's tags are one 16-byte load");
+static_assert(kColSmallRecords >= 8 * kColTile + 1, "a test can reach the carry between the small kernel's rounds");
 
 CLG_COL_HD uint32_t col_class(uint32_t tag) {
   return tag <= CLG_TAG_RNG ? tag : tag == CLG_TAG_BUFFER_BUILT ? kColBufferBuilt : tag < CLG_TAG_BUFFER_BUILT ? kColWide : kColBad;
@@ -81,6 +90,23 @@ inline const char* col_short_column(const clg_columns& c, uint64_t n, const uint
     if (col_cap(p, c.cap_wide) < tot[kColWide]) return "wide";
   return nullptr;
 }
+
+// The packed layout of the twelve arrays (tag, order, timestamp, rng, buffer_built, w_idx, w_rc,
+// w_v1, w_var_off, w_var_len, w_sub, w_v0) in one buffer: off[i] is array i's offset, a
+// multiple of 16, and off[12] the end.
+CLG_COL_HD void col_pack_offsets(uint64_t n, const uint64_t tot[kColClasses], uint64_t off[13]) {
+  const uint64_t nw = tot[kColWide];
+  const uint64_t bytes[12] = {n,      tot[kColOrder], 8 * tot[kColTimestamp], 4 * tot[kColRng], 4 * tot[kColBufferBuilt],
+                              4 * nw, 4 * nw,         8 * nw,                 4 * nw,           4 * nw,
+                              nw,     8 * nw};
+  off[0] = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 12; ++i) off[i + 1] = (off[i] + bytes[i] + 15) & ~uint64_t(15);
+}
+// An upper bound of col_pack_offsets' end that needs no totals.
+inline uint64_t col_pack_bound(uint64_t n, uint64_t n_wide) { return 9 * n + 33 * n_wide + 13 * 16; }
 
 inline void col_reset_result(clg_columns* out) {
   out->n_rec = 0;

@@ -181,6 +181,7 @@ struct DevSwitches {
   bool small_decode = env_num("CLONOS_SMALL", 1) != 0;        // 0: no single-launch small batches
   bool sidecar = env_num("CLONOS_SIDECAR", 1) != 0;           // 0: no Serializable candidate lists (developer A/B)
   bool keep_errors = env_num("CLONOS_KEEP_ERRORS", 1) != 0;   // 0: decode errors not kept on the fast path
+  bool columns_small = env_num("CLONOS_COLUMNS_SMALL", 1) != 0;  // 0: no one-launch columns / payloads for small batches
   uint32_t fused_perturb = uint32_t(env_num("CLONOS_FUSED_PERTURB", 0, 0));  // test switch (FusedCtl::perturb)
   // initial spill arena bytes (tests: force its growth); 0: the default
   size_t jser_arena = getenv("CLONOS_JSER_ARENA") ? std::max<size_t>(256, size_t(env_num("CLONOS_JSER_ARENA", 0, 0))) : 0;
@@ -286,10 +287,14 @@ struct clg_engine {
   // (pinned: the kernel writes them), host-output staging
   DevBuf d_colcnt, d_colbase, d_colsrb, d_colsb, d_colout;
   PinBuf h_colres, h_colsb;
+  // ... the one-launch form: result block | span bases | span boundaries (pinned: the kernel
+  // reads and writes them), and the packed columns of a host caller read back in one copy
+  PinBuf h_colsmall, h_colpack;
   // the payload column: span table | segment table | row_base (pinned, then device), the rows of
   // a host caller, per-tile sums / bad rows / bases, the scan's results, host-output staging
   DevBuf d_paydesc, d_payrows, d_paytile, d_payout;
   PinBuf h_paydesc, h_payres;
+  PinBuf h_paypack;  // the one-launch form: pos | var of a host caller read back in one copy
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 
@@ -3869,6 +3874,109 @@ ColPtrs col_ptrs(const clg_columns& c) {
                  {false, false, false, false, false, true, true, true, true, true, true, true}};
 }
 
+// A batch of at most kColSmallRecords records and kColSmallSpans spans, in one launch
+// (k_col_small): the kernel does the check below itself and reports it in pinned memory, so the
+// call has one host sync (two for CLG_MEM_HOST outputs, whose packed size is known only then).
+// columnize_device has checked the arguments.
+int columnize_small(clg_engine* e, const clg_decoded& in, const uint64_t* span_rec_base, uint32_t n_spans,
+                    clg_columns* out) {
+  const uint64_t n = in.n_rec, nw = in.n_wide;
+  const ColPtrs cp = col_ptrs(*out);
+  const bool sizes_only = clg::col_sizes_only(*out);
+  const bool want_sb = out->span_base && n_spans;
+  // pinned: result block | span bases | span boundaries
+  const size_t o_sb = clg_engine::al16(sizeof(clg::ColSmallRes)), sbn = size_t(n_spans) + 1;
+  const size_t o_srb = o_sb + sbn * clg::kColClasses * 8;
+  CHK(e->h_colsmall.ensure(o_srb + sbn * 8));
+  uint8_t* hp = e->h_colsmall.as<uint8_t>();
+  clg::ColSmallRes* res = reinterpret_cast<clg::ColSmallRes*>(hp);
+  uint64_t* h_sb = reinterpret_cast<uint64_t*>(hp + o_sb);
+  uint64_t* h_srb = reinterpret_cast<uint64_t*>(hp + o_srb);
+  if (want_sb) memcpy(h_srb, span_rec_base, sbn * 8);
+
+  // where the kernel writes: the caller's device arrays, the device side of registered host
+  // arrays, or (plain host memory, and registered memory that is not wholly inside one registered
+  // range) one packed engine buffer that is read back in one copy
+  void* dev[12];
+  bool packed = out->out_kind == CLG_MEM_HOST;
+  const uint64_t caps[12] = {out->cap_tag, out->cap_order, out->cap_timestamp, out->cap_rng, out->cap_buffer_built,
+                             out->cap_wide, out->cap_wide, out->cap_wide, out->cap_wide, out->cap_wide, out->cap_wide,
+                             out->cap_wide};
+  for (int i = 0; i < 12; ++i) {
+    dev[i] = cp.p[i];
+    if (out->out_kind == CLG_MEM_MAPPED && cp.p[i] && !sizes_only && !packed &&
+        !(dev[i] = reinterpret_cast<void*>(clg_mapped_device_address(cp.p[i], caps[i] * cp.width[i]))))
+      packed = true;
+  }
+  clg::ColSmallOut so{};
+  if (packed && !sizes_only) {
+    CHK(e->d_colout.ensure(clg::col_pack_bound(n, nw) + 16));
+    so.pack = e->d_colout.as<uint8_t>();
+  } else if (!sizes_only) {
+    // (an array that is the input's own stays as it is)
+    const void* src[12] = {in.tag,   nullptr,      nullptr,      nullptr,  nullptr, in.w_idx, in.w_rc,
+                           in.w_v1,  in.w_var_off, in.w_var_len, in.w_sub, nullptr};
+    for (int i = 0; i < 12; ++i)
+      if (src[i] && dev[i] == src[i]) dev[i] = nullptr;
+    so.tag = static_cast<uint8_t*>(dev[0]), so.order = static_cast<int8_t*>(dev[1]);
+    so.timestamp = static_cast<int64_t*>(dev[2]), so.rng = static_cast<int32_t*>(dev[3]);
+    so.buffer_built = static_cast<int32_t*>(dev[4]), so.w_idx = static_cast<uint32_t*>(dev[5]);
+    so.w_rc = static_cast<int32_t*>(dev[6]), so.w_v1 = static_cast<int64_t*>(dev[7]);
+    so.w_var_off = static_cast<uint32_t*>(dev[8]), so.w_var_len = static_cast<uint32_t*>(dev[9]);
+    so.w_sub = static_cast<uint8_t*>(dev[10]), so.w_v0 = static_cast<int64_t*>(dev[11]);
+  }
+  so.cap[0] = clg::col_cap(out->tag, out->cap_tag), so.cap[1] = clg::col_cap(out->order, out->cap_order);
+  so.cap[2] = clg::col_cap(out->timestamp, out->cap_timestamp), so.cap[3] = clg::col_cap(out->rng, out->cap_rng);
+  so.cap[4] = clg::col_cap(out->buffer_built, out->cap_buffer_built);
+  so.cap[5] = out->cap_wide;
+  for (int i = 5; i < 12; ++i)
+    if (!cp.p[i]) so.cap[5] = 0;
+  const clg::ColSmallIn si{in.tag,       in.v0,       in.w_idx, in.w_rc, in.w_v1, in.w_var_off,
+                           in.w_var_len, in.w_sub,    want_sb ? h_srb : nullptr,  n,       nw,
+                           want_sb ? n_spans : 0u, sizes_only ? 1u : 0u};
+  e->stats["columns_small"].launches++;
+  // (bytes: the tags twice and v0 once, the columns, the side rows in and out; as the multi-kernel form counts them)
+  const uint64_t moved = (want_sb ? sbn * 48 : 0) + (sizes_only ? n : 2 * n + 8 * n + 8 * (n - std::min(n, nw)) + 58 * nw);
+  CHK(e->timed("decode_columns", moved, [&] { return clg::launch_col_small(si, so, res, want_sb ? h_sb : nullptr, e->stream); }));
+  CHK(e->sync());
+  out->n_rec = n;
+  if (res->verdict == clg::kColSmallBadTag) {
+    out->err_status = CLG_E_INVALID_ARG;
+    out->err_span = clg::col_span_of(span_rec_base, n_spans, res->bad_index);
+    out->err_off = int64_t(res->bad_index);
+    out->err_tag = int32_t(res->bad_tag);
+    return fail(CLG_E_INVALID_ARG, "record %llu has tag %llu", (unsigned long long)res->bad_index,
+                (unsigned long long)res->bad_tag);
+  }
+  uint64_t tot[clg::kColClasses];
+  for (uint32_t c = 0; c < clg::kColClasses; ++c) out->n_class[c] = tot[c] = res->total[c];
+  if (res->verdict == clg::kColSmallWideCount)
+    return fail(CLG_E_INVALID_ARG, "n_wide is %llu, the tags hold %llu wide records", (unsigned long long)nw,
+                (unsigned long long)tot[clg::kColWide]);
+  if (res->verdict == clg::kColSmallWritten && packed && res->pack_off[12]) {
+    const uint64_t end = res->pack_off[12];
+    if (end > clg::col_pack_bound(n, nw)) return fail(CLG_E_DEVICE, "the packed columns end at %llu", (unsigned long long)end);
+    CHK(e->h_colpack.ensure(end));
+    HIPCHK(hipMemcpyAsync(e->h_colpack.p, so.pack, end, hipMemcpyDeviceToHost, e->stream));
+    CHK(e->sync());
+    const uint64_t cnt[12] = {n, tot[0], tot[1], tot[2], tot[3], nw, nw, nw, nw, nw, nw, nw};
+    for (int i = 0; i < 12; ++i)
+      if (cnt[i]) memcpy(cp.p[i], e->h_colpack.as<uint8_t>() + res->pack_off[i], cnt[i] * cp.width[i]);
+  }
+  if (out->span_base) {
+    if (n_spans) memcpy(out->span_base, h_sb, sbn * 8 * clg::kColClasses);
+    else memcpy(out->span_base, tot, sizeof tot);
+  }
+  if (res->verdict == clg::kColSmallCapacity) {
+    static const char* const kName[6] = {"tag", "order", "timestamp", "rng", "buffer_built", "wide"};
+    return fail(CLG_E_CAPACITY, "column %s is too small (records %llu; totals %llu %llu %llu %llu %llu)",
+                kName[res->short_cap < 6 ? res->short_cap : 5], (unsigned long long)n, (unsigned long long)tot[0],
+                (unsigned long long)tot[1], (unsigned long long)tot[2], (unsigned long long)tot[3],
+                (unsigned long long)tot[4]);
+  }
+  return CLG_OK;
+}
+
 // `in`: device addresses (the caller's device arrays, engine scratch, or the device side of
 // registered host memory).
 int columnize_device(clg_engine* e, const clg_decoded& in, const uint64_t* span_rec_base, uint32_t n_spans,
@@ -3886,6 +3994,8 @@ int columnize_device(clg_engine* e, const clg_decoded& in, const uint64_t* span_
   if (out->out_kind != CLG_MEM_HOST)
     for (int i = 0; i < 12; ++i)
       if (uintptr_t(cp.p[i]) % cp.width[i]) return fail(CLG_E_INVALID_ARG, "column %d is not aligned to its element", i);
+  if (e->sw.columns_small && n <= clg::kColSmallRecords && n_spans <= clg::kColSmallSpans)
+    return columnize_small(e, in, span_rec_base, n_spans, out);
   const uint32_t n_tiles = uint32_t((n + clg::kColTile - 1) / clg::kColTile);
   const clg::ColIn cin{in.tag, in.v0, in.w_idx, n, nw};
 
@@ -4037,6 +4147,58 @@ int decode_columns(clg_engine* e, const std::function<int(clg_decoded*, uint64_t
 // scan's totals, then pos and the copy.  Host work is O(spans + segments covered): a PaySpan per
 // span and the segment table; the rows stay on the device.
 //
+// At most kPaySmallRows rows over spans of at most kPaySmallBytes bytes, in one launch
+// (k_pay_small): the kernel does the check itself and reports it in pinned memory.  One host sync
+// (two for outputs that are not device memory: pos | var come back packed in one copy).
+// gather_payloads_device has checked the arguments and uploaded the descriptors behind `in`.
+int gather_payloads_small(clg_engine* e, const clg::PayIn& in, clg_payloads* out, bool sizes_only, uint64_t span_bytes,
+                          uint64_t desc_bytes) {
+  const uint64_t n = in.n_rows;
+  const bool direct = out->out_kind == CLG_MEM_DEVICE;
+  CHK(e->h_payres.ensure(sizeof(clg::PaySmallRes)));
+  clg::PaySmallRes* res = e->h_payres.as<clg::PaySmallRes>();
+  const uint64_t cap_pos = out->pos ? out->cap_pos : 0, cap_var = out->var ? out->cap_var : 0;
+  // where the kernel writes: the caller's device arrays, or engine staging (pos | var, var at a
+  // 16-byte boundary)
+  uint64_t* dpos = out->pos;
+  uint8_t* dvar = out->var;
+  const size_t pb = clg_engine::al16((n + 1) * 8);
+  // Staging holds what the spans hold.  Rows of a caller may overlap, so n_var can be more: then
+  // the kernel reports the staging as short, and runs once more with staging of n_var bytes.
+  uint64_t stage = std::min(cap_var, span_bytes);
+  e->stats["payloads_small"].launches++;
+  for (int round = 0;; ++round) {
+    if (!direct && !sizes_only) {
+      CHK(e->d_payout.ensure(pb + stage + 16));
+      dpos = e->d_payout.as<uint64_t>();
+      dvar = e->d_payout.as<uint8_t>() + pb;
+    }
+    CHK(e->timed("decode_payloads", n * 20 + (n + 1) * 8 + desc_bytes, [&] {
+      return clg::launch_pay_small(in, dpos, dvar, cap_pos, direct ? cap_var : stage, sizes_only, res, e->stream);
+    }));
+    CHK(e->sync());
+    if (round || direct || res->verdict != clg::kPaySmallCapacity || !res->short_cap || res->n_var > cap_var) break;
+    stage = res->n_var;
+  }
+  out->n_var = res->n_var;
+  if (res->verdict == clg::kPaySmallBadRow) {
+    out->bad_row = res->bad_row;
+    return fail(CLG_E_INVALID_ARG, "row %llu passes its span's end", (unsigned long long)res->bad_row);
+  }
+  if (res->verdict == clg::kPaySmallCapacity)
+    return fail(CLG_E_CAPACITY, "%s is too small (rows %llu, payload bytes %llu)", res->short_cap ? "var" : "pos",
+                (unsigned long long)n, (unsigned long long)res->n_var);
+  if (res->verdict == clg::kPaySmallWritten && !direct) {
+    const uint64_t nv = res->n_var;
+    CHK(e->h_paypack.ensure(pb + nv));
+    HIPCHK(hipMemcpyAsync(e->h_paypack.p, dpos, pb + nv, hipMemcpyDeviceToHost, e->stream));
+    CHK(e->sync());
+    memcpy(out->pos, e->h_paypack.p, (n + 1) * 8);
+    if (nv) memcpy(out->var, e->h_paypack.as<uint8_t>() + pb, nv);
+  }
+  return CLG_OK;
+}
+
 // d_off / d_len: device addresses of the rows.  sizes_forced: fill the results, write nothing.
 int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans, const std::vector<uint32_t>& segtab,
                            const uint32_t* d_off, const uint32_t* d_len, const uint64_t* row_base, clg_payloads* out,
@@ -4075,6 +4237,10 @@ int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans
   const uint8_t* dd = e->d_paydesc.as<uint8_t>();
   const clg::PayIn in{d_off, d_len, reinterpret_cast<const uint64_t*>(dd + sb), reinterpret_cast<const clg::PaySpan*>(dd),
                       reinterpret_cast<const uint32_t*>(dd + sb + rb), e->pool, n, ns, e->C()};
+  uint64_t span_bytes = 0;  // (an upper bound of n_var)
+  for (const clg::PaySpan& sp : spans) span_bytes += sp.len;
+  if (e->sw.columns_small && n <= clg::kPaySmallRows && span_bytes <= clg::kPaySmallBytes)
+    return gather_payloads_small(e, in, out, sizes_only, span_bytes, sb + rb);
   CHK(e->d_paytile.ensure(size_t(n_tiles) * 24 + 64));
   uint64_t* d_sum = e->d_paytile.as<uint64_t>();
   uint64_t* d_bad = d_sum + n_tiles;
@@ -4348,20 +4514,80 @@ int clg_replay_prep(clg_engine* e, const uint64_t* key, const uint8_t* bytes, co
 // LogReplayerImpl (:51-158), batched over failed vertices.  Main logs go through the
 // batched decode; subpartition recovery buffers through k_bufsizes (5-byte BufferBuilt
 // records, no chain walk).  All inputs are staged to HBM in one copy.
-static int replay_prepare(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_out* out, bool dev_in);
+//
+// replay_prepare is both forms' lookup, staging, subpartition kernels and outputs; only the
+// main-log step differs: `main(build, main_bytes, staged)` decodes the main logs (span i = vertex
+// i) from the plan `build` fills over the staged bytes, whose places `staged` gives as contiguous
+// PaySpans.  finish_sub: a main step that fails does not end the call before the subpartition
+// outputs are delivered (the columns form: a decode error is a result there); its status is the
+// call's.
+namespace {
+struct ReplaySubOut {  // clg_replay_out's subpartition fields
+  int32_t* buffer_sizes;
+  uint64_t sizes_cap;
+  uint64_t* sizes_base;
+  uint64_t* sub_count;
+  int32_t* sub_status;
+  int64_t* sub_err_off;
+  int32_t* sub_err_tag;
+};
+using ReplayBuild = std::function<void(clg_engine::DecodePlan&, uint32_t)>;
+using ReplayMain = std::function<int(const ReplayBuild&, uint64_t, const std::vector<clg::PaySpan>&)>;
+}  // namespace
+static int replay_prepare(clg_engine* e, const clg_replay_vertex* v, uint32_t n, const ReplaySubOut* out, bool dev_in,
+                          bool finish_sub, const ReplayMain& main);
+static int replay_prepare_soa(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_out* out, bool dev_in) {
+  ENGINE_GUARD(e);
+  if (!out || !out->main || !out->main_rec_base || (n && !v)) return fail(CLG_E_INVALID_ARG, "null argument");
+  const ReplaySubOut so{out->buffer_sizes, out->sizes_cap,   out->sizes_base, out->sub_count,
+                        out->sub_status,   out->sub_err_off, out->sub_err_tag};
+  return replay_prepare(e, v, n, &so, dev_in, false,
+                        [&](const ReplayBuild& build, uint64_t main_bytes, const std::vector<clg::PaySpan>&) {
+                          return e->decode(build, main_bytes, out->main, out->main_rec_base);
+                        });
+}
 int clg_replay_prepare(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_out* out) {
-  return replay_prepare(e, v, n, out, false);
+  return replay_prepare_soa(e, v, n, out, false);
 }
 int clg_replay_prepare_device(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_out* out) {
-  return replay_prepare(e, v, n, out, true);
+  return replay_prepare_soa(e, v, n, out, true);
+}
+// The columns form: the main step is the decode into engine scratch, the columns of what it
+// produced, and (var set) the payload column of the wide rows, gathered from the bytes where
+// replay_prepare staged them.  They are not staged a second time: d_stage has two writers,
+// flush() and stage_spans(), and neither runs between the staging and the payload gather -- the
+// decode and its fallbacks re-plan at the same addresses, the column kernels do not touch it, and
+// the spans handed to the gather are contiguous device memory already (no payload_spans_bytes).
+static int replay_prepare_columns(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_columns_out* out,
+                                  bool dev_in) {
+  ENGINE_GUARD(e);
+  if (!out || !out->main || (n && !v)) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::col_reset_result(out->main);
+  if (out->var) clg::pay_reset_result(out->var);
+  const ReplaySubOut so{out->buffer_sizes, out->sizes_cap,   out->sizes_base, out->sub_count,
+                        out->sub_status,   out->sub_err_off, out->sub_err_tag};
+  return replay_prepare(
+      e, v, n, &so, dev_in, true, [&](const ReplayBuild& build, uint64_t main_bytes, const std::vector<clg::PaySpan>& staged) {
+        const auto run = [&](clg_decoded* d, uint64_t* base) { return e->decode(build, main_bytes, d, base); };
+        if (!out->var) return decode_columns(e, run, n, out->main);
+        return decode_columns_var(e, run, n, out->main, out->var, [&](std::vector<clg::PaySpan>& spans, std::vector<uint32_t>&) {
+          spans = staged;
+          return CLG_OK;
+        });
+      });
+}
+int clg_replay_prepare_columns(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_columns_out* out) {
+  return replay_prepare_columns(e, v, n, out, false);
+}
+int clg_replay_prepare_columns_device(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_columns_out* out) {
+  return replay_prepare_columns(e, v, n, out, true);
 }
 // Pinned read-back of replay-prep's subpartition results: sizes, then count, err_off (8 B
 // each), status, err_tag (4 B each) per subpartition, as they lie on the device.
 static size_t o_rout_cnt(uint64_t n_sizes) { return (size_t(n_sizes) * 4 + 15) & ~size_t(15); }
 static size_t o_rout_end(uint32_t ns, uint64_t n_sizes) { return o_rout_cnt(n_sizes) + size_t(ns) * 24 + 64; }
-static int replay_prepare(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_out* out, bool dev_in) {
-  ENGINE_GUARD(e);
-  if (!out || !out->main || !out->main_rec_base || (n && !v)) return fail(CLG_E_INVALID_ARG, "null argument");
+static int replay_prepare(clg_engine* e, const clg_replay_vertex* v, uint32_t n, const ReplaySubOut* out, bool dev_in,
+                          bool finish_sub, const ReplayMain& main) {
   clg_engine::HostTimer lap(e, "host_replay_rest");  // (laps below: the sections)
   struct Piece {
     const uint8_t* p;
@@ -4518,10 +4744,14 @@ static int replay_prepare(clg_engine* e, const clg_replay_vertex* v, uint32_t n,
   }
   lap.lap("host_replay_sizes");
   // main logs: the batched decode (span i = vertex i)
-  auto build = [&](clg_engine::DecodePlan& p, uint32_t T) {
+  const ReplayBuild build = [&](clg_engine::DecodePlan& p, uint32_t T) {
     for (uint32_t i = 0; i < n; ++i) e->plan_host_span(p, dst + at[i], mains[i].len, i, T);
   };
-  CHK(e->decode(build, main_bytes, out->main, out->main_rec_base));
+  std::vector<clg::PaySpan> staged(n);
+  for (uint32_t i = 0; i < n; ++i) staged[i] = clg::PaySpan{mains[i].len ? dst + at[i] : nullptr, 0, mains[i].len, 0, 0};
+  const int main_status = main(build, main_bytes, staged);
+  if (main_status != CLG_OK && !finish_sub) return main_status;
+  const std::string main_err = main_status != CLG_OK ? g_err : std::string();
   lap.lap("host_replay_decode");
   CHK(e->sync());
   // a Serializable walk in a subpartition buffer found the spill arena full: again, larger
@@ -4544,7 +4774,8 @@ static int replay_prepare(clg_engine* e, const clg_replay_vertex* v, uint32_t n,
     memcpy(out->sub_err_tag, hr + oc + size_t(ns) * 20, size_t(ns) * 4);
   }
   lap.lap("host_replay_finish");
-  return CLG_OK;
+  if (main_status != CLG_OK) g_err = main_err;
+  return main_status;
 }
 
 // SimpleDeterminantEncoder.encodeTo over a batch (encode.hip): sizes pass, one host read

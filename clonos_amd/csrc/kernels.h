@@ -590,6 +590,60 @@ int launch_col_write(const ColIn& in, uint32_t n_tiles, const uint64_t* d_base, 
                      const ColOut& out, const uint64_t* d_span_rec_base, uint32_t n_spans, uint64_t* span_base,
                      void* stream);
 
+// The one-launch form for small batches (k_col_small: one workgroup does count, scan, the
+// check the host does for the multi-kernel form, write, span bases, wide v0 and the copies).
+struct ColSmallIn {  // device addresses of the decoded batch; span_rec_base: pinned or device, null without spans
+  const uint8_t* tag;
+  const int64_t* v0;
+  const uint32_t* w_idx;
+  const int32_t* w_rc;
+  const int64_t* w_v1;
+  const uint32_t* w_var_off;
+  const uint32_t* w_var_len;
+  const uint8_t* w_sub;
+  const uint64_t* span_rec_base;  // [n_spans + 1]
+  uint64_t n, n_wide;
+  uint32_t n_spans;
+  uint32_t sizes_only;
+};
+// Where the columns go.  pack null: the twelve addresses as given (a null one is not written:
+// the array is the input's own, or holds nothing).  pack set: the kernel lays all twelve out
+// in pack, each section 16-byte aligned (col_pack_offsets), and the addresses are ignored.
+struct ColSmallOut {
+  uint8_t* tag;
+  int8_t* order;
+  int64_t* timestamp;
+  int32_t* rng;
+  int32_t* buffer_built;
+  uint32_t* w_idx;
+  int32_t* w_rc;
+  int64_t* w_v1;
+  uint32_t* w_var_off;
+  uint32_t* w_var_len;
+  uint8_t* w_sub;
+  int64_t* w_v0;
+  uint8_t* pack;
+  uint64_t cap[6];  // usable capacities: tag, order, timestamp, rng, buffer_built, the wide rows
+};
+enum : uint32_t {
+  kColSmallWritten = 0,   // the columns are written
+  kColSmallSizes = 1,     // a sizes-only call: totals and span bases
+  kColSmallBadTag = 2,    // bad_index / bad_tag
+  kColSmallWideCount = 3, // n_wide differs from the wide total
+  kColSmallCapacity = 4,  // short: the first short capacity's index in ColSmallOut::cap
+};
+struct ColSmallRes {  // pinned memory; with any verdict but kColSmallWritten no column is written
+  uint64_t total[5];
+  uint64_t bad_index;
+  uint64_t bad_tag;
+  uint32_t verdict;
+  uint32_t short_cap;
+  uint64_t pack_off[13];  // the packed sections' offsets in ColPtrs order; [12]: the end
+};
+// span_base: pinned, (n_spans + 1) * 5 entries, written with every verdict but kColSmallBadTag
+// (null or n_spans 0: none).
+int launch_col_small(const ColSmallIn& in, const ColSmallOut& out, ColSmallRes* res, uint64_t* span_base, void* stream);
+
 // ---- the payload column (payload.h, payload.hip) -----------------------------------
 // Where a span's bytes lie, one entry per span (empty spans included, so a row's span index is
 // the entry's index).  base set: contiguous memory (a caller's device buffer, staged host
@@ -627,6 +681,24 @@ int launch_pay_size_scan(const PayIn& in, uint32_t n_tiles, uint64_t* d_sum, uin
 // copy scans its tile's lengths again and does not read pos, which may lie across the link.
 int launch_pay_write(const PayIn& in, uint32_t n_tiles, const uint64_t* d_base, uint64_t n_var, uint64_t* pos,
                      uint8_t* var, void* stream);
+
+// The one-launch form for small batches (k_pay_small: one workgroup does size, scan, the check
+// the host does for the multi-kernel form, pos and the copy).
+enum : uint32_t {
+  kPaySmallWritten = 0,   // pos and var are written
+  kPaySmallSizes = 1,     // a sizes-only call
+  kPaySmallBadRow = 2,    // bad_row
+  kPaySmallCapacity = 3,  // short: 0 pos, 1 var
+};
+struct PaySmallRes {  // pinned memory; with any verdict but kPaySmallWritten nothing is written
+  uint64_t n_var;
+  uint64_t bad_row;  // kPayNoRow: none
+  uint32_t verdict;
+  uint32_t short_cap;
+};
+// cap_pos / cap_var: usable capacities (0 for a null array).
+int launch_pay_small(const PayIn& in, uint64_t* pos, uint8_t* var, uint64_t cap_pos, uint64_t cap_var, bool sizes_only,
+                     PaySmallRes* res, void* stream);
 
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {

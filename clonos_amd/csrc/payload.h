@@ -44,6 +44,16 @@ constexpr uint32_t kPayScanThreads = 1024;
 // Rows of at least this many bytes are copied by a wave, shorter ones by one lane.
 constexpr uint32_t kPayWaveRow = 64;
 constexpr uint64_t kPayNoRow = ~0ull;
+// The one-launch form (k_pay_small: one workgroup of kPayScanThreads threads, four tiles a
+// round) takes calls of at most this many rows whose spans hold at most this many bytes (an upper
+// bound of n_var that the host knows); larger ones take the multi-kernel form.  kPaySmallRows is
+// its floor, two rounds plus one row: the measured crossover is 2048 to 4096 rows of 41 bytes on average,
+// and between the two the one-launch form loses.  kPaySmallBytes lies between the
+// last payload size measured faster (81 KB) and the first measured slower (168 KB).
+constexpr uint32_t kPaySmallRows = 8193;
+constexpr uint32_t kPaySmallBytes = 131072;
+static_assert(kPaySmallRows >= 2 * (kPayScanThreads / kPayThreads) * kPayTile + 1,
+              "a test can reach the carry between the small kernel's rounds");
 
 // A row's range lies inside its span (64-bit: off + len of two u32 does not wrap).
 CLG_PAY_HD bool pay_row_ok(uint32_t off, uint32_t len, uint64_t span_len) { return uint64_t(off) + len <= span_len; }

@@ -237,52 +237,157 @@ __global__ __launch_bounds__(kPayThreads) void k_pay_pos(const PayIn in, const u
   if (blockIdx.x == gridDim.x - 1 && tid == 0) pos[in.n_rows] = n_var;
 }
 
-__global__ __launch_bounds__(kPayThreads) void k_pay_copy(const PayIn in, const uint64_t* __restrict__ base,
-                                                         uint64_t n_var, uint8_t* __restrict__ var) {
-  __shared__ uint32_t rng[2];
-  __shared__ uint64_t ws[kPayWaves];
-  __shared__ uint64_t s_pos[kPayTile];   // the long rows' destinations
-  __shared__ uint32_t s_span[kPayTile];  // ... and spans
-  __shared__ uint16_t s_long[kPayTile];  // the tile's long rows, in any order
-  __shared__ uint32_t s_nlong;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint64_t tile0 = uint64_t(blockIdx.x) * kPayTile, k0 = tile0 + uint64_t(tid) * kPayPerThread;
+// A tile's LDS for pay_copy_tile.
+struct PayTileLds {
+  uint64_t s_pos[kPayTile];   // the long rows' destinations
+  uint64_t ws[kPayWaves];
+  uint32_t s_span[kPayTile];  // ... and spans
+  uint32_t rng[2];
+  uint32_t s_nlong;
+  uint16_t s_long[kPayTile];  // the tile's long rows, in any order
+};
+
+// One tile's pos and copy, by kPayThreads threads (tid 0 .. 255) that all call it: the rows
+// tile0 .. tile0 + kPayTile (those below n_rows), whose bytes start at `base`.  pos null: not
+// written.  l is the calling threads' own LDS; three __syncthreads inside.
+__device__ __forceinline__ void pay_copy_tile(const PayIn& in, uint64_t tile0, uint32_t tid, uint64_t base, uint64_t n_var,
+                                              uint64_t* __restrict__ pos, uint8_t* __restrict__ var, PayTileLds& l) {
+  const uint32_t lane = tid & 63, w = tid >> 6;
+  const uint64_t k0 = tile0 + uint64_t(tid) * kPayPerThread;
   if (tid == 0) {
-    pay_tile_spans(in, tile0, rng);
-    s_nlong = 0;
+    if (tile0 < in.n_rows) pay_tile_spans(in, tile0, l.rng);
+    l.s_nlong = 0;
   }
   __syncthreads();
   PayRows r;
-  pay_rows(in, k0, rng, r);
-  uint64_t at = base[blockIdx.x] + pay_tile_excl(uint64_t(r.len[0]) + r.len[1] + r.len[2] + r.len[3], tid, ws);
+  pay_rows(in, k0, l.rng, r);
+  uint64_t at = base + pay_tile_excl(uint64_t(r.len[0]) + r.len[1] + r.len[2] + r.len[3], tid, l.ws);
 #pragma unroll
   for (uint32_t j = 0; j < kPayPerThread; ++j) {
     const uint32_t L = r.len[j];
-    if (L && at + L <= n_var) {  // (n_var: the total the host checked against the capacity)
+    if (pos && k0 + j < in.n_rows) pos[k0 + j] = at;
+    if (L && at + L <= n_var) {  // (n_var: the total that was checked against the capacity)
       if (L < kPayWaveRow) {
         pay_copy_lane(in, in.spans[r.span[j]], r.off[j], L, var + at);
       } else {
-        const uint32_t q = tid * kPayPerThread + j, i = atomicAdd(&s_nlong, 1u);  // (LDS, this workgroup's own)
-        s_long[i] = uint16_t(q);
-        s_pos[q] = at;
-        s_span[q] = r.span[j];
+        const uint32_t q = tid * kPayPerThread + j, i = atomicAdd(&l.s_nlong, 1u);  // (LDS, this workgroup's own)
+        l.s_long[i] = uint16_t(q);
+        l.s_pos[q] = at;
+        l.s_span[q] = r.span[j];
       }
     }
     at += L;
   }
   __syncthreads();
-  const uint32_t n_long = s_nlong;
+  const uint32_t n_long = l.s_nlong;
   for (uint32_t i = w; i < n_long; i += kPayWaves) {
-    const uint32_t q = s_long[i];
+    const uint32_t q = l.s_long[i];
     const uint64_t k = tile0 + q;
-    pay_copy_wave(in, in.spans[s_span[q]], in.off[k], in.len[k], var + s_pos[q], lane);
+    pay_copy_wave(in, in.spans[l.s_span[q]], in.off[k], in.len[k], var + l.s_pos[q], lane);
   }
+}
+
+__global__ __launch_bounds__(kPayThreads) void k_pay_copy(const PayIn in, const uint64_t* __restrict__ base,
+                                                         uint64_t n_var, uint8_t* __restrict__ var) {
+  __shared__ PayTileLds l;
+  pay_copy_tile(in, uint64_t(blockIdx.x) * kPayTile, threadIdx.x, base[blockIdx.x], n_var, nullptr, var, l);
+}
+
+// ---- small batches, one launch --------------------------------------------------------------
+// ONE workgroup does size, scan, the check the host does between the multi-kernel form's
+// passes, pos and the copy, for at most kPaySmallRows rows.  A round is four tiles, one per 256
+// threads.  Phase 1: the rows' spans and ranges, the tiles' byte sums in LDS, n_var, the lowest
+// bad row, the capacities; the result block goes to pinned memory.  Phase 2, only when the
+// check passed: the tiles through pay_copy_tile with the bases from LDS.  No byte of a bad row is
+// loaded (a bad row ends the kernel before any copy) and no store lands at or past n_var.
+namespace {
+constexpr uint32_t kPaySmallWaves = kPayScanThreads / 64;
+constexpr uint32_t kPaySmallRoundTiles = kPayScanThreads / kPayThreads;
+constexpr uint32_t kPaySmallMaxTiles = (kPaySmallRows + kPayTile - 1) / kPayTile;
+}  // namespace
+
+__global__ __launch_bounds__(kPayScanThreads) void k_pay_small(const PayIn in, uint64_t* __restrict__ pos,
+                                                              uint8_t* __restrict__ var, uint64_t cap_pos, uint64_t cap_var,
+                                                              uint32_t sizes_only, PaySmallRes* __restrict__ res) {
+  __shared__ PayTileLds l[kPaySmallRoundTiles];
+  __shared__ uint64_t ws[kPaySmallWaves], wb[kPaySmallWaves];
+  __shared__ uint64_t tsum[kPaySmallMaxTiles];  // a tile's byte sum, then the bytes before it
+  __shared__ uint64_t tbad[kPaySmallMaxTiles];
+  __shared__ uint64_t s_nvar;
+  __shared__ uint32_t s_write;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint32_t q = tid / kPayThreads, ttid = tid % kPayThreads;
+  const uint32_t n_tiles = uint32_t((in.n_rows + kPayTile - 1) / kPayTile);  // (<= kPaySmallMaxTiles: the host's eligibility)
+
+  // ---- phase 1: sizes
+  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kPaySmallRoundTiles) {
+    const uint64_t tile0 = uint64_t(t0 + q) * kPayTile, k0 = tile0 + uint64_t(ttid) * kPayPerThread;
+    if (ttid == 0 && tile0 < in.n_rows) pay_tile_spans(in, tile0, l[q].rng);
+    __syncthreads();
+    PayRows r;
+    pay_rows(in, k0, l[q].rng, r);
+    uint64_t acc = 0, b = kPayNoRow;
+#pragma unroll
+    for (uint32_t j = 0; j < kPayPerThread; ++j) {
+      if (k0 + j >= in.n_rows) continue;
+      if (pay_row_ok(r.off[j], r.len[j], in.spans[r.span[j]].len)) acc += r.len[j];
+      else if (b == kPayNoRow) b = k0 + j;
+    }
+    acc = pay_wave_sum(acc);
+    b = pay_wave_min(b);
+    if (lane == 0) ws[w] = acc, wb[w] = b;
+    __syncthreads();
+    if (ttid == 0 && t0 + q < n_tiles) {
+      for (uint32_t k = 1; k < kPayWaves; ++k) acc += ws[w + k], b = wb[w + k] < b ? wb[w + k] : b;
+      tsum[t0 + q] = acc;
+      tbad[t0 + q] = b;
+    }
+    __syncthreads();  // (ws, wb and rng are written again in the next round)
+  }
+  if (tid == 0) {
+    uint64_t run = 0, b = kPayNoRow;
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+      const uint64_t x = tsum[t];
+      tsum[t] = run;
+      run += x;
+      b = tbad[t] < b ? tbad[t] : b;
+    }
+    uint32_t verdict = kPaySmallWritten, short_cap = 0;
+    if (b != kPayNoRow) verdict = kPaySmallBadRow;
+    else if (sizes_only) verdict = kPaySmallSizes;
+    else if (cap_pos < in.n_rows + 1) verdict = kPaySmallCapacity, short_cap = 0;
+    else if (cap_var < run) verdict = kPaySmallCapacity, short_cap = 1;
+    res->n_var = run;
+    res->bad_row = b;
+    res->verdict = verdict;
+    res->short_cap = short_cap;
+    s_nvar = run;
+    s_write = verdict == kPaySmallWritten;
+  }
+  __syncthreads();
+  if (!s_write) return;  // nothing written
+
+  // ---- phase 2: pos and the copy
+  const uint64_t n_var = s_nvar;
+  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kPaySmallRoundTiles) {
+    const uint32_t t = t0 + q;
+    pay_copy_tile(in, uint64_t(t) * kPayTile, ttid, t < n_tiles ? tsum[t] : n_var, n_var, pos, var, l[q]);
+    __syncthreads();  // (l is written again in the next round)
+  }
+  if (tid == 0) pos[in.n_rows] = n_var;
 }
 
 int launch_pay_size_scan(const PayIn& in, uint32_t n_tiles, uint64_t* d_sum, uint64_t* d_bad, uint64_t* d_base,
                          PayRes* res, void* stream) {
   if (n_tiles) hipLaunchKernelGGL(k_pay_size, dim3(n_tiles), dim3(kPayThreads), 0, (hipStream_t)stream, in, d_sum, d_bad);
   hipLaunchKernelGGL(k_pay_scan, dim3(1), dim3(kPayScanThreads), 0, (hipStream_t)stream, d_sum, d_bad, n_tiles, d_base, res);
+  return launch_status(hipGetLastError());
+}
+
+int launch_pay_small(const PayIn& in, uint64_t* pos, uint8_t* var, uint64_t cap_pos, uint64_t cap_var, bool sizes_only,
+                     PaySmallRes* res, void* stream) {
+  hipLaunchKernelGGL(k_pay_small, dim3(1), dim3(kPayScanThreads), 0, (hipStream_t)stream, in, pos, var, cap_pos, cap_var,
+                     uint32_t(sizes_only), res);
   return launch_status(hipGetLastError());
 }
 

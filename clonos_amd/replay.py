@@ -27,7 +27,8 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from . import determinants as D
-from .engine import CausalLogID, DecodedBatch, Engine, ThreadCausalLog, _np_ptr, _wide_determinant
+from .engine import (CausalLogID, DecodedBatch, DecodedColumns, Engine, ThreadCausalLog, _columns_struct, _np_ptr,
+                     _payloads_struct, _wide_determinant)
 
 
 # numpy views of the C structs (include/clonos_engine.h)
@@ -348,6 +349,93 @@ def prepare_replay(engine: Engine, jobs: Sequence[Tuple[int, DeterminantResponse
             j += 1
         res.append(VertexReplay(vid, main, main.span_slice(i), sp))
     return main, res
+
+
+@dataclass
+class ReplayColumns:
+    """clg_replay_prepare_columns' outputs (prepare_replay_columns): the main logs as typed
+    columns (span i = job i; with payloads main.var / main.var_pos / main.payload(k)), and
+    ReplayArrays' subpartition arrays.  A decode error in a main log is in main.error; the
+    columns then hold each vertex's records up to its first error."""
+    main: DecodedColumns
+    sizes: np.ndarray
+    base: np.ndarray
+    count: np.ndarray
+    status: np.ndarray
+    err_off: np.ndarray
+    err_tag: np.ndarray
+    vertex_ids: List[int]
+    tables: List[np.ndarray]  # per job its subpartition table (LOG_ID)
+
+    def replayer(self, i: int) -> "ColumnReplayer":
+        """LogReplayerImpl's cursor over job i's main log."""
+        return ColumnReplayer(self.main, i)
+
+    def vertex(self, i: int) -> List[SubpartitionReplay]:
+        """Job i's subpartitions, as prepare_replay gives them."""
+        j = sum(len(t) for t in self.tables[:i])
+        out = []
+        for s in self.tables[i]:
+            lid = CausalLogID.sub(self.vertex_ids[i], int(s["irp_lower"]), int(s["irp_upper"]), int(s["subpartition"]))
+            b0 = int(self.base[j])
+            out.append(SubpartitionReplay(lid, self.sizes[b0:b0 + int(self.count[j])].copy(), int(self.status[j]),
+                                          int(self.err_off[j]), int(self.err_tag[j])))
+            j += 1
+        return out
+
+
+def prepare_replay_columns(engine: Engine, jobs: Sequence[Tuple[int, DeterminantResponseEvent, Sequence]],
+                           device_input: bool = False, payloads: bool = True) -> ReplayColumns:
+    """clg_replay_prepare_columns over jobs (vertex_id, merged response, subpartition table: a
+    LOG_ID array or a sequence of CausalLogID, in the task's order): prepare_replay with the main
+    logs delivered as typed columns and, with payloads, the wide rows' payload bytes -- one engine
+    call.  device_input: the responses' bytes are in device memory."""
+    n = len(jobs)
+    vs = (_lib.ReplayVertex * max(1, n))()
+    tables = []
+    main_bytes, sub_bytes, n_sub = 0, 0, 0
+    for i, (vid, acc, subs) in enumerate(jobs):
+        t = np.ascontiguousarray(subs, LOG_ID) if isinstance(subs, np.ndarray) else log_id_array(list(subs))
+        tables.append(t)
+        n_sub += len(t)
+        vs[i] = _lib.ReplayVertex(C.pointer(acc._c), C.cast(t.ctypes.data, C.POINTER(_lib.CausalLogIdC)), len(t), vid, 0)
+        if acc._bytes is not None:
+            mb, ab = acc._bytes
+        else:
+            e = acc.entries()
+            ln = e["len"]
+            mb, ab = int(ln[e["id"]["is_main"] != 0].sum()), int(ln.sum())
+        main_bytes += mb
+        sub_bytes += ab - mb  # a bound: the table may name fewer
+    sizes = np.empty(max(1, sub_bytes // 5), np.int32)
+    sbase = np.zeros(n_sub + 1, np.uint64)
+    cnt = np.zeros(max(1, n_sub), np.uint64)
+    sst = np.zeros(max(1, n_sub), np.int32)
+    soff = np.zeros(max(1, n_sub), np.int64)
+    stag = np.zeros(max(1, n_sub), np.int32)
+    fn = lib.clg_replay_prepare_columns_device if device_input else lib.clg_replay_prepare_columns
+    arrs = engine._column_bounds(main_bytes, n)
+    var, pos = engine._payload_bounds(main_bytes, n) if payloads else (None, None)
+    for attempt in range(2):
+        base = np.zeros((n + 1) * _lib.COL_CLASSES, np.uint64)
+        c = _columns_struct(arrs, base, _lib.CLG_MEM_HOST)
+        p = _payloads_struct(var, pos) if payloads else None
+        out = _lib.ReplayColumnsOut(C.pointer(c), C.pointer(p) if payloads else None, _np_ptr(sizes), sizes.size,
+                                    _np_ptr(sbase), _np_ptr(cnt), _np_ptr(sst), _np_ptr(soff), _np_ptr(stag))
+        st = fn(engine.handle, vs, n, C.byref(out))
+        if st != _lib.CLG_E_CAPACITY or attempt or not int(c.n_rec):
+            break
+        # (the bounds hold for every decodable log, so this is not expected: the reported totals, once)
+        nc = [int(x) for x in c.n_class]
+        want = {"tag": int(c.n_rec), "order": nc[0], "timestamp": nc[1], "rng": nc[2], "buffer_built": nc[3]}
+        arrs = {k: np.empty(want.get(k, nc[4]) + 1, a.dtype) for k, a in arrs.items()}
+        if payloads:
+            var, pos = np.empty(int(p.n_var) + 1, np.uint8), np.empty(int(p.n_rows) + 2, np.uint64)
+    main = engine._columns_finish(st, c, arrs, base, None, True)
+    if payloads:
+        engine._payloads_attach(main, p, var, pos)
+    return ReplayColumns(main, sizes, sbase[:n_sub], cnt[:n_sub], sst[:n_sub], soff[:n_sub], stag[:n_sub],
+                         [int(j[0]) for j in jobs], tables)
 
 
 # ---- replay verification -----------------------------------------------------------------

@@ -600,6 +600,32 @@ int clg_replay_prepare(clg_engine* e, const clg_replay_vertex* v, uint32_t n, cl
  * allocation. */
 int clg_replay_prepare_device(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_out* out);
 
+/* Replay preparation that delivers the main logs as typed columns (clg_columns, above) and,
+ * with `var`, the wide rows' payload bytes (clg_payloads) -- what a LogReplayerImpl cursor
+ * consumes, with no byte offsets into the responses left to resolve.  Lookup, staging, the
+ * subpartition kernels and every subpartition output are clg_replay_prepare's; only the
+ * main-log step differs.  Status and errors are clg_decode_host_columns_var's: the columns'
+ * status wins when it is not CLG_OK; with a decode error each vertex's records up to its first
+ * error are delivered and main's error fields are filled; on CLG_E_CAPACITY the totals,
+ * main->span_base and the payload sizes are filled and no column is written.  The sizes_cap
+ * check comes first, as in clg_replay_prepare; the subpartition outputs are complete whenever
+ * the call got past it.  An absent main log is an empty span; n == 0 is valid. */
+typedef struct clg_replay_columns_out {
+  clg_columns* main;       /* span i = vertex i; main->span_base: (n + 1) * 5 host entries or NULL */
+  clg_payloads* var;       /* the wide rows' payloads of `main`; NULL: none */
+  int32_t* buffer_sizes;   /* from here on exactly clg_replay_out's subpartition fields */
+  uint64_t sizes_cap;
+  uint64_t* sizes_base;
+  uint64_t* sub_count;
+  int32_t* sub_status;
+  int64_t* sub_err_off;
+  int32_t* sub_err_tag;
+} clg_replay_columns_out;
+int clg_replay_prepare_columns(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_columns_out* out);
+/* ... with every response entry's bytes in device memory (clg_replay_prepare_device's rules). */
+int clg_replay_prepare_columns_device(clg_engine* e, const clg_replay_vertex* v, uint32_t n,
+                                      clg_replay_columns_out* out);
+
 /* getDeterminants(start_epoch[i]) of log[i] (:285-313) for n logs -- the copies
  * respondToDeterminantRequest answers with (JobCausalLogImpl.java:188-204) -- gathered by ONE
  * kernel back to back in request order into `out` (host or device); len[i] and out_off[i]

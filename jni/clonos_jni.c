@@ -689,6 +689,116 @@ JNIEXPORT jint JNICALL FN(nReplayPrepare)(JNIEnv* env, jclass cls, jlong e, jsho
   return s;
 }
 
+/* nReplayPrepare with the main log delivered as typed columns and the payload column
+ * (clg_replay_prepare_columns): nReplayPrepare's inputs, then nDecodeLogsColumnsVar's output
+ * buffers (var and pos null: no payload column), its result array (13 longs) and its span-base
+ * array ((1 + 1) * 5 longs), then `sizes` and sub_res as in nReplayPrepare. */
+JNIEXPORT jint JNICALL FN(nReplayPrepareColumns)(JNIEnv* env, jclass cls, jlong e, jshort vertex, jobjectArray bufs,
+                                                 jintArray lens, jlongArray subparts, jobject tag, jobject order,
+                                                 jobject timestamp, jobject rng, jobject buffer_built, jobject w_idx,
+                                                 jobject w_rc, jobject w_v1, jobject w_var_off, jobject w_var_len,
+                                                 jobject w_sub, jobject w_v0, jobject var, jobject pos, jlongArray res,
+                                                 jlongArray span_base, jobject sizes, jlongArray sub_res) {
+  (void)cls;
+  const jsize ns = (*env)->GetArrayLength(env, subparts) / 3;
+  jlong* sp = (*env)->GetLongArrayElements(env, subparts, NULL);
+  jint* ln = (*env)->GetIntArrayElements(env, lens, NULL);
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  clg_response_entry* ents = (clg_response_entry*)calloc((size_t)ns + 1u, sizeof(clg_response_entry));
+  clg_causal_log_id* ids = (clg_causal_log_id*)calloc((size_t)ns + 1u, sizeof(clg_causal_log_id));
+  uint64_t* sbase = (uint64_t*)calloc((size_t)ns + 1u, 8);
+  uint64_t* cnt = (uint64_t*)calloc((size_t)ns + 1u, 8);
+  int32_t* sst = (int32_t*)calloc((size_t)ns + 1u, 4);
+  int64_t* soff = (int64_t*)calloc((size_t)ns + 1u, 8);
+  int32_t* stg = (int32_t*)calloc((size_t)ns + 1u, 4);
+  clg_response acc;
+  memset(&acc, 0, sizeof acc);
+  acc.found = 1;
+  acc.vertex_id = vertex;
+  acc.entries = ents;
+  acc.cap = (uint32_t)ns + 1u;
+  int s = CLG_OK;
+  for (jsize i = 0; i <= ns && s == CLG_OK; ++i) {
+    jobject b = (*env)->GetObjectArrayElement(env, bufs, i);
+    clg_causal_log_id id;
+    memset(&id, 0, sizeof id);
+    id.vertex_id = vertex;
+    id.is_main = i == 0;
+    if (i > 0) {
+      id.irp_lower = sp[3 * (i - 1)];
+      id.irp_upper = sp[3 * (i - 1) + 1];
+      id.subpartition = (int8_t)sp[3 * (i - 1) + 2];
+      ids[i - 1] = id;
+    }
+    if (b) {
+      s = clg_response_put(&acc, &id, addr(env, b, 0), (uint64_t)(uint32_t)ln[i]);
+      (*env)->DeleteLocalRef(env, b);
+    }
+  }
+  clg_columns c;
+  memset(&c, 0, sizeof c);
+  c.tag = addr(env, tag, 0);
+  c.order = (int8_t*)addr(env, order, 0);
+  c.timestamp = (int64_t*)addr(env, timestamp, 0);
+  c.rng = (int32_t*)addr(env, rng, 0);
+  c.buffer_built = (int32_t*)addr(env, buffer_built, 0);
+  c.w_idx = (uint32_t*)addr(env, w_idx, 0);
+  c.w_rc = (int32_t*)addr(env, w_rc, 0);
+  c.w_v1 = (int64_t*)addr(env, w_v1, 0);
+  c.w_var_off = (uint32_t*)addr(env, w_var_off, 0);
+  c.w_var_len = (uint32_t*)addr(env, w_var_len, 0);
+  c.w_sub = addr(env, w_sub, 0);
+  c.w_v0 = (int64_t*)addr(env, w_v0, 0);
+  c.span_base = (uint64_t*)base;
+  c.cap_tag = cap(env, tag);
+  c.cap_order = cap(env, order);
+  c.cap_timestamp = cap(env, timestamp) / 8;
+  c.cap_rng = cap(env, rng) / 4;
+  c.cap_buffer_built = cap(env, buffer_built) / 4;
+  c.cap_wide = cap(env, w_sub);
+  c.out_kind = CLG_MEM_HOST;
+  clg_payloads p;
+  memset(&p, 0, sizeof p);
+  p.var = addr(env, var, 0);
+  p.pos = (uint64_t*)addr(env, pos, 0);
+  p.cap_var = cap(env, var);
+  p.cap_pos = cap(env, pos) / 8;
+  p.out_kind = CLG_MEM_HOST;
+  if (s == CLG_OK) {
+    clg_replay_vertex v;
+    memset(&v, 0, sizeof v);
+    v.acc = &acc;
+    v.subpartitions = ids;
+    v.n_subpartitions = (uint32_t)ns;
+    v.vertex_id = vertex;
+    clg_replay_columns_out o;
+    memset(&o, 0, sizeof o);
+    o.main = &c;
+    o.var = (var || pos) ? &p : NULL;
+    o.buffer_sizes = (int32_t*)addr(env, sizes, 0);
+    o.sizes_cap = cap(env, sizes) / 4u;
+    o.sizes_base = sbase;
+    o.sub_count = cnt;
+    o.sub_status = sst;
+    o.sub_err_off = soff;
+    o.sub_err_tag = stg;
+    s = clg_replay_prepare_columns(ENG(e), &v, 1, &o);
+  }
+  jlong r[13] = {(jlong)c.n_rec,      (jlong)c.n_class[0], (jlong)c.n_class[1], (jlong)c.n_class[2], (jlong)c.n_class[3],
+                 (jlong)c.n_class[4], c.err_status,        c.err_span,          c.err_off,           c.err_tag,
+                 (jlong)p.n_rows,     (jlong)p.n_var,      (jlong)p.bad_row};
+  (*env)->SetLongArrayRegion(env, res, 0, 13, r);
+  for (jsize i = 0; i < ns; ++i) {
+    jlong w[5] = {(jlong)cnt[i], sst[i], soff[i], stg[i], (jlong)sbase[i]};
+    (*env)->SetLongArrayRegion(env, sub_res, 5 * i, 5, w);
+  }
+  (*env)->ReleaseLongArrayElements(env, span_base, base, 0);
+  (*env)->ReleaseLongArrayElements(env, subparts, sp, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, lens, ln, JNI_ABORT);
+  free(ids), free(sbase), free(cnt), free(sst), free(soff), free(stg), free(ents);
+  return s;
+}
+
 /* ---- in-flight (data) log: InMemorySubpartitionInFlightLogger (inflightlogging/, :28-207) or
  * SpillableSubpartitionInFlightLogger (:45-341), by type (CLG_IFL_IN_MEMORY / CLG_IFL_SPILLABLE) ---- */
 JNIEXPORT jint JNICALL FN(nIflOpen)(JNIEnv* env, jclass cls, jlong e, jint type, jintArray out) {

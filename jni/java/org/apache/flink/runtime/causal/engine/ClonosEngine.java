@@ -193,6 +193,33 @@ public final class ClonosEngine implements AutoCloseable {
 		return c;
 	}
 
+	/**
+	 * Replay preparation for one failed task with the main log delivered as typed columns and the payload
+	 * column (clg_replay_prepare_columns), in ONE native call: the buffers are sized by bounds no main log
+	 * of mainLen bytes can exceed (the shortest record of each class: ORDER 2 B, TIMESTAMP 9, RNG and
+	 * BUFFER_BUILT 5, wide 6), so no sizes-only call comes first.  buffers / lens / subpartitions /
+	 * bufferSizes / subpartitionResults are nReplayPrepare's.  A decode error of the main log is in the
+	 * result's errStatus(); the columns then hold the records before it.
+	 */
+	public EngineDecodedColumns replayPrepareColumns(short vertexId, ByteBuffer[] buffers, int[] lens,
+													 long[] subpartitions, ByteBuffer bufferSizes,
+													 long[] subpartitionResults) {
+		final long mainLen = lens[0];
+		final long[] res = new long[13];
+		final long[] bounds = {mainLen / 2 + 1, mainLen / 2 + 1, mainLen / 9 + 1, mainLen / 5 + 1, mainLen / 5 + 1,
+			mainLen / 6 + 1, CLG_OK, 0, 0, 0};
+		final EngineDecodedColumns c = new EngineDecodedColumns(bounds, 1);
+		c.allocatePayloads(mainLen / 6 + 1, mainLen + 1);
+		final int st = nReplayPrepareColumns(handle, vertexId, buffers, lens, subpartitions, c.tag, c.order, c.timestamp,
+			c.rng, c.bufferBuilt, c.wIdx, c.wRc, c.wV1, c.wVarOff, c.wVarLen, c.wSub, c.wV0, c.var, c.varPos, res,
+			c.spanBase, bufferSizes, subpartitionResults);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st); // an engine failure, not a decode error of the main log
+		}
+		c.setResult(res);
+		return c;
+	}
+
 	@Override
 	public void close() {
 		nDestroy(handle);
@@ -354,4 +381,12 @@ public final class ClonosEngine implements AutoCloseable {
 									 ByteBuffer off, ByteBuffer tag, ByteBuffer v0, ByteBuffer wIdx, ByteBuffer wRc,
 									 ByteBuffer wV1, ByteBuffer wVarOff, ByteBuffer wVarLen, ByteBuffer wSub,
 									 long[] result, ByteBuffer bufferSizes, long[] subpartitionResults);
+	/** clg_replay_prepare_columns: nReplayPrepare's inputs, nDecodeLogsColumnsVar's outputs (result: 13 longs;
+	 *  spanBase: 10), then nReplayPrepare's subpartition outputs. */
+	static native int nReplayPrepareColumns(long engine, short vertexId, ByteBuffer[] buffers, int[] lens,
+											long[] subpartitions, ByteBuffer tag, ByteBuffer order, ByteBuffer timestamp,
+											ByteBuffer rng, ByteBuffer bufferBuilt, ByteBuffer wIdx, ByteBuffer wRc,
+											ByteBuffer wV1, ByteBuffer wVarOff, ByteBuffer wVarLen, ByteBuffer wSub,
+											ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos, long[] result,
+											long[] spanBase, ByteBuffer bufferSizes, long[] subpartitionResults);
 }

@@ -24,6 +24,7 @@ package org.apache.flink.runtime.causal.recovery;
 
 import org.apache.flink.runtime.causal.DeterminantResponseEvent;
 import org.apache.flink.runtime.causal.engine.ClonosEngine;
+import org.apache.flink.runtime.causal.engine.EngineDecodedColumns;
 import org.apache.flink.runtime.causal.engine.EngineDecodedLog;
 import org.apache.flink.runtime.causal.log.job.CausalLogID;
 import org.apache.flink.runtime.io.network.partition.PipelinedSubpartition;
@@ -73,10 +74,24 @@ public final class EngineReplayPreparation {
 	private final ByteBuffer recOff;
 	private final ByteBuffer tag;
 	private final long[] mainResult = new long[6];
+	private final EngineDecodedColumns mainColumns; // the columns form: the main log with its payload column
 	private final Map<IntermediateResultPartitionID, Map<Integer, SubpartitionSizes>> bySubpartition = new HashMap<>();
 
 	public EngineReplayPreparation(ClonosEngine engine, RecoveryManagerContext context,
 								   DeterminantResponseEvent determinantAccumulator) {
+		this(engine, context, determinantAccumulator, false);
+	}
+
+	/** The columns form (nReplayPrepareColumns -> clg_replay_prepare_columns): the same sizes, and the main
+	 *  log as {@link #mainColumns()} -- typed columns with the payload column, what a columns cursor in
+	 *  LogReplayerImpl consumes -- instead of {@link #mainLog}. */
+	public static EngineReplayPreparation columns(ClonosEngine engine, RecoveryManagerContext context,
+												  DeterminantResponseEvent determinantAccumulator) {
+		return new EngineReplayPreparation(engine, context, determinantAccumulator, true);
+	}
+
+	private EngineReplayPreparation(ClonosEngine engine, RecoveryManagerContext context,
+									DeterminantResponseEvent determinantAccumulator, boolean columns) {
 		this.engine = engine;
 		this.context = context;
 		final short vertex = context.getTaskVertexID().getVertexID();
@@ -111,20 +126,27 @@ public final class EngineReplayPreparation {
 				sizeSlots += lens[i] / 5;
 			}
 		}
-		final int mainLen = lens[0];
-		final int cap = mainLen / 2 + 1, wcap = mainLen / 6 + 1;
-		this.recOff = ByteBuffer.allocateDirect(4 * cap).order(ByteOrder.nativeOrder());
-		this.tag = ByteBuffer.allocateDirect(cap);
-		final ByteBuffer v0 = ByteBuffer.allocateDirect(8 * cap);
-		final ByteBuffer wIdx = ByteBuffer.allocateDirect(4 * wcap), wRc = ByteBuffer.allocateDirect(4 * wcap);
-		final ByteBuffer wV1 = ByteBuffer.allocateDirect(8 * wcap), wVo = ByteBuffer.allocateDirect(4 * wcap);
-		final ByteBuffer wVl = ByteBuffer.allocateDirect(4 * wcap), wSub = ByteBuffer.allocateDirect(wcap);
 		final ByteBuffer sizes = ByteBuffer.allocateDirect((int) Math.max(4, 4 * sizeSlots)).order(ByteOrder.nativeOrder());
 		final long[] subRes = new long[5 * Math.max(1, ns)];
-		final int st = nReplayPrepare(engine.handle(), vertex, bufs, lens, subs, recOff, tag, v0, wIdx, wRc, wV1, wVo,
-			wVl, wSub, mainResult, sizes, subRes);
-		if (st != CLG_OK && mainResult[2] == CLG_OK) {
-			check(st); // an engine failure, not a decode error of the main log
+		if (columns) {
+			this.recOff = null;
+			this.tag = null;
+			this.mainColumns = engine.replayPrepareColumns(vertex, bufs, lens, subs, sizes, subRes);
+		} else {
+			final int mainLen = lens[0];
+			final int cap = mainLen / 2 + 1, wcap = mainLen / 6 + 1;
+			this.recOff = ByteBuffer.allocateDirect(4 * cap).order(ByteOrder.nativeOrder());
+			this.tag = ByteBuffer.allocateDirect(cap);
+			this.mainColumns = null;
+			final ByteBuffer v0 = ByteBuffer.allocateDirect(8 * cap);
+			final ByteBuffer wIdx = ByteBuffer.allocateDirect(4 * wcap), wRc = ByteBuffer.allocateDirect(4 * wcap);
+			final ByteBuffer wV1 = ByteBuffer.allocateDirect(8 * wcap), wVo = ByteBuffer.allocateDirect(4 * wcap);
+			final ByteBuffer wVl = ByteBuffer.allocateDirect(4 * wcap), wSub = ByteBuffer.allocateDirect(wcap);
+			final int st = nReplayPrepare(engine.handle(), vertex, bufs, lens, subs, recOff, tag, v0, wIdx, wRc, wV1, wVo,
+				wVl, wSub, mainResult, sizes, subRes);
+			if (st != CLG_OK && mainResult[2] == CLG_OK) {
+				check(st); // an engine failure, not a decode error of the main log
+			}
 		}
 		j = 0;
 		for (Table.Cell<IntermediateResultPartitionID, Integer, PipelinedSubpartition> cell : table.cellSet()) {
@@ -137,9 +159,15 @@ public final class EngineReplayPreparation {
 		}
 	}
 
+	/** The columns form's main log: span 0 of the columns, payload(k) for the wide rows' names, references
+	 *  and streams (null unless built by {@link #columns}).  An absent main log is an empty span. */
+	public EngineDecodedColumns mainColumns() {
+		return mainColumns;
+	}
+
 	/** The main log's records for LogReplayerImpl (null when the response holds no main log). */
 	public EngineDecodedLog mainLog(ByteBuf log) {
-		if (log == null) {
+		if (log == null || recOff == null) {
 			return null;
 		}
 		return new EngineDecodedLog(log, context.causalLog.getDeterminantEncoder(), recOff, tag, (int) mainResult[0],
