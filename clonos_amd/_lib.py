@@ -69,6 +69,7 @@ EXPORTED = [
     "clg_gather_payloads", "clg_gather_payloads_logs", "clg_decode_logs_columns_var", "clg_decode_host_columns_var",
     "clg_gather_payloads_host",
     "clg_replay_prepare_columns", "clg_replay_prepare_columns_device",
+    "clg_encode_columns", "clg_encode_columns_host", "clg_append_columns",
 ]
 
 
@@ -186,6 +187,31 @@ class Payloads(C.Structure):  # clg_payloads
         ("cap_var", C.c_uint64), ("cap_pos", C.c_uint64),
         ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
         ("n_rows", C.c_uint64), ("n_var", C.c_uint64), ("bad_row", C.c_uint64),
+    ]
+
+
+class ColumnsIn(C.Structure):  # clg_columns_in
+    _fields_ = [
+        ("tag", C.c_void_p), ("order", C.c_void_p), ("timestamp", C.c_void_p), ("rng", C.c_void_p),
+        ("buffer_built", C.c_void_p),
+        ("w_rc", C.c_void_p), ("w_v1", C.c_void_p), ("w_var_len", C.c_void_p), ("w_sub", C.c_void_p),
+        ("w_v0", C.c_void_p), ("w_idx", C.c_void_p),
+        ("pos", C.c_void_p), ("var", C.c_void_p), ("span_base", C.c_void_p),
+        ("n_rec", C.c_uint64), ("n_class", C.c_uint64 * COL_CLASSES), ("n_var", C.c_uint64),
+        ("n_spans", C.c_uint32), ("in_kind", C.c_uint32),
+    ]
+
+
+# clg_encoded.bad_what
+ENC_BAD_NONE, ENC_BAD_TAG, ENC_BAD_TOTALS, ENC_BAD_SPAN, ENC_BAD_ROW = range(5)
+
+
+class Encoded(C.Structure):  # clg_encoded
+    _fields_ = [
+        ("bytes", C.c_void_p), ("cap", C.c_uint64),
+        ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
+        ("span_byte_base", C.c_void_p),
+        ("n_bytes", C.c_uint64), ("bad_what", C.c_uint32), ("reserved2", C.c_uint32), ("bad_index", C.c_uint64),
     ]
 
 
@@ -386,6 +412,9 @@ def _load() -> C.CDLL:
         "clg_decode_logs_columns_var": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads)]),
         "clg_decode_host_columns_var": (C.c_int, [P, P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads)]),
         "clg_gather_payloads_host": (C.c_int, [P, P, P, C.c_uint32, P, P, P, C.POINTER(Payloads)]),
+        "clg_encode_columns": (C.c_int, [P, C.POINTER(ColumnsIn), C.POINTER(Encoded)]),
+        "clg_encode_columns_host": (C.c_int, [C.POINTER(ColumnsIn), C.POINTER(Encoded)]),
+        "clg_append_columns": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(ColumnsIn), P, P]),
         "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),

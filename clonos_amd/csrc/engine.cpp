@@ -34,6 +34,7 @@
 #include "columns.h"
 #include "diff.h"
 #include "digest.h"
+#include "encode_columns.h"
 #include "engine_host.h"
 #include "kernels.h"
 #include "payload.h"
@@ -43,6 +44,8 @@ static_assert(sizeof(clg_delta_req) == 32, "clg_delta_req layout");
 static_assert(sizeof(clg_diff) == 24, "clg_diff layout");
 static_assert(sizeof(clg_columns) == 232, "clg_columns layout");
 static_assert(sizeof(clg_payloads) == 64, "clg_payloads layout");
+static_assert(sizeof(clg_columns_in) == 176, "clg_columns_in layout");
+static_assert(sizeof(clg_encoded) == 56, "clg_encoded layout");
 
 using namespace clg_internal;  // the host-only types (engine_host.h)
 
@@ -257,6 +260,11 @@ struct clg_engine {
   DevBuf d_rmeta, d_rsizes;          // replay-prep: subpartition span tables / BufferBuilt sizes
   DevBuf d_encin, d_encw, d_encout;  // encode: staged host input, block prefixes, host-output staging
   DevBuf d_hdr;                      // piggyback: delta headers staged for the gather
+  // encode of typed columns: staged host input | span_base, per-tile counts / bases / sums, the
+  // encoded bytes (host-output staging, and what clg_append_columns scatters); the scans' results
+  // and the span bases (pinned: the kernels write them)
+  DevBuf d_ecolin, d_ecolw, d_ecolout;
+  PinBuf h_ecolres;
   // The Serializable walker's spill arena (kernels.h JArena): [used u64 | pad to 256 | bytes].
   // Grown (doubled) whenever a decode reports CLG_E_NOSPACE, i.e. a walk found it full.
   DevBuf d_jarena;
@@ -4844,6 +4852,236 @@ int clg_encode_batch(clg_engine* e, const clg_encode_in* in, void* out, uint64_t
                [&] { return clg::launch_encode(d, wsum, wbase, bsum, bbase, bad, dst, 1, e->stream); }));
   if (out_kind != CLG_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dst, hres[0], hipMemcpyDeviceToHost, e->stream));
   return e->sync();
+}
+
+// ---- encode typed columns (encode_columns.h) ------------------------------------------------
+namespace {
+
+// A checked, sized encode: what the write pass needs.
+struct EcolPlan {
+  clg::EcolIn d{};
+  uint32_t n_tiles = 0;
+  const uint64_t* d_base = nullptr;
+  const uint64_t* d_bbase = nullptr;
+  uint64_t n_bytes = 0;
+  uint64_t in_bytes = 0;  // bytes of the input arrays (for the stats)
+};
+
+int ecol_invalid(clg_encoded* out, uint32_t what, uint64_t index) {
+  static const char* const kind[] = {"", "tag", "totals", "span", "row"};
+  out->n_bytes = 0;
+  out->bad_what = what;
+  out->bad_index = index;
+  return fail(CLG_E_INVALID_ARG, "encode columns: bad %s, index %llu", kind[what], (unsigned long long)index);
+}
+
+// Count, scan, bytes, scan64 and span bases, then the host's check of their results (pinned) --
+// before any byte is written anywhere.  Fills out's results and, when given, sbb[ns + 1].
+int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPlan* p, uint64_t* sbb) {
+  clg::ecol_reset_result(out);
+  if (!clg::ecol_args_ok(*in)) return fail(CLG_E_INVALID_ARG, "encode columns: null input array or unknown in_kind");
+  const uint64_t n = in->n_rec, *nc = in->n_class, nw = nc[clg::kColWide];
+  const uint32_t ns = clg::ecol_spans(*in);
+  const uint64_t rows_bad = clg::ecol_span_rows_bad(*in);
+  const bool has_pos = in->pos != nullptr, has_idx = in->w_idx != nullptr;
+  // the arrays, in EcolIn's order: bytes, and element sizes for the alignment check
+  const void* src[13] = {in->tag,  in->order,     in->timestamp, in->rng,  in->buffer_built, in->w_rc, in->w_v1,
+                         in->w_var_len, in->w_sub, in->w_v0,     in->w_idx, in->pos,          in->var};
+  const size_t el[13] = {1, 1, 8, 4, 4, 4, 8, 4, 1, 8, 4, 8, 1};
+  const uint64_t cnt[13] = {n, nc[0], nc[1], nc[2], nc[3], nw, nw, nw, nw, nw, has_idx ? nw : 0, has_pos ? nw + 1 : 0,
+                            in->var ? in->n_var : 0};
+  uintptr_t dev[13];
+  size_t off[14], tot = 0;
+  for (int i = 0; i < 13; ++i) {
+    off[i] = tot;
+    tot += clg_engine::al16(size_t(cnt[i]) * el[i]);
+    p->in_bytes += cnt[i] * el[i];
+  }
+  off[13] = tot;
+  const size_t sb_bytes = in->n_spans ? size_t(ns + 1) * clg::kColClasses * 8 : 0;
+  const bool staged = in->in_kind == CLG_MEM_HOST;
+  CHK(e->d_ecolin.ensure((staged ? tot : 0) + sb_bytes + 16));
+  uint8_t* din = e->d_ecolin.as<uint8_t>();
+  const size_t o_sb = staged ? tot : 0;
+  for (int i = 0; i < 13; ++i) {
+    if (!src[i] || !cnt[i]) {
+      dev[i] = staged || !src[i] ? 0 : uintptr_t(src[i]);
+      if (staged && src[i]) dev[i] = uintptr_t(din + off[i]);  // (an empty array: a valid address, never read)
+      continue;
+    }
+    if (staged) {
+      HIPCHK(hipMemcpyAsync(din + off[i], src[i], size_t(cnt[i]) * el[i], hipMemcpyHostToDevice, e->stream));
+      dev[i] = uintptr_t(din + off[i]);
+    } else if (in->in_kind == CLG_MEM_MAPPED) {
+      dev[i] = clg_mapped_device_address(src[i], cnt[i] * el[i]);
+      if (!dev[i]) return fail(CLG_E_INVALID_ARG, "an input array is not inside memory registered with clg_host_register");
+    } else {
+      dev[i] = uintptr_t(src[i]);
+    }
+    if (dev[i] % el[i]) return fail(CLG_E_INVALID_ARG, "an input array is not aligned to its element");
+  }
+  if (!has_pos) dev[11] = 0;
+  if (!has_idx) dev[10] = 0;
+  if (!in->var) dev[12] = 0;
+  clg::EcolIn& d = p->d;
+  d = clg::EcolIn{reinterpret_cast<const uint8_t*>(dev[0]),  reinterpret_cast<const int8_t*>(dev[1]),
+                  reinterpret_cast<const int64_t*>(dev[2]),  reinterpret_cast<const int32_t*>(dev[3]),
+                  reinterpret_cast<const int32_t*>(dev[4]),  reinterpret_cast<const int32_t*>(dev[5]),
+                  reinterpret_cast<const int64_t*>(dev[6]),  reinterpret_cast<const uint32_t*>(dev[7]),
+                  reinterpret_cast<const uint8_t*>(dev[8]),  reinterpret_cast<const int64_t*>(dev[9]),
+                  reinterpret_cast<const uint32_t*>(dev[10]), reinterpret_cast<const uint64_t*>(dev[11]),
+                  reinterpret_cast<const uint8_t*>(dev[12]), n, {nc[0], nc[1], nc[2], nc[3], nc[4]}, in->n_var};
+  const uint64_t* d_sb = nullptr;
+  if (sb_bytes && rows_bad == clg::kEcolNone) {
+    HIPCHK(hipMemcpyAsync(din + o_sb, in->span_base, sb_bytes, hipMemcpyHostToDevice, e->stream));
+    d_sb = reinterpret_cast<const uint64_t*>(din + o_sb);
+  }
+
+  // work: counts | class bases | byte sums | bad rows | byte bases
+  const uint64_t n_tiles64 = (n + clg::kEcolTile - 1) / clg::kEcolTile;
+  if (n_tiles64 > 0x7FFFFFFFull) return fail(CLG_E_INVALID_ARG, "%llu records in one call", (unsigned long long)n);
+  const uint32_t nt = uint32_t(n_tiles64);
+  const size_t o_cnt = 0, o_base = clg_engine::al16(size_t(nt) * clg::kColCountWords * 4),
+               o_sum = o_base + clg_engine::al16(size_t(nt) * clg::kColClasses * 8), o_bad = o_sum + clg_engine::al16(size_t(nt) * 8),
+               o_bb = o_bad + clg_engine::al16(size_t(nt) * 8), w_end = o_bb + clg_engine::al16(size_t(nt) * 8);
+  CHK(e->d_ecolw.ensure(w_end + 16));
+  uint8_t* wk = e->d_ecolw.as<uint8_t>();
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(wk + o_cnt);
+  uint64_t* d_base = reinterpret_cast<uint64_t*>(wk + o_base);
+  uint64_t* d_sum = reinterpret_cast<uint64_t*>(wk + o_sum);
+  uint64_t* d_bad = reinterpret_cast<uint64_t*>(wk + o_bad);
+  uint64_t* d_bbase = reinterpret_cast<uint64_t*>(wk + o_bb);
+  const size_t o_eres = clg_engine::al16(sizeof(clg::ColRes)), o_so = o_eres + clg_engine::al16(sizeof(clg::EcolRes));
+  CHK(e->h_ecolres.ensure(o_so + size_t(ns + 1) * 16));
+  clg::ColRes* cres = e->h_ecolres.as<clg::ColRes>();
+  clg::EcolRes* eres = reinterpret_cast<clg::EcolRes*>(e->h_ecolres.as<uint8_t>() + o_eres);
+  uint64_t* span_out = reinterpret_cast<uint64_t*>(e->h_ecolres.as<uint8_t>() + o_so);
+  p->n_tiles = nt, p->d_base = d_base, p->d_bbase = d_bbase;
+
+  const clg::ColIn cin{d.tag, nullptr, nullptr, n, nw};
+  CHK(e->timed("encode_columns", n + 13 * nw + uint64_t(nt) * 120 + sb_bytes, [&] {
+    CHK(clg::launch_col_count_scan(cin, nt, d_counts, d_base, cres, e->stream));
+    return clg::launch_ecol_sizes(d, nt, d_base, d_sum, d_bad, d_bbase, cres, eres, d_sb, in->n_spans, span_out, e->stream);
+  }));
+  CHK(e->sync());
+  if (cres->bad_tile != clg::kColNoTile) {
+    CHK(clg::launch_col_find_bad(cin, cres->bad_tile, cres, e->stream));
+    CHK(e->sync());
+    return ecol_invalid(out, CLG_ENC_BAD_TAG, cres->bad_index);
+  }
+  for (uint32_t c = 0; c < clg::kColClasses; ++c)
+    if (cres->total[c] != nc[c]) return ecol_invalid(out, CLG_ENC_BAD_TOTALS, c);
+  if (rows_bad != clg::kEcolNone) return ecol_invalid(out, CLG_ENC_BAD_SPAN, rows_bad);
+  if (d_sb)
+    for (uint32_t s = 0; s <= ns; ++s)
+      if (span_out[size_t(s) * 2 + 1]) return ecol_invalid(out, CLG_ENC_BAD_SPAN, s);
+  if (eres->bad_row != clg::kEcolNone) return ecol_invalid(out, CLG_ENC_BAD_ROW, eres->bad_row);
+  p->n_bytes = out->n_bytes = eres->n_bytes;
+  for (uint32_t s = 0; s <= ns; ++s) {
+    const uint64_t b = d_sb ? span_out[size_t(s) * 2] : s ? eres->n_bytes : 0;
+    if (sbb) sbb[s] = b;
+    if (out->span_byte_base) out->span_byte_base[s] = b;
+  }
+  return CLG_OK;
+}
+
+int ecol_write(clg_engine* e, const EcolPlan& p, uint8_t* d_dst) {
+  return e->timed("encode_columns", p.in_bytes + uint64_t(p.n_tiles) * 48 + p.n_bytes, [&] {
+    return clg::launch_ecol_write(p.d, p.n_tiles, p.d_base, p.d_bbase, p.n_bytes, d_dst, e->stream);
+  });
+}
+
+}  // namespace
+
+int clg_encode_columns(clg_engine* e, const clg_columns_in* in, clg_encoded* out) {
+  ENGINE_GUARD(e);
+  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  EcolPlan p;
+  CHK(ecol_sizes(e, in, out, &p, nullptr));
+  if (!out->bytes) return CLG_OK;  // sizes only
+  if (out->cap < p.n_bytes) return fail(CLG_E_CAPACITY, "encode columns needs %llu bytes", (unsigned long long)p.n_bytes);
+  if (!p.n_bytes) return CLG_OK;
+  uint8_t* dst = static_cast<uint8_t*>(out->bytes);
+  const bool direct = out->out_kind == CLG_MEM_DEVICE;
+  if (!direct) {  // host and registered memory alike: the edge byte stores stay off the link
+    CHK(e->d_ecolout.ensure(p.n_bytes + 16));
+    dst = e->d_ecolout.as<uint8_t>();
+  }
+  CHK(ecol_write(e, p, dst));
+  if (!direct) HIPCHK(hipMemcpyAsync(out->bytes, dst, p.n_bytes, hipMemcpyDeviceToHost, e->stream));
+  return e->sync();
+}
+
+int clg_encode_columns_host(const clg_columns_in* in, clg_encoded* out) {
+  const char* what = "";
+  const int st = clg::ecol_build_host(in, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "encode columns: %s", what);
+}
+
+int clg_append_columns(clg_engine* e, const uint32_t* log, const int64_t* epoch, uint32_t n_spans,
+                       const clg_columns_in* in, uint64_t* span_bytes, int32_t* status) {
+  ENGINE_GUARD(e);
+  if (!in || !log || !epoch || !status) return fail(CLG_E_INVALID_ARG, "null argument");
+  const uint32_t ns = clg::ecol_spans(*in);
+  if (n_spans != ns) return fail(CLG_E_INVALID_ARG, "%u logs for %u spans", n_spans, ns);
+  for (uint32_t s = 0; s < ns; ++s) status[s] = CLG_OK;
+  CHK(e->flush());  // pending host bytes first: the logs keep their byte order
+  clg_encoded enc{};
+  enc.out_kind = CLG_MEM_DEVICE;
+  EcolPlan p;
+  std::vector<uint64_t> sbb(size_t(ns) + 1);
+  CHK(ecol_sizes(e, in, &enc, &p, sbb.data()));
+  for (uint32_t s = 0; s < ns && span_bytes; ++s) span_bytes[s] = sbb[s + 1] - sbb[s];
+  CHK(e->d_ecolout.ensure(p.n_bytes + 16));
+  CHK(ecol_write(e, p, e->d_ecolout.as<uint8_t>()));
+  CHK(e->gwait());  // the scatter below writes segments an in-flight gather may read
+
+  size_t bound = 0;
+  for (uint32_t s = 0; s < ns; ++s) bound += size_t((sbb[s + 1] - sbb[s]) / e->C()) + 2;
+  CHK(e->h_desc.ensure(bound * sizeof(clg::ScatterChunk)));
+  clg::ScatterChunk* ch = e->h_desc.as<clg::ScatterChunk>();
+  size_t nch = 0, total = 0;
+  {
+    std::lock_guard<std::mutex> pool_guard(e->pool_mu);
+    for (uint32_t s = 0; s < ns; ++s) {  // clg_engine::append's steps, a span at a time
+      const uint64_t len = sbb[s + 1] - sbb[s];
+      Log* l;
+      if ((status[s] = e->get_log(log[s], &l)) != CLG_OK) continue;
+      if (l->depth == 0) continue;
+      if (len >> 31) {
+        status[s] = fail(CLG_E_INVALID_ARG, "span %u holds %llu bytes", s, (unsigned long long)len);
+        continue;
+      }
+      if ((status[s] = e->ensure_space_locked(*l, int32_t(len))) != CLG_OK) continue;
+      clg_engine::compute_if_absent(*l, epoch[s]);
+      int32_t at = l->writer;
+      uint64_t src = sbb[s];
+      uint32_t left = uint32_t(len);
+      while (left) {
+        const uint32_t si = uint32_t(at) / e->C(), so = uint32_t(at) % e->C();
+        const uint32_t take = std::min<uint32_t>(left, e->C() - so);
+        ch[nch++] = clg::ScatterChunk{e->seg_addr(l->segs[si]) + so, src, take, e->life_word(l->segs[si], left > take)};
+        at += int32_t(take);
+        src += take;
+        left -= take;
+      }
+      l->writer += int32_t(len);
+      l->flushed = l->writer;
+      clg_engine::reset_tail(*l);  // these bytes are in HBM only
+      total += size_t(len);
+    }
+  }
+  if (!nch) return e->sync();
+  const size_t db = nch * sizeof(clg::ScatterChunk);
+  CHK(e->d_desc.ensure(db));
+  HIPCHK(hipMemcpyAsync(e->d_desc.p, e->h_desc.p, db, hipMemcpyHostToDevice, e->stream));
+  CHK(e->timed("append_columns_scatter", 2 * total, [&] {
+    return clg::launch_scatter(e->d_desc.as<clg::ScatterChunk>(), uint32_t(nch), e->d_ecolout.as<uint8_t>(), e->stream,
+                               e->side_arg());
+  }));
+  return e->sync();  // the pinned descriptors are free again
 }
 
 namespace {

@@ -781,6 +781,40 @@ struct EncodeIn {  // device pointers, the decode's SoA layout (clg_decoded)
 int launch_encode(const EncodeIn& in, uint32_t* d_wsum, uint64_t* d_wbase, uint64_t* d_bsum, uint64_t* d_bbase,
                   uint32_t* d_bad, uint8_t* d_out, uint32_t phase, void* stream);
 
+// ---- encode typed columns (encode_columns.h, encode_columns.hip) -----------------
+struct EcolIn {  // device addresses of clg_columns_in's arrays (w_idx, pos, var: null when not given)
+  const uint8_t* tag;
+  const int8_t* order;
+  const int64_t* timestamp;
+  const int32_t* rng;
+  const int32_t* buffer_built;
+  const int32_t* w_rc;
+  const int64_t* w_v1;
+  const uint32_t* w_var_len;
+  const uint8_t* w_sub;
+  const int64_t* w_v0;
+  const uint32_t* w_idx;
+  const uint64_t* pos;
+  const uint8_t* var;
+  uint64_t n;
+  uint64_t n_class[5];  // the stated column lengths: no column is indexed at or past them
+  uint64_t n_var;
+};
+struct EcolRes {  // pinned memory: the byte scan's results
+  uint64_t n_bytes;
+  uint64_t bad_row;  // kEcolNone: none
+};
+// Bytes (a workgroup per tile of kEcolTile records -> d_sum[tile], d_bad[tile]), scan64 (one
+// workgroup -> d_bbase[tile]; *eres) and span bases (a wave per boundary; none when d_span_base is
+// null): span_out[s * 2] the byte base, [s * 2 + 1] 1 for a row that is not the tags' counts.
+// d_base / cres: k_col_scan's per-tile class bases and totals over the same tags.
+int launch_ecol_sizes(const EcolIn& in, uint32_t n_tiles, const uint64_t* d_base, uint64_t* d_sum, uint64_t* d_bad,
+                      uint64_t* d_bbase, const ColRes* cres, EcolRes* eres, const uint64_t* d_span_base, uint32_t n_spans,
+                      uint64_t* span_out, void* stream);
+// Write (a workgroup per tile): no store at or past d_out + n_bytes.
+int launch_ecol_write(const EcolIn& in, uint32_t n_tiles, const uint64_t* d_base, const uint64_t* d_bbase,
+                      uint64_t n_bytes, uint8_t* d_out, void* stream);
+
 // ---- replay preparation: subpartition recovery buffers ----------------------------
 // A recovery buffer may hold BufferBuilt determinants only (ReplayingState.java:172-177),
 // which are 5 bytes each, so record k of a well-formed buffer starts at 5k: no chain walk.

@@ -375,6 +375,74 @@ def gather_payloads_host(data: Union[bytes, np.ndarray], span_off, span_len, w_v
                                                                   _np_ptr(wo), _np_ptr(wl), _np_ptr(rb), C.byref(p)))
 
 
+# clg_columns_in's arrays that come from DecodedColumns fields of the same name
+_ECOL_FIELDS = (("tag", np.uint8), ("order", np.int8), ("timestamp", np.int64), ("rng", np.int32),
+                ("buffer_built", np.int32), ("w_rc", np.int32), ("w_v1", np.int64), ("w_var_len", np.uint32),
+                ("w_sub", np.uint8), ("w_v0", np.int64))
+
+
+def _columns_in(cols: "DecodedColumns", check_idx: bool = True) -> Tuple[_lib.ColumnsIn, list]:
+    """clg_columns_in over cols' host arrays and its payload column; the second value keeps the
+    arrays alive.  Columns without a payload column raise ValueError."""
+    if cols.var is None or cols.var_pos is None:
+        raise ValueError("the columns carry no payload column (payloads=True)")
+    cin = _lib.ColumnsIn()
+    keep = []
+    for name, dt in _ECOL_FIELDS:
+        a = np.ascontiguousarray(getattr(cols, name), dt)
+        keep.append(a)
+        setattr(cin, name, _np_ptr(a) or None)
+    if check_idx and cols.w_idx is not None:
+        a = np.ascontiguousarray(cols.w_idx, np.uint32)
+        keep.append(a)
+        cin.w_idx = _np_ptr(a) or None
+    pos, var = np.ascontiguousarray(cols.var_pos, np.uint64), np.ascontiguousarray(cols.var, np.uint8)
+    keep += [pos, var]
+    cin.pos, cin.var, cin.n_var = _np_ptr(pos) or None, _np_ptr(var) or None, var.size
+    cin.n_rec = cols.n_rec
+    for c, name in enumerate(("order", "timestamp", "rng", "buffer_built", "w_v0")):
+        cin.n_class[c] = len(getattr(cols, name))
+    if cols.n_spans:
+        sb = np.ascontiguousarray(cols.span_base, np.uint64).reshape(-1)
+        keep.append(sb)
+        cin.span_base, cin.n_spans = _np_ptr(sb), cols.n_spans
+    cin.in_kind = _lib.CLG_MEM_HOST
+    return cin, keep
+
+
+def _encoded_error(st: int, enc: _lib.Encoded) -> ClonosError:
+    err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
+    err.n_bytes, err.bad_what, err.bad_index = int(enc.n_bytes), int(enc.bad_what), int(enc.bad_index)
+    return err
+
+
+def _encode_twice(call, n_spans: int, per_span: bool):
+    """call(clg_encoded) -> status, first for the sizes, then into a host buffer of exactly those."""
+    sbb = np.zeros(max(n_spans, 1) + 1, np.uint64)
+    enc = _lib.Encoded()
+    enc.span_byte_base, enc.out_kind = _np_ptr(sbb), _lib.CLG_MEM_HOST
+    st = call(enc)
+    if st != _lib.CLG_OK:
+        raise _encoded_error(st, enc)
+    out = np.empty(max(1, int(enc.n_bytes)), np.uint8)
+    enc.bytes, enc.cap = _np_ptr(out), out.size
+    st = call(enc)
+    if st != _lib.CLG_OK:
+        raise _encoded_error(st, enc)
+    n = int(enc.n_bytes)
+    if not per_span:
+        return out[:n].tobytes()
+    return [out[int(sbb[s]):int(sbb[s + 1])].tobytes() for s in range(max(n_spans, 1))]
+
+
+def encode_columns_host(cols: "DecodedColumns", per_span: bool = False):
+    """clg_encode_columns_host: the log bytes of typed columns that carry their payload column, on
+    the CPU (no engine, no GPU) -- what Engine.encode_columns computes on the device.  per_span: one
+    bytes per span instead of the whole stream."""
+    cin, keep = _columns_in(cols)
+    return _encode_twice(lambda enc: lib.clg_encode_columns_host(C.byref(cin), C.byref(enc)), cols.n_spans, per_span)
+
+
 # clg_digest rows: two spans are equal only when both fields are equal
 DIGEST =np.dtype([("hash", np.uint64), ("len", np.uint64)])
 
@@ -1084,17 +1152,41 @@ class Engine:
                                    C.byref(bad)))
         return out[:n_out.value].tobytes()
 
-    def encode_columns(self, cols: "DecodedColumns") -> bytes:
-        """Re-encode columns that carry their payload column: encode_batch over to_soa()'s arrays
-        with w_var_off = var_pos[:-1] and var = cols.var -- the batch's bytes, without the log
-        crossing the link."""
-        if cols.var is None or cols.var_pos is None:
-            raise ValueError("the columns carry no payload column (payloads=True)")
-        if len(cols.var) >> 32:
-            raise ValueError(f"{len(cols.var)} payload bytes do not fit clg_encode_in's u32 offsets")
-        b = cols.to_soa()
-        return self.encode_batch(b.tag, b.v0, b.w_idx, b.w_rc, b.w_v1, cols.var_pos[:-1].astype(np.uint32), b.w_var_len,
-                                 b.w_sub, cols.var.tobytes())
+    def encode_columns(self, cols: "DecodedColumns", per_span: bool = False):
+        """clg_encode_columns: re-encode columns that carry their payload column, on the GPU -- the
+        batch's bytes, without the log crossing the link.  The columns go up as they are (no SoA
+        rows are rebuilt).  per_span=True: one bytes per span instead of the whole stream."""
+        cin, keep = _columns_in(cols)
+        return _encode_twice(lambda enc: lib.clg_encode_columns(self._h, C.byref(cin), C.byref(enc)), cols.n_spans,
+                             per_span)
+
+    def encode_columns_raw(self, cin: _lib.ColumnsIn, enc: _lib.Encoded) -> int:
+        """clg_encode_columns over a clg_columns_in and a clg_encoded the caller set up (any in_kind
+        and out_kind; enc.bytes null: sizes only).  Returns the status; the results are in enc."""
+        return lib.clg_encode_columns(self._h, C.byref(cin), C.byref(enc))
+
+    def append_columns(self, logs, epochs: Sequence[int], cols: "DecodedColumns", statuses: bool = False):
+        """clg_append_columns: encode cols on the device and append span s to logs[s] (a
+        ThreadCausalLog or a handle) in epochs[s], as one appendDeterminant batch each, without an
+        encoded byte crossing the link.  Returns the per-span byte counts; a span that could not be
+        applied raises its status after the others were applied, or, with statuses=True, nothing
+        raises for a span and (byte counts, statuses) is returned."""
+        h = np.array([getattr(l, "handle", l) for l in logs], np.uint32)
+        ep = np.ascontiguousarray(epochs, np.int64)
+        cin, keep = _columns_in(cols)
+        ns = max(cols.n_spans, 1)
+        if len(h) != ns or len(ep) != ns:
+            raise ValueError(f"{len(h)} logs and {len(ep)} epochs for {ns} spans")
+        nb, st = np.zeros(ns, np.uint64), np.zeros(ns, np.int32)
+        check(lib.clg_append_columns(self._h, _np_ptr(h), _np_ptr(ep), ns, C.byref(cin), _np_ptr(nb), _np_ptr(st)))
+        if statuses:
+            return nb, st
+        for s in range(ns):
+            if st[s] != _lib.CLG_OK:
+                err = ClonosError(int(st[s]), f"span {s} was not appended")
+                err.span, err.statuses, err.span_bytes = s, st, nb
+                raise err
+        return nb
 
     def encode_decoded(self, dec: "DecodedBatch", span_bytes: bytes) -> bytes:
         """Round trip: re-encode a decoded span (its var fields index the span bytes)."""

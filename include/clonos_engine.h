@@ -519,6 +519,83 @@ typedef struct clg_encode_in {
 int clg_encode_batch(clg_engine* e, const clg_encode_in* in, void* out, uint64_t cap, uint32_t out_kind,
                      uint64_t* n_out, uint64_t* bad_index);
 
+/* ---- encode typed columns --------------------------------------------------
+ * The inverse of clg_decode_logs_columns_var: typed columns and their payload column go in, each
+ * span's exact log bytes come out.  Record i's bytes are the ones clg_encode_batch writes for the
+ * columns' SoA row: its value comes from its class column at its rank in that class; a wide
+ * record's rc / v1 / sub / len from wide row k, its rank among the wide tags; its payload is
+ * var[pos[k] : pos[k] + w_var_len[k]], read only where the format carries one (a TimerTrigger with
+ * sub == 6, a SourceCheckpoint with sub & 0x80, a Serializable).  w_var_off is not an input (it
+ * indexes bytes that are not there); w_idx is optional (NULL: not checked).  pos and var may be
+ * NULL when no wide row carries a payload.  span_base is host memory, (n_spans + 1) x 5 entries
+ * as clg_columns.span_base; NULL with n_spans 0: one span.  in_kind holds for every other array
+ * (CLG_MEM_HOST: staged; CLG_MEM_DEVICE; CLG_MEM_MAPPED: registered host memory, read in place). */
+typedef struct clg_columns_in {
+  const uint8_t* tag;          /* [n_rec] */
+  const int8_t* order;         /* [n_class[0]] */
+  const int64_t* timestamp;    /* [n_class[1]] */
+  const int32_t* rng;          /* [n_class[2]] */
+  const int32_t* buffer_built; /* [n_class[3]] */
+  const int32_t* w_rc;         /* the wide rows, [n_class[4]] each */
+  const int64_t* w_v1;
+  const uint32_t* w_var_len;
+  const uint8_t* w_sub;
+  const int64_t* w_v0;
+  const uint32_t* w_idx;       /* optional */
+  const uint64_t* pos;         /* [n_class[4] + 1] */
+  const uint8_t* var;          /* [n_var] */
+  const uint64_t* span_base;   /* host memory */
+  uint64_t n_rec;
+  uint64_t n_class[CLG_COL_CLASSES];
+  uint64_t n_var;
+  uint32_t n_spans;
+  uint32_t in_kind;
+} clg_columns_in;
+
+/* What was wrong with the input (clg_encoded.bad_what); bad_index is always the lowest index of
+ * the kind reported.  When several kinds are present the first in this order is reported. */
+enum {
+  CLG_ENC_BAD_NONE = 0,
+  CLG_ENC_BAD_TAG = 1,    /* a tag above 7: the record */
+  CLG_ENC_BAD_TOTALS = 2, /* a class's tag count differs from n_class[c]: the class */
+  CLG_ENC_BAD_SPAN = 3,   /* span_base rows decrease, the last row is not n_class, or the class
+                             counts of the tags before a span's first record are not its row: the span */
+  CLG_ENC_BAD_ROW = 4     /* pos[k] + w_var_len[k] > n_var (64 bits) for a row whose format carries
+                             a payload, or w_idx[k] is not the k-th wide record: the row */
+};
+typedef struct clg_encoded {
+  void* bytes;              /* NULL: sizes only (n_bytes and span_byte_base are filled) */
+  uint64_t cap;
+  uint32_t out_kind;        /* CLG_MEM_HOST / CLG_MEM_DEVICE / CLG_MEM_MAPPED */
+  uint32_t reserved;
+  uint64_t* span_byte_base; /* host memory, n_spans + 1 entries (one span: 2), or NULL: the byte
+                               offset of each span's first record; the last entry is n_bytes */
+  /* results */
+  uint64_t n_bytes;
+  uint32_t bad_what;
+  uint32_t reserved2;
+  uint64_t bad_index;       /* ~0 when none */
+} clg_encoded;
+
+/* Invalid input (the kinds above): CLG_E_INVALID_ARG, nothing written.  cap < n_bytes:
+ * CLG_E_CAPACITY with n_bytes and span_byte_base filled and nothing written.  CLG_MEM_DEVICE
+ * output is written by the kernels; CLG_MEM_HOST and CLG_MEM_MAPPED output goes through engine
+ * scratch and one copy.  Synchronous. */
+int clg_encode_columns(clg_engine* e, const clg_columns_in* in, clg_encoded* out);
+/* The same bytes on the CPU (no engine, no GPU): every array is host memory. */
+int clg_encode_columns_host(const clg_columns_in* in, clg_encoded* out);
+/* Encode into engine scratch in HBM, then span s becomes one appendDeterminant batch of log[s] in
+ * epoch[s], in span order, scattered into the log's segments on the device (no encoded byte
+ * crosses the link; the write path's Serializable sidecar is filled as for any other byte).
+ * n_spans is in->n_spans (1 when that is 0).  Pending host bytes are flushed first.  status[s]:
+ * CLG_OK, CLG_E_NO_LOG, CLG_E_NOSPACE, or CLG_E_INVALID_ARG for a span of 2^31 bytes or more; a
+ * failed span leaves its log untouched and the other spans are applied; a depth-0 log is skipped.
+ * A log may appear more than once: its spans apply in order.  span_bytes[s] (may be NULL): the
+ * span's encoded length.  An invalid `in` fails the whole call before any log changes (the kinds
+ * are clg_encode_columns'; the call's error text names them). */
+int clg_append_columns(clg_engine* e, const uint32_t* log, const int64_t* epoch, uint32_t n_spans,
+                       const clg_columns_in* in, uint64_t* span_bytes, int32_t* status);
+
 /* ---- DeterminantResponseEvent (DeterminantResponseEvent.java:36-148) ---------------------
  * The event's map CausalLogID -> log bytes is held as an entry array in the iteration
  * order of the reference's java.util.HashMap (JDK 8: 2^k buckets from 16, load factor

@@ -311,6 +311,91 @@ JNIEXPORT jint JNICALL FN(nDecodeLogsColumnsVar)(JNIEnv* env, jclass cls, jlong 
   return s;
 }
 
+/* The columns of an EngineDecodedColumns with its payload column as clg_columns_in (host memory):
+ * the class counts are span_base's last row, n_var is pos[n_wide]. */
+static void columns_in_of(JNIEnv* env, clg_columns_in* in, jobject tag, jobject order, jobject timestamp, jobject rng,
+                          jobject buffer_built, jobject w_idx, jobject w_rc, jobject w_v1, jobject w_var_len,
+                          jobject w_sub, jobject w_v0, jobject var, jobject pos, const jlong* base, jsize n_spans,
+                          jlong n_rec) {
+  memset(in, 0, sizeof *in);
+  in->tag = addr(env, tag, 0);
+  in->order = (const int8_t*)addr(env, order, 0);
+  in->timestamp = (const int64_t*)addr(env, timestamp, 0);
+  in->rng = (const int32_t*)addr(env, rng, 0);
+  in->buffer_built = (const int32_t*)addr(env, buffer_built, 0);
+  in->w_idx = (const uint32_t*)addr(env, w_idx, 0);
+  in->w_rc = (const int32_t*)addr(env, w_rc, 0);
+  in->w_v1 = (const int64_t*)addr(env, w_v1, 0);
+  in->w_var_len = (const uint32_t*)addr(env, w_var_len, 0);
+  in->w_sub = addr(env, w_sub, 0);
+  in->w_v0 = (const int64_t*)addr(env, w_v0, 0);
+  in->var = addr(env, var, 0);
+  in->pos = (const uint64_t*)addr(env, pos, 0);
+  in->span_base = (const uint64_t*)base;
+  in->n_spans = (uint32_t)n_spans;
+  in->n_rec = (uint64_t)n_rec;
+  for (int c = 0; c < CLG_COL_CLASSES; ++c) in->n_class[c] = (uint64_t)base[(size_t)n_spans * CLG_COL_CLASSES + c];
+  in->n_var = in->pos ? in->pos[in->n_class[CLG_COL_WIDE]] : 0;
+  in->in_kind = CLG_MEM_HOST;
+}
+
+/* clg_encode_columns: the columns' log bytes into `out` (a direct buffer; null: sizes only).
+ * span_base: 5 * (n_spans + 1) longs; span_byte_base: n_spans + 1 longs.  res = {n_bytes, bad_what,
+ * bad_index}. */
+JNIEXPORT jint JNICALL FN(nEncodeColumns)(JNIEnv* env, jclass cls, jlong e, jobject tag, jobject order, jobject timestamp,
+                                          jobject rng, jobject buffer_built, jobject w_idx, jobject w_rc, jobject w_v1,
+                                          jobject w_var_len, jobject w_sub, jobject w_v0, jobject var, jobject pos,
+                                          jlongArray span_base, jlong n_rec, jobject out, jlongArray span_byte_base,
+                                          jlongArray res) {
+  (void)cls;
+  const jsize n_spans = (*env)->GetArrayLength(env, span_base) / CLG_COL_CLASSES - 1;
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  jlong* sbb = (*env)->GetLongArrayElements(env, span_byte_base, NULL);
+  clg_columns_in in;
+  columns_in_of(env, &in, tag, order, timestamp, rng, buffer_built, w_idx, w_rc, w_v1, w_var_len, w_sub, w_v0, var, pos,
+                base, n_spans, n_rec);
+  clg_encoded enc;
+  memset(&enc, 0, sizeof enc);
+  enc.bytes = addr(env, out, 0);
+  enc.cap = cap(env, out);
+  enc.out_kind = CLG_MEM_HOST;
+  enc.span_byte_base = (uint64_t*)sbb;
+  int s = clg_encode_columns(ENG(e), &in, &enc);
+  jlong r[3] = {(jlong)enc.n_bytes, (jlong)enc.bad_what, (jlong)enc.bad_index};
+  (*env)->SetLongArrayRegion(env, res, 0, 3, r);
+  (*env)->ReleaseLongArrayElements(env, span_byte_base, sbb, 0);
+  (*env)->ReleaseLongArrayElements(env, span_base, base, JNI_ABORT);
+  return s;
+}
+
+/* clg_append_columns: span s of the columns appended to logs[s] in epochs[s] on the device.
+ * span_bytes: n_spans longs; status: n_spans ints. */
+JNIEXPORT jint JNICALL FN(nAppendColumns)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray epochs, jobject tag,
+                                          jobject order, jobject timestamp, jobject rng, jobject buffer_built,
+                                          jobject w_idx, jobject w_rc, jobject w_v1, jobject w_var_len, jobject w_sub,
+                                          jobject w_v0, jobject var, jobject pos, jlongArray span_base, jlong n_rec,
+                                          jlongArray span_bytes, jintArray status) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  const jsize n_spans = (*env)->GetArrayLength(env, span_base) / CLG_COL_CLASSES - 1;
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* ep = (*env)->GetLongArrayElements(env, epochs, NULL);
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  jlong* nb = (*env)->GetLongArrayElements(env, span_bytes, NULL);
+  jint* st = (*env)->GetIntArrayElements(env, status, NULL);
+  clg_columns_in in;
+  columns_in_of(env, &in, tag, order, timestamp, rng, buffer_built, w_idx, w_rc, w_v1, w_var_len, w_sub, w_v0, var, pos,
+                base, n_spans, n_rec);
+  int s = clg_append_columns(ENG(e), (const uint32_t*)lg, (const int64_t*)ep, (uint32_t)n, &in, (uint64_t*)nb,
+                             (int32_t*)st);
+  (*env)->ReleaseIntArrayElements(env, status, st, 0);
+  (*env)->ReleaseLongArrayElements(env, span_bytes, nb, 0);
+  (*env)->ReleaseLongArrayElements(env, span_base, base, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, epochs, ep, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  return s;
+}
+
 /* clg_decode_logs_async: the decode is queued; ctx[0] receives a handle that nDecodeWait
  * completes and frees (the output ByteBuffers must stay reachable until then). */
 typedef struct {

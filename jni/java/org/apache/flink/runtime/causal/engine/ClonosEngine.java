@@ -194,6 +194,58 @@ public final class ClonosEngine implements AutoCloseable {
 	}
 
 	/**
+	 * The log bytes of typed columns that carry their payload column (clg_encode_columns), encoded on the
+	 * device from the columns as they are: the inverse of decodeLogsColumns(logs, startEpochs, true).  Span
+	 * s's bytes are [spanByteBase[s], spanByteBase[s + 1]) of the returned buffer when spanByteBase
+	 * (cols.spans() + 1 longs, may be null) is given.  Two native calls: the size, then the bytes.
+	 */
+	public ByteBuffer encodeColumns(EngineDecodedColumns cols, long[] spanByteBase) {
+		if (!cols.hasPayloads()) {
+			throw new IllegalStateException("decoded without payloads");
+		}
+		final long[] res = new long[3];
+		final long[] sbb = spanByteBase != null ? spanByteBase : new long[cols.spans() + 1];
+		check(nEncodeColumns(handle, cols.tag, cols.order, cols.timestamp, cols.rng, cols.bufferBuilt, cols.wIdx,
+			cols.wRc, cols.wV1, cols.wVarLen, cols.wSub, cols.wV0, cols.var, cols.varPos, cols.spanBase,
+			cols.records(), null, sbb, res));
+		final ByteBuffer out = ByteBuffer.allocateDirect((int) Math.max(1, res[0]));
+		check(nEncodeColumns(handle, cols.tag, cols.order, cols.timestamp, cols.rng, cols.bufferBuilt, cols.wIdx,
+			cols.wRc, cols.wV1, cols.wVarLen, cols.wSub, cols.wV0, cols.var, cols.varPos, cols.spanBase,
+			cols.records(), out, sbb, res));
+		out.limit((int) res[0]);
+		return out;
+	}
+
+	public ByteBuffer encodeColumns(EngineDecodedColumns cols) {
+		return encodeColumns(cols, null);
+	}
+
+	/**
+	 * The batched write path from columns (clg_append_columns): the columns are encoded on the device and
+	 * span s becomes one appendDeterminant batch of logs[s] in epochs[s], scattered into the log's segments
+	 * without an encoded byte crossing the link.  Returns per span the bytes appended, or the span's
+	 * (negative) status when it was not applied (CLG_E_NO_LOG, CLG_E_NOSPACE: the caller applies
+	 * backpressure and sends that span again); the other spans are applied.  Invalid columns throw before
+	 * any log changes.
+	 */
+	public long[] appendColumns(int[] logs, long[] epochs, EngineDecodedColumns cols) {
+		if (!cols.hasPayloads()) {
+			throw new IllegalStateException("decoded without payloads");
+		}
+		final long[] spanBytes = new long[logs.length];
+		final int[] status = new int[logs.length];
+		check(nAppendColumns(handle, logs, epochs, cols.tag, cols.order, cols.timestamp, cols.rng, cols.bufferBuilt,
+			cols.wIdx, cols.wRc, cols.wV1, cols.wVarLen, cols.wSub, cols.wV0, cols.var, cols.varPos, cols.spanBase,
+			cols.records(), spanBytes, status));
+		for (int s = 0; s < logs.length; s++) {
+			if (status[s] != CLG_OK) {
+				spanBytes[s] = status[s];
+			}
+		}
+		return spanBytes;
+	}
+
+	/**
 	 * Replay preparation for one failed task with the main log delivered as typed columns and the payload
 	 * column (clg_replay_prepare_columns), in ONE native call: the buffers are sized by bounds no main log
 	 * of mainLen bytes can exceed (the shortest record of each class: ORDER 2 B, TIMESTAMP 9, RNG and
@@ -346,6 +398,17 @@ public final class ClonosEngine implements AutoCloseable {
 											ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff, ByteBuffer wVarLen,
 											ByteBuffer wSub, ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos,
 											long[] result, long[] spanBase);
+	/** clg_encode_columns over host columns; out null: sizes only.  result = {n_bytes, bad_what, bad_index}. */
+	static native int nEncodeColumns(long engine, ByteBuffer tag, ByteBuffer order, ByteBuffer timestamp, ByteBuffer rng,
+									 ByteBuffer bufferBuilt, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1,
+									 ByteBuffer wVarLen, ByteBuffer wSub, ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos,
+									 long[] spanBase, long nRec, ByteBuffer out, long[] spanByteBase, long[] result);
+	/** clg_append_columns: spanBytes and status hold an entry per span. */
+	static native int nAppendColumns(long engine, int[] logs, long[] epochs, ByteBuffer tag, ByteBuffer order,
+									 ByteBuffer timestamp, ByteBuffer rng, ByteBuffer bufferBuilt, ByteBuffer wIdx,
+									 ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarLen, ByteBuffer wSub, ByteBuffer wV0,
+									 ByteBuffer var, ByteBuffer varPos, long[] spanBase, long nRec, long[] spanBytes,
+									 int[] status);
 	/** clg_decode_logs_async: ctx[0] = a handle for nDecodeWait (the buffers stay reachable until then). */
 	static native int nDecodeLogsAsync(long engine, int[] logs, long[] startEpochs, ByteBuffer off, ByteBuffer tag,
 									   ByteBuffer v0, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff,
