@@ -70,6 +70,8 @@ EXPORTED = [
     "clg_gather_payloads_host",
     "clg_replay_prepare_columns", "clg_replay_prepare_columns_device",
     "clg_encode_columns", "clg_encode_columns_host", "clg_append_columns",
+    "clg_pack_columns", "clg_decode_logs_columns_packed", "clg_decode_host_columns_packed",
+    "clg_pack_columns_host", "clg_unpack_columns_host",
 ]
 
 
@@ -187,6 +189,25 @@ class Payloads(C.Structure):  # clg_payloads
         ("cap_var", C.c_uint64), ("cap_pos", C.c_uint64),
         ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
         ("n_rows", C.c_uint64), ("n_var", C.c_uint64), ("bad_row", C.c_uint64),
+    ]
+
+
+PACK_STREAMS = 5  # clg_packed: the tag, order, timestamp, rng and buffer_built columns
+PACK_BLOCK = 1024
+PACK_TAG, PACK_ORDER, PACK_TIMESTAMP, PACK_RNG, PACK_BUFFER_BUILT = range(5)
+
+
+class PackBlock(C.Structure):  # clg_pack_block (32 bytes)
+    _fields_ = [("ref", C.c_int64), ("first", C.c_int64), ("pos", C.c_uint64), ("width", C.c_uint32),
+                ("count", C.c_uint32)]
+
+
+class Packed(C.Structure):  # clg_packed
+    _fields_ = [
+        ("desc", C.c_void_p), ("bits", C.c_void_p),
+        ("cap_desc", C.c_uint64), ("cap_bits", C.c_uint64),
+        ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
+        ("n_val", C.c_uint64 * PACK_STREAMS), ("blk_base", C.c_uint64 * (PACK_STREAMS + 1)), ("n_bits", C.c_uint64),
     ]
 
 
@@ -415,6 +436,13 @@ def _load() -> C.CDLL:
         "clg_encode_columns": (C.c_int, [P, C.POINTER(ColumnsIn), C.POINTER(Encoded)]),
         "clg_encode_columns_host": (C.c_int, [C.POINTER(ColumnsIn), C.POINTER(Encoded)]),
         "clg_append_columns": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(ColumnsIn), P, P]),
+        "clg_pack_columns": (C.c_int, [P, C.POINTER(Columns), C.POINTER(Packed)]),
+        "clg_decode_logs_columns_packed": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads),
+                                                     C.POINTER(Packed)]),
+        "clg_decode_host_columns_packed": (C.c_int, [P, P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads),
+                                                     C.POINTER(Packed)]),
+        "clg_pack_columns_host": (C.c_int, [C.POINTER(Columns), C.POINTER(Packed)]),
+        "clg_unpack_columns_host": (C.c_int, [C.POINTER(Packed), C.c_uint32, C.c_uint64, C.c_uint64, P]),
         "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),

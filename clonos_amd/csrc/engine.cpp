@@ -37,6 +37,7 @@
 #include "encode_columns.h"
 #include "engine_host.h"
 #include "kernels.h"
+#include "pack.h"
 #include "payload.h"
 #include "slice_order.h"
 
@@ -45,6 +46,7 @@ static_assert(sizeof(clg_diff) == 24, "clg_diff layout");
 static_assert(sizeof(clg_columns) == 232, "clg_columns layout");
 static_assert(sizeof(clg_payloads) == 64, "clg_payloads layout");
 static_assert(sizeof(clg_columns_in) == 176, "clg_columns_in layout");
+static_assert(sizeof(clg_packed) == 136, "clg_packed layout");
 static_assert(sizeof(clg_encoded) == 56, "clg_encoded layout");
 
 using namespace clg_internal;  // the host-only types (engine_host.h)
@@ -303,6 +305,10 @@ struct clg_engine {
   DevBuf d_paydesc, d_payrows, d_paytile, d_payout;
   PinBuf h_paydesc, h_payres;
   PinBuf h_paypack;  // the one-launch form: pos | var of a host caller read back in one copy
+  // packed columns: staged host input, the decode's narrow columns, the blocks' descriptors, the
+  // scan groups' sums, host-output staging; the scan's total (pinned: the kernel writes it)
+  DevBuf d_packin, d_packcol, d_packdesc, d_packsum, d_packout;
+  PinBuf h_packres;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 
@@ -4377,7 +4383,255 @@ int decode_columns_var(clg_engine* e, const std::function<int(clg_decoded*, uint
   return ps;
 }
 
+// ---- packed typed columns (pack.h) ----------------------------------------------------------
+// The five narrow columns bit-packed where they lie: measure and the offset scan, the host's
+// capacity check on the scan's total, then the write.  A LogReplayerImpl cursor
+// (LogReplayerImpl.java:61-119) pops one typed value at a time from the blocks.
+
+// Measure and scan over device-side streams: out's results are filled, the descriptors (with
+// their offsets) are left in d_packdesc.
+int pack_sizes(clg_engine* e, const clg::PackSrc& src, clg_packed* out, clg::PackIn* pin) {
+  clg::pack_reset_result(out);
+  clg::pack_layout(src.n, out);
+  const uint64_t nb = out->blk_base[clg::kPackStreams];
+  if (nb >> 31) return fail(CLG_E_INVALID_ARG, "%llu blocks in one call", (unsigned long long)nb);
+  uint64_t in_bytes = 0;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) {
+    if (src.n[c] && !src.col[c]) return fail(CLG_E_INVALID_ARG, "null input array (stream %u)", c);
+    if (uintptr_t(src.col[c]) % clg::pack_elem(c)) return fail(CLG_E_INVALID_ARG, "stream %u is not aligned to its element", c);
+    pin->col[c] = src.col[c], pin->n[c] = src.n[c];
+    in_bytes += src.n[c] * clg::pack_elem(c);
+  }
+  for (uint32_t c = 0; c <= clg::kPackStreams; ++c) pin->blk_base[c] = out->blk_base[c];
+  const uint64_t ng = (nb + clg::kPackScanGroup - 1) / clg::kPackScanGroup;
+  CHK(e->d_packdesc.ensure(size_t(nb) * sizeof(clg_pack_block) + 64));
+  CHK(e->d_packsum.ensure(size_t(ng) * 8 + 64));
+  CHK(e->h_packres.ensure(sizeof(clg::PackRes)));
+  clg::PackRes* res = e->h_packres.as<clg::PackRes>();
+  // (bytes: the columns once, a descriptor written, read and written again, the groups' sums)
+  CHK(e->timed("pack_columns", in_bytes + nb * 72 + ng * 24, [&] {
+    return clg::launch_pack_measure_scan(*pin, uint32_t(nb), e->d_packdesc.as<clg_pack_block>(), e->d_packsum.as<uint64_t>(),
+                                         res, e->stream);
+  }));
+  CHK(e->sync());
+  out->n_bits = res->n_bits;
+  return CLG_OK;
+}
+
+int pack_out_check(const clg_packed& out) {
+  if (out.out_kind != CLG_MEM_HOST && out.out_kind != CLG_MEM_DEVICE && out.out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "out_kind %u", out.out_kind);
+  if (out.out_kind != CLG_MEM_HOST && (uintptr_t(out.desc) % 8 || uintptr_t(out.bits) % 16))
+    return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
+  return CLG_OK;
+}
+
+// The write pass, after pack_sizes and the capacity check: device and registered outputs are
+// written by the kernel, host ones through engine staging and one copy each.
+int pack_write(clg_engine* e, const clg::PackIn& pin, clg_packed* out) {
+  const uint64_t nb = out->blk_base[clg::kPackStreams], nbits = out->n_bits;
+  if (!nb) return CLG_OK;
+  const size_t db = clg_engine::al16(size_t(nb) * sizeof(clg_pack_block));
+  clg_pack_block* ddesc = out->desc;
+  uint8_t* dbits = out->bits;
+  bool staged = out->out_kind == CLG_MEM_HOST;
+  if (out->out_kind == CLG_MEM_MAPPED) {
+    ddesc = reinterpret_cast<clg_pack_block*>(clg_mapped_device_address(out->desc, nb * sizeof(clg_pack_block)));
+    dbits = nbits ? reinterpret_cast<uint8_t*>(clg_mapped_device_address(out->bits, nbits)) : nullptr;
+    if (!ddesc || (nbits && !dbits)) staged = true;  // (not wholly inside one registered range)
+  }
+  if (staged) {
+    CHK(e->d_packout.ensure(db + nbits + 16));
+    ddesc = e->d_packout.as<clg_pack_block>();
+    dbits = e->d_packout.as<uint8_t>() + db;
+  }
+  uint64_t in_bytes = 0;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) in_bytes += pin.n[c] * clg::pack_elem(c);
+  CHK(e->timed("pack_columns", in_bytes + nb * 64 + nbits, [&] {
+    return clg::launch_pack_write(pin, uint32_t(nb), e->d_packdesc.as<clg_pack_block>(), ddesc, dbits, nb, nbits, e->stream);
+  }));
+  if (staged) {
+    HIPCHK(hipMemcpyAsync(out->desc, ddesc, nb * sizeof(clg_pack_block), hipMemcpyDeviceToHost, e->stream));
+    if (nbits) HIPCHK(hipMemcpyAsync(out->bits, dbits, nbits, hipMemcpyDeviceToHost, e->stream));
+  }
+  return e->sync();
+}
+
+int pack_capacity_error(const clg_packed& out, const char* name) {
+  return fail(CLG_E_CAPACITY, "packed columns: %s is too small (blocks %llu, payload bytes %llu)", name,
+              (unsigned long long)out.blk_base[clg::kPackStreams], (unsigned long long)out.n_bits);
+}
+
+// The decode into engine scratch and the columns of what it produced, also in engine scratch;
+// then the pack, the wide rows as they are and (var) the payload column of the same rows.
+// Every size is known before anything is written to the caller.
+int decode_columns_packed(clg_engine* e, const std::function<int(clg_decoded*, uint64_t*)>& run, uint32_t n,
+                          clg_columns* wide, clg_payloads* var, clg_packed* out,
+                          const std::function<int(std::vector<clg::PaySpan>&, std::vector<uint32_t>&)>& spans_of) {
+  if (wide->tag || wide->order || wide->timestamp || wide->rng || wide->buffer_built)
+    return fail(CLG_E_INVALID_ARG, "the narrow column pointers of `wide` must be NULL: those columns are delivered packed");
+  if (wide->out_kind != CLG_MEM_HOST && wide->out_kind != CLG_MEM_DEVICE && wide->out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "out_kind %u", wide->out_kind);
+  CHK(pack_out_check(*out));
+  clg::col_reset_result(wide);
+  clg::pack_reset_result(out);
+  if (var) clg::pay_reset_result(var);
+
+  // the decode, and the columns' sizes and span bases
+  std::vector<uint64_t> sb(size_t(n + 1) * clg::kColClasses, 0);
+  clg_columns sizes{};
+  sizes.span_base = sb.data();
+  sizes.out_kind = CLG_MEM_DEVICE;
+  ColKeep keep;
+  const int cs = decode_columns(e, run, n, &sizes, &keep);
+  const std::string col_err = g_err;
+  wide->n_rec = sizes.n_rec;
+  for (uint32_t c = 0; c < clg::kColClasses; ++c) wide->n_class[c] = sizes.n_class[c];
+  wide->err_status = sizes.err_status, wide->err_span = sizes.err_span;
+  wide->err_off = sizes.err_off, wide->err_tag = sizes.err_tag;
+  if (!keep.valid || keep.col_status != CLG_OK) return cs;
+  if (wide->span_base) memcpy(wide->span_base, sb.data(), sb.size() * 8);
+  const uint64_t nr = sizes.n_rec, nw = sizes.n_class[clg::kColWide];
+  const uint64_t* tot = sizes.n_class;
+
+  // the narrow columns and w_v0 into engine scratch (the tags and the side rows stay where the
+  // decode left them)
+  const uint64_t cb[5] = {tot[0], tot[1] * 8, tot[2] * 4, tot[3] * 4, nw * 8};
+  uint64_t at[6] = {0};
+  for (int i = 0; i < 5; ++i) at[i + 1] = clg_engine::al16(at[i] + cb[i]);
+  CHK(e->d_packcol.ensure(at[5] + 16));
+  uint8_t* sc = e->d_packcol.as<uint8_t>();
+  clg_columns full{};
+  full.tag = keep.d.tag, full.order = reinterpret_cast<int8_t*>(sc + at[0]);
+  full.timestamp = reinterpret_cast<int64_t*>(sc + at[1]), full.rng = reinterpret_cast<int32_t*>(sc + at[2]);
+  full.buffer_built = reinterpret_cast<int32_t*>(sc + at[3]), full.w_v0 = reinterpret_cast<int64_t*>(sc + at[4]);
+  full.w_idx = keep.d.w_idx, full.w_rc = keep.d.w_rc, full.w_v1 = keep.d.w_v1, full.w_var_off = keep.d.w_var_off;
+  full.w_var_len = keep.d.w_var_len, full.w_sub = keep.d.w_sub;
+  full.cap_tag = nr, full.cap_order = tot[0], full.cap_timestamp = tot[1], full.cap_rng = tot[2];
+  full.cap_buffer_built = tot[3], full.cap_wide = nw;
+  full.out_kind = CLG_MEM_DEVICE;
+  CHK(columnize_device(e, keep.d, nullptr, 0, &full));
+
+  // every size, before anything is written to the caller
+  const clg::PackSrc src{{full.tag, full.order, full.timestamp, full.rng, full.buffer_built}, {nr, tot[0], tot[1], tot[2], tot[3]}};
+  clg::PackIn pin{};
+  CHK(pack_sizes(e, src, out, &pin));
+  int ps = CLG_OK;
+  std::vector<clg::PaySpan> spans;
+  std::vector<uint32_t> segtab;
+  std::vector<uint64_t> row_base(size_t(n) + 1);
+  for (uint32_t s = 0; s <= n; ++s) row_base[s] = sb[size_t(s) * clg::kColClasses + clg::kColWide];
+  if (var) {
+    ps = spans_of(spans, segtab);
+    if (ps == CLG_OK) ps = gather_payloads_device(e, spans, segtab, keep.d.w_var_off, keep.d.w_var_len, row_base.data(), var, true);
+  }
+  const std::string pay_err = g_err;
+  void* const wdst[7] = {wide->w_idx, wide->w_rc, wide->w_v1, wide->w_var_off, wide->w_var_len, wide->w_sub, wide->w_v0};
+  const void* const wsrc[7] = {full.w_idx, full.w_rc, full.w_v1, full.w_var_off, full.w_var_len, full.w_sub, full.w_v0};
+  const uint32_t wwd[7] = {4, 4, 8, 4, 4, 1, 8};
+  bool wide_any = false, wide_short = false;
+  for (int i = 0; i < 7; ++i) wide_any = wide_any || wdst[i];
+  for (int i = 0; i < 7; ++i) wide_short = wide_short || (wide_any && clg::col_cap(wdst[i], wide->cap_wide) < nw);
+  const char* pk_short = clg::pack_sizes_only(*out) ? nullptr : clg::pack_short(*out);
+  const char* pay_short = var && ps == CLG_OK && !clg::pay_sizes_only(*var) ? clg::pay_short(*var, var->n_rows, var->n_var) : nullptr;
+  if (wide_short) return fail(CLG_E_CAPACITY, "the wide rows' arrays are too small (rows %llu)", (unsigned long long)nw);
+  if (pk_short) return pack_capacity_error(*out, pk_short);
+  if (pay_short)
+    return fail(CLG_E_CAPACITY, "%s is too small (rows %llu, payload bytes %llu)", pay_short, (unsigned long long)var->n_rows,
+                (unsigned long long)var->n_var);
+
+  // the writes
+  if (!clg::pack_sizes_only(*out)) CHK(pack_write(e, pin, out));
+  if (wide_any && nw) {
+    for (int i = 0; i < 7; ++i) HIPCHK(hipMemcpyAsync(wdst[i], wsrc[i], nw * wwd[i], hipMemcpyDefault, e->stream));
+    CHK(e->sync());
+  }
+  if (var && ps == CLG_OK && !clg::pay_sizes_only(*var))
+    ps = gather_payloads_device(e, spans, segtab, keep.d.w_var_off, keep.d.w_var_len, row_base.data(), var);
+  else if (ps != CLG_OK)
+    g_err = pay_err;
+  if (cs != CLG_OK) {
+    g_err = col_err;
+    return cs;
+  }
+  return ps;
+}
+
 }  // namespace
+
+int clg_pack_columns(clg_engine* e, const clg_columns* in, clg_packed* out) {
+  ENGINE_GUARD(e);
+  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::pack_reset_result(out);
+  CHK(pack_out_check(*out));
+  clg::PackSrc src = clg::pack_src(*in);
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c)
+    if (src.n[c] && !src.col[c]) return fail(CLG_E_INVALID_ARG, "null input array (stream %u)", c);
+  bool stage = in->out_kind == CLG_MEM_HOST;
+  if (in->out_kind == CLG_MEM_MAPPED) {  // registered host memory: its device side
+    const void* dev[clg::kPackStreams];
+    for (uint32_t c = 0; c < clg::kPackStreams && !stage; ++c) {
+      dev[c] = src.col[c];
+      if (src.n[c] && !(dev[c] = reinterpret_cast<const void*>(clg_mapped_device_address(src.col[c], src.n[c] * clg::pack_elem(c)))))
+        stage = true;  // (not wholly inside one registered range)
+    }
+    if (!stage)
+      for (uint32_t c = 0; c < clg::kPackStreams; ++c) src.col[c] = dev[c];
+  } else if (in->out_kind != CLG_MEM_HOST && in->out_kind != CLG_MEM_DEVICE) {
+    return fail(CLG_E_INVALID_ARG, "the columns' out_kind %u", in->out_kind);
+  }
+  if (stage) {
+    uint64_t at[clg::kPackStreams + 1] = {0};
+    for (uint32_t c = 0; c < clg::kPackStreams; ++c) at[c + 1] = clg_engine::al16(at[c] + src.n[c] * clg::pack_elem(c));
+    CHK(e->d_packin.ensure(at[clg::kPackStreams] + 16));
+    for (uint32_t c = 0; c < clg::kPackStreams; ++c) {
+      if (src.n[c])
+        HIPCHK(hipMemcpyAsync(e->d_packin.as<uint8_t>() + at[c], src.col[c], src.n[c] * clg::pack_elem(c), hipMemcpyHostToDevice,
+                              e->stream));
+      src.col[c] = e->d_packin.as<uint8_t>() + at[c];
+    }
+  }
+  clg::PackIn pin{};
+  CHK(pack_sizes(e, src, out, &pin));
+  if (clg::pack_sizes_only(*out)) return CLG_OK;
+  if (const char* name = clg::pack_short(*out)) return pack_capacity_error(*out, name);
+  return pack_write(e, pin, out);
+}
+
+int clg_decode_logs_columns_packed(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                                   clg_columns* wide, clg_payloads* var, clg_packed* out) {
+  ENGINE_GUARD(e);
+  if (!wide || !out || (n && (!log || !start_epoch))) return fail(CLG_E_INVALID_ARG, "null argument");
+  return decode_columns_packed(
+      e, [&](clg_decoded* d, uint64_t* base) { return clg_decode_logs(e, log, start_epoch, n, d, base); }, n, wide, var, out,
+      [&](std::vector<clg::PaySpan>& spans, std::vector<uint32_t>& segtab) {
+        return payload_spans_logs(e, log, start_epoch, n, spans, segtab);
+      });
+}
+
+int clg_decode_host_columns_packed(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off,
+                                   const uint64_t* span_len, uint32_t n, clg_columns* wide, clg_payloads* var,
+                                   clg_packed* out) {
+  ENGINE_GUARD(e);
+  if (!wide || !out || (n && (!span_off || !span_len))) return fail(CLG_E_INVALID_ARG, "null argument");
+  return decode_columns_packed(
+      e, [&](clg_decoded* d, uint64_t* base) { return clg_decode_host(e, bytes, span_off, span_len, n, d, base); }, n, wide,
+      var, out, [&](std::vector<clg::PaySpan>& spans, std::vector<uint32_t>&) {
+        return payload_spans_bytes(e, bytes, span_off, span_len, n, CLG_MEM_HOST, spans);
+      });
+}
+
+int clg_pack_columns_host(const clg_columns* in, clg_packed* out) {
+  const char* what = "";
+  const int st = clg::pack_build_host(in, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "packed columns: %s", what);
+}
+
+int clg_unpack_columns_host(const clg_packed* in, uint32_t stream, uint64_t first, uint64_t count, void* out) {
+  const char* what = "";
+  const int st = clg::pack_unpack_host(in, stream, first, count, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "unpack columns: %s", what);
+}
 
 int clg_gather_payloads(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
                         uint32_t n_spans, const uint32_t* w_var_off, const uint32_t* w_var_len,

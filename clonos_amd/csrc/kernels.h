@@ -8,6 +8,7 @@
 
 struct clg_digest;  // include/clonos_engine.h
 struct clg_diff;
+struct clg_pack_block;
 
 namespace clg {
 
@@ -699,6 +700,27 @@ struct PaySmallRes {  // pinned memory; with any verdict but kPaySmallWritten no
 // cap_pos / cap_var: usable capacities (0 for a null array).
 int launch_pay_small(const PayIn& in, uint64_t* pos, uint8_t* var, uint64_t cap_pos, uint64_t cap_var, bool sizes_only,
                      PaySmallRes* res, void* stream);
+
+// ---- packed typed columns (pack.h, pack.hip) ----------------------------------------
+struct PackIn {  // device addresses of the five streams, their lengths and block bases
+  const void* col[5];
+  uint64_t n[5];
+  uint64_t blk_base[6];
+};
+// The offset scan's total, in pinned memory the host reads before anything is written to the caller.
+struct PackRes {
+  uint64_t n_bits;
+};
+// Measure (a workgroup per block -> d_desc[block]: ref, first, width, count, and the payload's
+// size in pos) and the offsets (group sums, one workgroup over the sums, then every group's
+// scan plus its base: d_desc[block].pos becomes the payload's offset; *res the total).
+// d_gsum: a u64 per group of kPackScanGroup blocks.
+int launch_pack_measure_scan(const PackIn& in, uint32_t n_blocks, clg_pack_block* d_desc, uint64_t* d_gsum, PackRes* res,
+                             void* stream);
+// Write (a workgroup per block): descriptor b to out_desc[b] for b < lim_desc, its payload to
+// bits + pos; no store at or past bits + lim_bits.
+int launch_pack_write(const PackIn& in, uint32_t n_blocks, const clg_pack_block* d_desc, clg_pack_block* out_desc,
+                      uint8_t* bits, uint64_t lim_desc, uint64_t lim_bits, void* stream);
 
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {

@@ -203,6 +203,12 @@ class DecodedColumns:
         """Each span's first record index (the decode's span_rec_base): the row sums."""
         return self.span_base.sum(axis=1, dtype=np.uint64)
 
+    @property
+    def n_bytes(self) -> int:
+        """The delivered size: every column, span_base and the payload column when present."""
+        arrs = [getattr(self, k) for k, _ in _COL_FIELDS] + [self.span_base, self.var, self.var_pos]
+        return int(sum(a.nbytes for a in arrs if a is not None))
+
     def span(self, s: int) -> SpanColumns:
         if not 0 <= s < self.n_spans:
             raise IndexError("span index")
@@ -441,6 +447,158 @@ def encode_columns_host(cols: "DecodedColumns", per_span: bool = False):
     bytes per span instead of the whole stream."""
     cin, keep = _columns_in(cols)
     return _encode_twice(lambda enc: lib.clg_encode_columns_host(C.byref(cin), C.byref(enc)), cols.n_spans, per_span)
+
+
+# clg_pack_block rows
+PACK_BLOCK = np.dtype([("ref", np.int64), ("first", np.int64), ("pos", np.uint64), ("width", np.uint32),
+                       ("count", np.uint32)])
+# the packed streams' element types, in stream order (the clg_columns arrays of the same names)
+PACK_STREAM_FIELDS = (("tag", np.uint8), ("order", np.int8), ("timestamp", np.int64), ("rng", np.int32),
+                      ("buffer_built", np.int32))
+
+
+def _packed_struct(desc: Optional[np.ndarray], bits: Optional[np.ndarray], kind: int = _lib.CLG_MEM_HOST) -> _lib.Packed:
+    """clg_packed over host arrays (capacity = their lengths); both None: sizes only."""
+    p = _lib.Packed()
+    if desc is not None:
+        p.desc, p.cap_desc = _np_ptr(desc), desc.size
+    if bits is not None:
+        p.bits, p.cap_bits = _np_ptr(bits), bits.size
+    p.out_kind = kind
+    return p
+
+
+def _packed_error(st: int, p: _lib.Packed) -> ClonosError:
+    err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
+    err.n_blocks, err.n_bits = int(p.blk_base[_lib.PACK_STREAMS]), int(p.n_bits)
+    return err
+
+
+class PackedColumns:
+    """Typed replay columns with the five narrow columns bit-packed (layout: include/clonos_engine.h
+    clg_packed; the format: clonos_amd/csrc/pack.h): desc, one PACK_BLOCK row per block of 1024
+    values, stream c's rows at desc[blk_base[c]:blk_base[c + 1]], and bits, the blocks' payloads.
+    The wide rows, span_base and the payload column are as DecodedColumns holds them.  span(s)
+    unpacks only the blocks span s's ranges cover, so replay.ColumnReplayer(packed, s) works as it
+    does over DecodedColumns; unpack() gives the whole DecodedColumns back."""
+
+    def __init__(self, desc, bits, n_val, blk_base, w_idx, w_rc, w_v1, w_var_off, w_var_len, w_sub, w_v0, span_base,
+                 spans_bytes=None):
+        self.desc, self.bits = desc, bits
+        self.n_val = [int(x) for x in n_val]
+        self.blk_base = [int(x) for x in blk_base]
+        self.w_idx, self.w_rc, self.w_v1, self.w_v0 = w_idx, w_rc, w_v1, w_v0
+        self.w_var_off, self.w_var_len, self.w_sub = w_var_off, w_var_len, w_sub
+        self.span_base = np.asarray(span_base, np.uint64).reshape(-1, _lib.COL_CLASSES)
+        self.spans_bytes = spans_bytes
+        self.var: Optional[np.ndarray] = None
+        self.var_pos: Optional[np.ndarray] = None
+        self.error: Optional[ClonosError] = None
+
+    @property
+    def n_rec(self) -> int:
+        return self.n_val[_lib.PACK_TAG]
+
+    @property
+    def n_spans(self) -> int:
+        return int(self.span_base.shape[0]) - 1
+
+    @property
+    def n_bytes(self) -> int:
+        """The delivered size: descriptors, payload bits, the wide rows, span_base and the
+        payload column when present."""
+        arrs = [self.desc, self.bits, self.span_base, self.var, self.var_pos] + [getattr(self, k) for k in _COL_WIDE]
+        return int(sum(a.nbytes for a in arrs if a is not None))
+
+    def _struct(self) -> _lib.Packed:
+        p = _packed_struct(self.desc, self.bits)
+        for c in range(_lib.PACK_STREAMS):
+            p.n_val[c] = self.n_val[c]
+        for c in range(_lib.PACK_STREAMS + 1):
+            p.blk_base[c] = self.blk_base[c]
+        p.n_bits = self.bits.size
+        return p
+
+    def unpack_stream(self, stream: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """clg_unpack_columns_host: values [first, first + count) of one stream, in its own type;
+        only the blocks that range covers are read."""
+        if not 0 <= stream < _lib.PACK_STREAMS:
+            raise IndexError("stream index")
+        if count is None:
+            count = self.n_val[stream] - first
+        out = np.empty(max(count, 0), PACK_STREAM_FIELDS[stream][1])
+        p = self._struct()
+        st = lib.clg_unpack_columns_host(C.byref(p), stream, first, count, _np_ptr(out) or None)
+        if st != _lib.CLG_OK:
+            raise _packed_error(st, p)
+        return out
+
+    def unpack(self) -> "DecodedColumns":
+        cols = DecodedColumns(*[self.unpack_stream(c) for c in range(_lib.PACK_STREAMS)],
+                              *[getattr(self, k) for k in _COL_WIDE], self.span_base, self.spans_bytes)
+        cols.var, cols.var_pos, cols.error = self.var, self.var_pos, self.error
+        return cols
+
+    def span(self, s: int) -> SpanColumns:
+        if not 0 <= s < self.n_spans:
+            raise IndexError("span index")
+        a, b = self.span_base[s].astype(np.int64), self.span_base[s + 1].astype(np.int64)
+        r0, r1 = int(a.sum()), int(b.sum())
+        cut = [(r0, r1)] + [(int(a[c]), int(b[c])) for c in range(4)]
+        return SpanColumns(*[self.unpack_stream(c, lo, hi - lo) for c, (lo, hi) in enumerate(cut)], int(a[4]),
+                           int(b[4] - a[4]))
+
+    def payload(self, k: int) -> bytes:
+        if self.var is None or self.var_pos is None:
+            raise ValueError("the columns carry no payload column (payloads=True)")
+        if not 0 <= k < len(self.var_pos) - 1:
+            raise IndexError("wide row index")
+        return self.var[int(self.var_pos[k]):int(self.var_pos[k + 1])].tobytes()
+
+
+def _pack_in(cols: "DecodedColumns") -> Tuple[_lib.Columns, list]:
+    """clg_columns over cols' five narrow host arrays, as the pack reads them."""
+    c = _lib.Columns()
+    keep = []
+    for name, dt in PACK_STREAM_FIELDS:
+        a = np.ascontiguousarray(getattr(cols, name), dt)
+        keep.append(a)
+        setattr(c, name, _np_ptr(a) or None)
+    c.n_rec = keep[0].size
+    for k in range(4):
+        c.n_class[k] = keep[k + 1].size
+    c.n_class[4] = len(cols.w_v0)
+    c.out_kind = _lib.CLG_MEM_HOST
+    return c, keep
+
+
+def _pack_twice(call, cols: "DecodedColumns") -> PackedColumns:
+    """call(clg_packed) -> status, first for the sizes, then into host arrays of exactly those."""
+    p = _lib.Packed()
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _packed_error(st, p)
+    desc, bits = np.zeros(int(p.blk_base[_lib.PACK_STREAMS]), PACK_BLOCK), np.zeros(int(p.n_bits), np.uint8)
+    p = _packed_struct(desc, bits)
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _packed_error(st, p)
+    out = PackedColumns(desc, bits, p.n_val, p.blk_base, *[getattr(cols, k) for k in _COL_WIDE], cols.span_base,
+                        cols.spans_bytes)
+    out.var, out.var_pos, out.error = cols.var, cols.var_pos, cols.error
+    return out
+
+
+def pack_columns_host(cols: "DecodedColumns") -> PackedColumns:
+    """clg_pack_columns_host: the five narrow columns bit-packed on the CPU (no engine, no GPU) --
+    the same bytes Engine.pack_columns produces on the device."""
+    cin, keep = _pack_in(cols)
+    return _pack_twice(lambda p: lib.clg_pack_columns_host(C.byref(cin), C.byref(p)), cols)
+
+
+def unpack_columns_host(packed: PackedColumns, stream: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+    """clg_unpack_columns_host (PackedColumns.unpack_stream)."""
+    return packed.unpack_stream(stream, first, count)
 
 
 # clg_digest rows: two spans are equal only when both fields are equal
@@ -996,17 +1154,69 @@ class Engine:
         cols.var, cols.var_pos = var[:int(p.n_var)], pos[:int(p.n_rows) + 1]
         return cols
 
+    # ---- packed typed columns (clg_packed)
+    def pack_columns(self, cols: DecodedColumns) -> PackedColumns:
+        """clg_pack_columns: the five narrow columns of host columns bit-packed on the device (staged
+        in, packed, read back); the bytes are pack_columns_host's."""
+        cin, keep = _pack_in(cols)
+        return _pack_twice(lambda p: lib.clg_pack_columns(self._h, C.byref(cin), C.byref(p)), cols)
+
+    def pack_columns_raw(self, cin: _lib.Columns, out: _lib.Packed) -> int:
+        """clg_pack_columns over a clg_columns and a clg_packed the caller set up (any kinds; desc
+        and bits null: sizes only).  Returns the status; the results are in out."""
+        return lib.clg_pack_columns(self._h, C.byref(cin), C.byref(out))
+
+    def _decode_packed(self, call, total: int, n: int, spans_bytes, partial: bool, payloads: bool) -> PackedColumns:
+        """call(wide, var or None, packed) -> status, over bounds no batch of `total` encoded bytes
+        can exceed: a record is at least 2 bytes and its value at most its encoded length less the
+        tag, so the streams hold at most `total` bytes in at most total / 1024 + 5 blocks, each
+        padded by less than 16 bytes."""
+        arrs = {k: np.empty(total // 6 + n + 1, dt) for k, dt in _COL_FIELDS if k in _COL_WIDE}
+        base = np.zeros((n + 1) * _lib.COL_CLASSES, np.uint64)
+        c = _lib.Columns()
+        for k in _COL_WIDE:
+            setattr(c, k, _np_ptr(arrs[k]))
+        c.cap_wide = min(a.size for a in arrs.values())
+        c.span_base, c.out_kind = _np_ptr(base), _lib.CLG_MEM_HOST
+        desc = np.empty(total // 1024 + 5, PACK_BLOCK)
+        bits = np.empty(total + 16 * desc.size, np.uint8)
+        pk = _packed_struct(desc, bits)
+        var = pos = p = None
+        if payloads:
+            var, pos = self._payload_bounds(total, n)
+            p = _payloads_struct(var, pos)
+        st = call(c, p, pk)
+        if st != _lib.CLG_OK and not (partial and c.err_status == st):
+            raise _columns_error(st, c)
+        nw = int(c.n_class[_lib.COL_WIDE])
+        out = PackedColumns(desc[:int(pk.blk_base[_lib.PACK_STREAMS])], bits[:int(pk.n_bits)], pk.n_val, pk.blk_base,
+                            *[arrs[k][:nw] for k in _COL_WIDE], base, spans_bytes)
+        if st != _lib.CLG_OK:
+            out.error = _columns_error(st, c)
+        if payloads:
+            out.var, out.var_pos = var[:int(p.n_var)], pos[:int(p.n_rows) + 1]
+        return out
+
     def decode_logs_columns(self, logs: Sequence["ThreadCausalLog"], start_epochs: Sequence[int],
-                            keep_bytes: bool = False, partial: bool = False, payloads: bool = False) -> DecodedColumns:
+                            keep_bytes: bool = False, partial: bool = False, payloads: bool = False,
+                            packed: bool = False) -> Union[DecodedColumns, PackedColumns]:
         """clg_decode_logs_columns: decode_logs' ranges decoded on the GPU and delivered as typed
         columns.  A decode error raises as decode_logs' does; partial=True returns the columns of
         each span's records up to its first error instead, the error in .error.  payloads=True
         (clg_decode_logs_columns_var): the wide rows' payload bytes come with the columns, gathered
-        on the device (.var, .var_pos, .payload(k)); the logs' bytes do not cross the link."""
+        on the device (.var, .var_pos, .payload(k)); the logs' bytes do not cross the link.
+        packed=True (clg_decode_logs_columns_packed): the five narrow columns come bit-packed, as
+        PackedColumns."""
         n = len(logs)
         h = np.array([l.handle for l in logs], np.uint32)
         ep = np.array(start_epochs, np.int64)
         total = self.log_lengths(h)[1] if n else 0
+        if packed:
+            sb = [np.frombuffer(l.getDeterminants(e), np.uint8) for l, e in zip(logs, start_epochs)] if keep_bytes else None
+            return self._decode_packed(
+                lambda c, p, pk: lib.clg_decode_logs_columns_packed(self._h, _np_ptr(h), _np_ptr(ep), n, C.byref(c),
+                                                                    C.byref(p) if p is not None else None, C.byref(pk)),
+                total, n, sb, partial, payloads)
         arrs = self._column_bounds(total, n)
         base = np.zeros((n + 1) * _lib.COL_CLASSES, np.uint64)
         c = _columns_struct(arrs, base, _lib.CLG_MEM_HOST)
@@ -1026,15 +1236,22 @@ class Engine:
         return lib.clg_decode_logs_columns(self._h, _np_ptr(handles), _np_ptr(start_epochs), len(handles), C.byref(cols))
 
     def decode_host_columns(self, data: Union[bytes, np.ndarray], spans: Optional[Sequence[Tuple[int, int]]] = None,
-                            partial: bool = False, payloads: bool = False) -> DecodedColumns:
+                            partial: bool = False, payloads: bool = False, packed: bool = False
+                            ) -> Union[DecodedColumns, PackedColumns]:
         """clg_decode_host_columns: decode_host's spans decoded on the GPU and delivered as typed
-        columns (errors and payloads as decode_logs_columns)."""
+        columns (errors, payloads and packed as decode_logs_columns)."""
         buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(
             data, np.uint8)
         if spans is None:
             spans = [(0, buf.size)]
         so = np.array([s[0] for s in spans], np.uint64)
         sl = np.array([s[1] for s in spans], np.uint64)
+        if packed:
+            return self._decode_packed(
+                lambda c, p, pk: lib.clg_decode_host_columns_packed(self._h, _np_ptr(buf), _np_ptr(so), _np_ptr(sl), len(spans),
+                                                                    C.byref(c), C.byref(p) if p is not None else None,
+                                                                    C.byref(pk)),
+                int(sl.sum()), len(spans), [buf[int(o):int(o) + int(k)] for o, k in zip(so, sl)], partial, payloads)
         arrs = self._column_bounds(int(sl.sum()), len(spans))
         base = np.zeros((len(spans) + 1) * _lib.COL_CLASSES, np.uint64)
         c = _columns_struct(arrs, base, _lib.CLG_MEM_HOST)

@@ -62,8 +62,8 @@ enum {
 /* CLG_MEM_MAPPED: host memory registered with clg_host_register.  For decode outputs
  * (clg_decoded.out_kind) the single-launch small decode writes it straight from the GPU (no
  * staging copy), and so do the column kernels for clg_columns.out_kind; clg_columnize also reads
- * a decoded batch from it (clg_decoded.out_kind of its input).  Every other path treats it as
- * CLG_MEM_HOST. */
+ * a decoded batch from it (clg_decoded.out_kind of its input), and the pack kernels read columns
+ * from it and write clg_packed's arrays to it.  Every other path treats it as CLG_MEM_HOST. */
 enum { CLG_MEM_HOST = 0, CLG_MEM_DEVICE = 1, CLG_MEM_MAPPED = 2 };
 
 /* Pin and map [p, p + bytes) of host memory for the device (hipHostRegister, mapped); a
@@ -442,6 +442,88 @@ int clg_decode_host_columns_var(clg_engine* e, const uint8_t* bytes, const uint6
 int clg_gather_payloads_host(const uint8_t* bytes, const uint64_t* span_off, const uint64_t* span_len,
                              uint32_t n_spans, const uint32_t* w_var_off, const uint32_t* w_var_len,
                              const uint64_t* row_base, clg_payloads* out);
+
+/* ---- packed typed columns --------------------------------------------------
+ * The five narrow columns bit-packed on the device, so that what crosses the link is the bits the
+ * values hold: block-wise frame of reference, 1024 values a block (clonos_amd/csrc/pack.h is the
+ * format's one definition).  Five streams, each the clg_columns array of the same name:
+ *   CLG_PACK_TAG          tag          u8   FOR
+ *   CLG_PACK_ORDER        order        i8   FOR
+ *   CLG_PACK_TIMESTAMP    timestamp    i64  DELTA
+ *   CLG_PACK_RNG          rng          i32  FOR
+ *   CLG_PACK_BUFFER_BUILT buffer_built i32  FOR
+ * A stream of n values is ceil(n / 1024) independent blocks, each of 1024 values but the last.
+ * All arithmetic is on values sign-extended to 64 bits (tags zero-extended), modulo 2^64.  For a
+ * block x_0 .. x_{m-1}:
+ *   FOR    residuals r_i = x_i, k = m, first = 0
+ *   DELTA  first = x_0, residuals r_i = x_i - x_{i-1} for i = 1 .. m-1, k = m - 1
+ *   ref    the minimum residual compared as int64 (0 when k = 0)
+ *   range  the maximum residual minus ref, in uint64; width = 0 if range == 0, else 64 - clz(range)
+ *   p_i    (uint64)r_i - (uint64)ref, below 2^width
+ * The block's payload is the k * width bit little-endian bit string with p_i in bits
+ * [i * width, (i + 1) * width) -- bit j is bit j % 64 of the little-endian u64 word j / 64 --
+ * zero-padded to 16 * ceil(k * width / 128) bytes: the packed bytes are a pure function of the
+ * columns.  desc holds one clg_pack_block per block, stream c's at desc[blk_base[c] ..
+ * blk_base[c + 1]); bits holds all payloads back to back in stream order, then block order, so
+ * every pos is a multiple of 16.  The wide rows, span_base and the payload column are not
+ * packed.  LogReplayerImpl pops one typed value at a time (LogReplayerImpl.java:61-119): a cursor
+ * over the blocks serves it without unpacking whole arrays. */
+#define CLG_PACK_STREAMS 5
+#define CLG_PACK_BLOCK 1024
+enum { CLG_PACK_TAG = 0, CLG_PACK_ORDER = 1, CLG_PACK_TIMESTAMP = 2, CLG_PACK_RNG = 3, CLG_PACK_BUFFER_BUILT = 4 };
+typedef struct clg_pack_block {
+  int64_t ref;
+  int64_t first;
+  uint64_t pos;    /* byte offset of the block's payload in bits */
+  uint32_t width;  /* 0 .. 64 */
+  uint32_t count;  /* the block's values, 1 .. 1024 */
+} clg_pack_block;
+typedef struct clg_packed {
+  clg_pack_block* desc;
+  uint8_t* bits;
+  uint64_t cap_desc;      /* blocks */
+  uint64_t cap_bits;      /* bytes */
+  uint32_t out_kind;      /* CLG_MEM_HOST / CLG_MEM_DEVICE / CLG_MEM_MAPPED (both arrays) */
+  uint32_t reserved;
+  /* results */
+  uint64_t n_val[CLG_PACK_STREAMS];
+  uint64_t blk_base[CLG_PACK_STREAMS + 1];
+  uint64_t n_bits;        /* bytes used of bits */
+} clg_packed;
+
+/* Pack in->tag (n_rec values), order, timestamp, rng and buffer_built (n_class[0 .. 3] values);
+ * nothing else of `in` is read.  in->out_kind says where the five arrays live: device memory and
+ * registered host memory (CLG_MEM_MAPPED) are read in place, host memory is staged.  desc and bits
+ * both NULL: sizes only (the results are filled, nothing is written).  cap_desc or cap_bits too
+ * small: CLG_E_CAPACITY with the results filled and nothing written to the caller (the totals are
+ * read from pinned memory and checked before the write pass, as clg_columnize does).
+ * CLG_MEM_DEVICE and CLG_MEM_MAPPED outputs (16-byte aligned) are written by the kernels;
+ * CLG_MEM_HOST ones through engine staging and one copy each.  Synchronous; the kernels' time is
+ * the stat "pack_columns". */
+int clg_pack_columns(clg_engine* e, const clg_columns* in, clg_packed* out);
+/* clg_decode_logs_columns_var / clg_decode_host_columns_var with the five narrow columns delivered
+ * packed: decode and columnize run into engine-owned device scratch (kept between calls), then the
+ * pack.  In `wide` the five narrow column pointers must be NULL (CLG_E_INVALID_ARG otherwise); its
+ * w_* arrays (all NULL: the wide rows are sized, not delivered), span_base, the totals and the
+ * error fields are filled exactly as clg_decode_logs_columns_var fills them.  var may be NULL;
+ * otherwise it is the payload column of the same rows.  Ranges, flush rules, decode errors and
+ * statuses are the existing calls': each span's records up to its first error are packed and the
+ * decode's status is returned.  A capacity failure of any of the three outputs fills every size
+ * and writes nothing.  One engine guard covers the whole call. */
+int clg_decode_logs_columns_packed(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                                   clg_columns* wide, clg_payloads* var, clg_packed* out);
+int clg_decode_host_columns_packed(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off,
+                                   const uint64_t* span_len, uint32_t n, clg_columns* wide, clg_payloads* var,
+                                   clg_packed* out);
+/* The same bytes on the CPU (no engine, no GPU; a measure pass, then the write once the sizes are
+ * known to fit): every array is host memory. */
+int clg_pack_columns_host(const clg_columns* in, clg_packed* out);
+/* `count` values of `stream` from value index `first` into out, in the stream's own element type
+ * (u8, i8, i64, i32, i32); only the blocks that range covers are touched.  What is read is
+ * validated, for the bytes may come from another process: width <= 64, count in 1 .. 1024 and
+ * 1024 for every block but the stream's last, pos + size <= n_bits, blk_base consistent with
+ * n_val, and every value inside the stream's type: CLG_E_INVALID_ARG otherwise. */
+int clg_unpack_columns_host(const clg_packed* in, uint32_t stream, uint64_t first, uint64_t count, void* out);
 
 /* ---- replay-prep (DeterminantResponseEvent.merge + LogReplayer decode) ----------------
  * `n` candidate copies of logs (e.g. one per responding GPU / downstream):

@@ -311,6 +311,61 @@ JNIEXPORT jint JNICALL FN(nDecodeLogsColumnsVar)(JNIEnv* env, jclass cls, jlong 
   return s;
 }
 
+/* clg_decode_logs_columns_packed: the five narrow columns bit-packed (desc: 32-byte block
+ * descriptors, bits: the payloads), the wide rows and the payload column as nDecodeLogsColumnsVar
+ * delivers them (var and pos null: no payload column); every buffer null: sizes only.  res is
+ * nDecodeLogsColumnsVar's thirteen entries, then {n_val[0..5), blk_base[0..6), n_bits}. */
+JNIEXPORT jint JNICALL FN(nDecodeLogsColumnsPacked)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray starts,
+                                                    jobject desc, jobject bits, jobject w_idx, jobject w_rc, jobject w_v1,
+                                                    jobject w_var_off, jobject w_var_len, jobject w_sub, jobject w_v0,
+                                                    jobject var, jobject pos, jboolean with_payloads, jlongArray res,
+                                                    jlongArray span_base) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* st = (*env)->GetLongArrayElements(env, starts, NULL);
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  clg_columns c;
+  memset(&c, 0, sizeof c);
+  c.w_idx = (uint32_t*)addr(env, w_idx, 0);
+  c.w_rc = (int32_t*)addr(env, w_rc, 0);
+  c.w_v1 = (int64_t*)addr(env, w_v1, 0);
+  c.w_var_off = (uint32_t*)addr(env, w_var_off, 0);
+  c.w_var_len = (uint32_t*)addr(env, w_var_len, 0);
+  c.w_sub = addr(env, w_sub, 0);
+  c.w_v0 = (int64_t*)addr(env, w_v0, 0);
+  c.span_base = (uint64_t*)base;
+  c.cap_wide = cap(env, w_sub);
+  c.out_kind = CLG_MEM_HOST;
+  clg_payloads p;
+  memset(&p, 0, sizeof p);
+  p.var = addr(env, var, 0);
+  p.pos = (uint64_t*)addr(env, pos, 0);
+  p.cap_var = cap(env, var);
+  p.cap_pos = cap(env, pos) / 8;
+  p.out_kind = CLG_MEM_HOST;
+  clg_packed k;
+  memset(&k, 0, sizeof k);
+  k.desc = (clg_pack_block*)addr(env, desc, 0);
+  k.bits = addr(env, bits, 0);
+  k.cap_desc = cap(env, desc) / sizeof(clg_pack_block);
+  k.cap_bits = cap(env, bits);
+  k.out_kind = CLG_MEM_HOST;
+  int s = clg_decode_logs_columns_packed(ENG(e), (const uint32_t*)lg, (const int64_t*)st, (uint32_t)n, &c,
+                                         with_payloads ? &p : NULL, &k);
+  jlong r[25] = {(jlong)c.n_rec,      (jlong)c.n_class[0], (jlong)c.n_class[1], (jlong)c.n_class[2], (jlong)c.n_class[3],
+                 (jlong)c.n_class[4], c.err_status,        c.err_span,          c.err_off,           c.err_tag,
+                 (jlong)p.n_rows,     (jlong)p.n_var,      (jlong)p.bad_row};
+  for (int i = 0; i < CLG_PACK_STREAMS; ++i) r[13 + i] = (jlong)k.n_val[i];
+  for (int i = 0; i <= CLG_PACK_STREAMS; ++i) r[18 + i] = (jlong)k.blk_base[i];
+  r[24] = (jlong)k.n_bits;
+  (*env)->SetLongArrayRegion(env, res, 0, 25, r);
+  (*env)->ReleaseLongArrayElements(env, span_base, base, 0);
+  (*env)->ReleaseLongArrayElements(env, starts, st, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  return s;
+}
+
 /* The columns of an EngineDecodedColumns with its payload column as clg_columns_in (host memory):
  * the class counts are span_base's last row, n_var is pos[n_wide]. */
 static void columns_in_of(JNIEnv* env, clg_columns_in* in, jobject tag, jobject order, jobject timestamp, jobject rng,

@@ -193,6 +193,30 @@ public final class ClonosEngine implements AutoCloseable {
 		return c;
 	}
 
+	/** decodeLogsColumns with the five narrow columns delivered bit-packed (clg_decode_logs_columns_packed):
+	 *  tags, channels, timestamps, random numbers and buffer sizes cross the link as the bits they hold, in
+	 *  blocks of 1024 values, and EnginePackedColumns.cursor(s) pops them one typed value at a time, as
+	 *  LogReplayerImpl does (LogReplayerImpl.java:61-119), without unpacking whole arrays.  The wide rows and
+	 *  (withPayloads) the payload column come as decodeLogsColumns delivers them.  Two native calls: every
+	 *  size, then the buffers. */
+	public EnginePackedColumns decodeLogsColumnsPacked(int[] logs, long[] startEpochs, boolean withPayloads) {
+		long[] res = new long[25];
+		long[] spanBase = new long[5 * (logs.length + 1)];
+		int st = nDecodeLogsColumnsPacked(handle, logs, startEpochs, null, null, null, null, null, null, null, null,
+			null, null, null, withPayloads, res, spanBase);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st); // engine failure, not a decode error
+		}
+		EnginePackedColumns c = new EnginePackedColumns(res, logs.length, withPayloads);
+		st = nDecodeLogsColumnsPacked(handle, logs, startEpochs, c.desc, c.bits, c.wIdx, c.wRc, c.wV1, c.wVarOff,
+			c.wVarLen, c.wSub, c.wV0, c.var, c.varPos, withPayloads, res, c.spanBase);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st);
+		}
+		c.setResult(res);
+		return c;
+	}
+
 	/**
 	 * The log bytes of typed columns that carry their payload column (clg_encode_columns), encoded on the
 	 * device from the columns as they are: the inverse of decodeLogsColumns(logs, startEpochs, true).  Span
@@ -398,6 +422,14 @@ public final class ClonosEngine implements AutoCloseable {
 											ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarOff, ByteBuffer wVarLen,
 											ByteBuffer wSub, ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos,
 											long[] result, long[] spanBase);
+	/** clg_decode_logs_columns_packed: desc (32-byte block descriptors) and bits, the wide rows, the payload
+	 *  column when withPayloads (all buffers null: sizes only); result = nDecodeLogsColumnsVar's thirteen
+	 *  entries, then {nVal[5], blkBase[6], nBits}. */
+	static native int nDecodeLogsColumnsPacked(long engine, int[] logs, long[] startEpochs, ByteBuffer desc,
+											   ByteBuffer bits, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1,
+											   ByteBuffer wVarOff, ByteBuffer wVarLen, ByteBuffer wSub, ByteBuffer wV0,
+											   ByteBuffer var, ByteBuffer varPos, boolean withPayloads, long[] result,
+											   long[] spanBase);
 	/** clg_encode_columns over host columns; out null: sizes only.  result = {n_bytes, bad_what, bad_index}. */
 	static native int nEncodeColumns(long engine, ByteBuffer tag, ByteBuffer order, ByteBuffer timestamp, ByteBuffer rng,
 									 ByteBuffer bufferBuilt, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1,
