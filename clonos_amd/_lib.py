@@ -72,6 +72,7 @@ EXPORTED = [
     "clg_encode_columns", "clg_encode_columns_host", "clg_append_columns",
     "clg_pack_columns", "clg_decode_logs_columns_packed", "clg_decode_host_columns_packed",
     "clg_pack_columns_host", "clg_unpack_columns_host",
+    "clg_unpack_columns", "clg_unpack_columns_all_host", "clg_encode_columns_packed", "clg_append_columns_packed",
 ]
 
 
@@ -209,6 +210,14 @@ class Packed(C.Structure):  # clg_packed
         ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
         ("n_val", C.c_uint64 * PACK_STREAMS), ("blk_base", C.c_uint64 * (PACK_STREAMS + 1)), ("n_bits", C.c_uint64),
     ]
+
+
+# clg_unpack_bad.what
+UNPACK_BAD_NONE, UNPACK_BAD_LAYOUT, UNPACK_BAD_BLOCK, UNPACK_BAD_VALUE = range(4)
+
+
+class UnpackBad(C.Structure):  # clg_unpack_bad (16 bytes)
+    _fields_ = [("what", C.c_uint32), ("stream", C.c_uint32), ("block", C.c_uint64)]
 
 
 class ColumnsIn(C.Structure):  # clg_columns_in
@@ -443,6 +452,12 @@ def _load() -> C.CDLL:
                                                      C.POINTER(Packed)]),
         "clg_pack_columns_host": (C.c_int, [C.POINTER(Columns), C.POINTER(Packed)]),
         "clg_unpack_columns_host": (C.c_int, [C.POINTER(Packed), C.c_uint32, C.c_uint64, C.c_uint64, P]),
+        "clg_unpack_columns": (C.c_int, [P, C.POINTER(Packed), C.POINTER(Columns), C.POINTER(UnpackBad)]),
+        "clg_unpack_columns_all_host": (C.c_int, [C.POINTER(Packed), C.POINTER(Columns), C.POINTER(UnpackBad)]),
+        "clg_encode_columns_packed": (C.c_int, [P, C.POINTER(Packed), C.POINTER(ColumnsIn), C.POINTER(Encoded),
+                                                C.POINTER(UnpackBad)]),
+        "clg_append_columns_packed": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Packed), C.POINTER(ColumnsIn), P, P,
+                                                C.POINTER(UnpackBad)]),
         "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),

@@ -47,6 +47,7 @@ static_assert(sizeof(clg_columns) == 232, "clg_columns layout");
 static_assert(sizeof(clg_payloads) == 64, "clg_payloads layout");
 static_assert(sizeof(clg_columns_in) == 176, "clg_columns_in layout");
 static_assert(sizeof(clg_packed) == 136, "clg_packed layout");
+static_assert(sizeof(clg_unpack_bad) == 16, "clg_unpack_bad layout");
 static_assert(sizeof(clg_encoded) == 56, "clg_encoded layout");
 
 using namespace clg_internal;  // the host-only types (engine_host.h)
@@ -309,6 +310,10 @@ struct clg_engine {
   // scan groups' sums, host-output staging; the scan's total (pinned: the kernel writes it)
   DevBuf d_packin, d_packcol, d_packdesc, d_packsum, d_packout;
   PinBuf h_packres;
+  // packed columns as input: staged host input, the plain narrow columns the packed encode reads,
+  // host-output staging, and the check's verdict (device words, read back into pinned memory)
+  DevBuf d_unpackin, d_unpackcol, d_unpackout, d_unpackres;
+  PinBuf h_unpackres;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 
@@ -5131,7 +5136,10 @@ int ecol_invalid(clg_encoded* out, uint32_t what, uint64_t index) {
 
 // Count, scan, bytes, scan64 and span bases, then the host's check of their results (pinned) --
 // before any byte is written anywhere.  Fills out's results and, when given, sbb[ns + 1].
-int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPlan* p, uint64_t* sbb) {
+// dev_narrow (the packed calls): device addresses of the five narrow columns, used as they are
+// whatever in_kind says of the other arrays.
+int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPlan* p, uint64_t* sbb,
+               const void* const* dev_narrow = nullptr) {
   clg::ecol_reset_result(out);
   if (!clg::ecol_args_ok(*in)) return fail(CLG_E_INVALID_ARG, "encode columns: null input array or unknown in_kind");
   const uint64_t n = in->n_rec, *nc = in->n_class, nw = nc[clg::kColWide];
@@ -5148,7 +5156,7 @@ int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPl
   size_t off[14], tot = 0;
   for (int i = 0; i < 13; ++i) {
     off[i] = tot;
-    tot += clg_engine::al16(size_t(cnt[i]) * el[i]);
+    if (!(dev_narrow && i < 5)) tot += clg_engine::al16(size_t(cnt[i]) * el[i]);
     p->in_bytes += cnt[i] * el[i];
   }
   off[13] = tot;
@@ -5158,6 +5166,10 @@ int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPl
   uint8_t* din = e->d_ecolin.as<uint8_t>();
   const size_t o_sb = staged ? tot : 0;
   for (int i = 0; i < 13; ++i) {
+    if (dev_narrow && i < 5) {
+      dev[i] = uintptr_t(dev_narrow[i]);
+      continue;
+    }
     if (!src[i] || !cnt[i]) {
       dev[i] = staged || !src[i] ? 0 : uintptr_t(src[i]);
       if (staged && src[i]) dev[i] = uintptr_t(din + off[i]);  // (an empty array: a valid address, never read)
@@ -5245,15 +5257,10 @@ int ecol_write(clg_engine* e, const EcolPlan& p, uint8_t* d_dst) {
   });
 }
 
-}  // namespace
-
-int clg_encode_columns(clg_engine* e, const clg_columns_in* in, clg_encoded* out) {
-  ENGINE_GUARD(e);
-  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
-  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+// clg_encode_columns after its argument checks (the engine guard held); dev_narrow as ecol_sizes'.
+int encode_columns_checked(clg_engine* e, const clg_columns_in* in, clg_encoded* out, const void* const* dev_narrow) {
   EcolPlan p;
-  CHK(ecol_sizes(e, in, out, &p, nullptr));
+  CHK(ecol_sizes(e, in, out, &p, nullptr, dev_narrow));
   if (!out->bytes) return CLG_OK;  // sizes only
   if (out->cap < p.n_bytes) return fail(CLG_E_CAPACITY, "encode columns needs %llu bytes", (unsigned long long)p.n_bytes);
   if (!p.n_bytes) return CLG_OK;
@@ -5266,6 +5273,19 @@ int clg_encode_columns(clg_engine* e, const clg_columns_in* in, clg_encoded* out
   CHK(ecol_write(e, p, dst));
   if (!direct) HIPCHK(hipMemcpyAsync(out->bytes, dst, p.n_bytes, hipMemcpyDeviceToHost, e->stream));
   return e->sync();
+}
+
+int append_columns_checked(clg_engine* e, const uint32_t* log, const int64_t* epoch, const clg_columns_in* in,
+                           uint64_t* span_bytes, int32_t* status, const void* const* dev_narrow);
+
+}  // namespace
+
+int clg_encode_columns(clg_engine* e, const clg_columns_in* in, clg_encoded* out) {
+  ENGINE_GUARD(e);
+  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  return encode_columns_checked(e, in, out, nullptr);
 }
 
 int clg_encode_columns_host(const clg_columns_in* in, clg_encoded* out) {
@@ -5281,12 +5301,21 @@ int clg_append_columns(clg_engine* e, const uint32_t* log, const int64_t* epoch,
   const uint32_t ns = clg::ecol_spans(*in);
   if (n_spans != ns) return fail(CLG_E_INVALID_ARG, "%u logs for %u spans", n_spans, ns);
   for (uint32_t s = 0; s < ns; ++s) status[s] = CLG_OK;
+  return append_columns_checked(e, log, epoch, in, span_bytes, status, nullptr);
+}
+
+namespace {
+// clg_append_columns after its argument checks (the engine guard held, every status CLG_OK);
+// dev_narrow as ecol_sizes'.
+int append_columns_checked(clg_engine* e, const uint32_t* log, const int64_t* epoch, const clg_columns_in* in,
+                           uint64_t* span_bytes, int32_t* status, const void* const* dev_narrow) {
+  const uint32_t ns = clg::ecol_spans(*in);
   CHK(e->flush());  // pending host bytes first: the logs keep their byte order
   clg_encoded enc{};
   enc.out_kind = CLG_MEM_DEVICE;
   EcolPlan p;
   std::vector<uint64_t> sbb(size_t(ns) + 1);
-  CHK(ecol_sizes(e, in, &enc, &p, sbb.data()));
+  CHK(ecol_sizes(e, in, &enc, &p, sbb.data(), dev_narrow));
   for (uint32_t s = 0; s < ns && span_bytes; ++s) span_bytes[s] = sbb[s + 1] - sbb[s];
   CHK(e->d_ecolout.ensure(p.n_bytes + 16));
   CHK(ecol_write(e, p, e->d_ecolout.as<uint8_t>()));
@@ -5336,6 +5365,188 @@ int clg_append_columns(clg_engine* e, const uint32_t* log, const int64_t* epoch,
                                e->side_arg());
   }));
   return e->sync();  // the pinned descriptors are free again
+}
+}  // namespace
+
+// ---- packed typed columns as input (pack.h, unpack.hip) --------------------------------------
+// The way back in: a clg_packed is checked and unpacked on the device.  The check's verdict is
+// read by the host after a sync, before the write pass is queued, so invalid input writes nothing.
+namespace {
+
+// Device addresses of a packed input that passed the host's layout check: device and registered
+// memory in place, host memory (and registered memory not wholly inside one range) staged.
+int unpack_input(clg_engine* e, const clg_packed* in, clg::UnpackIn* uin) {
+  const uint64_t nb = in->blk_base[clg::kPackStreams], nbits = in->n_bits;
+  if (nb >> 31) return fail(CLG_E_INVALID_ARG, "%llu blocks in one call", (unsigned long long)nb);
+  if (in->out_kind != CLG_MEM_HOST && in->out_kind != CLG_MEM_DEVICE && in->out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "the packed input's out_kind %u", in->out_kind);
+  if (in->out_kind != CLG_MEM_HOST && (uintptr_t(in->desc) % 8 || uintptr_t(in->bits) % 16))
+    return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
+  const clg_pack_block* ddesc = in->desc;
+  const uint8_t* dbits = in->bits;
+  bool staged = in->out_kind == CLG_MEM_HOST;
+  if (in->out_kind == CLG_MEM_MAPPED) {
+    ddesc = nb ? reinterpret_cast<const clg_pack_block*>(clg_mapped_device_address(in->desc, nb * sizeof(clg_pack_block))) : nullptr;
+    dbits = nbits ? reinterpret_cast<const uint8_t*>(clg_mapped_device_address(in->bits, nbits)) : nullptr;
+    if ((nb && !ddesc) || (nbits && !dbits)) staged = true;  // (not wholly inside one registered range)
+  }
+  if (staged) {
+    const size_t db = clg_engine::al16(size_t(nb) * sizeof(clg_pack_block));
+    CHK(e->d_unpackin.ensure(db + nbits + 16));
+    if (nb) HIPCHK(hipMemcpyAsync(e->d_unpackin.p, in->desc, nb * sizeof(clg_pack_block), hipMemcpyHostToDevice, e->stream));
+    if (nbits) HIPCHK(hipMemcpyAsync(e->d_unpackin.as<uint8_t>() + db, in->bits, nbits, hipMemcpyHostToDevice, e->stream));
+    ddesc = e->d_unpackin.as<clg_pack_block>();
+    dbits = e->d_unpackin.as<uint8_t>() + db;
+  }
+  uin->desc = ddesc, uin->bits = dbits, uin->n_bits = nbits;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) uin->n[c] = in->n_val[c];
+  for (uint32_t c = 0; c <= clg::kPackStreams; ++c) uin->blk_base[c] = in->blk_base[c];
+  return CLG_OK;
+}
+
+// The check pass and the host's reading of its verdict: CLG_E_INVALID_ARG with `bad` filled, or
+// CLG_OK with the stream idle and nothing written anywhere yet.
+int unpack_check(clg_engine* e, const clg::UnpackIn& uin, clg_unpack_bad* bad) {
+  const uint64_t nb = uin.blk_base[clg::kPackStreams];
+  if (!nb) return CLG_OK;
+  CHK(e->d_unpackres.ensure(sizeof(clg::UnpackVerdict)));
+  CHK(e->h_unpackres.ensure(sizeof(clg::UnpackVerdict)));
+  clg::UnpackVerdict* res = e->h_unpackres.as<clg::UnpackVerdict>();
+  // (bytes: a descriptor a block; payloads are read only where the type does not hold the range)
+  CHK(e->timed("unpack_columns", nb * sizeof(clg_pack_block),
+               [&] { return clg::launch_unpack_check(uin, uint32_t(nb), e->d_unpackres.as<clg::UnpackVerdict>(), e->stream); }));
+  HIPCHK(hipMemcpyAsync(res, e->d_unpackres.p, sizeof(clg::UnpackVerdict), hipMemcpyDeviceToHost, e->stream));
+  CHK(e->sync());
+  const bool block = res->bad_block != 0;
+  if (!block && !res->bad_value) return CLG_OK;
+  const uint64_t blk = ~uint64_t(block ? res->bad_block : res->bad_value);
+  uint32_t c = 0;
+  while (c + 1 < clg::kPackStreams && blk >= uin.blk_base[c + 1]) ++c;
+  clg::pack_bad_set(bad, block ? CLG_UNPACK_BAD_BLOCK : CLG_UNPACK_BAD_VALUE, c, blk - uin.blk_base[c]);
+  return fail(CLG_E_INVALID_ARG, "unpack columns: %s (stream %u, block %llu)",
+              block ? "malformed block descriptor" : "a value outside the stream's type", c,
+              (unsigned long long)(blk - uin.blk_base[c]));
+}
+
+int unpack_write(clg_engine* e, const clg::UnpackIn& uin, const clg::UnpackOut& uout) {
+  const uint64_t nb = uin.blk_base[clg::kPackStreams];
+  uint64_t out_bytes = 0;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) out_bytes += uin.n[c] * clg::pack_elem(c);
+  // (bytes: the descriptors again, the payloads, the plain columns once)
+  return e->timed("unpack_columns", nb * sizeof(clg_pack_block) + uin.n_bits + out_bytes,
+                  [&] { return clg::launch_unpack_write(uin, uout, uint32_t(nb), e->stream); });
+}
+
+// `narrow` unpacked into engine scratch for the encode: the layout and `rest`'s totals on the
+// host, the check, then the write queued on the engine's stream (the encode's kernels follow it
+// there).  col[5]: the plain columns' device addresses.
+int unpack_for_encode(clg_engine* e, const clg_packed* narrow, const clg_columns_in* rest, clg_unpack_bad* bad,
+                      const void* col[clg::kPackStreams]) {
+  clg::pack_bad_reset(bad);
+  if (rest->tag || rest->order || rest->timestamp || rest->rng || rest->buffer_built)
+    return fail(CLG_E_INVALID_ARG, "the narrow column pointers of `rest` must be NULL: those columns are given packed");
+  uint32_t stream;
+  if (!clg::pack_layout_in_ok(*narrow, &stream)) {
+    clg::pack_bad_set(bad, CLG_UNPACK_BAD_LAYOUT, stream, 0);
+    return fail(CLG_E_INVALID_ARG, "unpack columns: blk_base, n_val, the capacities and the pointers disagree (stream %u)", stream);
+  }
+  const uint64_t want[clg::kPackStreams] = {rest->n_rec, rest->n_class[0], rest->n_class[1], rest->n_class[2], rest->n_class[3]};
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c)
+    if (want[c] != narrow->n_val[c]) {
+      clg::pack_bad_set(bad, CLG_UNPACK_BAD_LAYOUT, c, 0);
+      return fail(CLG_E_INVALID_ARG, "stream %u holds %llu values, `rest` says %llu", c, (unsigned long long)narrow->n_val[c],
+                  (unsigned long long)want[c]);
+    }
+  clg::UnpackIn uin{};
+  CHK(unpack_input(e, narrow, &uin));
+  uint64_t at[clg::kPackStreams + 1] = {0};
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) at[c + 1] = clg_engine::al16(at[c] + narrow->n_val[c] * clg::pack_elem(c));
+  CHK(e->d_unpackcol.ensure(at[clg::kPackStreams] + 16));
+  clg::UnpackOut uout{};
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) col[c] = uout.col[c] = e->d_unpackcol.as<uint8_t>() + at[c];
+  CHK(unpack_check(e, uin, bad));
+  return unpack_write(e, uin, uout);
+}
+
+// `rest` with the scratch columns in place of its null narrow pointers (ecol_args_ok wants them).
+clg_columns_in with_narrow(const clg_columns_in& rest, const void* const col[clg::kPackStreams]) {
+  clg_columns_in full = rest;
+  full.tag = static_cast<const uint8_t*>(col[0]), full.order = static_cast<const int8_t*>(col[1]);
+  full.timestamp = static_cast<const int64_t*>(col[2]), full.rng = static_cast<const int32_t*>(col[3]);
+  full.buffer_built = static_cast<const int32_t*>(col[4]);
+  return full;
+}
+
+}  // namespace
+
+int clg_unpack_columns(clg_engine* e, const clg_packed* in, clg_columns* out, clg_unpack_bad* bad) {
+  ENGINE_GUARD(e);
+  bool done;
+  const char* what = "";
+  const int st = clg::pack_unpack_begin(in, out, bad, &done, &what);
+  if (st != CLG_OK) return fail(st, "unpack columns: %s", what);
+  if (done) return CLG_OK;
+  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  const clg::UnpackDst dst = clg::unpack_dst(*out);
+  clg::UnpackOut uout{};
+  bool staged = out->out_kind == CLG_MEM_HOST;
+  for (uint32_t c = 0; c < clg::kPackStreams && !staged; ++c) {
+    if (!in->n_val[c]) continue;
+    if (uintptr_t(dst.col[c]) % clg::pack_elem(c)) return fail(CLG_E_INVALID_ARG, "column %u is not aligned to its element", c);
+    uout.col[c] = dst.col[c];
+    if (out->out_kind == CLG_MEM_MAPPED &&
+        !(uout.col[c] = reinterpret_cast<void*>(clg_mapped_device_address(dst.col[c], in->n_val[c] * clg::pack_elem(c)))))
+      staged = true;  // (not wholly inside one registered range)
+  }
+  clg::UnpackIn uin{};
+  CHK(unpack_input(e, in, &uin));
+  uint64_t at[clg::kPackStreams + 1] = {0};
+  if (staged) {
+    for (uint32_t c = 0; c < clg::kPackStreams; ++c) at[c + 1] = clg_engine::al16(at[c] + in->n_val[c] * clg::pack_elem(c));
+    CHK(e->d_unpackout.ensure(at[clg::kPackStreams] + 16));
+    for (uint32_t c = 0; c < clg::kPackStreams; ++c) uout.col[c] = e->d_unpackout.as<uint8_t>() + at[c];
+  }
+  CHK(unpack_check(e, uin, bad));
+  CHK(unpack_write(e, uin, uout));
+  if (staged)
+    for (uint32_t c = 0; c < clg::kPackStreams; ++c)
+      if (in->n_val[c])
+        HIPCHK(hipMemcpyAsync(dst.col[c], uout.col[c], in->n_val[c] * clg::pack_elem(c), hipMemcpyDeviceToHost, e->stream));
+  return e->sync();
+}
+
+int clg_unpack_columns_all_host(const clg_packed* in, clg_columns* out, clg_unpack_bad* bad) {
+  const char* what = "";
+  const int st = clg::pack_unpack_all_host(in, out, bad, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "unpack columns: %s", what);
+}
+
+int clg_encode_columns_packed(clg_engine* e, const clg_packed* narrow, const clg_columns_in* rest, clg_encoded* out,
+                              clg_unpack_bad* bad) {
+  ENGINE_GUARD(e);
+  if (!narrow || !rest || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
+    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  clg::ecol_reset_result(out);
+  const void* col[clg::kPackStreams];
+  CHK(unpack_for_encode(e, narrow, rest, bad, col));
+  const clg_columns_in full = with_narrow(*rest, col);
+  return encode_columns_checked(e, &full, out, col);
+}
+
+int clg_append_columns_packed(clg_engine* e, const uint32_t* log, const int64_t* epoch, uint32_t n_spans,
+                              const clg_packed* narrow, const clg_columns_in* rest, uint64_t* span_bytes, int32_t* status,
+                              clg_unpack_bad* bad) {
+  ENGINE_GUARD(e);
+  if (!narrow || !rest || !log || !epoch || !status) return fail(CLG_E_INVALID_ARG, "null argument");
+  const uint32_t ns = clg::ecol_spans(*rest);
+  if (n_spans != ns) return fail(CLG_E_INVALID_ARG, "%u logs for %u spans", n_spans, ns);
+  for (uint32_t s = 0; s < ns; ++s) status[s] = CLG_OK;
+  const void* col[clg::kPackStreams];
+  CHK(unpack_for_encode(e, narrow, rest, bad, col));
+  const clg_columns_in full = with_narrow(*rest, col);
+  return append_columns_checked(e, log, epoch, &full, span_bytes, status, col);
 }
 
 namespace {

@@ -722,6 +722,33 @@ int launch_pack_measure_scan(const PackIn& in, uint32_t n_blocks, clg_pack_block
 int launch_pack_write(const PackIn& in, uint32_t n_blocks, const clg_pack_block* d_desc, clg_pack_block* out_desc,
                       uint8_t* bits, uint64_t lim_desc, uint64_t lim_bits, void* stream);
 
+// ---- packed typed columns as input (pack.h, unpack.hip) -----------------------------
+struct UnpackIn {  // device addresses of a clg_packed read as input, after the host's layout check
+  const clg_pack_block* desc;
+  const uint8_t* bits;
+  uint64_t n[5];
+  uint64_t blk_base[6];
+  uint64_t n_bits;
+};
+struct UnpackOut {  // device addresses of the five plain columns, each aligned to its element
+  void* col[5];
+};
+// The check's verdict: ~(the lowest bad block's index in desc) per kind, 0 when none.  Device
+// memory that launch_unpack_check zeroes through the stream before the kernel's vector atomicMax
+// (only a bad block issues one); copy it to the host after the kernel.
+struct UnpackVerdict {
+  unsigned long long bad_block;
+  unsigned long long bad_value;
+};
+// Check (a wave per block, all five streams in one grid): the block check on every descriptor
+// and, where the type does not already hold [ref, ref + 2^width - 1], every value.  No address
+// is formed from a descriptor that failed the block check.
+int launch_unpack_check(const UnpackIn& in, uint32_t n_blocks, UnpackVerdict* d_verdict, void* stream);
+// Write (a workgroup per block), after a clean check: the plain values of every block to
+// out.col[stream] + the block's first index.  A descriptor that fails the block check (the
+// input changed under the call) writes nothing; no store at or past a stream's n.
+int launch_unpack_write(const UnpackIn& in, const UnpackOut& out, uint32_t n_blocks, void* stream);
+
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {
   uint8_t* dst;        // inside one segment

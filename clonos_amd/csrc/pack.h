@@ -1,5 +1,6 @@
 // pack.h -- packed typed columns: the format's one definition, for the pack kernels (pack.hip),
-// the engine and the CPU version.
+// the unpack kernels (unpack.hip: a packed input's rules are at the end), the engine and the CPU
+// version.
 //
 // The five narrow columns of clg_columns (tag, order, timestamp, rng, buffer_built) carry far
 // more bits than their values hold: a tag is one of eight values in a byte, an Order channel a
@@ -275,6 +276,154 @@ inline int pack_unpack_host(const clg_packed* in, uint32_t stream, uint64_t firs
           return *what = "a value outside the stream's type", CLG_E_INVALID_ARG;
     }
   }
+  return CLG_OK;
+}
+
+// ---- a clg_packed read as input: the whole-call unpack (clg_unpack_columns) -------------------
+// The descriptors may come from another process, so nothing is trusted.  Three checks, reported
+// in this order (clg_unpack_bad.what), each with the lowest (stream, block) of its kind:
+//   layout  blk_base[0] == 0, blk_base does not decrease, every stream has
+//           blk_base[c + 1] - blk_base[c] == pack_blocks(n_val[c]); cap_desc >= blk_base[5],
+//           cap_bits >= n_bits, desc and bits non-null where something is read
+//   block   pack_block_ok's conditions plus pos % 16 == 0 (the format's own rule: the kernel then
+//           fetches payloads with aligned 16-byte loads only).  pack_unpack_host above does NOT
+//           test the alignment and keeps accepting what it always accepted.  Blocks need not lie
+//           in payload order and may share or overlap payload bytes: they are only read
+//   value   every unpacked value inside its stream's type (pack_store's rule; timestamps pass)
+
+// pack_blocks without the wrap for n near 2^64.
+CLG_PACK_HD uint64_t pack_blocks_of(uint64_t n) { return n / kPackBlock + (n % kPackBlock ? 1u : 0u); }
+
+// The type's bounds of a stream narrower than 64 bits.
+CLG_PACK_HD int64_t pack_type_lo(uint32_t stream) {
+  return stream == CLG_PACK_TAG ? 0 : stream == CLG_PACK_ORDER ? -128 : int64_t(INT32_MIN);
+}
+CLG_PACK_HD int64_t pack_type_hi(uint32_t stream) {
+  return stream == CLG_PACK_TAG ? 255 : stream == CLG_PACK_ORDER ? 127 : int64_t(INT32_MAX);
+}
+CLG_PACK_HD bool pack_value_ok(uint32_t stream, int64_t v) {
+  return stream == CLG_PACK_TIMESTAMP || (v >= pack_type_lo(stream) && v <= pack_type_hi(stream));
+}
+// Does [ref, ref + 2^width - 1] lie inside the stream's type?  Then no payload bit can give a
+// value outside it and the payload need not be read for the value check.  No overflow: the span
+// is compared with hi - ref only once ref is known to lie inside the (narrow) type.
+CLG_PACK_HD bool pack_range_inside(uint32_t stream, int64_t ref, uint32_t width) {
+  if (stream == CLG_PACK_TIMESTAMP) return true;
+  if (width > 32 || ref < pack_type_lo(stream) || ref > pack_type_hi(stream)) return false;
+  return (uint64_t(1) << width) - 1 <= uint64_t(pack_type_hi(stream) - ref);
+}
+
+// The block check: descriptor d of block b of `stream` (n values), payloads inside [0, n_bits).
+CLG_PACK_HD bool pack_block_in_ok(const clg_pack_block& d, uint32_t stream, uint64_t b, uint64_t n, uint64_t n_bits) {
+  const uint64_t nb = pack_blocks_of(n);
+  if (b >= nb) return false;
+  const uint32_t want = b + 1 < nb ? kPackBlock : uint32_t(n - b * kPackBlock);
+  if (d.width > 64 || d.count < 1 || d.count > kPackBlock || d.count != want) return false;
+  if (d.pos % 16) return false;
+  const uint64_t bytes = pack_payload_bytes(pack_resid(stream, d.count), d.width);
+  return d.pos <= n_bits && bytes <= n_bits - d.pos;
+}
+
+inline void pack_bad_reset(clg_unpack_bad* bad) {
+  if (bad) bad->what = CLG_UNPACK_BAD_NONE, bad->stream = 0, bad->block = ~0ull;
+}
+inline int pack_bad_set(clg_unpack_bad* bad, uint32_t what, uint32_t stream, uint64_t block) {
+  if (bad) bad->what = what, bad->stream = stream, bad->block = block;
+  return CLG_E_INVALID_ARG;
+}
+
+// The layout check.  False: *stream is the lowest stream whose blk_base or n_val disagree, or 0
+// for the capacities and the pointers.
+inline bool pack_layout_in_ok(const clg_packed& p, uint32_t* stream) {
+  *stream = 0;
+  if (p.blk_base[0] != 0) return false;
+  for (uint32_t c = 0; c < kPackStreams; ++c)
+    if (p.blk_base[c + 1] < p.blk_base[c] || p.blk_base[c + 1] - p.blk_base[c] != pack_blocks_of(p.n_val[c]))
+      return *stream = c, false;
+  if (p.cap_desc < p.blk_base[kPackStreams] || p.cap_bits < p.n_bits) return false;
+  if ((p.blk_base[kPackStreams] && !p.desc) || (p.n_bits && !p.bits)) return false;
+  return true;
+}
+
+// The five output arrays and their capacities, from a clg_columns (a null column holds nothing).
+struct UnpackDst {
+  void* col[kPackStreams];
+  uint64_t cap[kPackStreams];
+};
+inline UnpackDst unpack_dst(const clg_columns& c) {
+  return UnpackDst{{c.tag, c.order, c.timestamp, c.rng, c.buffer_built},
+                   {c.tag ? c.cap_tag : 0, c.order ? c.cap_order : 0, c.timestamp ? c.cap_timestamp : 0,
+                    c.rng ? c.cap_rng : 0, c.buffer_built ? c.cap_buffer_built : 0}};
+}
+
+// What every whole-call unpack does before it reads a descriptor, in this order: the layout check
+// (CLG_E_INVALID_ARG, bad filled), the sizes into out (n_rec, n_class[0..3]; nothing else of out
+// is touched), the sizes-only call (all five pointers null: CLG_OK, *done), the capacities
+// (CLG_E_CAPACITY).  CLG_OK without *done: go on to the block and value checks.
+inline int pack_unpack_begin(const clg_packed* in, clg_columns* out, clg_unpack_bad* bad, bool* done, const char** what) {
+  *done = true;
+  *what = "";
+  pack_bad_reset(bad);
+  if (!in || !out) return *what = "null argument", CLG_E_INVALID_ARG;
+  uint32_t stream;
+  if (!pack_layout_in_ok(*in, &stream))
+    return *what = "blk_base, n_val, the capacities and the pointers disagree", pack_bad_set(bad, CLG_UNPACK_BAD_LAYOUT, stream, 0);
+  out->n_rec = in->n_val[0];
+  for (uint32_t c = 1; c < kPackStreams; ++c) out->n_class[c - 1] = in->n_val[c];
+  const UnpackDst dst = unpack_dst(*out);
+  bool any = false;
+  for (uint32_t c = 0; c < kPackStreams; ++c) any = any || dst.col[c];
+  if (!any) return CLG_OK;  // sizes only
+  for (uint32_t c = 0; c < kPackStreams; ++c)
+    if (dst.cap[c] < in->n_val[c]) return *what = "an output column is too small", CLG_E_CAPACITY;
+  *done = false;
+  return CLG_OK;
+}
+
+// Every value of a well-formed block inside its stream's type?
+inline bool pack_block_values_ok(uint32_t stream, const clg_pack_block& d, const uint8_t* bits) {
+  if (pack_range_inside(stream, d.ref, d.width)) return true;
+  for (uint32_t i = 0; i < d.count; ++i)
+    if (!pack_value_ok(stream, int64_t(pack_get(bits + d.pos, d.width, i) + uint64_t(d.ref)))) return false;
+  return true;
+}
+
+// The whole call on the CPU (clg_unpack_columns_all_host): the reference the device unpack is held
+// to.  A checking pass over every block, then the writes: invalid input writes nothing.
+inline int pack_unpack_all_host(const clg_packed* in, clg_columns* out, clg_unpack_bad* bad, const char** what = nullptr) {
+  const char* dummy;
+  if (!what) what = &dummy;
+  bool done;
+  const int st = pack_unpack_begin(in, out, bad, &done, what);
+  if (st != CLG_OK || done) return st;
+  bool bad_value = false;
+  uint32_t v_stream = 0;
+  uint64_t v_block = 0;
+  for (uint32_t c = 0; c < kPackStreams; ++c)
+    for (uint64_t b = 0; b < pack_blocks_of(in->n_val[c]); ++b) {
+      const clg_pack_block& d = in->desc[in->blk_base[c] + b];
+      if (!pack_block_in_ok(d, c, b, in->n_val[c], in->n_bits))
+        return *what = "malformed block descriptor", pack_bad_set(bad, CLG_UNPACK_BAD_BLOCK, c, b);
+      if (!bad_value && !pack_block_values_ok(c, d, in->bits)) bad_value = true, v_stream = c, v_block = b;
+    }
+  if (bad_value) return *what = "a value outside the stream's type", pack_bad_set(bad, CLG_UNPACK_BAD_VALUE, v_stream, v_block);
+  const UnpackDst dst = unpack_dst(*out);
+  for (uint32_t c = 0; c < kPackStreams; ++c)
+    for (uint64_t b = 0; b < pack_blocks_of(in->n_val[c]); ++b) {
+      const clg_pack_block& d = in->desc[in->blk_base[c] + b];
+      const uint8_t* payload = in->bits + d.pos;
+      const uint64_t i0 = b * kPackBlock;
+      if (pack_is_delta(c)) {
+        uint64_t x = uint64_t(d.first);
+        for (uint32_t i = 0; i < d.count; ++i) {
+          if (i) x += pack_get(payload, d.width, i - 1) + uint64_t(d.ref);
+          pack_store(c, dst.col[c], i0 + i, int64_t(x));
+        }
+      } else {
+        for (uint32_t i = 0; i < d.count; ++i)
+          pack_store(c, dst.col[c], i0 + i, int64_t(pack_get(payload, d.width, i) + uint64_t(d.ref)));
+      }
+    }
   return CLG_OK;
 }
 

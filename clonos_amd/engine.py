@@ -387,14 +387,16 @@ _ECOL_FIELDS = (("tag", np.uint8), ("order", np.int8), ("timestamp", np.int64), 
                 ("w_sub", np.uint8), ("w_v0", np.int64))
 
 
-def _columns_in(cols: "DecodedColumns", check_idx: bool = True) -> Tuple[_lib.ColumnsIn, list]:
+def _columns_in(cols: Union["DecodedColumns", "PackedColumns"], check_idx: bool = True) -> Tuple[_lib.ColumnsIn, list]:
     """clg_columns_in over cols' host arrays and its payload column; the second value keeps the
-    arrays alive.  Columns without a payload column raise ValueError."""
+    arrays alive.  For a PackedColumns the five narrow pointers stay null (they are given packed)
+    and the totals are n_val's.  Columns without a payload column raise ValueError."""
     if cols.var is None or cols.var_pos is None:
         raise ValueError("the columns carry no payload column (payloads=True)")
+    packed = isinstance(cols, PackedColumns)
     cin = _lib.ColumnsIn()
     keep = []
-    for name, dt in _ECOL_FIELDS:
+    for name, dt in _ECOL_FIELDS[5 if packed else 0:]:
         a = np.ascontiguousarray(getattr(cols, name), dt)
         keep.append(a)
         setattr(cin, name, _np_ptr(a) or None)
@@ -406,8 +408,9 @@ def _columns_in(cols: "DecodedColumns", check_idx: bool = True) -> Tuple[_lib.Co
     keep += [pos, var]
     cin.pos, cin.var, cin.n_var = _np_ptr(pos) or None, _np_ptr(var) or None, var.size
     cin.n_rec = cols.n_rec
-    for c, name in enumerate(("order", "timestamp", "rng", "buffer_built", "w_v0")):
-        cin.n_class[c] = len(getattr(cols, name))
+    for c, name in enumerate(("order", "timestamp", "rng", "buffer_built")):
+        cin.n_class[c] = cols.n_val[c + 1] if packed else len(getattr(cols, name))
+    cin.n_class[4] = len(cols.w_v0)
     if cols.n_spans:
         sb = np.ascontiguousarray(cols.span_base, np.uint64).reshape(-1)
         keep.append(sb)
@@ -599,6 +602,46 @@ def pack_columns_host(cols: "DecodedColumns") -> PackedColumns:
 def unpack_columns_host(packed: PackedColumns, stream: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
     """clg_unpack_columns_host (PackedColumns.unpack_stream)."""
     return packed.unpack_stream(stream, first, count)
+
+
+def _unpack_error(st: int, bad: _lib.UnpackBad, enc: Optional[_lib.Encoded] = None) -> ClonosError:
+    err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
+    err.bad_what, err.bad_stream, err.bad_block = int(bad.what), int(bad.stream), int(bad.block)
+    if enc is not None:
+        err.n_bytes, err.enc_bad_what, err.bad_index = int(enc.n_bytes), int(enc.bad_what), int(enc.bad_index)
+    return err
+
+
+def _unpack_out(n_val: Sequence[int]) -> Tuple[_lib.Columns, list]:
+    """clg_columns over fresh host arrays of exactly the streams' lengths."""
+    c = _lib.Columns()
+    arrs = []
+    for (name, dt), n in zip(PACK_STREAM_FIELDS, n_val):
+        a = np.empty(int(n), dt)
+        arrs.append(a)
+        setattr(c, name, _np_ptr(a) or None)
+        setattr(c, _COL_CAP[name], a.size)
+    c.out_kind = _lib.CLG_MEM_HOST
+    return c, arrs
+
+
+def _unpacked(packed: "PackedColumns", arrs: list) -> "DecodedColumns":
+    cols = DecodedColumns(*arrs, *[getattr(packed, k) for k in _COL_WIDE], packed.span_base, packed.spans_bytes)
+    cols.var, cols.var_pos, cols.error = packed.var, packed.var_pos, packed.error
+    return cols
+
+
+def unpack_packed_host(packed: "PackedColumns") -> "DecodedColumns":
+    """clg_unpack_columns_all_host: the whole unpack on the CPU under the device unpack's rules (no
+    engine, no GPU) -- what Engine.unpack_columns computes.  Invalid input raises ClonosError with
+    bad_what, bad_stream and bad_block."""
+    p = packed._struct()
+    c, arrs = _unpack_out(packed.n_val)
+    bad = _lib.UnpackBad()
+    st = lib.clg_unpack_columns_all_host(C.byref(p), C.byref(c), C.byref(bad))
+    if st != _lib.CLG_OK:
+        raise _unpack_error(st, bad)
+    return _unpacked(packed, arrs)
 
 
 # clg_digest rows: two spans are equal only when both fields are equal
@@ -1166,6 +1209,24 @@ class Engine:
         and bits null: sizes only).  Returns the status; the results are in out."""
         return lib.clg_pack_columns(self._h, C.byref(cin), C.byref(out))
 
+    def unpack_columns(self, packed: PackedColumns) -> DecodedColumns:
+        """clg_unpack_columns: the five narrow columns of host packed columns unpacked on the device
+        (staged in, checked, unpacked, read back); the wide rows, span_base, var, var_pos and error
+        are passed through as PackedColumns.unpack() does.  Invalid input raises ClonosError with
+        bad_what, bad_stream and bad_block."""
+        p = packed._struct()
+        c, arrs = _unpack_out(packed.n_val)
+        bad = _lib.UnpackBad()
+        st = lib.clg_unpack_columns(self._h, C.byref(p), C.byref(c), C.byref(bad))
+        if st != _lib.CLG_OK:
+            raise _unpack_error(st, bad)
+        return _unpacked(packed, arrs)
+
+    def unpack_columns_raw(self, pin: _lib.Packed, cols: _lib.Columns, bad: _lib.UnpackBad) -> int:
+        """clg_unpack_columns over a clg_packed and a clg_columns the caller set up (any kinds; the
+        five narrow pointers null: sizes only).  Returns the status; the results are in cols and bad."""
+        return lib.clg_unpack_columns(self._h, C.byref(pin), C.byref(cols), C.byref(bad))
+
     def _decode_packed(self, call, total: int, n: int, spans_bytes, partial: bool, payloads: bool) -> PackedColumns:
         """call(wide, var or None, packed) -> status, over bounds no batch of `total` encoded bytes
         can exceed: a record is at least 2 bytes and its value at most its encoded length less the
@@ -1372,7 +1433,18 @@ class Engine:
     def encode_columns(self, cols: "DecodedColumns", per_span: bool = False):
         """clg_encode_columns: re-encode columns that carry their payload column, on the GPU -- the
         batch's bytes, without the log crossing the link.  The columns go up as they are (no SoA
-        rows are rebuilt).  per_span=True: one bytes per span instead of the whole stream."""
+        rows are rebuilt).  per_span=True: one bytes per span instead of the whole stream.  A
+        PackedColumns goes up packed and is unpacked on the device (clg_encode_columns_packed); a bad
+        packed input raises ClonosError with bad_what, bad_stream and bad_block."""
+        if isinstance(cols, PackedColumns):
+            pk, (rest, keep), bad = cols._struct(), _columns_in(cols), _lib.UnpackBad()
+
+            def call(enc):
+                st = lib.clg_encode_columns_packed(self._h, C.byref(pk), C.byref(rest), C.byref(enc), C.byref(bad))
+                if st != _lib.CLG_OK and bad.what != _lib.UNPACK_BAD_NONE:
+                    raise _unpack_error(st, bad, enc)
+                return st
+            return _encode_twice(call, cols.n_spans, per_span)
         cin, keep = _columns_in(cols)
         return _encode_twice(lambda enc: lib.clg_encode_columns(self._h, C.byref(cin), C.byref(enc)), cols.n_spans,
                              per_span)
@@ -1390,12 +1462,19 @@ class Engine:
         raises for a span and (byte counts, statuses) is returned."""
         h = np.array([getattr(l, "handle", l) for l in logs], np.uint32)
         ep = np.ascontiguousarray(epochs, np.int64)
-        cin, keep = _columns_in(cols)
         ns = max(cols.n_spans, 1)
         if len(h) != ns or len(ep) != ns:
             raise ValueError(f"{len(h)} logs and {len(ep)} epochs for {ns} spans")
         nb, st = np.zeros(ns, np.uint64), np.zeros(ns, np.int32)
-        check(lib.clg_append_columns(self._h, _np_ptr(h), _np_ptr(ep), ns, C.byref(cin), _np_ptr(nb), _np_ptr(st)))
+        if isinstance(cols, PackedColumns):  # goes up packed, unpacked on the device
+            pk, (rest, keep), bad = cols._struct(), _columns_in(cols), _lib.UnpackBad()
+            rc = lib.clg_append_columns_packed(self._h, _np_ptr(h), _np_ptr(ep), ns, C.byref(pk), C.byref(rest), _np_ptr(nb),
+                                               _np_ptr(st), C.byref(bad))
+            if rc != _lib.CLG_OK:
+                raise _unpack_error(rc, bad)
+        else:
+            cin, keep = _columns_in(cols)
+            check(lib.clg_append_columns(self._h, _np_ptr(h), _np_ptr(ep), ns, C.byref(cin), _np_ptr(nb), _np_ptr(st)))
         if statuses:
             return nb, st
         for s in range(ns):

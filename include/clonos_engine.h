@@ -525,6 +525,42 @@ int clg_pack_columns_host(const clg_columns* in, clg_packed* out);
  * n_val, and every value inside the stream's type: CLG_E_INVALID_ARG otherwise. */
 int clg_unpack_columns_host(const clg_packed* in, uint32_t stream, uint64_t first, uint64_t count, void* out);
 
+/* ---- packed typed columns as input -----------------------------------------
+ * A clg_packed read as input: desc, bits, n_val, blk_base and n_bits as a pack filled them, with
+ * cap_desc >= blk_base[5] and cap_bits >= n_bits; out_kind names where desc and bits live.  The
+ * bytes may come from another process, so nothing is trusted (clonos_amd/csrc/pack.h holds the
+ * rules once, for the CPU version and the kernels).  What is wrong is reported in clg_unpack_bad:
+ * when several kinds are present the first in the enum's order is reported, with the lowest
+ * (stream, block) of that kind; block counts within its stream.
+ *   LAYOUT  blk_base[0] != 0, blk_base decreases, blk_base[c + 1] - blk_base[c] is not
+ *           ceil(n_val[c] / 1024) (stream: the lowest such c), a capacity below its total or a
+ *           null array that would be read (stream 0); block is 0
+ *   BLOCK   width > 64, count not 1024 (the stream's last block: what is left), pos + size >
+ *           n_bits, or pos not a multiple of 16 (clg_unpack_columns_host does not test that last
+ *           rule and is unchanged).  Blocks may lie in any payload order and may share payload bytes
+ *   VALUE   an unpacked value outside its stream's type (timestamps always pass)
+ * With what == NONE, stream is 0 and block ~0. */
+enum { CLG_UNPACK_BAD_NONE = 0, CLG_UNPACK_BAD_LAYOUT = 1, CLG_UNPACK_BAD_BLOCK = 2, CLG_UNPACK_BAD_VALUE = 3 };
+typedef struct clg_unpack_bad { uint32_t what; uint32_t stream; uint64_t block; } clg_unpack_bad;  /* 16 bytes */
+
+/* The whole unpack on the device: out->tag / order / timestamp / rng / buffer_built are written
+ * under their cap_* and out->out_kind, n_rec and n_class[0 .. 3] are filled from n_val; w_*,
+ * span_base, n_class[4] and the err_* fields are left alone.  The order of the checks: the layout
+ * (CLG_E_INVALID_ARG), then the sizes are filled; all five pointers NULL: sizes only (CLG_OK, no
+ * descriptor is read); a capacity below its total (a NULL column holds nothing): CLG_E_CAPACITY
+ * with the sizes filled and nothing written; then every block and value: CLG_E_INVALID_ARG with
+ * `bad` (may be NULL) filled and NOTHING written to the caller's arrays, whatever their kind.
+ * Input: CLG_MEM_DEVICE and CLG_MEM_MAPPED are read in place (bits 16-byte aligned, desc 8-byte
+ * aligned, else CLG_E_INVALID_ARG); CLG_MEM_HOST is staged with one copy each.  Output: device
+ * and registered arrays, aligned to their element (else CLG_E_INVALID_ARG), are written by the
+ * kernel; host arrays through engine scratch and one copy each.  No byte outside [0, n_val[c]) of
+ * a column is written.  Synchronous; takes the engine guard; the kernels' time is the stat
+ * "unpack_columns". */
+int clg_unpack_columns(clg_engine* e, const clg_packed* in, clg_columns* out, clg_unpack_bad* bad);
+/* The same call on the CPU (no engine, no GPU): every array is host memory and the kinds are not
+ * read.  Results, statuses and `bad` are clg_unpack_columns'. */
+int clg_unpack_columns_all_host(const clg_packed* in, clg_columns* out, clg_unpack_bad* bad);
+
 /* ---- replay-prep (DeterminantResponseEvent.merge + LogReplayer decode) ----------------
  * `n` candidate copies of logs (e.g. one per responding GPU / downstream):
  * copy i is (key[i], bytes[off[i], off[i]+len[i])).  For every distinct key the LONGEST
@@ -677,6 +713,22 @@ int clg_encode_columns_host(const clg_columns_in* in, clg_encoded* out);
  * are clg_encode_columns'; the call's error text names them). */
 int clg_append_columns(clg_engine* e, const uint32_t* log, const int64_t* epoch, uint32_t n_spans,
                        const clg_columns_in* in, uint64_t* span_bytes, int32_t* status);
+/* clg_encode_columns / clg_append_columns with the five narrow columns given packed: `narrow` is
+ * unpacked into engine-owned device scratch (kept between calls) and the existing encode runs on
+ * it, so no plain narrow column crosses the link.  `rest` carries everything else: its five narrow
+ * pointers must be NULL (CLG_E_INVALID_ARG), its n_rec and n_class[0 .. 3] must equal
+ * narrow->n_val[0 .. 4] (CLG_UNPACK_BAD_LAYOUT, stream: the lowest that differs); rest->in_kind
+ * holds for the wide rows, pos and var, independently of narrow->out_kind.  A bad packed input
+ * fails the whole call with CLG_E_INVALID_ARG and `bad` filled (out->bad_what stays 0; every
+ * status[s] stays CLG_OK) before anything is written or any log changes.  After a clean unpack
+ * the results, errors, per-span statuses and span_bytes are clg_encode_columns' /
+ * clg_append_columns' exactly (a tag above 7 is CLG_ENC_BAD_TAG).  One engine guard covers the
+ * whole call. */
+int clg_encode_columns_packed(clg_engine* e, const clg_packed* narrow, const clg_columns_in* rest,
+                              clg_encoded* out, clg_unpack_bad* bad);
+int clg_append_columns_packed(clg_engine* e, const uint32_t* log, const int64_t* epoch, uint32_t n_spans,
+                              const clg_packed* narrow, const clg_columns_in* rest,
+                              uint64_t* span_bytes, int32_t* status, clg_unpack_bad* bad);
 
 /* ---- DeterminantResponseEvent (DeterminantResponseEvent.java:36-148) ---------------------
  * The event's map CausalLogID -> log bytes is held as an entry array in the iteration

@@ -451,6 +451,54 @@ JNIEXPORT jint JNICALL FN(nAppendColumns)(JNIEnv* env, jclass cls, jlong e, jint
   return s;
 }
 
+/* clg_append_columns_packed: nAppendColumns with the five narrow columns given packed (desc, bits:
+ * direct buffers; n_val: 5 longs; blk_base: 6 longs) and unpacked on the device.  bad = {bad_what,
+ * bad_stream, bad_block} of clg_unpack_bad. */
+JNIEXPORT jint JNICALL FN(nAppendColumnsPacked)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray epochs,
+                                                jobject desc, jobject bits, jlongArray n_val, jlongArray blk_base,
+                                                jlong n_bits, jobject w_idx, jobject w_rc, jobject w_v1,
+                                                jobject w_var_len, jobject w_sub, jobject w_v0, jobject var, jobject pos,
+                                                jlongArray span_base, jlongArray span_bytes, jintArray status,
+                                                jlongArray bad) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  const jsize n_spans = (*env)->GetArrayLength(env, span_base) / CLG_COL_CLASSES - 1;
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* ep = (*env)->GetLongArrayElements(env, epochs, NULL);
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  jlong* nb = (*env)->GetLongArrayElements(env, span_bytes, NULL);
+  jint* st = (*env)->GetIntArrayElements(env, status, NULL);
+  clg_packed k;
+  memset(&k, 0, sizeof k);
+  k.desc = (clg_pack_block*)addr(env, desc, 0);
+  k.bits = addr(env, bits, 0);
+  k.cap_desc = cap(env, desc) / sizeof(clg_pack_block);
+  k.cap_bits = cap(env, bits);
+  k.out_kind = CLG_MEM_HOST;
+  jlong* nv = (*env)->GetLongArrayElements(env, n_val, NULL);
+  jlong* bb = (*env)->GetLongArrayElements(env, blk_base, NULL);
+  for (int i = 0; i < CLG_PACK_STREAMS; ++i) k.n_val[i] = (uint64_t)nv[i];
+  for (int i = 0; i <= CLG_PACK_STREAMS; ++i) k.blk_base[i] = (uint64_t)bb[i];
+  k.n_bits = (uint64_t)n_bits;
+  clg_columns_in in;
+  columns_in_of(env, &in, NULL, NULL, NULL, NULL, NULL, w_idx, w_rc, w_v1, w_var_len, w_sub, w_v0, var, pos, base, n_spans,
+                nv[0]);
+  clg_unpack_bad ub;
+  memset(&ub, 0, sizeof ub);
+  int s = clg_append_columns_packed(ENG(e), (const uint32_t*)lg, (const int64_t*)ep, (uint32_t)n, &k, &in, (uint64_t*)nb,
+                                    (int32_t*)st, &ub);
+  jlong r[3] = {(jlong)ub.what, (jlong)ub.stream, (jlong)ub.block};
+  (*env)->SetLongArrayRegion(env, bad, 0, 3, r);
+  (*env)->ReleaseLongArrayElements(env, blk_base, bb, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, n_val, nv, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, status, st, 0);
+  (*env)->ReleaseLongArrayElements(env, span_bytes, nb, 0);
+  (*env)->ReleaseLongArrayElements(env, span_base, base, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, epochs, ep, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  return s;
+}
+
 /* clg_decode_logs_async: the decode is queued; ctx[0] receives a handle that nDecodeWait
  * completes and frees (the output ByteBuffers must stay reachable until then). */
 typedef struct {

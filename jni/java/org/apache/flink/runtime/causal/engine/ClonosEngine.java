@@ -270,6 +270,45 @@ public final class ClonosEngine implements AutoCloseable {
 	}
 
 	/**
+	 * appendColumns for packed columns (clg_append_columns_packed): desc and bits go up as they were
+	 * delivered -- the narrow form is what crosses the link -- and are checked and unpacked on the device
+	 * before the existing encode and scatter run.  The packed bytes are not trusted: a malformed layout,
+	 * block or value throws before any log changes, its message carrying {bad_what, bad_stream,
+	 * bad_block}, which are also left in lastUnpackBad().  Returns per span the bytes appended or the
+	 * span's (negative) status, as appendColumns does.
+	 */
+	public long[] appendColumnsPacked(int[] logs, long[] epochs, EnginePackedColumns cols) {
+		if (!cols.hasPayloads()) {
+			throw new IllegalStateException("decoded without payloads");
+		}
+		final long[] spanBytes = new long[logs.length];
+		final int[] status = new int[logs.length];
+		final long[] bad = new long[3];
+		final int st = nAppendColumnsPacked(handle, logs, epochs, cols.desc, cols.bits, cols.nVal, cols.blkBase, cols.nBits,
+			cols.wIdx, cols.wRc, cols.wV1, cols.wVarLen, cols.wSub, cols.wV0, cols.var, cols.varPos, cols.spanBase,
+			spanBytes, status, bad);
+		lastUnpackBad = bad;
+		if (st != CLG_OK && bad[0] != 0) {
+			throw new IllegalArgumentException("packed columns: bad_what " + bad[0] + ", bad_stream " + bad[1]
+				+ ", bad_block " + bad[2] + ": " + nLastError());
+		}
+		check(st);
+		for (int s = 0; s < logs.length; s++) {
+			if (status[s] != CLG_OK) {
+				spanBytes[s] = status[s];
+			}
+		}
+		return spanBytes;
+	}
+
+	private long[] lastUnpackBad = new long[3];
+
+	/** {bad_what, bad_stream, bad_block} of the last appendColumnsPacked call (all 0, 0, ~0 or zero when clean). */
+	public long[] lastUnpackBad() {
+		return lastUnpackBad.clone();
+	}
+
+	/**
 	 * Replay preparation for one failed task with the main log delivered as typed columns and the payload
 	 * column (clg_replay_prepare_columns), in ONE native call: the buffers are sized by bounds no main log
 	 * of mainLen bytes can exceed (the shortest record of each class: ORDER 2 B, TIMESTAMP 9, RNG and
@@ -436,6 +475,11 @@ public final class ClonosEngine implements AutoCloseable {
 									 ByteBuffer wVarLen, ByteBuffer wSub, ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos,
 									 long[] spanBase, long nRec, ByteBuffer out, long[] spanByteBase, long[] result);
 	/** clg_append_columns: spanBytes and status hold an entry per span. */
+	static native int nAppendColumnsPacked(long engine, int[] logs, long[] epochs, ByteBuffer desc, ByteBuffer bits,
+		long[] nVal, long[] blkBase, long nBits, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarLen,
+		ByteBuffer wSub, ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos, long[] spanBase, long[] spanBytes,
+		int[] status, long[] bad);
+
 	static native int nAppendColumns(long engine, int[] logs, long[] epochs, ByteBuffer tag, ByteBuffer order,
 									 ByteBuffer timestamp, ByteBuffer rng, ByteBuffer bufferBuilt, ByteBuffer wIdx,
 									 ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarLen, ByteBuffer wSub, ByteBuffer wV0,

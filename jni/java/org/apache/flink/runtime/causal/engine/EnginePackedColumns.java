@@ -43,6 +43,7 @@ public final class EnginePackedColumns {
 	final long[] blkBase = new long[STREAMS + 1];
 	private final int nSpans;
 	private long nRec;
+	long nBits;
 	private int errStatus, errSpan, errTag;
 	private long errOff;
 
@@ -79,6 +80,7 @@ public final class EnginePackedColumns {
 		this.errTag = (int) res[9];
 		System.arraycopy(res, 13, nVal, 0, STREAMS);
 		System.arraycopy(res, 18, blkBase, 0, STREAMS + 1);
+		this.nBits = res[24];
 	}
 
 	public int spans() {
