@@ -73,21 +73,43 @@ CLG_COL_HD int32_t col_i32(int64_t v0) { return int32_t(uint32_t(uint64_t(v0)));
 // A column pointer's usable capacity: a null pointer holds nothing.
 inline uint64_t col_cap(const void* p, uint64_t cap) { return p ? cap : 0; }
 
+// The twelve arrays of a clg_columns in the struct's own order, which col_pack_offsets below and
+// the small kernel's ColSmallOut share (col_ptr gives the pointer): the element width, the class whose total is its length
+// (kColClasses: n_rec), and the name error texts give it.  The first five are the narrow columns;
+// the seven wide arrays share one capacity and one name.
+struct ColArray {
+  uint32_t width, cls;
+  const char* name;
+};
+constexpr int kColArrays = 12, kColNarrowArrays = 5;
+constexpr ColArray kColArray[kColArrays] = {
+    {1, kColClasses, "tag"}, {1, kColOrder, "order"}, {8, kColTimestamp, "timestamp"}, {4, kColRng, "rng"},
+    {4, kColBufferBuilt, "buffer_built"}, {4, kColWide, "wide"}, {4, kColWide, "wide"}, {8, kColWide, "wide"},
+    {4, kColWide, "wide"}, {4, kColWide, "wide"}, {1, kColWide, "wide"}, {8, kColWide, "wide"}};
+inline void* col_ptr(const clg_columns& c, int i) {
+  void* const p[kColArrays] = {c.tag,   c.order, c.timestamp, c.rng,       c.buffer_built, c.w_idx,
+                               c.w_rc,  c.w_v1,  c.w_var_off, c.w_var_len, c.w_sub,        c.w_v0};
+  return p[i];
+}
+// Array i's usable capacity, and its length in a batch of n records with the class totals tot.
+inline uint64_t col_array_cap(const clg_columns& c, int i) {
+  const uint64_t cap[6] = {c.cap_tag, c.cap_order, c.cap_timestamp, c.cap_rng, c.cap_buffer_built, c.cap_wide};
+  return col_cap(col_ptr(c, i), cap[i < kColNarrowArrays ? i : kColNarrowArrays]);
+}
+inline uint64_t col_array_len(int i, uint64_t n, const uint64_t tot[kColClasses]) {
+  return kColArray[i].cls == kColClasses ? n : tot[kColArray[i].cls];
+}
+
 inline bool col_sizes_only(const clg_columns& c) {
-  return !c.tag && !c.order && !c.timestamp && !c.rng && !c.buffer_built && !c.w_idx && !c.w_rc && !c.w_v1 &&
-         !c.w_var_off && !c.w_var_len && !c.w_sub && !c.w_v0;
+  for (int i = 0; i < kColArrays; ++i)
+    if (col_ptr(c, i)) return false;
+  return true;
 }
 
 // The first column whose capacity is below its total (its name), or null.
 inline const char* col_short_column(const clg_columns& c, uint64_t n, const uint64_t tot[kColClasses]) {
-  if (col_cap(c.tag, c.cap_tag) < n) return "tag";
-  if (col_cap(c.order, c.cap_order) < tot[kColOrder]) return "order";
-  if (col_cap(c.timestamp, c.cap_timestamp) < tot[kColTimestamp]) return "timestamp";
-  if (col_cap(c.rng, c.cap_rng) < tot[kColRng]) return "rng";
-  if (col_cap(c.buffer_built, c.cap_buffer_built) < tot[kColBufferBuilt]) return "buffer_built";
-  const void* w[7] = {c.w_idx, c.w_rc, c.w_v1, c.w_var_off, c.w_var_len, c.w_sub, c.w_v0};
-  for (const void* p : w)
-    if (col_cap(p, c.cap_wide) < tot[kColWide]) return "wide";
+  for (int i = 0; i < kColArrays; ++i)
+    if (col_array_cap(c, i) < col_array_len(i, n, tot)) return kColArray[i].name;
   return nullptr;
 }
 

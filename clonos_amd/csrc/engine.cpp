@@ -39,6 +39,7 @@
 #include "kernels.h"
 #include "pack.h"
 #include "payload.h"
+#include "placement.h"
 #include "slice_order.h"
 
 static_assert(sizeof(clg_delta_req) == 32, "clg_delta_req layout");
@@ -165,6 +166,15 @@ uintptr_t clg_mapped_device_address(const void* h, uint64_t n) {
     if (uintptr_t(h) >= m.host && uintptr_t(h) < m.host + m.bytes && n <= m.host + m.bytes - uintptr_t(h))
       return m.dev + (uintptr_t(h) - m.host);
   return 0;
+}
+// How many of the n bytes at h one copy may take: up to the first edge of a registered range
+// inside them (the HIP runtime refuses a copy that crosses the end of registered memory).
+uint64_t clg_mapped_piece(const void* h, uint64_t n) {
+  std::lock_guard<std::mutex> g(g_map_mu);
+  for (const Mapped& m : g_mapped)
+    for (const uintptr_t edge : {m.host, m.host + uintptr_t(m.bytes)})
+      if (edge > uintptr_t(h) && edge - uintptr_t(h) < n) n = edge - uintptr_t(h);
+  return n;
 }
 }  // namespace
 
@@ -3881,16 +3891,76 @@ int clg_decode_wait(clg_engine* e) {
 // typed value at a time and never for a record's offset: the columns are what it consumes.
 namespace {
 
-struct ColPtrs {  // a clg_columns' arrays, for copies and checks
-  void* p[12];
-  uint32_t width[12];
-  bool wide[12];
-};
-ColPtrs col_ptrs(const clg_columns& c) {
-  return ColPtrs{{c.tag, c.order, c.timestamp, c.rng, c.buffer_built, c.w_idx, c.w_rc, c.w_v1, c.w_var_off,
-                  c.w_var_len, c.w_sub, c.w_v0},
-                 {1, 1, 8, 4, 4, 4, 4, 8, 4, 4, 1, 8},
-                 {false, false, false, false, false, true, true, true, true, true, true, true}};
+// ---- placement (placement.h): where the kernels of this family read and write ------------------
+static_assert(clg::kPlaceHost == CLG_MEM_HOST && clg::kPlaceDevice == CLG_MEM_DEVICE && clg::kPlaceMapped == CLG_MEM_MAPPED,
+              "placement.h numbers the memory kinds as the ABI does");
+using clg::mem_kind_ok;
+using clg::PlacePolicy;
+using clg::PlaceSpec;
+
+// The placement of n arrays of one memory kind; a misaligned or (reject_unresolved) unregistered
+// array fails the call, naming `what` the arrays are.
+int place_arrays(const PlaceSpec* s, int n, uint32_t kind, PlacePolicy policy, const char* what, clg::Placement* pl) {
+  *pl = clg::place(s, n, kind, policy, clg_mapped_device_address);
+  if (pl->verdict != clg::PlaceVerdict::misaligned && pl->verdict != clg::PlaceVerdict::not_registered) return CLG_OK;
+  return fail(CLG_E_INVALID_ARG, "%s array %d is not %s", what, pl->bad,
+              pl->verdict == clg::PlaceVerdict::misaligned ? "aligned to its element"
+                                                           : "inside memory registered with clg_host_register");
+}
+// A copy to or from a caller's array (the source of a host-to-device copy, else the destination),
+// in pieces that cross no edge of a registered range: an array need not lie wholly inside one.
+int copy_caller(clg_engine* e, void* dst, const void* src, uint64_t bytes, hipMemcpyKind kind,
+                uint32_t mem_kind = CLG_MEM_HOST) {
+  const char* caller = static_cast<const char*>(kind == hipMemcpyHostToDevice ? src : dst);
+  for (uint64_t at = 0, k; at < bytes; at += k) {
+    k = mem_kind == CLG_MEM_DEVICE ? bytes : clg_mapped_piece(caller + at, bytes - at);  // (device memory: one copy)
+    HIPCHK(hipMemcpyAsync(static_cast<char*>(dst) + at, static_cast<const char*>(src) + at, k, kind, e->stream));
+  }
+  return CLG_OK;
+}
+// The placement of outputs; staged: `buf` grown to the slots, `extra` bytes behind them and 16
+// spare, and the arrays bound to their slots.
+int place_out(DevBuf& buf, const PlaceSpec* s, int n, uint32_t kind, PlacePolicy policy, const char* what, clg::Placement* pl,
+              size_t extra = 0) {
+  CHK(place_arrays(s, n, kind, policy, what, pl));
+  if (!pl->staged()) return CLG_OK;
+  CHK(buf.ensure(pl->total + extra + 16));
+  pl->bind(s, n, buf.p);
+  return CLG_OK;
+}
+// The placement of inputs: the same, and a staged array's copy in queued (not an absent or empty one's).
+int place_in(clg_engine* e, DevBuf& buf, const PlaceSpec* s, int n, uint32_t kind, PlacePolicy policy, const char* what,
+             clg::Placement* pl, size_t extra = 0) {
+  CHK(place_out(buf, s, n, kind, policy, what, pl, extra));
+  for (int i = 0; i < n && pl->staged(); ++i)
+    if (s[i].p && s[i].bytes) CHK(copy_caller(e, pl->at<void>(i), s[i].p, s[i].bytes, hipMemcpyHostToDevice));
+  return CLG_OK;
+}
+// A staged output's copies out, queued behind the kernels that filled the slots (no-op in place).
+int stage_out(clg_engine* e, const PlaceSpec* s, int n, const clg::Placement& pl) {
+  for (int i = 0; i < n && pl.staged(); ++i)
+    if (s[i].p && s[i].bytes) CHK(copy_caller(e, const_cast<void*>(s[i].p), pl.at<void>(i), s[i].bytes, hipMemcpyDeviceToHost));
+  return CLG_OK;
+}
+
+// The input's array that column array i passes through unchanged (null: the kernels compute it).
+const void* col_through(const clg_decoded& in, int i) {
+  const void* const src[clg::kColArrays] = {in.tag,  nullptr,      nullptr,      nullptr,  nullptr, in.w_idx, in.w_rc,
+                                            in.w_v1, in.w_var_off, in.w_var_len, in.w_sub, nullptr};
+  return src[i];
+}
+// The two failures columnize_small and columnize_device share.
+int col_bad_tag(clg_columns* out, const uint64_t* span_rec_base, uint32_t n_spans, uint64_t index, uint64_t tag) {
+  out->err_status = CLG_E_INVALID_ARG;
+  out->err_span = clg::col_span_of(span_rec_base, n_spans, index);
+  out->err_off = int64_t(index);
+  out->err_tag = int32_t(tag);
+  return fail(CLG_E_INVALID_ARG, "record %llu has tag %llu", (unsigned long long)index, (unsigned long long)tag);
+}
+int col_too_small(const char* name, uint64_t n, const uint64_t tot[clg::kColClasses]) {
+  return fail(CLG_E_CAPACITY, "column %s is too small (records %llu; totals %llu %llu %llu %llu %llu)", name,
+              (unsigned long long)n, (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2],
+              (unsigned long long)tot[3], (unsigned long long)tot[4]);
 }
 
 // A batch of at most kColSmallRecords records and kColSmallSpans spans, in one launch
@@ -3900,7 +3970,6 @@ ColPtrs col_ptrs(const clg_columns& c) {
 int columnize_small(clg_engine* e, const clg_decoded& in, const uint64_t* span_rec_base, uint32_t n_spans,
                     clg_columns* out) {
   const uint64_t n = in.n_rec, nw = in.n_wide;
-  const ColPtrs cp = col_ptrs(*out);
   const bool sizes_only = clg::col_sizes_only(*out);
   const bool want_sb = out->span_base && n_spans;
   // pinned: result block | span bases | span boundaries
@@ -3915,28 +3984,23 @@ int columnize_small(clg_engine* e, const clg_decoded& in, const uint64_t* span_r
 
   // where the kernel writes: the caller's device arrays, the device side of registered host
   // arrays, or (plain host memory, and registered memory that is not wholly inside one registered
-  // range) one packed engine buffer that is read back in one copy
-  void* dev[12];
-  bool packed = out->out_kind == CLG_MEM_HOST;
-  const uint64_t caps[12] = {out->cap_tag, out->cap_order, out->cap_timestamp, out->cap_rng, out->cap_buffer_built,
-                             out->cap_wide, out->cap_wide, out->cap_wide, out->cap_wide, out->cap_wide, out->cap_wide,
-                             out->cap_wide};
-  for (int i = 0; i < 12; ++i) {
-    dev[i] = cp.p[i];
-    if (out->out_kind == CLG_MEM_MAPPED && cp.p[i] && !sizes_only && !packed &&
-        !(dev[i] = reinterpret_cast<void*>(clg_mapped_device_address(cp.p[i], caps[i] * cp.width[i]))))
-      packed = true;
-  }
+  // range) one packed engine buffer that is read back in one copy.  The registry is asked for
+  // each array's capacity, not its length: the lengths are known only after the one launch.
+  PlaceSpec spec[clg::kColArrays];
+  for (int i = 0; i < clg::kColArrays; ++i)
+    spec[i] = {clg::col_ptr(*out, i), clg::col_array_cap(*out, i) * clg::kColArray[i].width, clg::kColArray[i].width};
+  clg::Placement pl;
+  CHK(place_arrays(spec, clg::kColArrays, out->out_kind, PlacePolicy::stage_if_unresolved, "column", &pl));
+  const bool packed = pl.staged();
+  void* dev[clg::kColArrays];
+  for (int i = 0; i < clg::kColArrays; ++i) dev[i] = pl.at<void>(i);
   clg::ColSmallOut so{};
   if (packed && !sizes_only) {
     CHK(e->d_colout.ensure(clg::col_pack_bound(n, nw) + 16));
     so.pack = e->d_colout.as<uint8_t>();
   } else if (!sizes_only) {
-    // (an array that is the input's own stays as it is)
-    const void* src[12] = {in.tag,   nullptr,      nullptr,      nullptr,  nullptr, in.w_idx, in.w_rc,
-                           in.w_v1,  in.w_var_off, in.w_var_len, in.w_sub, nullptr};
-    for (int i = 0; i < 12; ++i)
-      if (src[i] && dev[i] == src[i]) dev[i] = nullptr;
+    for (int i = 0; i < clg::kColArrays; ++i)  // (an array that is the input's own stays as it is)
+      if (dev[i] == col_through(in, i)) dev[i] = nullptr;
     so.tag = static_cast<uint8_t*>(dev[0]), so.order = static_cast<int8_t*>(dev[1]);
     so.timestamp = static_cast<int64_t*>(dev[2]), so.rng = static_cast<int32_t*>(dev[3]);
     so.buffer_built = static_cast<int32_t*>(dev[4]), so.w_idx = static_cast<uint32_t*>(dev[5]);
@@ -3944,12 +4008,9 @@ int columnize_small(clg_engine* e, const clg_decoded& in, const uint64_t* span_r
     so.w_var_off = static_cast<uint32_t*>(dev[8]), so.w_var_len = static_cast<uint32_t*>(dev[9]);
     so.w_sub = static_cast<uint8_t*>(dev[10]), so.w_v0 = static_cast<int64_t*>(dev[11]);
   }
-  so.cap[0] = clg::col_cap(out->tag, out->cap_tag), so.cap[1] = clg::col_cap(out->order, out->cap_order);
-  so.cap[2] = clg::col_cap(out->timestamp, out->cap_timestamp), so.cap[3] = clg::col_cap(out->rng, out->cap_rng);
-  so.cap[4] = clg::col_cap(out->buffer_built, out->cap_buffer_built);
-  so.cap[5] = out->cap_wide;
-  for (int i = 5; i < 12; ++i)
-    if (!cp.p[i]) so.cap[5] = 0;
+  for (int i = 0; i < clg::kColNarrowArrays; ++i) so.cap[i] = clg::col_array_cap(*out, i);
+  so.cap[5] = out->cap_wide;  // (the wide arrays share one capacity: none when one of them is absent)
+  for (int i = clg::kColNarrowArrays; i < clg::kColArrays; ++i) so.cap[5] = std::min(so.cap[5], clg::col_array_cap(*out, i));
   const clg::ColSmallIn si{in.tag,       in.v0,       in.w_idx, in.w_rc, in.w_v1, in.w_var_off,
                            in.w_var_len, in.w_sub,    want_sb ? h_srb : nullptr,  n,       nw,
                            want_sb ? n_spans : 0u, sizes_only ? 1u : 0u};
@@ -3959,14 +4020,7 @@ int columnize_small(clg_engine* e, const clg_decoded& in, const uint64_t* span_r
   CHK(e->timed("decode_columns", moved, [&] { return clg::launch_col_small(si, so, res, want_sb ? h_sb : nullptr, e->stream); }));
   CHK(e->sync());
   out->n_rec = n;
-  if (res->verdict == clg::kColSmallBadTag) {
-    out->err_status = CLG_E_INVALID_ARG;
-    out->err_span = clg::col_span_of(span_rec_base, n_spans, res->bad_index);
-    out->err_off = int64_t(res->bad_index);
-    out->err_tag = int32_t(res->bad_tag);
-    return fail(CLG_E_INVALID_ARG, "record %llu has tag %llu", (unsigned long long)res->bad_index,
-                (unsigned long long)res->bad_tag);
-  }
+  if (res->verdict == clg::kColSmallBadTag) return col_bad_tag(out, span_rec_base, n_spans, res->bad_index, res->bad_tag);
   uint64_t tot[clg::kColClasses];
   for (uint32_t c = 0; c < clg::kColClasses; ++c) out->n_class[c] = tot[c] = res->total[c];
   if (res->verdict == clg::kColSmallWideCount)
@@ -3978,21 +4032,16 @@ int columnize_small(clg_engine* e, const clg_decoded& in, const uint64_t* span_r
     CHK(e->h_colpack.ensure(end));
     HIPCHK(hipMemcpyAsync(e->h_colpack.p, so.pack, end, hipMemcpyDeviceToHost, e->stream));
     CHK(e->sync());
-    const uint64_t cnt[12] = {n, tot[0], tot[1], tot[2], tot[3], nw, nw, nw, nw, nw, nw, nw};
-    for (int i = 0; i < 12; ++i)
-      if (cnt[i]) memcpy(cp.p[i], e->h_colpack.as<uint8_t>() + res->pack_off[i], cnt[i] * cp.width[i]);
+    for (int i = 0; i < clg::kColArrays; ++i)
+      if (const uint64_t cnt = clg::col_array_len(i, n, tot))
+        memcpy(clg::col_ptr(*out, i), e->h_colpack.as<uint8_t>() + res->pack_off[i], cnt * clg::kColArray[i].width);
   }
   if (out->span_base) {
     if (n_spans) memcpy(out->span_base, h_sb, sbn * 8 * clg::kColClasses);
     else memcpy(out->span_base, tot, sizeof tot);
   }
-  if (res->verdict == clg::kColSmallCapacity) {
-    static const char* const kName[6] = {"tag", "order", "timestamp", "rng", "buffer_built", "wide"};
-    return fail(CLG_E_CAPACITY, "column %s is too small (records %llu; totals %llu %llu %llu %llu %llu)",
-                kName[res->short_cap < 6 ? res->short_cap : 5], (unsigned long long)n, (unsigned long long)tot[0],
-                (unsigned long long)tot[1], (unsigned long long)tot[2], (unsigned long long)tot[3],
-                (unsigned long long)tot[4]);
-  }
+  // (short_cap: the narrow array's index, 5 for the wide arrays)
+  if (res->verdict == clg::kColSmallCapacity) return col_too_small(clg::kColArray[std::min(res->short_cap, 5u)].name, n, tot);
   return CLG_OK;
 }
 
@@ -4002,17 +4051,15 @@ int columnize_device(clg_engine* e, const clg_decoded& in, const uint64_t* span_
                      clg_columns* out) {
   clg::col_reset_result(out);
   const uint64_t n = in.n_rec, nw = in.n_wide;
-  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
   if ((n && (!in.tag || !in.v0)) || (nw && (!in.w_idx || !in.w_rc || !in.w_v1 || !in.w_var_off || !in.w_var_len || !in.w_sub)))
     return fail(CLG_E_INVALID_ARG, "null input array");
   if (!clg::col_spans_ok(span_rec_base, n_spans, n))
     return fail(CLG_E_INVALID_ARG, "span_rec_base decreases or passes n_rec");
   if ((n + clg::kColTile - 1) / clg::kColTile >> 31) return fail(CLG_E_INVALID_ARG, "%llu records in one call", (unsigned long long)n);
-  const ColPtrs cp = col_ptrs(*out);
-  if (out->out_kind != CLG_MEM_HOST)
-    for (int i = 0; i < 12; ++i)
-      if (uintptr_t(cp.p[i]) % cp.width[i]) return fail(CLG_E_INVALID_ARG, "column %d is not aligned to its element", i);
+  for (int i = 0; i < clg::kColArrays && out->out_kind != CLG_MEM_HOST; ++i)  // (an empty array's too: no length is known yet)
+    if (uintptr_t(clg::col_ptr(*out, i)) % clg::kColArray[i].width)
+      return fail(CLG_E_INVALID_ARG, "column %d is not aligned to its element", i);
   if (e->sw.columns_small && n <= clg::kColSmallRecords && n_spans <= clg::kColSmallSpans)
     return columnize_small(e, in, span_rec_base, n_spans, out);
   const uint32_t n_tiles = uint32_t((n + clg::kColTile - 1) / clg::kColTile);
@@ -4031,12 +4078,7 @@ int columnize_device(clg_engine* e, const clg_decoded& in, const uint64_t* span_
   if (res->bad_tile != clg::kColNoTile) {  // a tag above 7: one wave finds the record
     CHK(clg::launch_col_find_bad(cin, res->bad_tile, res, e->stream));
     CHK(e->sync());
-    out->err_status = CLG_E_INVALID_ARG;
-    out->err_span = clg::col_span_of(span_rec_base, n_spans, res->bad_index);
-    out->err_off = int64_t(res->bad_index);
-    out->err_tag = int32_t(res->bad_tag);
-    return fail(CLG_E_INVALID_ARG, "record %llu has tag %llu", (unsigned long long)res->bad_index,
-                (unsigned long long)res->bad_tag);
+    return col_bad_tag(out, span_rec_base, n_spans, res->bad_index, res->bad_tag);
   }
   uint64_t tot[clg::kColClasses];
   for (uint32_t c = 0; c < clg::kColClasses; ++c) out->n_class[c] = tot[c] = res->total[c];
@@ -4049,24 +4091,15 @@ int columnize_device(clg_engine* e, const clg_decoded& in, const uint64_t* span_
 
   // where the kernels write: the caller's device arrays, the device side of registered host
   // arrays, or engine staging (plain host memory, and registered memory that is not wholly
-  // inside one registered range)
-  const uint64_t cnt[5] = {tot[0], tot[1], tot[2], tot[3], nw};  // order, timestamp, rng, buffer_built, w_v0
-  void* const host_dst[5] = {out->order, out->timestamp, out->rng, out->buffer_built, out->w_v0};
-  const uint32_t wd[5] = {1, 8, 4, 4, 8};
-  bool staged = out->out_kind == CLG_MEM_HOST;
-  void* dev_dst[5] = {host_dst[0], host_dst[1], host_dst[2], host_dst[3], host_dst[4]};
-  if (write && out->out_kind == CLG_MEM_MAPPED) {
-    for (int i = 0; i < 5 && !staged; ++i)
-      if (cnt[i] && !(dev_dst[i] = reinterpret_cast<void*>(clg_mapped_device_address(host_dst[i], cnt[i] * wd[i])))) staged = true;
-  }
-  uint64_t at[6] = {0};
-  if (write && staged) {
-    for (int i = 0; i < 5; ++i) at[i + 1] = (at[i] + cnt[i] * wd[i] + 15) & ~uint64_t(15);
-    CHK(e->d_colout.ensure(at[5] + 16));
-    for (int i = 0; i < 5; ++i) dev_dst[i] = e->d_colout.as<uint8_t>() + at[i];
-  }
-  const clg::ColOut cout_{static_cast<int8_t*>(dev_dst[0]), static_cast<int64_t*>(dev_dst[1]), static_cast<int32_t*>(dev_dst[2]),
-                          static_cast<int32_t*>(dev_dst[3]), static_cast<int64_t*>(dev_dst[4])};
+  // inside one registered range).  Only the arrays the kernels write, each with its length (known
+  // here, unlike in columnize_small); those passed through are copied below and absent here.
+  PlaceSpec wr[clg::kColArrays];
+  for (int i = 0; i < clg::kColArrays; ++i)
+    wr[i] = {col_through(in, i) ? nullptr : clg::col_ptr(*out, i), clg::col_array_len(i, n, tot) * clg::kColArray[i].width,
+             clg::kColArray[i].width};
+  clg::Placement pl;
+  if (write) CHK(place_out(e->d_colout, wr, clg::kColArrays, out->out_kind, PlacePolicy::stage_if_unresolved, "column", &pl));
+  const clg::ColOut cout_{pl.at<int8_t>(1), pl.at<int64_t>(2), pl.at<int32_t>(3), pl.at<int32_t>(4), pl.at<int64_t>(11)};
   const bool want_sb = out->span_base && n_spans;
   if (want_sb) {
     const size_t sb = size_t(n_spans + 1) * 8;
@@ -4086,25 +4119,19 @@ int columnize_device(clg_engine* e, const clg_decoded& in, const uint64_t* span_
     HIPCHK(hipMemcpyAsync(e->h_colsb.p, e->d_colsb.p, size_t(n_spans + 1) * 8 * clg::kColClasses, hipMemcpyDeviceToHost, e->stream));
   if (write) {
     // the arrays that stay as they are: the tags and the side rows
-    const void* src[6] = {in.tag, in.w_idx, in.w_rc, in.w_v1, in.w_var_off, in.w_var_len};
-    void* dst[6] = {out->tag, out->w_idx, out->w_rc, out->w_v1, out->w_var_off, out->w_var_len};
-    const uint64_t nb[6] = {n, nw * 4, nw * 4, nw * 8, nw * 4, nw * 4};
-    for (int i = 0; i < 6; ++i)
-      if (nb[i] && dst[i] != src[i]) HIPCHK(hipMemcpyAsync(dst[i], src[i], nb[i], hipMemcpyDefault, e->stream));
-    if (nw && out->w_sub != in.w_sub) HIPCHK(hipMemcpyAsync(out->w_sub, in.w_sub, nw, hipMemcpyDefault, e->stream));
-    if (staged)
-      for (int i = 0; i < 5; ++i)
-        if (cnt[i]) HIPCHK(hipMemcpyAsync(host_dst[i], dev_dst[i], cnt[i] * wd[i], hipMemcpyDeviceToHost, e->stream));
+    for (int i = 0; i < clg::kColArrays; ++i) {
+      const void* src = col_through(in, i);
+      void* dst = clg::col_ptr(*out, i);
+      if (src && wr[i].bytes && dst != src) CHK(copy_caller(e, dst, src, wr[i].bytes, hipMemcpyDefault, out->out_kind));
+    }
+    CHK(stage_out(e, wr, clg::kColArrays, pl));
   }
   CHK(e->sync());
   if (out->span_base) {
     if (n_spans) memcpy(out->span_base, e->h_colsb.p, size_t(n_spans + 1) * 8 * clg::kColClasses);
     else memcpy(out->span_base, tot, sizeof tot);
   }
-  if (short_col)
-    return fail(CLG_E_CAPACITY, "column %s is too small (records %llu; totals %llu %llu %llu %llu %llu)", short_col,
-                (unsigned long long)n, (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2],
-                (unsigned long long)tot[3], (unsigned long long)tot[4]);
+  if (short_col) return col_too_small(short_col, n, tot);
   return CLG_OK;
 }
 
@@ -4173,31 +4200,25 @@ int decode_columns(clg_engine* e, const std::function<int(clg_decoded*, uint64_t
 int gather_payloads_small(clg_engine* e, const clg::PayIn& in, clg_payloads* out, bool sizes_only, uint64_t span_bytes,
                           uint64_t desc_bytes) {
   const uint64_t n = in.n_rows;
-  const bool direct = out->out_kind == CLG_MEM_DEVICE;
   CHK(e->h_payres.ensure(sizeof(clg::PaySmallRes)));
   clg::PaySmallRes* res = e->h_payres.as<clg::PaySmallRes>();
   const uint64_t cap_pos = out->pos ? out->cap_pos : 0, cap_var = out->var ? out->cap_var : 0;
-  // where the kernel writes: the caller's device arrays, or engine staging (pos | var, var at a
-  // 16-byte boundary)
-  uint64_t* dpos = out->pos;
-  uint8_t* dvar = out->var;
-  const size_t pb = clg_engine::al16((n + 1) * 8);
+  // where the kernel writes: the caller's device arrays, or (host and registered memory alike:
+  // the short rows' byte stores stay off the link) engine staging, pos | var; sizes only: nowhere.
   // Staging holds what the spans hold.  Rows of a caller may overlap, so n_var can be more: then
   // the kernel reports the staging as short, and runs once more with staging of n_var bytes.
-  uint64_t stage = std::min(cap_var, span_bytes);
+  PlaceSpec dst[2] = {{out->pos, (n + 1) * 8, 8}, {out->var, std::min(cap_var, span_bytes), 1}};
+  clg::Placement pl;
   e->stats["payloads_small"].launches++;
   for (int round = 0;; ++round) {
-    if (!direct && !sizes_only) {
-      CHK(e->d_payout.ensure(pb + stage + 16));
-      dpos = e->d_payout.as<uint64_t>();
-      dvar = e->d_payout.as<uint8_t>() + pb;
-    }
+    if (!sizes_only) CHK(place_out(e->d_payout, dst, 2, out->out_kind, PlacePolicy::stage_unless_device, "payload", &pl));
     CHK(e->timed("decode_payloads", n * 20 + (n + 1) * 8 + desc_bytes, [&] {
-      return clg::launch_pay_small(in, dpos, dvar, cap_pos, direct ? cap_var : stage, sizes_only, res, e->stream);
+      return clg::launch_pay_small(in, pl.at<uint64_t>(0), pl.at<uint8_t>(1), cap_pos, pl.staged() ? dst[1].bytes : cap_var,
+                                   sizes_only, res, e->stream);
     }));
     CHK(e->sync());
-    if (round || direct || res->verdict != clg::kPaySmallCapacity || !res->short_cap || res->n_var > cap_var) break;
-    stage = res->n_var;
+    if (round || !pl.staged() || res->verdict != clg::kPaySmallCapacity || !res->short_cap || res->n_var > cap_var) break;
+    dst[1].bytes = res->n_var;
   }
   out->n_var = res->n_var;
   if (res->verdict == clg::kPaySmallBadRow) {
@@ -4207,10 +4228,10 @@ int gather_payloads_small(clg_engine* e, const clg::PayIn& in, clg_payloads* out
   if (res->verdict == clg::kPaySmallCapacity)
     return fail(CLG_E_CAPACITY, "%s is too small (rows %llu, payload bytes %llu)", res->short_cap ? "var" : "pos",
                 (unsigned long long)n, (unsigned long long)res->n_var);
-  if (res->verdict == clg::kPaySmallWritten && !direct) {
-    const uint64_t nv = res->n_var;
+  if (res->verdict == clg::kPaySmallWritten && pl.staged()) {  // pos | var come back in one copy
+    const uint64_t nv = res->n_var, pb = pl.off[1];
     CHK(e->h_paypack.ensure(pb + nv));
-    HIPCHK(hipMemcpyAsync(e->h_paypack.p, dpos, pb + nv, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_paypack.p, pl.at<void>(0), pb + nv, hipMemcpyDeviceToHost, e->stream));
     CHK(e->sync());
     memcpy(out->pos, e->h_paypack.p, (n + 1) * 8);
     if (nv) memcpy(out->var, e->h_paypack.as<uint8_t>() + pb, nv);
@@ -4224,8 +4245,7 @@ int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans
                            bool sizes_forced = false) {
   const uint32_t ns = uint32_t(spans.size());
   clg::pay_reset_result(out);
-  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
   if (!clg::pay_row_base_ok(row_base, ns)) return fail(CLG_E_INVALID_ARG, "row_base does not start at 0 or decreases");
   const uint64_t n = ns ? row_base[ns] : 0;
   if (n > 0xFFFFFFFFull) return fail(CLG_E_INVALID_ARG, "%llu rows in one call", (unsigned long long)n);
@@ -4285,21 +4305,13 @@ int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans
 
   // where the kernels write: the caller's device arrays, or engine staging and one copy each
   // (host and registered memory alike: the short rows' byte stores stay off the link)
-  uint64_t* dpos = out->pos;
-  uint8_t* dvar = out->var;
-  if (!direct) {
-    const size_t pb = clg_engine::al16((n + 1) * 8);
-    CHK(e->d_payout.ensure(pb + nv + 16));
-    dpos = e->d_payout.as<uint64_t>();
-    dvar = e->d_payout.as<uint8_t>() + pb;
-  }
+  const PlaceSpec dst[2] = {{out->pos, (n + 1) * 8, 8}, {out->var, nv, 1}};
+  clg::Placement pl;
+  CHK(place_out(e->d_payout, dst, 2, out->out_kind, PlacePolicy::stage_unless_device, "payload", &pl));
   CHK(e->timed("decode_payloads", n * 12 + (n + 1) * 8 + uint64_t(n_tiles) * 8 + 2 * nv, [&] {
-    return clg::launch_pay_write(in, n_tiles, d_base, nv, dpos, dvar, e->stream);
+    return clg::launch_pay_write(in, n_tiles, d_base, nv, pl.at<uint64_t>(0), pl.at<uint8_t>(1), e->stream);
   }));
-  if (!direct) {
-    HIPCHK(hipMemcpyAsync(out->pos, dpos, (n + 1) * 8, hipMemcpyDeviceToHost, e->stream));
-    if (nv) HIPCHK(hipMemcpyAsync(out->var, dvar, nv, hipMemcpyDeviceToHost, e->stream));
-  }
+  CHK(stage_out(e, dst, 2, pl));
   return e->sync();
 }
 
@@ -4310,13 +4322,11 @@ int stage_payload_rows(clg_engine* e, const uint32_t* off, const uint32_t* len, 
   *d_len = len;
   if (in_kind != CLG_MEM_HOST || !n) return CLG_OK;
   if (!off || !len) return fail(CLG_E_INVALID_ARG, "null row array");
-  const size_t b = clg_engine::al16(n * 4);
-  CHK(e->d_payrows.ensure(2 * b + 16));
-  uint8_t* d = e->d_payrows.as<uint8_t>();
-  HIPCHK(hipMemcpyAsync(d, off, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d + b, len, n * 4, hipMemcpyHostToDevice, e->stream));
-  *d_off = reinterpret_cast<const uint32_t*>(d);
-  *d_len = reinterpret_cast<const uint32_t*>(d + b);
+  const PlaceSpec rows[2] = {{off, n * 4, 4}, {len, n * 4, 4}};
+  clg::Placement pl;
+  CHK(place_in(e, e->d_payrows, rows, 2, in_kind, PlacePolicy::stage_unless_device, "row", &pl));
+  *d_off = pl.at<const uint32_t>(0);
+  *d_len = pl.at<const uint32_t>(1);
   return CLG_OK;
 }
 
@@ -4423,9 +4433,8 @@ int pack_sizes(clg_engine* e, const clg::PackSrc& src, clg_packed* out, clg::Pac
   return CLG_OK;
 }
 
-int pack_out_check(const clg_packed& out) {
-  if (out.out_kind != CLG_MEM_HOST && out.out_kind != CLG_MEM_DEVICE && out.out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "out_kind %u", out.out_kind);
+int pack_out_check(const clg_packed& out, const char* what = "") {  // (a packed input's, too)
+  if (!mem_kind_ok(out.out_kind)) return fail(CLG_E_INVALID_ARG, "%sout_kind %u", what, out.out_kind);
   if (out.out_kind != CLG_MEM_HOST && (uintptr_t(out.desc) % 8 || uintptr_t(out.bits) % 16))
     return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
   return CLG_OK;
@@ -4436,29 +4445,16 @@ int pack_out_check(const clg_packed& out) {
 int pack_write(clg_engine* e, const clg::PackIn& pin, clg_packed* out) {
   const uint64_t nb = out->blk_base[clg::kPackStreams], nbits = out->n_bits;
   if (!nb) return CLG_OK;
-  const size_t db = clg_engine::al16(size_t(nb) * sizeof(clg_pack_block));
-  clg_pack_block* ddesc = out->desc;
-  uint8_t* dbits = out->bits;
-  bool staged = out->out_kind == CLG_MEM_HOST;
-  if (out->out_kind == CLG_MEM_MAPPED) {
-    ddesc = reinterpret_cast<clg_pack_block*>(clg_mapped_device_address(out->desc, nb * sizeof(clg_pack_block)));
-    dbits = nbits ? reinterpret_cast<uint8_t*>(clg_mapped_device_address(out->bits, nbits)) : nullptr;
-    if (!ddesc || (nbits && !dbits)) staged = true;  // (not wholly inside one registered range)
-  }
-  if (staged) {
-    CHK(e->d_packout.ensure(db + nbits + 16));
-    ddesc = e->d_packout.as<clg_pack_block>();
-    dbits = e->d_packout.as<uint8_t>() + db;
-  }
+  const PlaceSpec dst[2] = {{out->desc, nb * sizeof(clg_pack_block), 8}, {out->bits, nbits, 16}};
+  clg::Placement pl;
+  CHK(place_out(e->d_packout, dst, 2, out->out_kind, PlacePolicy::stage_if_unresolved, "packed", &pl));
   uint64_t in_bytes = 0;
   for (uint32_t c = 0; c < clg::kPackStreams; ++c) in_bytes += pin.n[c] * clg::pack_elem(c);
   CHK(e->timed("pack_columns", in_bytes + nb * 64 + nbits, [&] {
-    return clg::launch_pack_write(pin, uint32_t(nb), e->d_packdesc.as<clg_pack_block>(), ddesc, dbits, nb, nbits, e->stream);
+    return clg::launch_pack_write(pin, uint32_t(nb), e->d_packdesc.as<clg_pack_block>(), pl.at<clg_pack_block>(0),
+                                  pl.at<uint8_t>(1), nb, nbits, e->stream);
   }));
-  if (staged) {
-    HIPCHK(hipMemcpyAsync(out->desc, ddesc, nb * sizeof(clg_pack_block), hipMemcpyDeviceToHost, e->stream));
-    if (nbits) HIPCHK(hipMemcpyAsync(out->bits, dbits, nbits, hipMemcpyDeviceToHost, e->stream));
-  }
+  CHK(stage_out(e, dst, 2, pl));
   return e->sync();
 }
 
@@ -4475,8 +4471,7 @@ int decode_columns_packed(clg_engine* e, const std::function<int(clg_decoded*, u
                           const std::function<int(std::vector<clg::PaySpan>&, std::vector<uint32_t>&)>& spans_of) {
   if (wide->tag || wide->order || wide->timestamp || wide->rng || wide->buffer_built)
     return fail(CLG_E_INVALID_ARG, "the narrow column pointers of `wide` must be NULL: those columns are delivered packed");
-  if (wide->out_kind != CLG_MEM_HOST && wide->out_kind != CLG_MEM_DEVICE && wide->out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "out_kind %u", wide->out_kind);
+  if (!mem_kind_ok(wide->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", wide->out_kind);
   CHK(pack_out_check(*out));
   clg::col_reset_result(wide);
   clg::pack_reset_result(out);
@@ -4502,9 +4497,8 @@ int decode_columns_packed(clg_engine* e, const std::function<int(clg_decoded*, u
   // the narrow columns and w_v0 into engine scratch (the tags and the side rows stay where the
   // decode left them)
   const uint64_t cb[5] = {tot[0], tot[1] * 8, tot[2] * 4, tot[3] * 4, nw * 8};
-  uint64_t at[6] = {0};
-  for (int i = 0; i < 5; ++i) at[i + 1] = clg_engine::al16(at[i] + cb[i]);
-  CHK(e->d_packcol.ensure(at[5] + 16));
+  size_t at[6];
+  CHK(e->d_packcol.ensure(clg::place_layout(cb, 5, at) + 16));
   uint8_t* sc = e->d_packcol.as<uint8_t>();
   clg_columns full{};
   full.tag = keep.d.tag, full.order = reinterpret_cast<int8_t*>(sc + at[0]);
@@ -4531,12 +4525,10 @@ int decode_columns_packed(clg_engine* e, const std::function<int(clg_decoded*, u
     if (ps == CLG_OK) ps = gather_payloads_device(e, spans, segtab, keep.d.w_var_off, keep.d.w_var_len, row_base.data(), var, true);
   }
   const std::string pay_err = g_err;
-  void* const wdst[7] = {wide->w_idx, wide->w_rc, wide->w_v1, wide->w_var_off, wide->w_var_len, wide->w_sub, wide->w_v0};
-  const void* const wsrc[7] = {full.w_idx, full.w_rc, full.w_v1, full.w_var_off, full.w_var_len, full.w_sub, full.w_v0};
-  const uint32_t wwd[7] = {4, 4, 8, 4, 4, 1, 8};
+  const int w0 = clg::kColNarrowArrays, w1 = clg::kColArrays;  // (the wide arrays: the table's last seven)
   bool wide_any = false, wide_short = false;
-  for (int i = 0; i < 7; ++i) wide_any = wide_any || wdst[i];
-  for (int i = 0; i < 7; ++i) wide_short = wide_short || (wide_any && clg::col_cap(wdst[i], wide->cap_wide) < nw);
+  for (int i = w0; i < w1; ++i) wide_any = wide_any || clg::col_ptr(*wide, i);
+  for (int i = w0; i < w1; ++i) wide_short = wide_short || (wide_any && clg::col_array_cap(*wide, i) < nw);
   const char* pk_short = clg::pack_sizes_only(*out) ? nullptr : clg::pack_short(*out);
   const char* pay_short = var && ps == CLG_OK && !clg::pay_sizes_only(*var) ? clg::pay_short(*var, var->n_rows, var->n_var) : nullptr;
   if (wide_short) return fail(CLG_E_CAPACITY, "the wide rows' arrays are too small (rows %llu)", (unsigned long long)nw);
@@ -4548,7 +4540,9 @@ int decode_columns_packed(clg_engine* e, const std::function<int(clg_decoded*, u
   // the writes
   if (!clg::pack_sizes_only(*out)) CHK(pack_write(e, pin, out));
   if (wide_any && nw) {
-    for (int i = 0; i < 7; ++i) HIPCHK(hipMemcpyAsync(wdst[i], wsrc[i], nw * wwd[i], hipMemcpyDefault, e->stream));
+    for (int i = w0; i < w1; ++i)
+      CHK(copy_caller(e, clg::col_ptr(*wide, i), clg::col_ptr(full, i), nw * clg::kColArray[i].width, hipMemcpyDefault,
+                      wide->out_kind));
     CHK(e->sync());
   }
   if (var && ps == CLG_OK && !clg::pay_sizes_only(*var))
@@ -4572,30 +4566,13 @@ int clg_pack_columns(clg_engine* e, const clg_columns* in, clg_packed* out) {
   clg::PackSrc src = clg::pack_src(*in);
   for (uint32_t c = 0; c < clg::kPackStreams; ++c)
     if (src.n[c] && !src.col[c]) return fail(CLG_E_INVALID_ARG, "null input array (stream %u)", c);
-  bool stage = in->out_kind == CLG_MEM_HOST;
-  if (in->out_kind == CLG_MEM_MAPPED) {  // registered host memory: its device side
-    const void* dev[clg::kPackStreams];
-    for (uint32_t c = 0; c < clg::kPackStreams && !stage; ++c) {
-      dev[c] = src.col[c];
-      if (src.n[c] && !(dev[c] = reinterpret_cast<const void*>(clg_mapped_device_address(src.col[c], src.n[c] * clg::pack_elem(c)))))
-        stage = true;  // (not wholly inside one registered range)
-    }
-    if (!stage)
-      for (uint32_t c = 0; c < clg::kPackStreams; ++c) src.col[c] = dev[c];
-  } else if (in->out_kind != CLG_MEM_HOST && in->out_kind != CLG_MEM_DEVICE) {
-    return fail(CLG_E_INVALID_ARG, "the columns' out_kind %u", in->out_kind);
-  }
-  if (stage) {
-    uint64_t at[clg::kPackStreams + 1] = {0};
-    for (uint32_t c = 0; c < clg::kPackStreams; ++c) at[c + 1] = clg_engine::al16(at[c] + src.n[c] * clg::pack_elem(c));
-    CHK(e->d_packin.ensure(at[clg::kPackStreams] + 16));
-    for (uint32_t c = 0; c < clg::kPackStreams; ++c) {
-      if (src.n[c])
-        HIPCHK(hipMemcpyAsync(e->d_packin.as<uint8_t>() + at[c], src.col[c], src.n[c] * clg::pack_elem(c), hipMemcpyHostToDevice,
-                              e->stream));
-      src.col[c] = e->d_packin.as<uint8_t>() + at[c];
-    }
-  }
+  if (!mem_kind_ok(in->out_kind)) return fail(CLG_E_INVALID_ARG, "the columns' out_kind %u", in->out_kind);
+  PlaceSpec ins[clg::kPackStreams];
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) ins[c] = {src.col[c], src.n[c] * clg::pack_elem(c), clg::pack_elem(c)};
+  clg::Placement pl;
+  const int st = place_in(e, e->d_packin, ins, clg::kPackStreams, in->out_kind, PlacePolicy::stage_if_unresolved, "stream", &pl);
+  if (st != CLG_OK) return clg::pack_layout(src.n, out), st;  // (a misaligned stream: the layout is filled, as pack_sizes fills it)
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) src.col[c] = pl.at<const void>(c);
   clg::PackIn pin{};
   CHK(pack_sizes(e, src, out, &pin));
   if (clg::pack_sizes_only(*out)) return CLG_OK;
@@ -4705,25 +4682,17 @@ int clg_columnize(clg_engine* e, const clg_decoded* in, const uint64_t* span_rec
                   clg_columns* out) {
   ENGINE_GUARD(e);
   if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
-  clg_decoded d = *in;
-  if (in->out_kind == CLG_MEM_MAPPED) {  // registered host memory: its device side
-    const uint64_t n = in->n_rec, w = in->n_wide;
-    const auto dev = [](void* p, uint64_t bytes, uintptr_t* a) {
-      *a = p && bytes ? clg_mapped_device_address(p, bytes) : uintptr_t(p);
-      return *a != 0 || !p;
-    };
-    uintptr_t a[8];
-    if (!(dev(d.tag, n, &a[0]) && dev(d.v0, n * 8, &a[1]) && dev(d.w_idx, w * 4, &a[2]) && dev(d.w_rc, w * 4, &a[3]) &&
-          dev(d.w_v1, w * 8, &a[4]) && dev(d.w_var_off, w * 4, &a[5]) && dev(d.w_var_len, w * 4, &a[6]) &&
-          dev(d.w_sub, w, &a[7])))
-      return fail(CLG_E_INVALID_ARG, "an input array is not inside memory registered with clg_host_register");
-    d.tag = reinterpret_cast<uint8_t*>(a[0]), d.v0 = reinterpret_cast<int64_t*>(a[1]);
-    d.w_idx = reinterpret_cast<uint32_t*>(a[2]), d.w_rc = reinterpret_cast<int32_t*>(a[3]);
-    d.w_v1 = reinterpret_cast<int64_t*>(a[4]), d.w_var_off = reinterpret_cast<uint32_t*>(a[5]);
-    d.w_var_len = reinterpret_cast<uint32_t*>(a[6]), d.w_sub = reinterpret_cast<uint8_t*>(a[7]);
-  } else if (in->out_kind != CLG_MEM_DEVICE) {
+  if (in->out_kind != CLG_MEM_DEVICE && in->out_kind != CLG_MEM_MAPPED)  // (host input is not staged here)
     return fail(CLG_E_INVALID_ARG, "the decoded batch must be device or registered memory (out_kind %u)", in->out_kind);
-  }
+  clg_decoded d = *in;
+  // registered host memory: its device side.  (Element size 1: the input's alignment is not checked.)
+  const uint64_t n = in->n_rec, w = in->n_wide;
+  const PlaceSpec ins[8] = {{d.tag, n, 1},       {d.v0, n * 8, 1},        {d.w_idx, w * 4, 1},     {d.w_rc, w * 4, 1},
+                            {d.w_v1, w * 8, 1},  {d.w_var_off, w * 4, 1}, {d.w_var_len, w * 4, 1}, {d.w_sub, w, 1}};
+  clg::Placement pl;
+  CHK(place_arrays(ins, 8, in->out_kind, PlacePolicy::reject_unresolved, "input", &pl));
+  d.tag = pl.at<uint8_t>(0), d.v0 = pl.at<int64_t>(1), d.w_idx = pl.at<uint32_t>(2), d.w_rc = pl.at<int32_t>(3);
+  d.w_v1 = pl.at<int64_t>(4), d.w_var_off = pl.at<uint32_t>(5), d.w_var_len = pl.at<uint32_t>(6), d.w_sub = pl.at<uint8_t>(7);
   return columnize_device(e, d, span_rec_base, n_spans, out);
 }
 
@@ -5145,58 +5114,28 @@ int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPl
   const uint64_t n = in->n_rec, *nc = in->n_class, nw = nc[clg::kColWide];
   const uint32_t ns = clg::ecol_spans(*in);
   const uint64_t rows_bad = clg::ecol_span_rows_bad(*in);
-  const bool has_pos = in->pos != nullptr, has_idx = in->w_idx != nullptr;
   // the arrays, in EcolIn's order: bytes, and element sizes for the alignment check
-  const void* src[13] = {in->tag,  in->order,     in->timestamp, in->rng,  in->buffer_built, in->w_rc, in->w_v1,
-                         in->w_var_len, in->w_sub, in->w_v0,     in->w_idx, in->pos,          in->var};
-  const size_t el[13] = {1, 1, 8, 4, 4, 4, 8, 4, 1, 8, 4, 8, 1};
-  const uint64_t cnt[13] = {n, nc[0], nc[1], nc[2], nc[3], nw, nw, nw, nw, nw, has_idx ? nw : 0, has_pos ? nw + 1 : 0,
-                            in->var ? in->n_var : 0};
-  uintptr_t dev[13];
-  size_t off[14], tot = 0;
-  for (int i = 0; i < 13; ++i) {
-    off[i] = tot;
-    if (!(dev_narrow && i < 5)) tot += clg_engine::al16(size_t(cnt[i]) * el[i]);
-    p->in_bytes += cnt[i] * el[i];
-  }
-  off[13] = tot;
+  PlaceSpec ins[13] = {{in->tag, n, 1},        {in->order, nc[0], 1},  {in->timestamp, nc[1] * 8, 8}, {in->rng, nc[2] * 4, 4},
+                       {in->buffer_built, nc[3] * 4, 4},                {in->w_rc, nw * 4, 4},         {in->w_v1, nw * 8, 8},
+                       {in->w_var_len, nw * 4, 4},                      {in->w_sub, nw, 1},            {in->w_v0, nw * 8, 8},
+                       {in->w_idx, nw * 4, 4}, {in->pos, (nw + 1) * 8, 8},                             {in->var, in->n_var, 1}};
+  for (const PlaceSpec& a : ins) p->in_bytes += a.p ? a.bytes : 0;
+  // registered arrays must be registered whole; host arrays are staged, an empty one too (a valid
+  // address, never read).  With dev_narrow the first five take no part (no slot, no lookup, no
+  // copy): they are absent from the placement, and their addresses are set behind it.
+  for (int i = 0; dev_narrow && i < 5; ++i) ins[i].p = nullptr;
   const size_t sb_bytes = in->n_spans ? size_t(ns + 1) * clg::kColClasses * 8 : 0;
-  const bool staged = in->in_kind == CLG_MEM_HOST;
-  CHK(e->d_ecolin.ensure((staged ? tot : 0) + sb_bytes + 16));
+  clg::Placement pl;
+  CHK(place_in(e, e->d_ecolin, ins, 13, in->in_kind, PlacePolicy::reject_unresolved, "encode columns: input", &pl, sb_bytes));
+  for (int i = 0; dev_narrow && i < 5; ++i) pl.dev[i] = uintptr_t(dev_narrow[i]);
+  const size_t o_sb = pl.staged() ? pl.total : 0;  // the span bases lie behind the staged arrays
+  if (!pl.staged()) CHK(e->d_ecolin.ensure(sb_bytes + 16));
   uint8_t* din = e->d_ecolin.as<uint8_t>();
-  const size_t o_sb = staged ? tot : 0;
-  for (int i = 0; i < 13; ++i) {
-    if (dev_narrow && i < 5) {
-      dev[i] = uintptr_t(dev_narrow[i]);
-      continue;
-    }
-    if (!src[i] || !cnt[i]) {
-      dev[i] = staged || !src[i] ? 0 : uintptr_t(src[i]);
-      if (staged && src[i]) dev[i] = uintptr_t(din + off[i]);  // (an empty array: a valid address, never read)
-      continue;
-    }
-    if (staged) {
-      HIPCHK(hipMemcpyAsync(din + off[i], src[i], size_t(cnt[i]) * el[i], hipMemcpyHostToDevice, e->stream));
-      dev[i] = uintptr_t(din + off[i]);
-    } else if (in->in_kind == CLG_MEM_MAPPED) {
-      dev[i] = clg_mapped_device_address(src[i], cnt[i] * el[i]);
-      if (!dev[i]) return fail(CLG_E_INVALID_ARG, "an input array is not inside memory registered with clg_host_register");
-    } else {
-      dev[i] = uintptr_t(src[i]);
-    }
-    if (dev[i] % el[i]) return fail(CLG_E_INVALID_ARG, "an input array is not aligned to its element");
-  }
-  if (!has_pos) dev[11] = 0;
-  if (!has_idx) dev[10] = 0;
-  if (!in->var) dev[12] = 0;
   clg::EcolIn& d = p->d;
-  d = clg::EcolIn{reinterpret_cast<const uint8_t*>(dev[0]),  reinterpret_cast<const int8_t*>(dev[1]),
-                  reinterpret_cast<const int64_t*>(dev[2]),  reinterpret_cast<const int32_t*>(dev[3]),
-                  reinterpret_cast<const int32_t*>(dev[4]),  reinterpret_cast<const int32_t*>(dev[5]),
-                  reinterpret_cast<const int64_t*>(dev[6]),  reinterpret_cast<const uint32_t*>(dev[7]),
-                  reinterpret_cast<const uint8_t*>(dev[8]),  reinterpret_cast<const int64_t*>(dev[9]),
-                  reinterpret_cast<const uint32_t*>(dev[10]), reinterpret_cast<const uint64_t*>(dev[11]),
-                  reinterpret_cast<const uint8_t*>(dev[12]), n, {nc[0], nc[1], nc[2], nc[3], nc[4]}, in->n_var};
+  d = clg::EcolIn{pl.at<const uint8_t>(0),  pl.at<const int8_t>(1),   pl.at<const int64_t>(2),  pl.at<const int32_t>(3),
+                  pl.at<const int32_t>(4),  pl.at<const int32_t>(5),  pl.at<const int64_t>(6),  pl.at<const uint32_t>(7),
+                  pl.at<const uint8_t>(8),  pl.at<const int64_t>(9),  pl.at<const uint32_t>(10), pl.at<const uint64_t>(11),
+                  pl.at<const uint8_t>(12), n, {nc[0], nc[1], nc[2], nc[3], nc[4]}, in->n_var};
   const uint64_t* d_sb = nullptr;
   if (sb_bytes && rows_bad == clg::kEcolNone) {
     HIPCHK(hipMemcpyAsync(din + o_sb, in->span_base, sb_bytes, hipMemcpyHostToDevice, e->stream));
@@ -5207,16 +5146,16 @@ int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPl
   const uint64_t n_tiles64 = (n + clg::kEcolTile - 1) / clg::kEcolTile;
   if (n_tiles64 > 0x7FFFFFFFull) return fail(CLG_E_INVALID_ARG, "%llu records in one call", (unsigned long long)n);
   const uint32_t nt = uint32_t(n_tiles64);
-  const size_t o_cnt = 0, o_base = clg_engine::al16(size_t(nt) * clg::kColCountWords * 4),
-               o_sum = o_base + clg_engine::al16(size_t(nt) * clg::kColClasses * 8), o_bad = o_sum + clg_engine::al16(size_t(nt) * 8),
-               o_bb = o_bad + clg_engine::al16(size_t(nt) * 8), w_end = o_bb + clg_engine::al16(size_t(nt) * 8);
-  CHK(e->d_ecolw.ensure(w_end + 16));
+  const uint64_t wb[5] = {uint64_t(nt) * clg::kColCountWords * 4, uint64_t(nt) * clg::kColClasses * 8, uint64_t(nt) * 8,
+                          uint64_t(nt) * 8, uint64_t(nt) * 8};
+  size_t wo[6];
+  CHK(e->d_ecolw.ensure(clg::place_layout(wb, 5, wo) + 16));
   uint8_t* wk = e->d_ecolw.as<uint8_t>();
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(wk + o_cnt);
-  uint64_t* d_base = reinterpret_cast<uint64_t*>(wk + o_base);
-  uint64_t* d_sum = reinterpret_cast<uint64_t*>(wk + o_sum);
-  uint64_t* d_bad = reinterpret_cast<uint64_t*>(wk + o_bad);
-  uint64_t* d_bbase = reinterpret_cast<uint64_t*>(wk + o_bb);
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(wk + wo[0]);
+  uint64_t* d_base = reinterpret_cast<uint64_t*>(wk + wo[1]);
+  uint64_t* d_sum = reinterpret_cast<uint64_t*>(wk + wo[2]);
+  uint64_t* d_bad = reinterpret_cast<uint64_t*>(wk + wo[3]);
+  uint64_t* d_bbase = reinterpret_cast<uint64_t*>(wk + wo[4]);
   const size_t o_eres = clg_engine::al16(sizeof(clg::ColRes)), o_so = o_eres + clg_engine::al16(sizeof(clg::EcolRes));
   CHK(e->h_ecolres.ensure(o_so + size_t(ns + 1) * 16));
   clg::ColRes* cres = e->h_ecolres.as<clg::ColRes>();
@@ -5264,14 +5203,12 @@ int encode_columns_checked(clg_engine* e, const clg_columns_in* in, clg_encoded*
   if (!out->bytes) return CLG_OK;  // sizes only
   if (out->cap < p.n_bytes) return fail(CLG_E_CAPACITY, "encode columns needs %llu bytes", (unsigned long long)p.n_bytes);
   if (!p.n_bytes) return CLG_OK;
-  uint8_t* dst = static_cast<uint8_t*>(out->bytes);
-  const bool direct = out->out_kind == CLG_MEM_DEVICE;
-  if (!direct) {  // host and registered memory alike: the edge byte stores stay off the link
-    CHK(e->d_ecolout.ensure(p.n_bytes + 16));
-    dst = e->d_ecolout.as<uint8_t>();
-  }
-  CHK(ecol_write(e, p, dst));
-  if (!direct) HIPCHK(hipMemcpyAsync(out->bytes, dst, p.n_bytes, hipMemcpyDeviceToHost, e->stream));
+  // host and registered memory alike go through staging: the edge byte stores stay off the link
+  const PlaceSpec dst[1] = {{out->bytes, p.n_bytes, 1}};
+  clg::Placement pl;
+  CHK(place_out(e->d_ecolout, dst, 1, out->out_kind, PlacePolicy::stage_unless_device, "output", &pl));
+  CHK(ecol_write(e, p, pl.at<uint8_t>(0)));
+  CHK(stage_out(e, dst, 1, pl));
   return e->sync();
 }
 
@@ -5283,8 +5220,7 @@ int append_columns_checked(clg_engine* e, const uint32_t* log, const int64_t* ep
 int clg_encode_columns(clg_engine* e, const clg_columns_in* in, clg_encoded* out) {
   ENGINE_GUARD(e);
   if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
-  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
   return encode_columns_checked(e, in, out, nullptr);
 }
 
@@ -5378,27 +5314,11 @@ namespace {
 int unpack_input(clg_engine* e, const clg_packed* in, clg::UnpackIn* uin) {
   const uint64_t nb = in->blk_base[clg::kPackStreams], nbits = in->n_bits;
   if (nb >> 31) return fail(CLG_E_INVALID_ARG, "%llu blocks in one call", (unsigned long long)nb);
-  if (in->out_kind != CLG_MEM_HOST && in->out_kind != CLG_MEM_DEVICE && in->out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "the packed input's out_kind %u", in->out_kind);
-  if (in->out_kind != CLG_MEM_HOST && (uintptr_t(in->desc) % 8 || uintptr_t(in->bits) % 16))
-    return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
-  const clg_pack_block* ddesc = in->desc;
-  const uint8_t* dbits = in->bits;
-  bool staged = in->out_kind == CLG_MEM_HOST;
-  if (in->out_kind == CLG_MEM_MAPPED) {
-    ddesc = nb ? reinterpret_cast<const clg_pack_block*>(clg_mapped_device_address(in->desc, nb * sizeof(clg_pack_block))) : nullptr;
-    dbits = nbits ? reinterpret_cast<const uint8_t*>(clg_mapped_device_address(in->bits, nbits)) : nullptr;
-    if ((nb && !ddesc) || (nbits && !dbits)) staged = true;  // (not wholly inside one registered range)
-  }
-  if (staged) {
-    const size_t db = clg_engine::al16(size_t(nb) * sizeof(clg_pack_block));
-    CHK(e->d_unpackin.ensure(db + nbits + 16));
-    if (nb) HIPCHK(hipMemcpyAsync(e->d_unpackin.p, in->desc, nb * sizeof(clg_pack_block), hipMemcpyHostToDevice, e->stream));
-    if (nbits) HIPCHK(hipMemcpyAsync(e->d_unpackin.as<uint8_t>() + db, in->bits, nbits, hipMemcpyHostToDevice, e->stream));
-    ddesc = e->d_unpackin.as<clg_pack_block>();
-    dbits = e->d_unpackin.as<uint8_t>() + db;
-  }
-  uin->desc = ddesc, uin->bits = dbits, uin->n_bits = nbits;
+  CHK(pack_out_check(*in, "the packed input's "));
+  const PlaceSpec ins[2] = {{in->desc, nb * sizeof(clg_pack_block), 8}, {in->bits, nbits, 16}};
+  clg::Placement pl;
+  CHK(place_in(e, e->d_unpackin, ins, 2, in->out_kind, PlacePolicy::stage_if_unresolved, "packed input", &pl));
+  uin->desc = pl.at<const clg_pack_block>(0), uin->bits = pl.at<const uint8_t>(1), uin->n_bits = nbits;
   for (uint32_t c = 0; c < clg::kPackStreams; ++c) uin->n[c] = in->n_val[c];
   for (uint32_t c = 0; c <= clg::kPackStreams; ++c) uin->blk_base[c] = in->blk_base[c];
   return CLG_OK;
@@ -5459,9 +5379,10 @@ int unpack_for_encode(clg_engine* e, const clg_packed* narrow, const clg_columns
     }
   clg::UnpackIn uin{};
   CHK(unpack_input(e, narrow, &uin));
-  uint64_t at[clg::kPackStreams + 1] = {0};
-  for (uint32_t c = 0; c < clg::kPackStreams; ++c) at[c + 1] = clg_engine::al16(at[c] + narrow->n_val[c] * clg::pack_elem(c));
-  CHK(e->d_unpackcol.ensure(at[clg::kPackStreams] + 16));
+  uint64_t cb[clg::kPackStreams];
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) cb[c] = narrow->n_val[c] * clg::pack_elem(c);
+  size_t at[clg::kPackStreams + 1];
+  CHK(e->d_unpackcol.ensure(clg::place_layout(cb, clg::kPackStreams, at) + 16));
   clg::UnpackOut uout{};
   for (uint32_t c = 0; c < clg::kPackStreams; ++c) col[c] = uout.col[c] = e->d_unpackcol.as<uint8_t>() + at[c];
   CHK(unpack_check(e, uin, bad));
@@ -5486,33 +5407,19 @@ int clg_unpack_columns(clg_engine* e, const clg_packed* in, clg_columns* out, cl
   const int st = clg::pack_unpack_begin(in, out, bad, &done, &what);
   if (st != CLG_OK) return fail(st, "unpack columns: %s", what);
   if (done) return CLG_OK;
-  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
   const clg::UnpackDst dst = clg::unpack_dst(*out);
-  clg::UnpackOut uout{};
-  bool staged = out->out_kind == CLG_MEM_HOST;
-  for (uint32_t c = 0; c < clg::kPackStreams && !staged; ++c) {
-    if (!in->n_val[c]) continue;
-    if (uintptr_t(dst.col[c]) % clg::pack_elem(c)) return fail(CLG_E_INVALID_ARG, "column %u is not aligned to its element", c);
-    uout.col[c] = dst.col[c];
-    if (out->out_kind == CLG_MEM_MAPPED &&
-        !(uout.col[c] = reinterpret_cast<void*>(clg_mapped_device_address(dst.col[c], in->n_val[c] * clg::pack_elem(c)))))
-      staged = true;  // (not wholly inside one registered range)
-  }
+  PlaceSpec outs[clg::kPackStreams];
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) outs[c] = {dst.col[c], in->n_val[c] * clg::pack_elem(c), clg::pack_elem(c)};
+  clg::Placement pl;
+  CHK(place_out(e->d_unpackout, outs, clg::kPackStreams, out->out_kind, PlacePolicy::stage_if_unresolved, "column", &pl));
   clg::UnpackIn uin{};
   CHK(unpack_input(e, in, &uin));
-  uint64_t at[clg::kPackStreams + 1] = {0};
-  if (staged) {
-    for (uint32_t c = 0; c < clg::kPackStreams; ++c) at[c + 1] = clg_engine::al16(at[c] + in->n_val[c] * clg::pack_elem(c));
-    CHK(e->d_unpackout.ensure(at[clg::kPackStreams] + 16));
-    for (uint32_t c = 0; c < clg::kPackStreams; ++c) uout.col[c] = e->d_unpackout.as<uint8_t>() + at[c];
-  }
+  clg::UnpackOut uout{};
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) uout.col[c] = pl.at<void>(c);
   CHK(unpack_check(e, uin, bad));
   CHK(unpack_write(e, uin, uout));
-  if (staged)
-    for (uint32_t c = 0; c < clg::kPackStreams; ++c)
-      if (in->n_val[c])
-        HIPCHK(hipMemcpyAsync(dst.col[c], uout.col[c], in->n_val[c] * clg::pack_elem(c), hipMemcpyDeviceToHost, e->stream));
+  CHK(stage_out(e, outs, clg::kPackStreams, pl));
   return e->sync();
 }
 
@@ -5526,8 +5433,7 @@ int clg_encode_columns_packed(clg_engine* e, const clg_packed* narrow, const clg
                               clg_unpack_bad* bad) {
   ENGINE_GUARD(e);
   if (!narrow || !rest || !out) return fail(CLG_E_INVALID_ARG, "null argument");
-  if (out->out_kind != CLG_MEM_HOST && out->out_kind != CLG_MEM_DEVICE && out->out_kind != CLG_MEM_MAPPED)
-    return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
   clg::ecol_reset_result(out);
   const void* col[clg::kPackStreams];
   CHK(unpack_for_encode(e, narrow, rest, bad, col));
