@@ -2032,16 +2032,20 @@ __device__ __forceinline__ bool wrong_entry(const FusedCtl& ctl, uint32_t c, uin
 }
 
 // Chunk c's request (k_decode_repair).  *walk_end: past the last tile a walk reached.
+// Returns false when its walk gave up (kZAbortExit): the span goes to the robust pipeline, and
+// from there on nothing of the span is known to lie on the true chain -- the tiles past the
+// walk keep the exits and failures of the chain that entered wrong, so neither check_chunk
+// nor a later chunk's walk (which would start from such an exit) may take a failure for real.
 template <bool J>
-__device__ __forceinline__ void serve_chunk(const TileDesc* __restrict__ tiles, const SpanDesc* __restrict__ spans,
+__device__ __forceinline__ bool serve_chunk(const TileDesc* __restrict__ tiles, const SpanDesc* __restrict__ spans,
                                             const FusedCtl& ctl, uint32_t* s_img, uint32_t* s_j, uint32_t lane,
                                             uint32_t c, uint32_t f, uint32_t ce, uint32_t* walk_end) {
-  if (f == 0 || f >= ce || tiles[f].span_off == 0) return;  // the chunk starts its span
+  if (f == 0 || f >= ce || tiles[f].span_off == 0) return true;  // the chunk starts its span
   if (f >= *walk_end) {  // (else a walk has rewritten this chunk's entry already)
     const uint64_t xe = ld_agent(&ctl.ex[f - 1]);
     if (!(xe & kZExValid)) {  // the tile before failed: its span (this chunk's first) is bad
       if (lane == 0) mark_bad(ctl, kZAbortBad, f - 1, tiles[f].span);
-      return;
+      return true;
     }
     uint64_t xs = xe & ~kZExValid;
     // the entry the chunk took (or, never stored, the published exit it would have taken)
@@ -2100,13 +2104,14 @@ __device__ __forceinline__ void serve_chunk(const TileDesc* __restrict__ tiles, 
               ctl.dbg[kZDbgWalkDisagree] = disagree;
             }
           }
-          break;
+          return false;
         }
         xs = x;
       }
     }
   }
   check_chunk(ctl, tiles, f, ce, lane);  // its failures past the walk are real
+  return true;
 }
 
 // Pass 1 kernel.  Persistent grid (at most what the device keeps resident, see
@@ -2290,7 +2295,7 @@ __global__ __launch_bounds__(64) void k_decode_repair(const TileDesc* __restrict
       // it failed, and its span is bad already
       if (lane == 0 && (ld_agent(&ctl.ex[f - 1]) & kZExValid)) atomicAdd(ctl.rep + kZRepServed, 1u);
     }
-    serve_chunk<J>(tiles, spans, ctl, s_img, s_j, lane, c, f, ce, &walk_end);
+    if (!serve_chunk<J>(tiles, spans, ctl, s_img, s_j, lane, c, f, ce, &walk_end)) break;  // the span goes robust
   }
 }
 

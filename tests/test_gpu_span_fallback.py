@@ -15,10 +15,9 @@ import numpy as np
 import pytest
 
 import _oracle as O
-from clonos_amd import Engine, _lib, synth
+from clonos_amd import Engine, synth
 from clonos_amd import determinants as D
-from clonos_amd._lib import lib
-from clonos_amd.engine import _np_ptr
+from _decode_util import _raw_decode, check_spans_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -36,35 +35,6 @@ def _corrupt(b: bytes, offs, rng, kind: int) -> bytes:
     r = bytearray(D.encode(D.TimerTriggerDeterminant(1, 2, 6, b"abcd")))  # a negative name length
     r[14:18] = (0xFFFFFFF0).to_bytes(4, "big")
     return b[:k] + bytes(r) + b[k:]
-
-
-def _raw_decode(eng, blob, spans):
-    buf = np.frombuffer(blob, np.uint8)
-    so = np.array([s[0] for s in spans], np.uint64)
-    sl = np.array([s[1] for s in spans], np.uint64)
-    cap, wcap = int(sl.sum()) // 2 + len(spans) + 1, int(sl.sum()) // 6 + len(spans) + 1
-    d, arrs = Engine._host_outputs(cap, wcap)
-    base = np.zeros(len(spans) + 1, np.uint64)
-    st = lib.clg_decode_host(eng.handle, _np_ptr(buf), _np_ptr(so), _np_ptr(sl), len(spans), _lib.C.byref(d),
-                             _np_ptr(base))
-    nr, nw = d.n_rec, d.n_wide
-    return (st, d.err_status, d.err_span, d.err_off, d.err_tag, nr, nw,
-            {k: v[:nr if k in ("off", "tag", "v0") else nw].copy() for k, v in arrs.items()}, base.copy())
-
-
-def check_spans_oracle(a, spans_b, key):
-    rec0, recs = a[8], a[7]
-    widx = recs["w_idx"].astype(np.int64)
-    for s, b in enumerate(spans_b):
-        st, rr, eo, _ = O.decode(b)
-        lo, hi = int(rec0[s]), int(rec0[s + 1])
-        assert hi - lo == len(rr["tag"]), (key, s, st)
-        for f in ("off", "tag", "v0"):
-            np.testing.assert_array_equal(recs[f][lo:hi], rr[f], err_msg=f"{key} span {s} {f}")
-        w = (widx >= lo) & (widx < hi)
-        np.testing.assert_array_equal(widx[w] - lo, rr["w_idx"].astype(np.int64), err_msg=f"{key} span {s} w_idx")
-        for f in ("w_rc", "w_v1", "w_var_off", "w_var_len", "w_sub"):
-            np.testing.assert_array_equal(recs[f][w], rr[f], err_msg=f"{key} span {s} {f}")
 
 
 @pytest.mark.parametrize("n_spans,every", [(60, 3), (600, 5)])
