@@ -20,6 +20,7 @@ SOURCES = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
     os.path.join(ROOT, "include", "clonos_engine.h")]
 ARCH = os.environ.get("CLONOS_OFFLOAD_ARCH", "gfx950")
+MAX_COMPILES = 16  # hipcc processes in flight at most
 
 
 def hipcc() -> str:
@@ -55,11 +56,11 @@ def _compile_cmd(src: str, obj: str) -> list:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every source whose object is older than it or any header (all of them with
-    force), in parallel, then link."""
+    force), MAX_COMPILES at a time, then link."""
     if not force and not needs_build():
         return LIB
     hdr_t = max(os.path.getmtime(h) for h in HEADERS)
-    objs, procs = [], []
+    objs, procs, bad = [], [], []
     for src in SOURCES:
         obj = os.path.join(CSRC, os.path.basename(src) + ".o")
         objs.append(obj)
@@ -68,8 +69,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         cmd = _compile_cmd(src, obj)
         if verbose:
             print(" ".join(cmd), flush=True)
+        if len(procs) == MAX_COMPILES:  # the running set is full: wait for its oldest
+            done_src, p = procs.pop(0)
+            if p.wait() != 0:
+                bad.append(done_src)
         procs.append((src, subprocess.Popen(cmd)))
-    bad = [src for src, p in procs if p.wait() != 0]
+    bad += [src for src, p in procs if p.wait() != 0]
     if bad:
         raise RuntimeError(f"hipcc failed for {bad}")
     link = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs

@@ -478,7 +478,7 @@ __device__ __forceinline__ uint32_t warm_len(uint32_t tg) {
 // records: a wide record on it is a skip, which spec_bad puts before the merge's meeting
 // point, so the true walk (full rules) crosses every wide record of the region itself and
 // the result is the same; only its cost grows with wide records, which is why the host
-// turns it off for batches that hold many (engine.cpp lean_hint).
+// turns it off for batches that hold many (lean_hint, engine_decode.cpp).
 // ---------------------------------------------------------------------------------
 template <bool SAFE>
 __device__ __forceinline__ SpecR lean_walk(const uint32_t* T, uint32_t ws, uint32_t rs, uint32_t re, uint32_t end_a,

@@ -1,4 +1,4 @@
-// kernels.h -- descriptors shared by the host engine (engine.cpp) and the gfx950
+// kernels.h -- descriptors shared by the host engine (engine*.cpp) and the gfx950
 // kernels (kernels.hip).  Plain structs, no HIP types.
 #pragma once
 #include <stddef.h>

@@ -14,22 +14,23 @@ Geometry restated from the C++ (each with its source):
   three-pass fast path, kTile = 16384 (kernels.h:24) for the robust path.  kZHalo = 64
   (kernels.h:217), kZJHalo = 1024 (decode_fused.hip:2499).
 
-  Host staging (stage_spans, engine.cpp:1036-1057).  The bytes [lo, hi) of the blob, lo the
+  Host staging (stage_spans, engine_gather.cpp).  The bytes [lo, hi) of the blob, lo the
   lowest start of a non-empty span and hi the highest end, are copied to the start of one
   device buffer, gaps between spans included.  The buffer is 16-byte aligned, so a span at
   blob offset o is staged at an address whose low four bits are (o - lo) & 15: `delta`.
 
-  Tile plan of a host span (plan_host_span, engine.cpp:1367-1382).  The first tile takes
+  Tile plan of a host span (plan_host_span, engine_decode.cpp).  The first tile takes
   T - delta bytes, later tiles T (their delta is 0), the last one what is left.
 
-  Tile window of a log (tile_unit, engine.cpp:1361-1365).  U = min(C, T) when one of C, T
+  Tile window of a log (tile_unit, engine_decode.cpp).  U = min(C, T) when one of C, T
   divides the other, else 0.
 
-  Tile plan of a log span, U != 0 (plan_log_span, engine.cpp:1387-1397; the device expands
-  it).  Tiles are cut at the multiples of U of the physical offset.
+  Tile plan of a log span, U != 0 (plan_log_span's device planning, engine_decode.cpp;
+  the device expands it).  Tiles are cut at the multiples of U of the physical offset.
 
-  Tile plan of a log span, U == 0 (plan_log_span, engine.cpp:1399-1419), e.g. C = 48.  Tiles
-  are cut per segment, and a segment part longer than T - delta again at T - delta.
+  Tile plan of a log span, U == 0 (plan_log_span's host-built tiles, engine_decode.cpp),
+  e.g. C = 48.  Tiles are cut per segment, and a segment part longer than T - delta again at
+  T - delta.
 
   Halo branch of a tile (StageGeom, decode_fused.hip:747-763; stage_finish, :795-887).
   after = span offset of the tile's end, halo = min(span length - after, H), H = 64 for the
@@ -45,9 +46,10 @@ Geometry restated from the C++ (each with its source):
   kernel (:2322) pass n1 with H = 64; phase 3 (:2507) passes n1 with H = 1024; the count
   pass's chunk-exit staging (:2142) passes no n1 with H = 64.
 
-  Small path (engine.cpp:2155-2175, kernels.h:471-474).  A batch of at most 1 MiB,
-  kZSmallSpans = 4096 spans and kZSmallTilesMax = 4096 tiles; a plan of at most 64 tiles
-  and 64 spans goes in the kernel argument, a larger one through memory.
+  Small path (small_ok, engine_decode.cpp; kSmallBytes, engine_impl.h; kernels.h:471-474).
+  A batch of at most 1 MiB, kZSmallSpans = 4096 spans and kZSmallTilesMax = 4096 tiles; a
+  plan of at most 64 tiles and 64 spans goes in the kernel argument, a larger one through
+  memory.
 """
 import struct
 from collections import namedtuple

@@ -3,6 +3,8 @@ and fails loudly (no CPU fallback) when no GPU is visible."""
 import ctypes
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 
@@ -23,6 +25,17 @@ def test_library_exports_header_symbols():
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing
     assert sorted(_lib.EXPORTED) == names
+
+
+@pytest.mark.skipif(not sys.platform.startswith("linux"), reason="reads the dynamic symbol table with nm")
+def test_library_exports_nothing_the_header_does_not_declare():
+    from clonos_amd import _lib
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = sorted({line.split()[-1] for line in out.splitlines() if re.fullmatch(r"clg_[a-z0-9_]+", line.split()[-1])})
+    assert len(exported) >= 30
+    declared = set(header_functions())
+    extra = [n for n in exported if n not in declared]
+    assert not extra, extra
 
 
 def test_abi_version_and_struct_sizes():

@@ -640,7 +640,7 @@ def test_many_span_decode_chunked_on_host_threads():
 @pytest.mark.parametrize("case", ["error", "serializable"])
 def test_many_span_staged_plan_fallbacks(case):
     """A 9000-log decode whose plan is staged straight into the decode slot's pinned buffer
-    (engine.cpp plan_parallel, DecodePlan::staged), synchronous and queued, when the fast run
+    (plan_parallel, engine_decode.cpp; DecodePlan::staged), synchronous and queued, when the fast run
     aborts and the fallbacks plan the batch again from its builder: a decode error in one log
     (the oracle's status, span, offset and tag; kept on the fast path or decoded by the per-span
     fallback), or Serializable records in a few logs while the engine's last batches had none

@@ -5,7 +5,7 @@ length) is decoded three ways:
     position and the records before it, k_err_classify confirms the error by the full rules,
     no robust decode -- decode_kept_errors);
   * the fast path with errors not kept (CLONOS_KEEP_ERRORS=0): every bad span in ONE robust
-    run, the records placed by one kernel (engine.cpp span_fallback, k_sf_place);
+    run, the records placed by one kernel (span_fallback, engine_decode.cpp; k_sf_place);
   * the robust pipeline alone.
 Every output array, every span's record base and the first error (status, span, offset, tag)
 are identical, and the oracle agrees with each good span.  SimpleDeterminantEncoder.decodeNext

@@ -14,12 +14,13 @@ else
   src=/tmp/ab_wt_$name; rm -rf "$src"; mkdir -p "$src"
   git -C "$root" archive "$rev" clonos_amd include | tar -x -C "$src"
 fi
-objs=(); pids=()
+objs=(); pids=(); waited=0
 for p in $(ls "$src"/clonos_amd/csrc/*.cpp "$src"/clonos_amd/csrc/*.hip | LC_ALL=C sort); do
   o=/tmp/ab_${name}_$(basename "$p").o
+  if [ $((${#pids[@]} - waited)) -ge 16 ]; then wait "${pids[$waited]}"; waited=$((waited + 1)); fi  # 16 compiles in flight at most
   /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w ${AB_DEFS:-} -I "$src/include" -c "$p" -o "$o" &
   pids+=($!); objs+=("$o")
 done
-for pid in "${pids[@]}"; do wait "$pid"; done
+for pid in "${pids[@]:$waited}"; do wait "$pid"; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/ab/lib$name.so" "${objs[@]}"
 echo "$root/ab/lib$name.so"
