@@ -334,6 +334,22 @@ bool clg_engine::mapped_direct(const clg_decoded& out) {
          mapped_outputs(out, nullptr);
 }
 
+int clg_engine::scratch_out(size_t cap, size_t wcap, clg::DecodeOut* o) {
+  CHK(d_o_off.ensure(cap * 4));
+  CHK(d_o_tag.ensure(cap));
+  CHK(d_o_v0.ensure(cap * 8));
+  CHK(d_o_widx.ensure(wcap * 4));
+  CHK(d_o_wrc.ensure(wcap * 4));
+  CHK(d_o_wv1.ensure(wcap * 8));
+  CHK(d_o_wvo.ensure(wcap * 4));
+  CHK(d_o_wvl.ensure(wcap * 4));
+  CHK(d_o_wsub.ensure(wcap));
+  *o = clg::DecodeOut{d_o_off.as<uint32_t>(), d_o_tag.as<uint8_t>(), d_o_v0.as<int64_t>(), d_o_widx.as<uint32_t>(),
+                     d_o_wrc.as<int32_t>(), d_o_wv1.as<int64_t>(), d_o_wvo.as<uint32_t>(), d_o_wvl.as<uint32_t>(),
+                     d_o_wsub.as<uint8_t>(), 0, 0};
+  return CLG_OK;
+}
+
 int clg_engine::prep_out(clg_decoded* out, clg::DecodeOut* o) {
   const bool dev = out->out_kind == CLG_MEM_DEVICE;
   if (mapped_direct(*out)) {
@@ -344,19 +360,8 @@ int clg_engine::prep_out(clg_decoded* out, clg::DecodeOut* o) {
     *o = clg::DecodeOut{out->off, out->tag, out->v0, out->w_idx, out->w_rc, out->w_v1, out->w_var_off,
                        out->w_var_len, out->w_sub, out->cap, out->wcap};
   } else {
-    const size_t cap = std::max<uint64_t>(1, out->cap), wcap = std::max<uint64_t>(1, out->wcap);
-    CHK(d_o_off.ensure(cap * 4));
-    CHK(d_o_tag.ensure(cap));
-    CHK(d_o_v0.ensure(cap * 8));
-    CHK(d_o_widx.ensure(wcap * 4));
-    CHK(d_o_wrc.ensure(wcap * 4));
-    CHK(d_o_wv1.ensure(wcap * 8));
-    CHK(d_o_wvo.ensure(wcap * 4));
-    CHK(d_o_wvl.ensure(wcap * 4));
-    CHK(d_o_wsub.ensure(wcap));
-    *o = clg::DecodeOut{d_o_off.as<uint32_t>(), d_o_tag.as<uint8_t>(), d_o_v0.as<int64_t>(), d_o_widx.as<uint32_t>(),
-                       d_o_wrc.as<int32_t>(), d_o_wv1.as<int64_t>(), d_o_wvo.as<uint32_t>(), d_o_wvl.as<uint32_t>(),
-                       d_o_wsub.as<uint8_t>(), out->cap, out->wcap};
+    CHK(scratch_out(std::max<uint64_t>(1, out->cap), std::max<uint64_t>(1, out->wcap), o));
+    o->cap = out->cap, o->wcap = out->wcap;
   }
   return CLG_OK;
 }

@@ -228,6 +228,21 @@ struct Log {
   std::unordered_map<ChKey, Consumer, ChKeyHash> consumers;
 };
 
+// The bytes [at, at + n) of a log split at the ends of its segments of C bytes, in order:
+// f(seg_index, seg_off, take, more) per chunk, `more` on all but the last.  No chunk for n == 0.
+template <class F>
+inline void for_each_chunk(uint32_t at, uint32_t n, uint32_t C, F&& f) {
+  while (n) {
+    const uint32_t si = at / C, so = at % C;
+    const uint32_t take = std::min(n, C - so);
+    f(si, so, take, n > take);
+    at += take;
+    n -= take;
+  }
+}
+// How many chunks that is: at most n / C + 2.
+inline uint32_t chunk_count(uint32_t at, uint32_t n, uint32_t C) { return n ? (at + n - 1) / C - at / C + 1 : 0u; }
+
 // In-flight (data) log of one subpartition (InMemorySubpartitionInFlightLogger.java:28-207):
 // SortedMap<epoch, List<Buffer>>; each buffer's bytes occupy whole pool segments.
 struct IflBuf {

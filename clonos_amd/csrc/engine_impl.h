@@ -302,6 +302,22 @@ struct clg_engine {
 
   uint32_t C() const { return cfg.segment_bytes; }
   uint8_t* seg_addr(uint32_t s) const { return pool + size_t(s) * C(); }
+  // The scatter chunks that write n source bytes from offset src on at [at, at + n) of log l, whose
+  // segments are attached: one per segment touched (for_each_chunk), written from ch on; returns the
+  // place behind them.  Inline: a config-4 step builds 66 k requests' chunks.
+  clg::ScatterChunk* add_chunks(clg::ScatterChunk* ch, const Log& l, uint32_t at, uint32_t n, uint64_t src) const {
+    for_each_chunk(at, n, C(), [&](uint32_t si, uint32_t so, uint32_t take, bool more) {
+      *ch++ = clg::ScatterChunk{seg_addr(l.segs[si]) + so, src, take, life_word(l.segs[si], more)};
+      src += take;
+    });
+    return ch;
+  }
+  // The n chunks in h_desc uploaded to d_desc and their scatter of `total` bytes from d_src queued
+  // under the stat `name` (side: with the write path's side car).  The caller waits as it needs to.
+  int scatter_chunks(const char* name, size_t n, uint64_t total, const uint8_t* d_src, bool side);
+  // The nine d_o_* decode scratch arrays grown to cap records and wcap wide rows, and their
+  // addresses in o (o->cap, o->wcap are the caller's to set).
+  int scratch_out(size_t cap, size_t wcap, clg::DecodeOut* o);
   hipEvent_t get_event();
   template <class F>
   int timed(const char* name, uint64_t bytes, F&& launch, hipStream_t on = nullptr) {
@@ -698,5 +714,18 @@ struct LogGuard {
 #define LOG_GUARD(e, h)                                    \
   if (!(e)) return fail(CLG_E_INVALID_ARG, "null engine"); \
   LogGuard lguard_((e), (h))
+
+// The decodes into typed columns (engine_columns.cpp), which replay preparation's columns form
+// (engine_replay.cpp) runs once per batch: `run` decodes into the arrays it is given, `spans_of`
+// gives the decoded spans to the payload gather.
+struct ColKeep;
+namespace clg {
+struct PaySpan;
+}
+using DecodeRun = std::function<int(clg_decoded*, uint64_t*)>;
+using PaySpansOf = std::function<int(std::vector<clg::PaySpan>&, std::vector<uint32_t>&)>;
+int decode_columns(clg_engine* e, const DecodeRun& run, uint32_t n_spans, clg_columns* out, ColKeep* keep = nullptr);
+int decode_columns_var(clg_engine* e, const DecodeRun& run, uint32_t n, clg_columns* out, clg_payloads* var,
+                       const PaySpansOf& spans_of);
 
 #pragma GCC visibility pop

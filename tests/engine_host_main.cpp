@@ -1,6 +1,7 @@
 // engine_host_main.cpp -- stand-alone checks of the engine's host containers
 // (clonos_amd/csrc/engine_host.h): EpochMap and SegList against std::map / std::vector models
-// over random operations, EpochAlloc across threads, EngineLock, WorkPool.  Built by
+// over random operations, EpochAlloc across threads, EngineLock, WorkPool; and of the split of a
+// byte range at segment ends (for_each_chunk, chunk_count) against a byte-by-byte model.  Built by
 // tests/test_engine_host.py with the address + undefined-behaviour sanitizers and again with
 // the thread sanitizer; exits 0 and writes nothing to stderr when all holds.
 #include <atomic>
@@ -302,7 +303,43 @@ static void test_work_pool(unsigned n, int calls) {
   REQUIRE(sum.load() == want + 10 * n);
 }
 
+// ---------------------------------------------------------------- for_each_chunk, chunk_count
+// Against a byte-by-byte model: the bytes of [at, at + n) taken one at a time, a byte opening a
+// new chunk when it is the first one or lies at a multiple of C.  (For one `at` the model of n
+// is the model of n - 1 and one more byte.)
+static void test_chunks(uint32_t C) {
+  struct Chunk {
+    uint32_t start, len;
+  };
+  for (uint32_t at = 0; at <= 2 * C + 1; ++at) {
+    std::vector<Chunk> model;
+    for (uint32_t n = 0; n <= 3 * C + 1; ++n) {
+      if (n) {
+        const uint32_t b = at + n - 1;
+        if (model.empty() || b % C == 0) model.push_back(Chunk{b, 1});
+        else ++model.back().len;
+      }
+      size_t k = 0;
+      uint32_t next = at;
+      bool last_seen = false;
+      for_each_chunk(at, n, C, [&](uint32_t si, uint32_t so, uint32_t take, bool more) {
+        REQUIRE(k < model.size() && !last_seen);
+        REQUIRE(take > 0 && so < C && so + take <= C);  // inside one segment
+        REQUIRE(si * C + so == next && next == model[k].start && take == model[k].len);  // in order, no gap or overlap
+        REQUIRE(more == (k + 1 != model.size()));
+        last_seen = !more;
+        next += take;
+        ++k;
+      });
+      REQUIRE(k == model.size() && next == at + n);
+      REQUIRE((n == 0) == (k == 0) && (k == 0 || last_seen));
+      REQUIRE(chunk_count(at, n, C) == k && k <= n / C + 2);
+    }
+  }
+}
+
 int main() {
+  for (uint32_t C : {16u, 64u, 256u}) test_chunks(C);
   for (uint32_t seed = 1; seed <= 4; ++seed) test_epoch_map(seed, 6000);
   for (uint32_t seed = 1; seed <= 4; ++seed) test_seg_list(seed, 4000);
   test_epoch_alloc();
