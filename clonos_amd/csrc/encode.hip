@@ -13,12 +13,15 @@
 //  * k_enc_write  per block: record lengths -> LDS scan -> records assembled in LDS
 //                 (big-endian fields) -> coalesced byte stores; blocks whose bytes do not
 //                 fit the LDS buffer (long payloads) store directly
+// Errors (the engine, CLG_E_INVALID_ARG, nothing written): *bad_index is the lowest invalid
+// record; with every record valid but more side rows given than the wide records use, it is n.
 // Memory-bound: reads 9 B per record (+ 25 B per wide record and the payloads), writes
 // the encoded bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/clonos_engine.h"
+#include "encode_columns.h"
 #include "kernels.h"
 
 namespace clg {
@@ -43,6 +46,12 @@ __device__ __forceinline__ uint64_t enc_len(const EncodeIn& in, uint32_t tg, uin
     case CLG_TAG_SERIALIZABLE: return 1ull + in.w_var_len[w];
     default: return 0;  // invalid tag: flagged by k_enc_sums
   }
+}
+
+// Side row w of a record with tag tg: where the format carries a payload, its range lies inside
+// var (encode_columns.h's rule; rows without a payload do not read w_var_off / w_var_len).
+__device__ __forceinline__ bool enc_payload_ok(const EncodeIn& in, uint32_t tg, uint64_t w) {
+  return !ecol_has_payload(tg, in.w_sub[w]) || ecol_row_ok(in.w_var_off[w], in.w_var_len[w], in.var_len);
 }
 
 // Wide records per block (their side-table rows are consecutive, in record order).
@@ -92,8 +101,8 @@ __global__ __launch_bounds__(1024) void k_enc_scan(uint32_t* __restrict__ wsum, 
 }
 
 // Per block: record lengths (side rows from the wide prefix) and their block total;
-// *bad = lowest invalid record (tag > 7, or a wide record whose side row names another
-// record), ~0 if none.
+// *bad = lowest invalid record (tag > 7, or a wide record that has no side row, whose side row
+// names another record, or whose payload range passes var), ~0 if none.
 __global__ __launch_bounds__(kEncThreads) void k_enc_bytes(EncodeIn in, const uint64_t* __restrict__ wbase,
                                                          uint64_t* __restrict__ bsum, uint32_t* __restrict__ bad) {
   __shared__ uint32_t s_w[kEncThreads];
@@ -120,7 +129,7 @@ __global__ __launch_bounds__(kEncThreads) void k_enc_bytes(EncodeIn in, const ui
   for (uint32_t k = 0; k < kEncPer; ++k) {
     if (i0 + k >= in.n) break;
     const bool wd = enc_wide(tg[k]);
-    if (tg[k] > 7u || (wd && (w >= in.n_wide || in.w_idx[w] != i0 + k))) {
+    if (tg[k] > 7u || (wd && (w >= in.n_wide || in.w_idx[w] != i0 + k || !enc_payload_ok(in, tg[k], w)))) {
       atomicMin(bad, (uint32_t)min(i0 + k, (uint64_t)0xFFFFFFFEu));
       break;
     }

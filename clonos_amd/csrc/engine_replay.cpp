@@ -333,7 +333,8 @@ int clg_encode_batch(clg_engine* e, const clg_encode_in* in, void* out, uint64_t
   if (bad_index) *bad_index = UINT64_MAX;
   if (in->n == 0) return CLG_OK;
   const uint64_t n = in->n, nw = in->n_wide;
-  clg::EncodeIn d{in->tag, in->v0, in->w_idx, in->w_rc, in->w_v1, in->w_var_off, in->w_var_len, in->w_sub, in->var, n, nw};
+  clg::EncodeIn d{in->tag,       in->v0,    in->w_idx, in->w_rc, in->w_v1, in->w_var_off,
+                  in->w_var_len, in->w_sub, in->var,   n,        nw,       in->var_len};
   if (in->in_kind != CLG_MEM_DEVICE) {  // stage the host arrays in one device buffer
     const size_t sz[9] = {n, 8 * n, 4 * nw, 4 * nw, 8 * nw, 4 * nw, 4 * nw, nw, size_t(in->var_len)};
     const void* src[9] = {in->tag, in->v0, in->w_idx, in->w_rc, in->w_v1, in->w_var_off, in->w_var_len, in->w_sub, in->var};
@@ -349,7 +350,7 @@ int clg_encode_batch(clg_engine* e, const clg_encode_in* in, void* out, uint64_t
     d = clg::EncodeIn{b + off[0], reinterpret_cast<const int64_t*>(b + off[1]), reinterpret_cast<const uint32_t*>(b + off[2]),
                       reinterpret_cast<const int32_t*>(b + off[3]), reinterpret_cast<const int64_t*>(b + off[4]),
                       reinterpret_cast<const uint32_t*>(b + off[5]), reinterpret_cast<const uint32_t*>(b + off[6]),
-                      b + off[7], b + off[8], n, nw};
+                      b + off[7], b + off[8], n, nw, in->var_len};
   }
   const uint64_t nb = (n + 1023) / 1024;
   const size_t o_wsum = 0, o_wbase = (nb * 4 + 15) & ~size_t(15), o_bsum = o_wbase + (((nb + 1) * 8 + 15) & ~size_t(15)),
@@ -371,7 +372,8 @@ int clg_encode_batch(clg_engine* e, const clg_encode_in* in, void* out, uint64_t
   CHK(e->sync());
   if (hbad != 0xFFFFFFFFu || hres[1] != nw) {
     if (bad_index) *bad_index = hbad != 0xFFFFFFFFu ? hbad : n;
-    return fail(CLG_E_INVALID_ARG, "record %llu: invalid tag or side-table row (%llu wide rows given, %llu used)",
+    return fail(CLG_E_INVALID_ARG,
+                "record %llu: invalid tag, side-table row or payload range (%llu wide rows given, %llu used)",
                 (unsigned long long)(hbad != 0xFFFFFFFFu ? hbad : n), (unsigned long long)nw,
                 (unsigned long long)hres[1]);
   }

@@ -824,6 +824,7 @@ struct EncodeIn {  // device pointers, the decode's SoA layout (clg_decoded)
   const uint8_t* w_sub;
   const uint8_t* var;
   uint64_t n, n_wide;
+  uint64_t var_len;  // bytes of var: a payload row's [w_var_off, + w_var_len) lies inside
 };
 // phase 0: wide prefix per block (wsum -> wbase, nb + 1), bytes per block (bsum -> bbase,
 // nb + 1), *bad = lowest invalid record; phase 1: write.  nb = ceil(n / 1024).

@@ -615,8 +615,13 @@ int clg_process_delta(clg_engine* e, uint32_t job, uint32_t strategy, const uint
  * w_var_off indexes `var`, the payload bytes: TimerTrigger names, storage references,
  * Serializable streams) are written back to back in record order -- exactly the bytes
  * the reference's appendDeterminant sequence would produce.  *n_out = bytes (also on
- * CLG_E_CAPACITY).  A record with tag > 7 or a side row naming another record:
- * CLG_E_INVALID_ARG with the record index in *bad_index. */
+ * CLG_E_CAPACITY).  A record with tag > 7, a wide record without a side row or whose side
+ * row names another record, or a side row whose format carries a payload (a Serializable, a
+ * TimerTrigger with sub == 6, a SourceCheckpoint with sub & 0x80) and whose
+ * w_var_off + w_var_len passes var_len (64 bits): CLG_E_INVALID_ARG with the lowest such
+ * record's index in *bad_index, nothing written.  Rows without a payload do not read
+ * w_var_off / w_var_len.  More side rows given than the wide records use: CLG_E_INVALID_ARG
+ * with *bad_index == n. */
 typedef struct clg_encode_in {
   const uint8_t* tag;
   const int64_t* v0;

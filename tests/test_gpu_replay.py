@@ -32,7 +32,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _bb(rng, n):
-    return b"".join(b"\x07" + struct.pack(">i", int(x)) for x in rng.integers(1, 1 << 20, n))
+    return b"".join(b"\x07" + struct.pack(">i", int(x)) for x in rng.integers(-(1 << 31), 1 << 31, n))
 
 
 def _rid(lid: CausalLogID) -> R.LogId:
