@@ -73,6 +73,8 @@ EXPORTED = [
     "clg_pack_columns", "clg_decode_logs_columns_packed", "clg_decode_host_columns_packed",
     "clg_pack_columns_host", "clg_unpack_columns_host",
     "clg_unpack_columns", "clg_unpack_columns_all_host", "clg_encode_columns_packed", "clg_append_columns_packed",
+    "clg_pack_wide", "clg_pack_wide_host", "clg_unpack_wide_host",
+    "clg_decode_logs_columns_packed_wide", "clg_decode_host_columns_packed_wide",
 ]
 
 
@@ -209,6 +211,21 @@ class Packed(C.Structure):  # clg_packed
         ("cap_desc", C.c_uint64), ("cap_bits", C.c_uint64),
         ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
         ("n_val", C.c_uint64 * PACK_STREAMS), ("blk_base", C.c_uint64 * (PACK_STREAMS + 1)), ("n_bits", C.c_uint64),
+    ]
+
+
+WPACK_KINDS, WPACK_FIELDS, WPACK_STREAMS = 4, 6, 26  # clg_packed_wide: KIND, IDX and a stream per (kind, field)
+WPACK_KIND, WPACK_IDX = 0, 1
+WPACK_RC, WPACK_V1, WPACK_VAR_OFF, WPACK_VAR_LEN, WPACK_SUB, WPACK_V0 = range(6)
+
+
+class PackedWideC(C.Structure):  # clg_packed_wide
+    _fields_ = [
+        ("desc", C.c_void_p), ("bits", C.c_void_p),
+        ("cap_desc", C.c_uint64), ("cap_bits", C.c_uint64),
+        ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
+        ("n_val", C.c_uint64 * WPACK_STREAMS), ("blk_base", C.c_uint64 * (WPACK_STREAMS + 1)), ("n_bits", C.c_uint64),
+        ("bad_row", C.c_uint64),
     ]
 
 
@@ -458,6 +475,13 @@ def _load() -> C.CDLL:
                                                 C.POINTER(UnpackBad)]),
         "clg_append_columns_packed": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Packed), C.POINTER(ColumnsIn), P, P,
                                                 C.POINTER(UnpackBad)]),
+        "clg_pack_wide": (C.c_int, [P, C.POINTER(Columns), C.POINTER(PackedWideC)]),
+        "clg_pack_wide_host": (C.c_int, [C.POINTER(Columns), C.POINTER(PackedWideC)]),
+        "clg_unpack_wide_host": (C.c_int, [C.POINTER(PackedWideC), C.POINTER(Columns), C.POINTER(UnpackBad)]),
+        "clg_decode_logs_columns_packed_wide": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads),
+                                                          C.POINTER(Packed), C.POINTER(PackedWideC)]),
+        "clg_decode_host_columns_packed_wide": (C.c_int, [P, P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads),
+                                                          C.POINTER(Packed), C.POINTER(PackedWideC)]),
         "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),

@@ -1,13 +1,15 @@
 // engine_columns.cpp -- the typed-columns family: the placement of its arrays (placement.h), the
 // columns of a decoded batch and the decodes into columns, the payload column, packed columns out
-// and in, the encode of typed columns and their append to logs; clg_pack_columns to
-// clg_columnize_host, clg_encode_columns*, clg_append_columns*, clg_unpack_columns*.  The placement
+// and in, packed wide rows, the encode of typed columns and their append to logs; clg_pack_columns to
+// clg_columnize_host, clg_pack_wide*, clg_unpack_wide_host, clg_decode_*_columns_packed_wide,
+// clg_encode_columns*, clg_append_columns*, clg_unpack_columns*.  The placement
 // helpers are file-local; decode_columns and decode_columns_var are declared in engine_impl.h for
 // replay preparation (engine_replay.cpp).
 #include "engine_impl.h"
 #include "columns.h"
 #include "encode_columns.h"
 #include "pack.h"
+#include "pack_wide.h"
 #include "payload.h"
 #include "placement.h"
 
@@ -369,7 +371,9 @@ int gather_payloads_small(clg_engine* e, const clg::PayIn& in, clg_payloads* out
 // d_off / d_len: device addresses of the rows.  sizes_forced: fill the results, write nothing.
 int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans, const std::vector<uint32_t>& segtab,
                            const uint32_t* d_off, const uint32_t* d_len, const uint64_t* row_base, clg_payloads* out,
-                           bool sizes_forced = false) {
+                           bool sizes_forced = false, bool no_pos = false) {
+  // (no_pos, the packed-wide decodes only: var is delivered without pos, which the caller rebuilds
+  // from the lengths; the kernels then write no pos and the one-launch form, which does, is not taken)
   const uint32_t ns = uint32_t(spans.size());
   clg::pay_reset_result(out);
   if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
@@ -381,7 +385,7 @@ int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans
   const bool direct = out->out_kind == CLG_MEM_DEVICE;
   if (!sizes_only && direct && uintptr_t(out->pos) % 8) return fail(CLG_E_INVALID_ARG, "pos is not aligned to its element");
   if (!n) {  // no rows: only pos[0]
-    if (sizes_only) return CLG_OK;
+    if (sizes_only || no_pos) return CLG_OK;
     if (const char* name = clg::pay_short(*out, 0, 0)) return fail(CLG_E_CAPACITY, "%s is too small (rows 0)", name);
     const uint64_t zero = 0;
     if (direct) HIPCHK(hipMemcpy(out->pos, &zero, 8, hipMemcpyHostToDevice));
@@ -405,7 +409,7 @@ int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans
                       reinterpret_cast<const uint32_t*>(dd + sb + rb), e->pool, n, ns, e->C()};
   uint64_t span_bytes = 0;  // (an upper bound of n_var)
   for (const clg::PaySpan& sp : spans) span_bytes += sp.len;
-  if (e->sw.columns_small && n <= clg::kPaySmallRows && span_bytes <= clg::kPaySmallBytes)
+  if (!no_pos && e->sw.columns_small && n <= clg::kPaySmallRows && span_bytes <= clg::kPaySmallBytes)
     return gather_payloads_small(e, in, out, sizes_only, span_bytes, sb + rb);
   CHK(e->d_paytile.ensure(size_t(n_tiles) * 24 + 64));
   uint64_t* d_sum = e->d_paytile.as<uint64_t>();
@@ -426,14 +430,15 @@ int gather_payloads_device(clg_engine* e, const std::vector<clg::PaySpan>& spans
   }
   if (sizes_only) return CLG_OK;
   const uint64_t nv = res->n_var;
-  if (const char* name = clg::pay_short(*out, n, nv)) return pay_too_small(name, n, nv);
+  const char* short_name = !no_pos ? clg::pay_short(*out, n, nv) : (out->var ? out->cap_var : 0) < nv ? "var" : nullptr;
+  if (short_name) return pay_too_small(short_name, n, nv);
 
   // where the kernels write: the caller's device arrays, or engine staging and one copy each
   // (host and registered memory alike: the short rows' byte stores stay off the link)
-  const PlaceSpec dst[2] = {{out->pos, (n + 1) * 8, 8}, {out->var, nv, 1}};
+  const PlaceSpec dst[2] = {{no_pos ? nullptr : out->pos, (n + 1) * 8, 8}, {out->var, nv, 1}};
   clg::Placement pl;
   CHK(place_out(e->d_payout, dst, 2, out->out_kind, PlacePolicy::stage_unless_device, "payload", &pl));
-  CHK(e->timed("decode_payloads", n * 12 + (n + 1) * 8 + uint64_t(n_tiles) * 8 + 2 * nv, [&] {
+  CHK(e->timed("decode_payloads", n * 12 + (no_pos ? 0 : (n + 1) * 8) + uint64_t(n_tiles) * 8 + 2 * nv, [&] {
     return clg::launch_pay_write(in, n_tiles, d_base, nv, pl.at<uint64_t>(0), pl.at<uint8_t>(1), e->stream);
   }));
   CHK(stage_out(e, dst, 2, pl));
@@ -597,18 +602,121 @@ int pack_capacity_error(const clg_packed& out, const char* name) {
               (unsigned long long)out.blk_base[clg::kPackStreams], (unsigned long long)out.n_bits);
 }
 
+// ---- packed wide rows (pack_wide.h) ---------------------------------------------------------
+// Kind and count and the scan of the tile counts, the host's check of the bad-row word and its
+// layout of the 26 streams from the four totals, the split into per-kind arrays in engine scratch,
+// measure and the offset scan, the host's capacity check, then the write.
+
+// Everything up to the sizes, over device-side rows: out's results are filled, the stream table is
+// left in d_wpacktab and the descriptors (with their offsets) in d_wpackdesc.
+int wpack_sizes(clg_engine* e, const clg::WPackSrc& src, clg_packed_wide* out) {
+  clg::wpack_reset_result(out);
+  const uint64_t nw = src.n_wide;
+  if (nw >> 32) return fail(CLG_E_INVALID_ARG, "%llu wide rows in one call", (unsigned long long)nw);
+  if (!nw) return CLG_OK;  // no rows: 26 empty streams, nothing to launch (a log without wide records pays nothing)
+  const uint32_t nt = uint32_t((nw + clg::kWPackTile - 1) / clg::kWPackTile);
+  const uint64_t kb[4] = {nw, uint64_t(nt) * clg::kWPackKinds * 4, uint64_t(nt) * clg::kWPackKinds * 8, 8};
+  size_t ka[5];
+  CHK(e->d_wpackkind.ensure(clg::place_layout(kb, 4, ka) + 16));
+  uint8_t* ks = e->d_wpackkind.as<uint8_t>();
+  uint8_t* d_kind = ks + ka[0];
+  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(ks + ka[1]);
+  uint64_t* d_base = reinterpret_cast<uint64_t*>(ks + ka[2]);
+  unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(ks + ka[3]);
+  CHK(e->h_wpackres.ensure(sizeof(clg::WPackRes) + sizeof(clg::PackRes)));
+  clg::WPackRes* res = e->h_wpackres.as<clg::WPackRes>();
+  clg::PackRes* pres = reinterpret_cast<clg::PackRes*>(res + 1);
+  // (bytes: w_idx, a tag and the kind byte a row; the tile counts written, read and their bases written)
+  CHK(e->timed("pack_wide", nw * 6 + uint64_t(nt) * 64,
+               [&] { return clg::launch_wpack_count_scan(src, nt, d_kind, d_cnt, d_base, d_bad, res, e->stream); }));
+  CHK(e->sync());
+  if (res->bad_row != ~0ull) {
+    out->bad_row = res->bad_row;
+    return fail(CLG_E_INVALID_ARG, "packed wide rows: row %llu's w_idx or tag is not a wide record's", (unsigned long long)res->bad_row);
+  }
+  if (res->tot[0] + res->tot[1] + res->tot[2] + res->tot[3] != nw) return fail(CLG_E_DEVICE, "packed wide rows: the kinds' totals do not sum to the rows");
+  clg::wpack_layout(nw, res->tot, out);
+  const uint64_t nb = out->blk_base[clg::kWPackStreams];
+
+  // the per-kind arrays and the stream table
+  constexpr int kArrays = int(clg::kWPackKinds * clg::kWPackFields);
+  uint64_t cb[kArrays];
+  size_t so[kArrays + 1];
+  for (uint32_t t = 0; t < clg::kWPackKinds; ++t)
+    for (uint32_t f = 0; f < clg::kWPackFields; ++f)
+      cb[t * clg::kWPackFields + f] = res->tot[t] * clg::wpack_elem_bytes(clg::kWPackField[f].elem);
+  CHK(e->d_wpacksoa.ensure(clg::place_layout(cb, kArrays, so) + 16));
+  CHK(e->h_wpacktab.ensure(sizeof(clg::WPackTab)));
+  CHK(e->d_wpacktab.ensure(sizeof(clg::WPackTab)));
+  clg::WPackTab* tab = e->h_wpacktab.as<clg::WPackTab>();
+  tab->col[CLG_WPACK_KIND] = d_kind, tab->col[CLG_WPACK_IDX] = src.w_idx;
+  for (int i = 0; i < kArrays; ++i) tab->col[2 + i] = e->d_wpacksoa.as<uint8_t>() + so[i];
+  for (uint32_t c = 0; c < clg::kWPackStreams; ++c) tab->n[c] = out->n_val[c];
+  for (uint32_t c = 0; c <= clg::kWPackStreams; ++c) tab->blk_base[c] = out->blk_base[c];
+  HIPCHK(hipMemcpyAsync(e->d_wpacktab.p, tab, sizeof(clg::WPackTab), hipMemcpyHostToDevice, e->stream));
+  const uint64_t ng = (nb + clg::kPackScanGroup - 1) / clg::kPackScanGroup;
+  CHK(e->d_wpackdesc.ensure(size_t(nb) * sizeof(clg_pack_block) + 64));
+  CHK(e->d_wpacksum.ensure(size_t(ng) * 8 + 64));
+  // (bytes: the split reads a kind byte and 29 B a row and writes them; the measure reads the 26
+  // streams, 34 B a row; a descriptor written, read and written again, the groups' sums)
+  CHK(e->timed("pack_wide", nw * (1 + 29 + 29 + 34) + nb * 72 + ng * 24, [&] {
+    const int st = clg::launch_wpack_split_measure(src, nt, d_kind, d_base, e->d_wpacktab.as<clg::WPackTab>(), uint32_t(nb),
+                                                   e->d_wpackdesc.as<clg_pack_block>(), e->stream);
+    if (st != CLG_OK) return st;
+    return clg::launch_pack_scan(uint32_t(nb), e->d_wpackdesc.as<clg_pack_block>(), e->d_wpacksum.as<uint64_t>(), pres, e->stream);
+  }));
+  CHK(e->sync());
+  out->n_bits = pres->n_bits;
+  return CLG_OK;
+}
+
+int wpack_out_check(const clg_packed_wide& out) {
+  if (!mem_kind_ok(out.out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out.out_kind);
+  if (out.out_kind != CLG_MEM_HOST && (uintptr_t(out.desc) % 8 || uintptr_t(out.bits) % 16))
+    return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
+  return CLG_OK;
+}
+
+// The write pass, after wpack_sizes and the capacity check.
+int wpack_write(clg_engine* e, clg_packed_wide* out) {
+  const uint64_t nb = out->blk_base[clg::kWPackStreams], nbits = out->n_bits;
+  if (!nb) return CLG_OK;
+  const PlaceSpec dst[2] = {{out->desc, nb * sizeof(clg_pack_block), 8}, {out->bits, nbits, 16}};
+  clg::Placement pl;
+  CHK(place_out(e->d_wpackout, dst, 2, out->out_kind, PlacePolicy::stage_if_unresolved, "packed", &pl));
+  CHK(e->timed("pack_wide", out->n_val[CLG_WPACK_KIND] * 34 + nb * 64 + nbits, [&] {
+    return clg::launch_wpack_write(e->d_wpacktab.as<clg::WPackTab>(), uint32_t(nb), e->d_wpackdesc.as<clg_pack_block>(),
+                                   pl.at<clg_pack_block>(0), pl.at<uint8_t>(1), nb, nbits, e->stream);
+  }));
+  CHK(stage_out(e, dst, 2, pl));
+  return e->sync();
+}
+
+int wpack_capacity_error(const clg_packed_wide& out, const char* name) {
+  return fail(CLG_E_CAPACITY, "packed wide rows: %s is too small (blocks %llu, payload bytes %llu)", name,
+              (unsigned long long)out.blk_base[clg::kWPackStreams], (unsigned long long)out.n_bits);
+}
+
 // The decode into engine scratch and the columns of what it produced, also in engine scratch;
 // then the pack, the wide rows as they are and (var) the payload column of the same rows.
-// Every size is known before anything is written to the caller.
+// Every size is known before anything is written to the caller.  wpk (the packed-wide decodes):
+// the wide rows are delivered packed as well and no plain row is copied to the caller; `wide` then
+// carries only sizes, and var may come without pos, which is the prefix sum of w_var_len.
 int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_columns* wide, clg_payloads* var,
-                          clg_packed* out, const PaySpansOf& spans_of) {
+                          clg_packed* out, const PaySpansOf& spans_of, clg_packed_wide* wpk = nullptr) {
   if (wide->tag || wide->order || wide->timestamp || wide->rng || wide->buffer_built)
     return fail(CLG_E_INVALID_ARG, "the narrow column pointers of `wide` must be NULL: those columns are delivered packed");
+  if (wpk)
+    for (int i = clg::kColNarrowArrays; i < clg::kColArrays; ++i)
+      if (clg::col_ptr(*wide, i)) return fail(CLG_E_INVALID_ARG, "every column pointer of `sizes` must be NULL: the wide rows are delivered packed");
   if (!mem_kind_ok(wide->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", wide->out_kind);
   CHK(pack_out_check(*out));
+  if (wpk) CHK(wpack_out_check(*wpk));
   clg::col_reset_result(wide);
   clg::pack_reset_result(out);
+  if (wpk) clg::wpack_reset_result(wpk);
   if (var) clg::pay_reset_result(var);
+  const bool no_pos = wpk && var && var->var && !var->pos;
 
   // the decode, and the columns' sizes and span bases
   std::vector<uint64_t> sb(size_t(n + 1) * clg::kColClasses, 0);
@@ -648,6 +756,9 @@ int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_c
   const clg::PackSrc src{{full.tag, full.order, full.timestamp, full.rng, full.buffer_built}, {nr, tot[0], tot[1], tot[2], tot[3]}};
   clg::PackIn pin{};
   CHK(pack_sizes(e, src, out, &pin));
+  if (wpk)
+    CHK(wpack_sizes(e, clg::WPackSrc{full.tag, full.w_idx, full.w_rc, full.w_v1, full.w_var_off, full.w_var_len, full.w_sub, full.w_v0, nr, nw},
+                    wpk));
   int ps = CLG_OK;
   std::vector<clg::PaySpan> spans;
   std::vector<uint32_t> segtab;
@@ -662,13 +773,19 @@ int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_c
   for (int i = w0; i < w1; ++i) wide_any = wide_any || clg::col_ptr(*wide, i);
   for (int i = w0; i < w1; ++i) wide_short = wide_short || (wide_any && clg::col_array_cap(*wide, i) < nw);
   const char* pk_short = clg::pack_sizes_only(*out) ? nullptr : clg::pack_short(*out);
-  const char* pay_short = var && ps == CLG_OK && !clg::pay_sizes_only(*var) ? clg::pay_short(*var, var->n_rows, var->n_var) : nullptr;
+  const char* wpk_short = wpk && !clg::wpack_sizes_only(*wpk) ? clg::wpack_short(*wpk) : nullptr;
+  const char* pay_short = !var || ps != CLG_OK || clg::pay_sizes_only(*var) ? nullptr
+                          : !no_pos                                         ? clg::pay_short(*var, var->n_rows, var->n_var)
+                          : var->cap_var < var->n_var                       ? "var"
+                                                                            : nullptr;
   if (wide_short) return fail(CLG_E_CAPACITY, "the wide rows' arrays are too small (rows %llu)", (unsigned long long)nw);
   if (pk_short) return pack_capacity_error(*out, pk_short);
+  if (wpk_short) return wpack_capacity_error(*wpk, wpk_short);
   if (pay_short) return pay_too_small(pay_short, var->n_rows, var->n_var);
 
   // the writes
   if (!clg::pack_sizes_only(*out)) CHK(pack_write(e, pin, out));
+  if (wpk && !clg::wpack_sizes_only(*wpk)) CHK(wpack_write(e, wpk));
   if (wide_any && nw) {
     for (int i = w0; i < w1; ++i)
       CHK(copy_caller(e, clg::col_ptr(*wide, i), clg::col_ptr(full, i), nw * clg::kColArray[i].width, hipMemcpyDefault,
@@ -676,7 +793,7 @@ int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_c
     CHK(e->sync());
   }
   if (var && ps == CLG_OK && !clg::pay_sizes_only(*var))
-    ps = gather_payloads_device(e, spans, segtab, keep.d.w_var_off, keep.d.w_var_len, row_base.data(), var);
+    ps = gather_payloads_device(e, spans, segtab, keep.d.w_var_off, keep.d.w_var_len, row_base.data(), var, false, no_pos);
   else if (ps != CLG_OK)
     g_err = pay_err;
   if (cs != CLG_OK) {
@@ -736,6 +853,41 @@ int clg_pack_columns(clg_engine* e, const clg_columns* in, clg_packed* out) {
   return pack_write(e, pin, out);
 }
 
+int clg_pack_wide(clg_engine* e, const clg_columns* in, clg_packed_wide* out) {
+  ENGINE_GUARD(e);
+  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::wpack_reset_result(out);
+  CHK(wpack_out_check(*out));
+  if (!mem_kind_ok(in->out_kind)) return fail(CLG_E_INVALID_ARG, "the columns' out_kind %u", in->out_kind);
+  const uint64_t nr = in->n_rec, nw = in->n_class[clg::kColWide];
+  const PlaceSpec ins[8] = {{in->tag, nw ? nr : 0, 1},         {in->w_idx, nw * 4, 4},     {in->w_rc, nw * 4, 4}, {in->w_v1, nw * 8, 8},
+                            {in->w_var_off, nw * 4, 4}, {in->w_var_len, nw * 4, 4}, {in->w_sub, nw, 1},    {in->w_v0, nw * 8, 8}};
+  for (int i = 1; i < 8; ++i)
+    if (nw && !ins[i].p) return fail(CLG_E_INVALID_ARG, "null input array (%d)", i);
+  if (nw && !in->tag) return fail(CLG_E_INVALID_ARG, "null input array (tag)");
+  clg::Placement pl;
+  CHK(place_in(e, e->d_wpackin, ins, 8, in->out_kind, PlacePolicy::stage_if_unresolved, "wide", &pl));
+  const clg::WPackSrc src{pl.at<const uint8_t>(0),  pl.at<const uint32_t>(1), pl.at<const int32_t>(2), pl.at<const int64_t>(3),
+                          pl.at<const uint32_t>(4), pl.at<const uint32_t>(5), pl.at<const uint8_t>(6), pl.at<const int64_t>(7),
+                          nr,                       nw};
+  CHK(wpack_sizes(e, src, out));
+  if (clg::wpack_sizes_only(*out)) return CLG_OK;
+  if (const char* name = clg::wpack_short(*out)) return wpack_capacity_error(*out, name);
+  return wpack_write(e, out);
+}
+
+int clg_pack_wide_host(const clg_columns* in, clg_packed_wide* out) {
+  const char* what = "";
+  const int st = clg::wpack_build_host(in, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "packed wide rows: %s", what);
+}
+
+int clg_unpack_wide_host(const clg_packed_wide* in, clg_columns* out, clg_unpack_bad* bad) {
+  const char* what = "";
+  const int st = clg::wpack_unpack_host(in, out, bad, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "unpack wide rows: %s", what);
+}
+
 int clg_decode_logs_columns_packed(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
                                    clg_columns* wide, clg_payloads* var, clg_packed* out) {
   ENGINE_GUARD(e);
@@ -751,6 +903,23 @@ int clg_decode_host_columns_packed(clg_engine* e, const uint8_t* bytes, const ui
   if (!wide || !out || (n && (!span_off || !span_len))) return fail(CLG_E_INVALID_ARG, "null argument");
   const DecodeSource src = source_host(e, bytes, span_off, span_len, n);
   return decode_columns_packed(e, src.run, n, wide, var, out, src.spans_of);
+}
+
+int clg_decode_logs_columns_packed_wide(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                                        clg_columns* sizes, clg_payloads* var, clg_packed* narrow, clg_packed_wide* wide) {
+  ENGINE_GUARD(e);
+  if (!sizes || !narrow || !wide || (n && (!log || !start_epoch))) return fail(CLG_E_INVALID_ARG, "null argument");
+  const DecodeSource src = source_logs(e, log, start_epoch, n);
+  return decode_columns_packed(e, src.run, n, sizes, var, narrow, src.spans_of, wide);
+}
+
+int clg_decode_host_columns_packed_wide(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off,
+                                        const uint64_t* span_len, uint32_t n, clg_columns* sizes, clg_payloads* var,
+                                        clg_packed* narrow, clg_packed_wide* wide) {
+  ENGINE_GUARD(e);
+  if (!sizes || !narrow || !wide || (n && (!span_off || !span_len))) return fail(CLG_E_INVALID_ARG, "null argument");
+  const DecodeSource src = source_host(e, bytes, span_off, span_len, n);
+  return decode_columns_packed(e, src.run, n, sizes, var, narrow, src.spans_of, wide);
 }
 
 int clg_pack_columns_host(const clg_columns* in, clg_packed* out) {

@@ -267,6 +267,11 @@ struct clg_engine {
   // host-output staging, and the check's verdict (device words, read back into pinned memory)
   DevBuf d_unpackin, d_unpackcol, d_unpackout, d_unpackres;
   PinBuf h_unpackres;
+  // packed wide rows: staged host input, kind bytes | tile counts | tile bases | the bad-row word,
+  // the per-kind field arrays, the stream table (pinned, then device), the blocks' descriptors,
+  // the scan groups' sums, host-output staging; the scans' results (pinned: the kernels write them)
+  DevBuf d_wpackin, d_wpackkind, d_wpacksoa, d_wpacktab, d_wpackdesc, d_wpacksum, d_wpackout;
+  PinBuf h_wpacktab, h_wpackres;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 

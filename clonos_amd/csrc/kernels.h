@@ -722,6 +722,51 @@ int launch_pack_measure_scan(const PackIn& in, uint32_t n_blocks, clg_pack_block
 int launch_pack_write(const PackIn& in, uint32_t n_blocks, const clg_pack_block* d_desc, clg_pack_block* out_desc,
                       uint8_t* bits, uint64_t lim_desc, uint64_t lim_bits, void* stream);
 
+// The offsets alone, over descriptors whose pos holds the payload's size (the three scan kernels
+// know nothing of streams: pack_wide.hip's descriptors go through them too).
+int launch_pack_scan(uint32_t n_blocks, clg_pack_block* d_desc, uint64_t* d_gsum, PackRes* res, void* stream);
+
+// ---- packed wide rows (pack_wide.h, pack_wide.hip) ----------------------------------
+struct WPackSrc {  // device addresses of the tags and the seven wide arrays
+  const uint8_t* tag;
+  const uint32_t* w_idx;
+  const int32_t* w_rc;
+  const int64_t* w_v1;
+  const uint32_t* w_var_off;
+  const uint32_t* w_var_len;
+  const uint8_t* w_sub;
+  const int64_t* w_v0;
+  uint64_t n_rec, n_wide;
+};
+// The 26 streams' arrays, lengths and block bases.  It lives in device memory and is passed by
+// address: the kernels index it with a wave-uniform stream number, which for a by-value kernel
+// argument would go through scratch.
+struct WPackTab {
+  const void* col[26];
+  uint64_t n[26];
+  uint64_t blk_base[27];
+};
+constexpr uint32_t kWPackTile = 1024;  // rows a workgroup of the kind and split passes
+// The scan's results, in pinned memory the host reads before it lays the streams out.
+struct WPackRes {
+  uint64_t tot[4];
+  uint64_t bad_row;  // ~0: none
+};
+// Kind and count (a workgroup per tile: d_kind[row], d_cnt[tile * 4 + kind]; the lowest bad row
+// into *d_bad by atomicMin, which this call first sets to ~0 through the stream) and the scan of
+// the tile counts (one workgroup: d_base[tile * 4 + kind] the rows of that kind before the tile;
+// *res).
+int launch_wpack_count_scan(const WPackSrc& src, uint32_t n_tiles, uint8_t* d_kind, uint32_t* d_cnt, uint64_t* d_base,
+                            unsigned long long* d_bad, WPackRes* res, void* stream);
+// Split (a workgroup per tile: the six fields of every row to d_tab's per-kind arrays at the
+// row's rank; no store at or past a kind's length) and measure (a workgroup per block of the 26
+// streams -> d_desc[block] with the payload's size in pos; launch_pack_scan turns it into the offset).
+int launch_wpack_split_measure(const WPackSrc& src, uint32_t n_tiles, const uint8_t* d_kind, const uint64_t* d_base,
+                               const WPackTab* d_tab, uint32_t n_blocks, clg_pack_block* d_desc, void* stream);
+// Write (a workgroup per block), as launch_pack_write.
+int launch_wpack_write(const WPackTab* d_tab, uint32_t n_blocks, const clg_pack_block* d_desc, clg_pack_block* out_desc,
+                       uint8_t* bits, uint64_t lim_desc, uint64_t lim_bits, void* stream);
+
 // ---- packed typed columns as input (pack.h, unpack.hip) -----------------------------
 struct UnpackIn {  // device addresses of a clg_packed read as input, after the host's layout check
   const clg_pack_block* desc;

@@ -24,61 +24,12 @@
 
 #include "../../include/clonos_engine.h"
 #include "pack.h"
+#include "pack_dev.h"
 #include "kernels.h"
 
 namespace clg {
 
 namespace {
-
-constexpr uint32_t kPackThreads = 256;
-constexpr uint32_t kPackWaves = kPackThreads / 64;
-constexpr uint32_t kPackPerThread = kPackBlock / kPackThreads;
-constexpr uint32_t kPackTopThreads = 1024;
-static_assert(kPackPerThread == 4, "four values a thread");
-static_assert(kPackScanGroup == kPackThreads, "the group passes take a block a thread");
-
-// v of the lane the DPP control names; a lane without a source keeps its own.
-template <int kCtrl>
-__device__ __forceinline__ int64_t pack_dpp(int64_t v) {
-  const uint32_t lo = uint32_t(uint64_t(v)), hi = uint32_t(uint64_t(v) >> 32);
-  const uint32_t a = (uint32_t)__builtin_amdgcn_update_dpp((int)lo, (int)lo, kCtrl, 0xF, 0xF, false);
-  const uint32_t b = (uint32_t)__builtin_amdgcn_update_dpp((int)hi, (int)hi, kCtrl, 0xF, 0xF, false);
-  return int64_t(uint64_t(a) | uint64_t(b) << 32);
-}
-__device__ __forceinline__ int64_t pack_lane63(int64_t v) {
-  const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)uint32_t(uint64_t(v)), 63);
-  const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)uint32_t(uint64_t(v) >> 32), 63);
-  return int64_t(uint64_t(a) | uint64_t(b) << 32);
-}
-__device__ __forceinline__ int64_t pack_min(int64_t a, int64_t b) { return b < a ? b : a; }
-__device__ __forceinline__ int64_t pack_max(int64_t a, int64_t b) { return b > a ? b : a; }
-// The wave's signed minimum / maximum: quads, the rows of 16 (row_ror 4 and 8), then
-// row_bcast 15 and 31; lane 63 holds the result.
-#define CLG_PACK_WAVE_REDUCE(op, v)       \
-  v = op(v, pack_dpp<0xB1>(v));           \
-  v = op(v, pack_dpp<0x4E>(v));           \
-  v = op(v, pack_dpp<0x124>(v));          \
-  v = op(v, pack_dpp<0x128>(v));          \
-  v = op(v, pack_dpp<0x142>(v));          \
-  v = op(v, pack_dpp<0x143>(v));          \
-  v = pack_lane63(v)
-
-__device__ __forceinline__ uint32_t pack_wave_incl(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-__device__ __forceinline__ uint64_t pack_wave_incl64(uint64_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
 
 // The stream that holds block blk: the last one whose base is at or below it (the bases do not
 // decrease, and an empty stream shares its base with the next).
@@ -302,11 +253,14 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_write(const PackIn in, co
 
 int launch_pack_measure_scan(const PackIn& in, uint32_t n_blocks, clg_pack_block* d_desc, uint64_t* d_gsum, PackRes* res,
                              void* stream) {
+  if (n_blocks) hipLaunchKernelGGL(k_pack_measure, dim3(n_blocks), dim3(kPackThreads), 0, (hipStream_t)stream, in, d_desc);
+  return launch_pack_scan(n_blocks, d_desc, d_gsum, res, stream);
+}
+
+int launch_pack_scan(uint32_t n_blocks, clg_pack_block* d_desc, uint64_t* d_gsum, PackRes* res, void* stream) {
   const uint32_t n_groups = (n_blocks + kPackScanGroup - 1) / kPackScanGroup;
-  if (n_blocks) {
-    hipLaunchKernelGGL(k_pack_measure, dim3(n_blocks), dim3(kPackThreads), 0, (hipStream_t)stream, in, d_desc);
+  if (n_blocks)
     hipLaunchKernelGGL(k_pack_scan_sums, dim3(n_groups), dim3(kPackThreads), 0, (hipStream_t)stream, d_desc, n_blocks, d_gsum);
-  }
   hipLaunchKernelGGL(k_pack_scan_top, dim3(1), dim3(kPackTopThreads), 0, (hipStream_t)stream, d_gsum, n_groups, res);
   if (n_blocks)
     hipLaunchKernelGGL(k_pack_scan_apply, dim3(n_groups), dim3(kPackThreads), 0, (hipStream_t)stream, d_desc, n_blocks, d_gsum);

@@ -483,20 +483,53 @@ class PackedColumns:
     values, stream c's rows at desc[blk_base[c]:blk_base[c + 1]], and bits, the blocks' payloads.
     The wide rows, span_base and the payload column are as DecodedColumns holds them.  span(s)
     unpacks only the blocks span s's ranges cover, so replay.ColumnReplayer(packed, s) works as it
-    does over DecodedColumns; unpack() gives the whole DecodedColumns back."""
+    does over DecodedColumns; unpack() gives the whole DecodedColumns back.
+
+    wide_packed (decode_logs_columns(..., packed=True, pack_wide=True)): the wide rows came packed
+    too, as a PackedWide, and the payload column without var_pos.  The seven w_* arrays and var_pos
+    are then not held: the first read of any of them unpacks the rows once through
+    clg_unpack_wide_host and rebuilds var_pos as the prefix sum of w_var_len, so unpack(), span(),
+    payload() and the encode and append of these columns work as they do over delivered rows."""
 
     def __init__(self, desc, bits, n_val, blk_base, w_idx, w_rc, w_v1, w_var_off, w_var_len, w_sub, w_v0, span_base,
-                 spans_bytes=None):
+                 spans_bytes=None, wide_packed: Optional["PackedWide"] = None):
         self.desc, self.bits = desc, bits
         self.n_val = [int(x) for x in n_val]
         self.blk_base = [int(x) for x in blk_base]
-        self.w_idx, self.w_rc, self.w_v1, self.w_v0 = w_idx, w_rc, w_v1, w_v0
-        self.w_var_off, self.w_var_len, self.w_sub = w_var_off, w_var_len, w_sub
+        self.wide_packed = wide_packed
+        if wide_packed is None:
+            self.w_idx, self.w_rc, self.w_v1, self.w_v0 = w_idx, w_rc, w_v1, w_v0
+            self.w_var_off, self.w_var_len, self.w_sub = w_var_off, w_var_len, w_sub
+            self.var_pos: Optional[np.ndarray] = None
         self.span_base = np.asarray(span_base, np.uint64).reshape(-1, _lib.COL_CLASSES)
         self.spans_bytes = spans_bytes
         self.var: Optional[np.ndarray] = None
-        self.var_pos: Optional[np.ndarray] = None
         self.error: Optional[ClonosError] = None
+
+    def _wide(self) -> dict:
+        """The seven w_* arrays of wide_packed columns, unpacked once (clg_unpack_wide_host) and kept."""
+        d = self.__dict__
+        if "w_idx" not in d:
+            d.update(self.wide_packed.unpack())
+        return {k: d[k] for k in _COL_WIDE}
+
+    def __getattr__(self, name):
+        # Reached only for a name the instance does not hold, which for wide_packed columns are the
+        # w_* arrays and var_pos: ColumnReplayer and _columns_in read them as attributes, as they do
+        # on DecodedColumns.  The rows are kept once unpacked; var_pos is kept only once there is a
+        # payload column to index (var may be attached after construction).
+        d = self.__dict__
+        if d.get("wide_packed") is None or (name not in _COL_WIDE and name != "var_pos"):
+            raise AttributeError(name)
+        wide = self._wide()
+        if name != "var_pos":
+            return wide[name]
+        if d.get("var") is None:
+            return None
+        pos = np.zeros(self.wide_packed.n_wide + 1, np.uint64)
+        np.cumsum(wide["w_var_len"], dtype=np.uint64, out=pos[1:])
+        d["var_pos"] = pos
+        return pos
 
     @property
     def n_rec(self) -> int:
@@ -510,7 +543,10 @@ class PackedColumns:
     def n_bytes(self) -> int:
         """The delivered size: descriptors, payload bits, the wide rows, span_base and the
         payload column when present."""
-        arrs = [self.desc, self.bits, self.span_base, self.var, self.var_pos] + [getattr(self, k) for k in _COL_WIDE]
+        arrs = [self.desc, self.bits, self.span_base, self.var]
+        if self.wide_packed is not None:  # (the rows and var_pos, once unpacked, were not delivered)
+            return int(sum(a.nbytes for a in arrs if a is not None)) + self.wide_packed.n_bytes
+        arrs += [self.var_pos] + [getattr(self, k) for k in _COL_WIDE]
         return int(sum(a.nbytes for a in arrs if a is not None))
 
     def _struct(self) -> _lib.Packed:
@@ -642,6 +678,148 @@ def unpack_packed_host(packed: "PackedColumns") -> "DecodedColumns":
     if st != _lib.CLG_OK:
         raise _unpack_error(st, bad)
     return _unpacked(packed, arrs)
+
+
+# the packed wide rows' six fields, in the format's order (clg_packed_wide, pack_wide.h)
+WPACK_FIELDS = (("w_rc", np.int32), ("w_v1", np.int64), ("w_var_off", np.uint32), ("w_var_len", np.uint32),
+                ("w_sub", np.uint8), ("w_v0", np.int64))
+
+
+def _packed_wide_struct(desc: Optional[np.ndarray], bits: Optional[np.ndarray],
+                        kind: int = _lib.CLG_MEM_HOST) -> _lib.PackedWideC:
+    """clg_packed_wide over host arrays (capacity = their lengths); both None: sizes only."""
+    p = _lib.PackedWideC()
+    if desc is not None:
+        p.desc, p.cap_desc = _np_ptr(desc), desc.size
+    if bits is not None:
+        p.bits, p.cap_bits = _np_ptr(bits), bits.size
+    p.out_kind = kind
+    return p
+
+
+def _packed_wide_error(st: int, p: _lib.PackedWideC) -> ClonosError:
+    err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
+    err.n_blocks, err.n_bits, err.bad_row = int(p.blk_base[_lib.WPACK_STREAMS]), int(p.n_bits), int(p.bad_row)
+    return err
+
+
+class PackedWide:
+    """The wide rows partitioned by record kind and bit-packed (layout: include/clonos_engine.h
+    clg_packed_wide; the format: clonos_amd/csrc/pack_wide.h): desc, one PACK_BLOCK row per block of
+    1024 values, stream c's rows at desc[blk_base[c]:blk_base[c + 1]], and bits, the blocks'
+    payloads.  unpack() gives the seven w_* arrays back in row order; rows(kind) the rows of one
+    kind."""
+
+    def __init__(self, desc, bits, n_val, blk_base):
+        self.desc, self.bits = desc, bits
+        self.n_val = [int(x) for x in n_val]
+        self.blk_base = [int(x) for x in blk_base]
+
+    @property
+    def n_wide(self) -> int:
+        return self.n_val[_lib.WPACK_KIND]
+
+    @property
+    def n_bytes(self) -> int:
+        """The delivered size: descriptors and payload bits."""
+        return int(self.desc.nbytes + self.bits.nbytes)
+
+    def _struct(self) -> _lib.PackedWideC:
+        p = _packed_wide_struct(self.desc, self.bits)
+        for c in range(_lib.WPACK_STREAMS):
+            p.n_val[c] = self.n_val[c]
+        for c in range(_lib.WPACK_STREAMS + 1):
+            p.blk_base[c] = self.blk_base[c]
+        p.n_bits = self.bits.size
+        return p
+
+    def unpack(self) -> dict:
+        """clg_unpack_wide_host: the seven w_* arrays by name, in row order.  Invalid input raises
+        ClonosError with bad_what, bad_stream and bad_block."""
+        return unpack_wide_host(self)
+
+    def kinds(self) -> np.ndarray:
+        """The kind (tag - 3) of every row: stream 0, read from its blocks (unpack() validates)."""
+        return _unpack_wide_kinds(self, np.empty(self.n_wide, np.uint8))
+
+    def rows(self, kind: int) -> dict:
+        """The rows of one kind (0 SERIALIZABLE .. 3 IGNORE_CHECKPOINT), the seven arrays by name."""
+        if not 0 <= kind < _lib.WPACK_KINDS:
+            raise IndexError("kind")
+        w = self.unpack()
+        sel = self.kinds() == kind
+        return {k: v[sel] for k, v in w.items()}
+
+
+def _unpack_wide_kinds(packed: "PackedWide", out: np.ndarray) -> np.ndarray:
+    # stream 0 is u8 FOR: its values are ref + the payload's width-bit fields
+    at = 0
+    for b in packed.desc[packed.blk_base[0]:packed.blk_base[1]]:
+        n, w = int(b["count"]), int(b["width"])
+        if w == 0:
+            out[at:at + n] = int(b["ref"])
+        else:
+            raw = packed.bits[int(b["pos"]):int(b["pos"]) + 16 * ((n * w + 127) // 128)]
+            bits = np.unpackbits(raw, bitorder="little")[:n * w].reshape(n, w)
+            out[at:at + n] = int(b["ref"]) + (bits << np.arange(w, dtype=np.uint8)).sum(axis=1)
+        at += n
+    return out
+
+
+def _pack_wide_in(cols: "DecodedColumns") -> Tuple[_lib.Columns, list]:
+    """clg_columns over cols' tags and seven wide host arrays, as the wide pack reads them."""
+    c = _lib.Columns()
+    keep = [np.ascontiguousarray(cols.tag, np.uint8)]
+    c.tag = _np_ptr(keep[0]) or None
+    for name, dt in _COL_FIELDS[5:]:
+        a = np.ascontiguousarray(getattr(cols, name), dt)
+        keep.append(a)
+        setattr(c, name, _np_ptr(a) or None)
+    c.n_rec = keep[0].size
+    c.n_class[4] = keep[1].size
+    c.out_kind = _lib.CLG_MEM_HOST
+    return c, keep
+
+
+def _pack_wide_twice(call) -> PackedWide:
+    """call(clg_packed_wide) -> status, first for the sizes, then into host arrays of exactly those."""
+    p = _lib.PackedWideC()
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _packed_wide_error(st, p)
+    desc, bits = np.zeros(int(p.blk_base[_lib.WPACK_STREAMS]), PACK_BLOCK), np.zeros(int(p.n_bits), np.uint8)
+    p = _packed_wide_struct(desc, bits)
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _packed_wide_error(st, p)
+    return PackedWide(desc, bits, p.n_val, p.blk_base)
+
+
+def pack_wide_host(cols: "DecodedColumns") -> PackedWide:
+    """clg_pack_wide_host: the wide rows partitioned by kind and bit-packed on the CPU (no engine,
+    no GPU) -- the same bytes Engine.pack_wide produces on the device.  A row that is no wide
+    record's raises ClonosError with bad_row."""
+    cin, keep = _pack_wide_in(cols)
+    return _pack_wide_twice(lambda p: lib.clg_pack_wide_host(C.byref(cin), C.byref(p)))
+
+
+def unpack_wide_host(packed: PackedWide) -> dict:
+    """clg_unpack_wide_host: the seven w_* arrays of packed wide rows, by name, in row order.
+    Invalid input raises ClonosError with bad_what, bad_stream and bad_block."""
+    p = packed._struct()
+    c = _lib.Columns()
+    st = lib.clg_unpack_wide_host(C.byref(p), C.byref(c), None)  # the layout check and the rows
+    bad = _lib.UnpackBad()
+    arrs = {}
+    if st == _lib.CLG_OK:
+        for name, dt in _COL_FIELDS[5:]:
+            arrs[name] = np.empty(int(c.n_class[4]), dt)
+            setattr(c, name, _np_ptr(arrs[name]) or None)
+        c.cap_wide = int(c.n_class[4])
+    st = lib.clg_unpack_wide_host(C.byref(p), C.byref(c), C.byref(bad))
+    if st != _lib.CLG_OK:
+        raise _unpack_error(st, bad)
+    return arrs
 
 
 # clg_digest rows: two spans are equal only when both fields are equal
@@ -1209,6 +1387,17 @@ class Engine:
         and bits null: sizes only).  Returns the status; the results are in out."""
         return lib.clg_pack_columns(self._h, C.byref(cin), C.byref(out))
 
+    def pack_wide(self, cols: DecodedColumns) -> PackedWide:
+        """clg_pack_wide: the wide rows of host columns partitioned by kind and bit-packed on the
+        device (staged in, packed, read back); the bytes are pack_wide_host's."""
+        cin, keep = _pack_wide_in(cols)
+        return _pack_wide_twice(lambda p: lib.clg_pack_wide(self._h, C.byref(cin), C.byref(p)))
+
+    def pack_wide_raw(self, cin: _lib.Columns, out: _lib.PackedWideC) -> int:
+        """clg_pack_wide over a clg_columns and a clg_packed_wide the caller set up (any kinds; desc
+        and bits NULL: sizes only); returns the status."""
+        return lib.clg_pack_wide(self._h, C.byref(cin), C.byref(out))
+
     def unpack_columns(self, packed: PackedColumns) -> DecodedColumns:
         """clg_unpack_columns: the five narrow columns of host packed columns unpacked on the device
         (staged in, checked, unpacked, read back); the wide rows, span_base, var, var_pos and error
@@ -1227,17 +1416,28 @@ class Engine:
         five narrow pointers null: sizes only).  Returns the status; the results are in cols and bad."""
         return lib.clg_unpack_columns(self._h, C.byref(pin), C.byref(cols), C.byref(bad))
 
-    def _decode_packed(self, call, total: int, n: int, spans_bytes, partial: bool, payloads: bool) -> PackedColumns:
-        """call(wide, var or None, packed) -> status, over bounds no batch of `total` encoded bytes
-        can exceed: a record is at least 2 bytes and its value at most its encoded length less the
-        tag, so the streams hold at most `total` bytes in at most total / 1024 + 5 blocks, each
-        padded by less than 16 bytes."""
-        arrs = {k: np.empty(total // 6 + n + 1, dt) for k, dt in _COL_FIELDS if k in _COL_WIDE}
+    def _decode_packed(self, call, total: int, n: int, spans_bytes, partial: bool, payloads: bool,
+                       pack_wide: bool = False) -> PackedColumns:
+        """call(wide, var or None, packed[, packed wide]) -> status, over bounds no batch of `total`
+        encoded bytes can exceed: a record is at least 2 bytes and its value at most its encoded
+        length less the tag, so the streams hold at most `total` bytes in at most total / 1024 + 5
+        blocks, each padded by less than 16 bytes.  pack_wide: the wide rows (at most total / 6 + n + 1
+        of them) come packed too, and the payload column without pos.  A residual is at most as wide
+        as its element, but for the DELTA of a zero-extended u32 (IDX, VAR_OFF), which can take 33
+        bits: 8 + 33 + 32 + 64 + 33 + 32 + 8 + 64 = 274 bits a row over KIND, IDX and a kind's six
+        streams, under 35 bytes."""
         base = np.zeros((n + 1) * _lib.COL_CLASSES, np.uint64)
         c = _lib.Columns()
-        for k in _COL_WIDE:
-            setattr(c, k, _np_ptr(arrs[k]))
-        c.cap_wide = min(a.size for a in arrs.values())
+        if pack_wide:
+            rows = total // 6 + n + 1
+            wdesc = np.empty(8 * (rows // 1024) + _lib.WPACK_STREAMS, PACK_BLOCK)
+            wbits = np.empty(35 * rows + 16 * wdesc.size, np.uint8)
+            wpk = _packed_wide_struct(wdesc, wbits)
+        else:
+            arrs = {k: np.empty(total // 6 + n + 1, dt) for k, dt in _COL_FIELDS if k in _COL_WIDE}
+            for k in _COL_WIDE:
+                setattr(c, k, _np_ptr(arrs[k]))
+            c.cap_wide = min(a.size for a in arrs.values())
         c.span_base, c.out_kind = _np_ptr(base), _lib.CLG_MEM_HOST
         desc = np.empty(total // 1024 + 5, PACK_BLOCK)
         bits = np.empty(total + 16 * desc.size, np.uint8)
@@ -1245,33 +1445,50 @@ class Engine:
         var = pos = p = None
         if payloads:
             var, pos = self._payload_bounds(total, n)
-            p = _payloads_struct(var, pos)
-        st = call(c, p, pk)
+            p = _payloads_struct(var, None if pack_wide else pos)
+        st = call(c, p, pk, wpk) if pack_wide else call(c, p, pk)
         if st != _lib.CLG_OK and not (partial and c.err_status == st):
             raise _columns_error(st, c)
         nw = int(c.n_class[_lib.COL_WIDE])
-        out = PackedColumns(desc[:int(pk.blk_base[_lib.PACK_STREAMS])], bits[:int(pk.n_bits)], pk.n_val, pk.blk_base,
-                            *[arrs[k][:nw] for k in _COL_WIDE], base, spans_bytes)
+        narrow = (desc[:int(pk.blk_base[_lib.PACK_STREAMS])], bits[:int(pk.n_bits)], pk.n_val, pk.blk_base)
+        if pack_wide:
+            wide = PackedWide(wdesc[:int(wpk.blk_base[_lib.WPACK_STREAMS])], wbits[:int(wpk.n_bits)], wpk.n_val, wpk.blk_base)
+            out = PackedColumns(*narrow, *[None] * len(_COL_WIDE), base, spans_bytes, wide_packed=wide)
+        else:
+            out = PackedColumns(*narrow, *[arrs[k][:nw] for k in _COL_WIDE], base, spans_bytes)
         if st != _lib.CLG_OK:
             out.error = _columns_error(st, c)
         if payloads:
-            out.var, out.var_pos = var[:int(p.n_var)], pos[:int(p.n_rows) + 1]
+            out.var = var[:int(p.n_var)]
+            if not pack_wide:
+                out.var_pos = pos[:int(p.n_rows) + 1]
         return out
 
     def decode_logs_columns(self, logs: Sequence["ThreadCausalLog"], start_epochs: Sequence[int],
                             keep_bytes: bool = False, partial: bool = False, payloads: bool = False,
-                            packed: bool = False) -> Union[DecodedColumns, PackedColumns]:
+                            packed: bool = False, pack_wide: bool = False) -> Union[DecodedColumns, PackedColumns]:
         """clg_decode_logs_columns: decode_logs' ranges decoded on the GPU and delivered as typed
         columns.  A decode error raises as decode_logs' does; partial=True returns the columns of
         each span's records up to its first error instead, the error in .error.  payloads=True
         (clg_decode_logs_columns_var): the wide rows' payload bytes come with the columns, gathered
         on the device (.var, .var_pos, .payload(k)); the logs' bytes do not cross the link.
         packed=True (clg_decode_logs_columns_packed): the five narrow columns come bit-packed, as
-        PackedColumns."""
+        PackedColumns.  pack_wide=True with packed=True (clg_decode_logs_columns_packed_wide): the
+        wide rows come packed by kind as well (PackedColumns.wide_packed) and the payload column
+        without var_pos, which is rebuilt from the lengths on first use."""
         n = len(logs)
         h = np.array([l.handle for l in logs], np.uint32)
         ep = np.array(start_epochs, np.int64)
         total = self.log_lengths(h)[1] if n else 0
+        if pack_wide and not packed:
+            raise ValueError("pack_wide needs packed=True")
+        if packed and pack_wide:
+            sb = [np.frombuffer(l.getDeterminants(e), np.uint8) for l, e in zip(logs, start_epochs)] if keep_bytes else None
+            return self._decode_packed(
+                lambda c, p, pk, wpk: lib.clg_decode_logs_columns_packed_wide(
+                    self._h, _np_ptr(h), _np_ptr(ep), n, C.byref(c), C.byref(p) if p is not None else None, C.byref(pk),
+                    C.byref(wpk)),
+                total, n, sb, partial, payloads, pack_wide=True)
         if packed:
             sb = [np.frombuffer(l.getDeterminants(e), np.uint8) for l, e in zip(logs, start_epochs)] if keep_bytes else None
             return self._decode_packed(
@@ -1297,16 +1514,25 @@ class Engine:
         return lib.clg_decode_logs_columns(self._h, _np_ptr(handles), _np_ptr(start_epochs), len(handles), C.byref(cols))
 
     def decode_host_columns(self, data: Union[bytes, np.ndarray], spans: Optional[Sequence[Tuple[int, int]]] = None,
-                            partial: bool = False, payloads: bool = False, packed: bool = False
-                            ) -> Union[DecodedColumns, PackedColumns]:
+                            partial: bool = False, payloads: bool = False, packed: bool = False,
+                            pack_wide: bool = False) -> Union[DecodedColumns, PackedColumns]:
         """clg_decode_host_columns: decode_host's spans decoded on the GPU and delivered as typed
-        columns (errors, payloads and packed as decode_logs_columns)."""
+        columns (errors, payloads, packed and pack_wide as decode_logs_columns)."""
         buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(
             data, np.uint8)
         if spans is None:
             spans = [(0, buf.size)]
         so = np.array([s[0] for s in spans], np.uint64)
         sl = np.array([s[1] for s in spans], np.uint64)
+        if pack_wide and not packed:
+            raise ValueError("pack_wide needs packed=True")
+        if packed and pack_wide:
+            return self._decode_packed(
+                lambda c, p, pk, wpk: lib.clg_decode_host_columns_packed_wide(
+                    self._h, _np_ptr(buf), _np_ptr(so), _np_ptr(sl), len(spans), C.byref(c),
+                    C.byref(p) if p is not None else None, C.byref(pk), C.byref(wpk)),
+                int(sl.sum()), len(spans), [buf[int(o):int(o) + int(k)] for o, k in zip(so, sl)], partial, payloads,
+                pack_wide=True)
         if packed:
             return self._decode_packed(
                 lambda c, p, pk: lib.clg_decode_host_columns_packed(self._h, _np_ptr(buf), _np_ptr(so), _np_ptr(sl), len(spans),

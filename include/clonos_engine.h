@@ -561,6 +561,79 @@ int clg_unpack_columns(clg_engine* e, const clg_packed* in, clg_columns* out, cl
  * read.  Results, statuses and `bad` are clg_unpack_columns'. */
 int clg_unpack_columns_all_host(const clg_packed* in, clg_columns* out, clg_unpack_bad* bad);
 
+/* ---- packed wide rows -------------------------------------------------------
+ * The seven w_* arrays packed after a stable partition of the rows by record kind, so that one
+ * stream holds one kind of number (clonos_amd/csrc/pack_wide.h is the format's one definition).
+ * A row's kind is tag[w_idx[k]] - 3: 0 SERIALIZABLE, 1 TIMER_TRIGGER, 2 SOURCE_CHECKPOINT,
+ * 3 IGNORE_CHECKPOINT.  26 streams, each cut into blocks of CLG_PACK_BLOCK values that are packed
+ * exactly as a clg_packed block is (ref / first / width, little-endian bit string, 16-byte
+ * padding, payloads in stream order and then block order):
+ *   0                KIND     the kind of every row       u8   FOR
+ *   1                IDX      w_idx of every row          u32  DELTA
+ *   2 + 6 * kind + 0 RC       w_rc of that kind's rows    i32  FOR
+ *   2 + 6 * kind + 1 V1       w_v1                        i64  DELTA
+ *   2 + 6 * kind + 2 VAR_OFF  w_var_off                   u32  DELTA
+ *   2 + 6 * kind + 3 VAR_LEN  w_var_len                   u32  FOR
+ *   2 + 6 * kind + 4 SUB      w_sub                       u8   FOR
+ *   2 + 6 * kind + 5 V0       w_v0                        i64  FOR for kind 0, DELTA for kinds 1-3
+ * u8 and u32 elements are zero-extended to 64 bits, i32 sign-extended.  Rank r of kind t is the
+ * r-th row of that kind; every field of every kind is packed, so any w_* content round-trips. */
+#define CLG_WPACK_KINDS 4
+#define CLG_WPACK_FIELDS 6
+#define CLG_WPACK_STREAMS 26
+enum { CLG_WPACK_KIND = 0, CLG_WPACK_IDX = 1 };
+enum { CLG_WPACK_RC = 0, CLG_WPACK_V1 = 1, CLG_WPACK_VAR_OFF = 2, CLG_WPACK_VAR_LEN = 3, CLG_WPACK_SUB = 4, CLG_WPACK_V0 = 5 };
+typedef struct clg_packed_wide {
+  clg_pack_block* desc;
+  uint8_t* bits;
+  uint64_t cap_desc;      /* blocks */
+  uint64_t cap_bits;      /* bytes */
+  uint32_t out_kind;      /* CLG_MEM_HOST / CLG_MEM_DEVICE / CLG_MEM_MAPPED (both arrays) */
+  uint32_t reserved;
+  /* results */
+  uint64_t n_val[CLG_WPACK_STREAMS];
+  uint64_t blk_base[CLG_WPACK_STREAMS + 1];
+  uint64_t n_bits;        /* bytes used of bits */
+  uint64_t bad_row;       /* the lowest row with w_idx >= n_rec or a tag outside 3 .. 6; ~0: none */
+} clg_packed_wide;
+
+/* Pack the wide rows of `in`: in->tag (n_rec values) and the seven w_* arrays (n_class[4] rows)
+ * are read under in->out_kind; nothing else of `in` is.  The rules are clg_pack_columns': desc and
+ * bits both NULL is the sizes-only call; a capacity below its total is CLG_E_CAPACITY with the
+ * results filled and nothing written; device and registered memory are read and written in place,
+ * host memory goes through engine staging; a misaligned array is CLG_E_INVALID_ARG.  A row whose
+ * w_idx is at or past n_rec, or whose tag is outside 3 .. 6: CLG_E_INVALID_ARG with the lowest such
+ * row in bad_row and nothing written.  Synchronous; takes the engine guard; the kernels' time is
+ * the stat "pack_wide". */
+int clg_pack_wide(clg_engine* e, const clg_columns* in, clg_packed_wide* out);
+/* The same bytes and rules on the CPU (no engine, no GPU): every array is host memory. */
+int clg_pack_wide_host(const clg_columns* in, clg_packed_wide* out);
+/* The way back on the CPU: the seven w_* arrays of `out` are written under cap_wide and n_class[4]
+ * is filled; nothing else of `out` is touched.  All seven pointers NULL: sizes only.  The input is
+ * not trusted; the checks run in clg_unpack_columns_all_host's order and invalid input writes
+ * nothing.  LAYOUT, beyond that call's rules: n_val[KIND] != n_val[IDX] (stream 1), the six streams
+ * of one kind with different n_val (the lowest stream that differs from its kind's RC), the four
+ * kinds' n_val not summing to n_val[KIND] (stream 0).  VALUE, beyond the type bounds (u32: 0 ..
+ * 2^32 - 1): a KIND value above 3, and a histogram of KIND that differs from the kinds' n_val
+ * (reported with stream 0, block 0). */
+int clg_unpack_wide_host(const clg_packed_wide* in, clg_columns* out, clg_unpack_bad* bad);
+/* clg_decode_logs_columns_packed / clg_decode_host_columns_packed with the wide rows delivered
+ * packed as well: no plain wide row is copied to the caller.  All twelve column pointers of `sizes`
+ * must be NULL (CLG_E_INVALID_ARG otherwise); its span_base, the totals and the error fields are
+ * filled as clg_decode_logs_columns_packed fills them.  var may be NULL.  When it is given,
+ * var->var non-NULL with var->pos NULL is legal IN THESE TWO CALLS ONLY: the bytes are delivered
+ * and pos, the exclusive prefix sum of w_var_len, is not (n_rows and n_var are still filled); both
+ * pointers NULL stays the sizes-only call.  `narrow` is clg_decode_logs_columns_packed's `out`,
+ * `wide` is clg_pack_wide's.  Ranges, flush rules, decode errors and statuses are the existing
+ * calls': each span's records up to its first error are packed and the decode's status is
+ * returned.  A capacity failure of any output fills every size and writes nothing.  One engine
+ * guard covers the whole call; the wide pack's kernel time is the stat "pack_wide". */
+int clg_decode_logs_columns_packed_wide(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                                        clg_columns* sizes, clg_payloads* var, clg_packed* narrow, clg_packed_wide* wide);
+int clg_decode_host_columns_packed_wide(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off,
+                                        const uint64_t* span_len, uint32_t n, clg_columns* sizes, clg_payloads* var,
+                                        clg_packed* narrow, clg_packed_wide* wide);
+
 /* ---- replay-prep (DeterminantResponseEvent.merge + LogReplayer decode) ----------------
  * `n` candidate copies of logs (e.g. one per responding GPU / downstream):
  * copy i is (key[i], bytes[off[i], off[i]+len[i])).  For every distinct key the LONGEST

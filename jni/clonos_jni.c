@@ -366,6 +366,60 @@ JNIEXPORT jint JNICALL FN(nDecodeLogsColumnsPacked)(JNIEnv* env, jclass cls, jlo
   return s;
 }
 
+/* clg_decode_logs_columns_packed_wide into direct buffers: the narrow columns and the wide rows both
+ * packed, the payload bytes without pos.  res[0..24] as nDecodeLogsColumnsPacked fills them, then
+ * the wide pack's n_val[26], blk_base[27], n_bits and bad_row: 80 longs. */
+JNIEXPORT jint JNICALL FN(nDecodeLogsColumnsPackedWide)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray starts,
+                                                        jobject desc, jobject bits, jobject wdesc, jobject wbits,
+                                                        jobject var, jboolean with_payloads, jlongArray res,
+                                                        jlongArray span_base) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* st = (*env)->GetLongArrayElements(env, starts, NULL);
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  clg_columns c;
+  memset(&c, 0, sizeof c);
+  c.span_base = (uint64_t*)base;
+  c.out_kind = CLG_MEM_HOST;
+  clg_payloads p;
+  memset(&p, 0, sizeof p);
+  p.var = addr(env, var, 0);
+  p.cap_var = cap(env, var);
+  p.out_kind = CLG_MEM_HOST;
+  clg_packed k;
+  memset(&k, 0, sizeof k);
+  k.desc = (clg_pack_block*)addr(env, desc, 0);
+  k.bits = addr(env, bits, 0);
+  k.cap_desc = cap(env, desc) / sizeof(clg_pack_block);
+  k.cap_bits = cap(env, bits);
+  k.out_kind = CLG_MEM_HOST;
+  clg_packed_wide w;
+  memset(&w, 0, sizeof w);
+  w.desc = (clg_pack_block*)addr(env, wdesc, 0);
+  w.bits = addr(env, wbits, 0);
+  w.cap_desc = cap(env, wdesc) / sizeof(clg_pack_block);
+  w.cap_bits = cap(env, wbits);
+  w.out_kind = CLG_MEM_HOST;
+  int s = clg_decode_logs_columns_packed_wide(ENG(e), (const uint32_t*)lg, (const int64_t*)st, (uint32_t)n, &c,
+                                              with_payloads ? &p : NULL, &k, &w);
+  jlong r[80] = {(jlong)c.n_rec,      (jlong)c.n_class[0], (jlong)c.n_class[1], (jlong)c.n_class[2], (jlong)c.n_class[3],
+                 (jlong)c.n_class[4], c.err_status,        c.err_span,          c.err_off,           c.err_tag,
+                 (jlong)p.n_rows,     (jlong)p.n_var,      (jlong)p.bad_row};
+  for (int i = 0; i < CLG_PACK_STREAMS; ++i) r[13 + i] = (jlong)k.n_val[i];
+  for (int i = 0; i <= CLG_PACK_STREAMS; ++i) r[18 + i] = (jlong)k.blk_base[i];
+  r[24] = (jlong)k.n_bits;
+  for (int i = 0; i < CLG_WPACK_STREAMS; ++i) r[25 + i] = (jlong)w.n_val[i];
+  for (int i = 0; i <= CLG_WPACK_STREAMS; ++i) r[51 + i] = (jlong)w.blk_base[i];
+  r[78] = (jlong)w.n_bits;
+  r[79] = (jlong)w.bad_row;
+  (*env)->SetLongArrayRegion(env, res, 0, 80, r);
+  (*env)->ReleaseLongArrayElements(env, span_base, base, 0);
+  (*env)->ReleaseLongArrayElements(env, starts, st, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  return s;
+}
+
 /* The columns of an EngineDecodedColumns with its payload column as clg_columns_in (host memory):
  * the class counts are span_base's last row, n_var is pos[n_wide]. */
 static void columns_in_of(JNIEnv* env, clg_columns_in* in, jobject tag, jobject order, jobject timestamp, jobject rng,

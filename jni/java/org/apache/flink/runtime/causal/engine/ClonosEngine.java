@@ -218,6 +218,30 @@ public final class ClonosEngine implements AutoCloseable {
 	}
 
 	/**
+	 * decodeLogsColumnsPacked with the wide rows delivered packed as well (clg_decode_logs_columns_packed_wide):
+	 * no plain wide row and no payload position crosses the link.  EnginePackedWide.narrow holds the five
+	 * narrow streams and the span bases, EnginePackedWide.cursor(s) pops span s's wide rows one at a time.
+	 * Two native calls: the sizes, then the bytes.
+	 */
+	public EnginePackedWide decodeLogsColumnsPackedWide(int[] logs, long[] startEpochs, boolean withPayloads) {
+		long[] res = new long[EnginePackedWide.R_LEN];
+		long[] spanBase = new long[5 * (logs.length + 1)];
+		int st = nDecodeLogsColumnsPackedWide(handle, logs, startEpochs, null, null, null, null, null, withPayloads,
+			res, spanBase);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st); // engine failure, not a decode error
+		}
+		EnginePackedWide c = new EnginePackedWide(res, logs.length, withPayloads);
+		st = nDecodeLogsColumnsPackedWide(handle, logs, startEpochs, c.narrow.desc, c.narrow.bits, c.desc, c.bits,
+			c.var, withPayloads, res, c.narrow.spanBase);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st);
+		}
+		c.setResult(res);
+		return c;
+	}
+
+	/**
 	 * The log bytes of typed columns that carry their payload column (clg_encode_columns), encoded on the
 	 * device from the columns as they are: the inverse of decodeLogsColumns(logs, startEpochs, true).  Span
 	 * s's bytes are [spanByteBase[s], spanByteBase[s + 1]) of the returned buffer when spanByteBase
@@ -469,6 +493,12 @@ public final class ClonosEngine implements AutoCloseable {
 											   ByteBuffer wVarOff, ByteBuffer wVarLen, ByteBuffer wSub, ByteBuffer wV0,
 											   ByteBuffer var, ByteBuffer varPos, boolean withPayloads, long[] result,
 											   long[] spanBase);
+	/** clg_decode_logs_columns_packed_wide: result[0..24] as nDecodeLogsColumnsPacked, then the wide pack's
+	 *  n_val[26], blk_base[27], n_bits and bad_row (80 longs); every buffer null: sizes only. */
+	static native int nDecodeLogsColumnsPackedWide(long engine, int[] logs, long[] startEpochs, ByteBuffer desc,
+												   ByteBuffer bits, ByteBuffer wideDesc, ByteBuffer wideBits,
+												   ByteBuffer var, boolean withPayloads, long[] result,
+												   long[] spanBase);
 	/** clg_encode_columns over host columns; out null: sizes only.  result = {n_bytes, bad_what, bad_index}. */
 	static native int nEncodeColumns(long engine, ByteBuffer tag, ByteBuffer order, ByteBuffer timestamp, ByteBuffer rng,
 									 ByteBuffer bufferBuilt, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1,
