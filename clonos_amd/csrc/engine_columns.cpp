@@ -552,9 +552,10 @@ int pack_sizes(clg_engine* e, const clg::PackSrc& src, clg_packed* out, clg::Pac
   uint64_t in_bytes = 0;
   for (uint32_t c = 0; c < clg::kPackStreams; ++c) {
     if (src.n[c] && !src.col[c]) return fail(CLG_E_INVALID_ARG, "null input array (stream %u)", c);
-    if (uintptr_t(src.col[c]) % clg::pack_elem(c)) return fail(CLG_E_INVALID_ARG, "stream %u is not aligned to its element", c);
+    if (uintptr_t(src.col[c]) % clg::pack_stream_bytes(c))
+      return fail(CLG_E_INVALID_ARG, "stream %u is not aligned to its element", c);
     pin->col[c] = src.col[c], pin->n[c] = src.n[c];
-    in_bytes += src.n[c] * clg::pack_elem(c);
+    in_bytes += src.n[c] * clg::pack_stream_bytes(c);
   }
   for (uint32_t c = 0; c <= clg::kPackStreams; ++c) pin->blk_base[c] = out->blk_base[c];
   const uint64_t ng = (nb + clg::kPackScanGroup - 1) / clg::kPackScanGroup;
@@ -572,34 +573,54 @@ int pack_sizes(clg_engine* e, const clg::PackSrc& src, clg_packed* out, clg::Pac
   return CLG_OK;
 }
 
-int pack_out_check(const clg_packed& out, const char* what = "") {  // (a packed input's, too)
+// ---- what the two packed families share, over a PackView of either's struct ---------------------
+
+int pack_out_check(const clg::PackView& out, const char* what = "") {  // (a packed input's, too)
   if (!mem_kind_ok(out.out_kind)) return fail(CLG_E_INVALID_ARG, "%sout_kind %u", what, out.out_kind);
   if (out.out_kind != CLG_MEM_HOST && (uintptr_t(out.desc) % 8 || uintptr_t(out.bits) % 16))
     return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
   return CLG_OK;
 }
 
-// The write pass, after pack_sizes and the capacity check: device and registered outputs are
-// written by the kernel, host ones through engine staging and one copy each.
-int pack_write(clg_engine* e, const clg::PackIn& pin, clg_packed* out) {
-  const uint64_t nb = out->blk_base[clg::kPackStreams], nbits = out->n_bits;
+// The write pass, after the sizes and the capacity check: device and registered outputs are
+// written by the kernel, host ones through engine staging and one copy each.  launch(desc, bits):
+// the family's write kernel over the placed outputs; in_bytes: what it reads of the values.
+template <class Launch>
+int pack_write(clg_engine* e, const clg::PackView& out, DevBuf& staging, const char* stat, uint64_t in_bytes,
+               const Launch& launch) {
+  const uint64_t nb = out.blocks(), nbits = *out.n_bits;
   if (!nb) return CLG_OK;
-  const PlaceSpec dst[2] = {{out->desc, nb * sizeof(clg_pack_block), 8}, {out->bits, nbits, 16}};
+  const PlaceSpec dst[2] = {{out.desc, nb * sizeof(clg_pack_block), 8}, {out.bits, nbits, 16}};
   clg::Placement pl;
-  CHK(place_out(e->d_packout, dst, 2, out->out_kind, PlacePolicy::stage_if_unresolved, "packed", &pl));
-  uint64_t in_bytes = 0;
-  for (uint32_t c = 0; c < clg::kPackStreams; ++c) in_bytes += pin.n[c] * clg::pack_elem(c);
-  CHK(e->timed("pack_columns", in_bytes + nb * 64 + nbits, [&] {
-    return clg::launch_pack_write(pin, uint32_t(nb), e->d_packdesc.as<clg_pack_block>(), pl.at<clg_pack_block>(0),
-                                  pl.at<uint8_t>(1), nb, nbits, e->stream);
-  }));
+  CHK(place_out(staging, dst, 2, out.out_kind, PlacePolicy::stage_if_unresolved, "packed", &pl));
+  CHK(e->timed(stat, in_bytes + nb * 64 + nbits, [&] { return launch(pl.at<clg_pack_block>(0), pl.at<uint8_t>(1)); }));
   CHK(stage_out(e, dst, 2, pl));
   return e->sync();
 }
 
-int pack_capacity_error(const clg_packed& out, const char* name) {
-  return fail(CLG_E_CAPACITY, "packed columns: %s is too small (blocks %llu, payload bytes %llu)", name,
-              (unsigned long long)out.blk_base[clg::kPackStreams], (unsigned long long)out.n_bits);
+// prefix: "packed columns" or "packed wide rows".
+int pack_capacity_error(const clg::PackView& out, const char* prefix, const char* name) {
+  return fail(CLG_E_CAPACITY, "%s: %s is too small (blocks %llu, payload bytes %llu)", prefix, name,
+              (unsigned long long)out.blocks(), (unsigned long long)*out.n_bits);
+}
+
+// Past the sizes: nothing more for the sizes-only call, the capacity error for a short output,
+// else the write.
+template <class Write>
+int pack_finish(const clg::PackView& out, const char* prefix, const Write& write) {
+  if (clg::pack_sizes_only(out)) return CLG_OK;
+  if (const char* name = clg::pack_short(out)) return pack_capacity_error(out, prefix, name);
+  return write();
+}
+
+int pack_write(clg_engine* e, const clg::PackIn& pin, const clg_packed* out) {
+  uint64_t in_bytes = 0;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) in_bytes += pin.n[c] * clg::pack_stream_bytes(c);
+  const uint64_t nb = out->blk_base[clg::kPackStreams];
+  const auto launch = [&](clg_pack_block* desc, uint8_t* bits) {
+    return clg::launch_pack_write(pin, uint32_t(nb), e->d_packdesc.as<clg_pack_block>(), desc, bits, nb, out->n_bits, e->stream);
+  };
+  return pack_write(e, clg::pack_view(*out), e->d_packout, "pack_columns", in_bytes, launch);
 }
 
 // ---- packed wide rows (pack_wide.h) ---------------------------------------------------------
@@ -644,7 +665,7 @@ int wpack_sizes(clg_engine* e, const clg::WPackSrc& src, clg_packed_wide* out) {
   size_t so[kArrays + 1];
   for (uint32_t t = 0; t < clg::kWPackKinds; ++t)
     for (uint32_t f = 0; f < clg::kWPackFields; ++f)
-      cb[t * clg::kWPackFields + f] = res->tot[t] * clg::wpack_elem_bytes(clg::kWPackField[f].elem);
+      cb[t * clg::kWPackFields + f] = res->tot[t] * clg::pack_elem_bytes(clg::kWPackField[f].elem);
   CHK(e->d_wpacksoa.ensure(clg::place_layout(cb, kArrays, so) + 16));
   CHK(e->h_wpacktab.ensure(sizeof(clg::WPackTab)));
   CHK(e->d_wpacktab.ensure(sizeof(clg::WPackTab)));
@@ -670,31 +691,13 @@ int wpack_sizes(clg_engine* e, const clg::WPackSrc& src, clg_packed_wide* out) {
   return CLG_OK;
 }
 
-int wpack_out_check(const clg_packed_wide& out) {
-  if (!mem_kind_ok(out.out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out.out_kind);
-  if (out.out_kind != CLG_MEM_HOST && (uintptr_t(out.desc) % 8 || uintptr_t(out.bits) % 16))
-    return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
-  return CLG_OK;
-}
-
-// The write pass, after wpack_sizes and the capacity check.
-int wpack_write(clg_engine* e, clg_packed_wide* out) {
-  const uint64_t nb = out->blk_base[clg::kWPackStreams], nbits = out->n_bits;
-  if (!nb) return CLG_OK;
-  const PlaceSpec dst[2] = {{out->desc, nb * sizeof(clg_pack_block), 8}, {out->bits, nbits, 16}};
-  clg::Placement pl;
-  CHK(place_out(e->d_wpackout, dst, 2, out->out_kind, PlacePolicy::stage_if_unresolved, "packed", &pl));
-  CHK(e->timed("pack_wide", out->n_val[CLG_WPACK_KIND] * 34 + nb * 64 + nbits, [&] {
-    return clg::launch_wpack_write(e->d_wpacktab.as<clg::WPackTab>(), uint32_t(nb), e->d_wpackdesc.as<clg_pack_block>(),
-                                   pl.at<clg_pack_block>(0), pl.at<uint8_t>(1), nb, nbits, e->stream);
-  }));
-  CHK(stage_out(e, dst, 2, pl));
-  return e->sync();
-}
-
-int wpack_capacity_error(const clg_packed_wide& out, const char* name) {
-  return fail(CLG_E_CAPACITY, "packed wide rows: %s is too small (blocks %llu, payload bytes %llu)", name,
-              (unsigned long long)out.blk_base[clg::kWPackStreams], (unsigned long long)out.n_bits);
+int wpack_write(clg_engine* e, const clg_packed_wide* out) {
+  const uint64_t nb = out->blk_base[clg::kWPackStreams];
+  const auto launch = [&](clg_pack_block* desc, uint8_t* bits) {
+    return clg::launch_wpack_write(e->d_wpacktab.as<clg::WPackTab>(), uint32_t(nb), e->d_wpackdesc.as<clg_pack_block>(), desc, bits,
+                                   nb, out->n_bits, e->stream);
+  };
+  return pack_write(e, clg::pack_view(*out), e->d_wpackout, "pack_wide", out->n_val[CLG_WPACK_KIND] * 34, launch);
 }
 
 // The decode into engine scratch and the columns of what it produced, also in engine scratch;
@@ -710,8 +713,8 @@ int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_c
     for (int i = clg::kColNarrowArrays; i < clg::kColArrays; ++i)
       if (clg::col_ptr(*wide, i)) return fail(CLG_E_INVALID_ARG, "every column pointer of `sizes` must be NULL: the wide rows are delivered packed");
   if (!mem_kind_ok(wide->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", wide->out_kind);
-  CHK(pack_out_check(*out));
-  if (wpk) CHK(wpack_out_check(*wpk));
+  CHK(pack_out_check(clg::pack_view(*out)));
+  if (wpk) CHK(pack_out_check(clg::pack_view(*wpk)));
   clg::col_reset_result(wide);
   clg::pack_reset_result(out);
   if (wpk) clg::wpack_reset_result(wpk);
@@ -772,20 +775,21 @@ int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_c
   bool wide_any = false, wide_short = false;
   for (int i = w0; i < w1; ++i) wide_any = wide_any || clg::col_ptr(*wide, i);
   for (int i = w0; i < w1; ++i) wide_short = wide_short || (wide_any && clg::col_array_cap(*wide, i) < nw);
-  const char* pk_short = clg::pack_sizes_only(*out) ? nullptr : clg::pack_short(*out);
-  const char* wpk_short = wpk && !clg::wpack_sizes_only(*wpk) ? clg::wpack_short(*wpk) : nullptr;
+  const clg::PackView pv = clg::pack_view(*out), wpv = wpk ? clg::pack_view(*wpk) : clg::PackView{};
+  const char* pk_short = clg::pack_sizes_only(pv) ? nullptr : clg::pack_short(pv);
+  const char* wpk_short = wpk && !clg::pack_sizes_only(wpv) ? clg::pack_short(wpv) : nullptr;
   const char* pay_short = !var || ps != CLG_OK || clg::pay_sizes_only(*var) ? nullptr
                           : !no_pos                                         ? clg::pay_short(*var, var->n_rows, var->n_var)
                           : var->cap_var < var->n_var                       ? "var"
                                                                             : nullptr;
   if (wide_short) return fail(CLG_E_CAPACITY, "the wide rows' arrays are too small (rows %llu)", (unsigned long long)nw);
-  if (pk_short) return pack_capacity_error(*out, pk_short);
-  if (wpk_short) return wpack_capacity_error(*wpk, wpk_short);
+  if (pk_short) return pack_capacity_error(pv, "packed columns", pk_short);
+  if (wpk_short) return pack_capacity_error(wpv, "packed wide rows", wpk_short);
   if (pay_short) return pay_too_small(pay_short, var->n_rows, var->n_var);
 
   // the writes
-  if (!clg::pack_sizes_only(*out)) CHK(pack_write(e, pin, out));
-  if (wpk && !clg::wpack_sizes_only(*wpk)) CHK(wpack_write(e, wpk));
+  if (!clg::pack_sizes_only(pv)) CHK(pack_write(e, pin, out));
+  if (wpk && !clg::pack_sizes_only(wpv)) CHK(wpack_write(e, wpk));
   if (wide_any && nw) {
     for (int i = w0; i < w1; ++i)
       CHK(copy_caller(e, clg::col_ptr(*wide, i), clg::col_ptr(full, i), nw * clg::kColArray[i].width, hipMemcpyDefault,
@@ -835,29 +839,28 @@ int clg_pack_columns(clg_engine* e, const clg_columns* in, clg_packed* out) {
   ENGINE_GUARD(e);
   if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
   clg::pack_reset_result(out);
-  CHK(pack_out_check(*out));
+  CHK(pack_out_check(clg::pack_view(*out)));
   clg::PackSrc src = clg::pack_src(*in);
   for (uint32_t c = 0; c < clg::kPackStreams; ++c)
     if (src.n[c] && !src.col[c]) return fail(CLG_E_INVALID_ARG, "null input array (stream %u)", c);
   if (!mem_kind_ok(in->out_kind)) return fail(CLG_E_INVALID_ARG, "the columns' out_kind %u", in->out_kind);
   PlaceSpec ins[clg::kPackStreams];
-  for (uint32_t c = 0; c < clg::kPackStreams; ++c) ins[c] = {src.col[c], src.n[c] * clg::pack_elem(c), clg::pack_elem(c)};
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c)
+    ins[c] = {src.col[c], src.n[c] * clg::pack_stream_bytes(c), clg::pack_stream_bytes(c)};
   clg::Placement pl;
   const int st = place_in(e, e->d_packin, ins, clg::kPackStreams, in->out_kind, PlacePolicy::stage_if_unresolved, "stream", &pl);
   if (st != CLG_OK) return clg::pack_layout(src.n, out), st;  // (a misaligned stream: the layout is filled, as pack_sizes fills it)
   for (uint32_t c = 0; c < clg::kPackStreams; ++c) src.col[c] = pl.at<const void>(c);
   clg::PackIn pin{};
   CHK(pack_sizes(e, src, out, &pin));
-  if (clg::pack_sizes_only(*out)) return CLG_OK;
-  if (const char* name = clg::pack_short(*out)) return pack_capacity_error(*out, name);
-  return pack_write(e, pin, out);
+  return pack_finish(clg::pack_view(*out), "packed columns", [&] { return pack_write(e, pin, out); });
 }
 
 int clg_pack_wide(clg_engine* e, const clg_columns* in, clg_packed_wide* out) {
   ENGINE_GUARD(e);
   if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
   clg::wpack_reset_result(out);
-  CHK(wpack_out_check(*out));
+  CHK(pack_out_check(clg::pack_view(*out)));
   if (!mem_kind_ok(in->out_kind)) return fail(CLG_E_INVALID_ARG, "the columns' out_kind %u", in->out_kind);
   const uint64_t nr = in->n_rec, nw = in->n_class[clg::kColWide];
   const PlaceSpec ins[8] = {{in->tag, nw ? nr : 0, 1},         {in->w_idx, nw * 4, 4},     {in->w_rc, nw * 4, 4}, {in->w_v1, nw * 8, 8},
@@ -871,9 +874,7 @@ int clg_pack_wide(clg_engine* e, const clg_columns* in, clg_packed_wide* out) {
                           pl.at<const uint32_t>(4), pl.at<const uint32_t>(5), pl.at<const uint8_t>(6), pl.at<const int64_t>(7),
                           nr,                       nw};
   CHK(wpack_sizes(e, src, out));
-  if (clg::wpack_sizes_only(*out)) return CLG_OK;
-  if (const char* name = clg::wpack_short(*out)) return wpack_capacity_error(*out, name);
-  return wpack_write(e, out);
+  return pack_finish(clg::pack_view(*out), "packed wide rows", [&] { return wpack_write(e, out); });
 }
 
 int clg_pack_wide_host(const clg_columns* in, clg_packed_wide* out) {
@@ -1251,7 +1252,7 @@ namespace {
 int unpack_input(clg_engine* e, const clg_packed* in, clg::UnpackIn* uin) {
   const uint64_t nb = in->blk_base[clg::kPackStreams], nbits = in->n_bits;
   if (nb >> 31) return fail(CLG_E_INVALID_ARG, "%llu blocks in one call", (unsigned long long)nb);
-  CHK(pack_out_check(*in, "the packed input's "));
+  CHK(pack_out_check(clg::pack_view(*in), "the packed input's "));
   const PlaceSpec ins[2] = {{in->desc, nb * sizeof(clg_pack_block), 8}, {in->bits, nbits, 16}};
   clg::Placement pl;
   CHK(place_in(e, e->d_unpackin, ins, 2, in->out_kind, PlacePolicy::stage_if_unresolved, "packed input", &pl));
@@ -1288,7 +1289,7 @@ int unpack_check(clg_engine* e, const clg::UnpackIn& uin, clg_unpack_bad* bad) {
 int unpack_write(clg_engine* e, const clg::UnpackIn& uin, const clg::UnpackOut& uout) {
   const uint64_t nb = uin.blk_base[clg::kPackStreams];
   uint64_t out_bytes = 0;
-  for (uint32_t c = 0; c < clg::kPackStreams; ++c) out_bytes += uin.n[c] * clg::pack_elem(c);
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) out_bytes += uin.n[c] * clg::pack_stream_bytes(c);
   // (bytes: the descriptors again, the payloads, the plain columns once)
   return e->timed("unpack_columns", nb * sizeof(clg_pack_block) + uin.n_bits + out_bytes,
                   [&] { return clg::launch_unpack_write(uin, uout, uint32_t(nb), e->stream); });
@@ -1303,7 +1304,7 @@ int unpack_for_encode(clg_engine* e, const clg_packed* narrow, const clg_columns
   if (rest->tag || rest->order || rest->timestamp || rest->rng || rest->buffer_built)
     return fail(CLG_E_INVALID_ARG, "the narrow column pointers of `rest` must be NULL: those columns are given packed");
   uint32_t stream;
-  if (!clg::pack_layout_in_ok(*narrow, &stream)) {
+  if (!clg::pack_layout_in_ok(clg::pack_view(*narrow), &stream)) {
     clg::pack_bad_set(bad, CLG_UNPACK_BAD_LAYOUT, stream, 0);
     return fail(CLG_E_INVALID_ARG, "unpack columns: blk_base, n_val, the capacities and the pointers disagree (stream %u)", stream);
   }
@@ -1317,7 +1318,7 @@ int unpack_for_encode(clg_engine* e, const clg_packed* narrow, const clg_columns
   clg::UnpackIn uin{};
   CHK(unpack_input(e, narrow, &uin));
   uint64_t cb[clg::kPackStreams];
-  for (uint32_t c = 0; c < clg::kPackStreams; ++c) cb[c] = narrow->n_val[c] * clg::pack_elem(c);
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) cb[c] = narrow->n_val[c] * clg::pack_stream_bytes(c);
   size_t at[clg::kPackStreams + 1];
   CHK(e->d_unpackcol.ensure(clg::place_layout(cb, clg::kPackStreams, at) + 16));
   clg::UnpackOut uout{};
@@ -1349,7 +1350,8 @@ int clg_unpack_columns(clg_engine* e, const clg_packed* in, clg_columns* out, cl
   if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
   const clg::UnpackDst dst = clg::unpack_dst(*out);
   PlaceSpec outs[clg::kPackStreams];
-  for (uint32_t c = 0; c < clg::kPackStreams; ++c) outs[c] = {dst.col[c], in->n_val[c] * clg::pack_elem(c), clg::pack_elem(c)};
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c)
+    outs[c] = {dst.col[c], in->n_val[c] * clg::pack_stream_bytes(c), clg::pack_stream_bytes(c)};
   clg::Placement pl;
   CHK(place_out(e->d_unpackout, outs, clg::kPackStreams, out->out_kind, PlacePolicy::stage_if_unresolved, "column", &pl));
   clg::UnpackIn uin{};

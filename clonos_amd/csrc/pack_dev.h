@@ -1,6 +1,7 @@
-// pack_dev.h -- what the pack kernels of pack.hip and pack_wide.hip share on the device: the
-// workgroup's shape, the wave's signed minimum / maximum by DPP and the wave scans.  Device code
-// only, file-local in each unit that includes it.
+// pack_dev.h -- what the kernels of pack.hip, pack_wide.hip and unpack.hip share on the device:
+// the workgroup's shape, the wave's signed minimum / maximum by DPP, the wave scans, the round of a
+// one-workgroup scan, and the block codec's measure and write, instantiated on (element, scheme).
+// Device code only, file-local in each unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,6 +59,152 @@ __device__ __forceinline__ uint64_t pack_wave_incl64(uint64_t x, uint32_t lane) 
     if (lane >= o) x += y;
   }
   return x;
+}
+
+// One round of a one-workgroup scan over kPackTopThreads values, a value a thread: x's exclusive
+// prefix within the round; *wtot then holds the round's total.  The wave scan, then the waves
+// through LDS (ws: a word a wave).  The caller ends the round with a __syncthreads() before the
+// next one writes ws and *wtot again.
+__device__ __forceinline__ uint64_t pack_scan_round(uint64_t x, uint32_t lane, uint64_t* ws, uint64_t* wtot) {
+  constexpr uint32_t kW = kPackTopThreads / 64;
+  const uint32_t tid = threadIdx.x, w = tid >> 6;
+  const uint64_t inc = pack_wave_incl64(x, lane);
+  if (lane == 63) ws[w] = inc;
+  __syncthreads();
+  if (tid < 64) {
+    const uint64_t y = lane < kW ? ws[lane] : 0;
+    const uint64_t s = pack_wave_incl64(y, lane);
+    if (lane < kW) ws[lane] = s - y;
+    if (lane == kW - 1) *wtot = s;
+  }
+  __syncthreads();
+  return ws[w] + (inc - x);
+}
+
+// ---- the block codec on the device: a workgroup of kPackThreads per block ----------------------
+
+// A block's place, which each unit finds in its own way: its stream's array, the block's first
+// value and how many it holds.
+struct PackAt {
+  const void* col;
+  uint64_t i0;
+  uint32_t m;
+};
+// The measure: four coalesced values a thread, the DELTA predecessor through LDS (s_x: kPackBlock
+// words), the residuals' signed minimum and maximum by the wave reduction and LDS across the waves
+// (s_lo, s_hi: a word a wave); thread 0 writes ref, first, width, count and, in pos, the payload's
+// size to desc[blockIdx.x].  The element and the scheme are constants in each instance.
+template <uint32_t kElem, bool kDelta>
+__device__ __forceinline__ void pack_block_measure(const PackAt at, clg_pack_block* __restrict__ desc, int64_t* s_x,
+                                                   int64_t* s_lo, int64_t* s_hi) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int64_t x[kPackPerThread];
+#pragma unroll
+  for (uint32_t k = 0; k < kPackPerThread; ++k) {
+    const uint32_t i = k * kPackThreads + tid;
+    x[k] = i < at.m ? pack_load(kElem, at.col, at.i0 + i) : 0;
+  }
+  int64_t lo = INT64_MAX, hi = INT64_MIN;
+  if (kDelta) {
+#pragma unroll
+    for (uint32_t k = 0; k < kPackPerThread; ++k) s_x[k * kPackThreads + tid] = x[k];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < kPackPerThread; ++k) {
+      const uint32_t i = k * kPackThreads + tid;
+      if (i >= 1 && i < at.m) {
+        const int64_t r = int64_t(uint64_t(x[k]) - uint64_t(s_x[i - 1]));
+        lo = pack_min(lo, r), hi = pack_max(hi, r);
+      }
+    }
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < kPackPerThread; ++k)
+      if (k * kPackThreads + tid < at.m) lo = pack_min(lo, x[k]), hi = pack_max(hi, x[k]);
+  }
+  CLG_PACK_WAVE_REDUCE(pack_min, lo);
+  CLG_PACK_WAVE_REDUCE(pack_max, hi);
+  if (lane == 0) s_lo[w] = lo, s_hi[w] = hi;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (uint32_t j = 1; j < kPackWaves; ++j) lo = pack_min(lo, s_lo[j]), hi = pack_max(hi, s_hi[j]);
+    const uint32_t k = pack_residuals(kDelta, at.m);
+    clg_pack_block d;
+    d.ref = k ? lo : 0;
+    d.first = kDelta && at.m ? x[0] : 0;  // (thread 0's first value is the block's)
+    d.width = k ? pack_width(uint64_t(hi) - uint64_t(lo)) : 0;
+    d.count = at.m;
+    d.pos = pack_payload_bytes(k, d.width);  // the size; the scan turns it into the offset
+    desc[blockIdx.x] = d;
+  }
+}
+
+// The write: the values reloaded, p_i formed, the payload assembled in LDS and stored with one
+// aligned 16-byte store a lane, below lim_bits.  s_w: 8 KiB, the block's values (the DELTA
+// predecessors), then the payload's words.
+template <uint32_t kElem, bool kDelta>
+__device__ __forceinline__ void pack_block_write(const PackAt at, const clg_pack_block d, unsigned long long* s_w,
+                                                 uint8_t* __restrict__ bits, uint64_t lim_bits) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t k = pack_residuals(kDelta, at.m), width = d.width;
+  const uint32_t bytes = pack_payload_bytes(k, width);
+  if (!bytes) return;  // (uniform: a constant block, or a DELTA block of one value)
+  const uint32_t n_words = bytes / 8;
+  uint64_t p[kPackPerThread];
+  uint32_t j[kPackPerThread];  // the residual's index; >= k: none
+#pragma unroll
+  for (uint32_t q = 0; q < kPackPerThread; ++q) {
+    const uint32_t i = q * kPackThreads + tid;
+    p[q] = i < at.m ? uint64_t(pack_load(kElem, at.col, at.i0 + i)) : 0;
+    j[q] = i < at.m ? i : kPackBlock;
+  }
+  if (kDelta) {
+#pragma unroll
+    for (uint32_t q = 0; q < kPackPerThread; ++q) s_w[q * kPackThreads + tid] = p[q];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < kPackPerThread; ++q) {
+      const uint32_t i = q * kPackThreads + tid;
+      if (i >= 1 && i < at.m) p[q] -= s_w[i - 1], j[q] = i - 1;
+      else j[q] = kPackBlock;
+    }
+    __syncthreads();  // (s_w is written again below)
+  }
+#pragma unroll
+  for (uint32_t q = 0; q < kPackPerThread; ++q) p[q] -= uint64_t(d.ref);
+
+  if (width == 64) {  // a word a value: no shifts
+#pragma unroll
+    for (uint32_t q = 0; q < kPackPerThread; ++q)
+      if (j[q] < k) s_w[j[q]] = p[q];
+    if (tid == 0 && (k & 1)) s_w[k] = 0;  // the padding word
+  } else if (width == 1 && !kDelta) {  // a wave's 64 values are one word: a ballot
+#pragma unroll
+    for (uint32_t q = 0; q < kPackPerThread; ++q) {
+      const uint64_t m = __ballot(j[q] < k && (p[q] & 1));
+      const uint32_t word = q * kPackWaves + wv;
+      if (lane == 0 && word < n_words) s_w[word] = m;
+    }
+  } else {
+    for (uint32_t i = tid; i < n_words; i += kPackThreads) s_w[i] = 0;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < kPackPerThread; ++q)
+      if (j[q] < k) {
+        const uint32_t bit = j[q] * width, sh = bit & 63;
+        atomicOr(&s_w[bit >> 6], (unsigned long long)(p[q] << sh));
+        if (sh + width > 64) atomicOr(&s_w[(bit >> 6) + 1], (unsigned long long)(p[q] >> (64 - sh)));  // (sh > 0)
+      }
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < bytes / 16; i += kPackThreads) {
+    const uint64_t a = d.pos + uint64_t(i) * 16;
+    if (a + 16 <= lim_bits) {
+      const unsigned long long lo = s_w[2 * i], hi = s_w[2 * i + 1];
+      *reinterpret_cast<uint4*>(bits + a) = make_uint4(uint32_t(lo), uint32_t(lo >> 32), uint32_t(hi), uint32_t(hi >> 32));
+    }
+  }
 }
 
 }  // namespace

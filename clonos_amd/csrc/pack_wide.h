@@ -7,13 +7,13 @@
 // first (stable: rank r of kind t is the r-th row of that kind) and every field of every kind is a
 // stream of its own; two more streams, the kinds and the w_idx of all rows in row order, let a
 // reader put the rows back.  26 streams (kWPackStreams), each cut into blocks of kPackBlock values
-// that are packed exactly as pack.h packs a block: residuals, ref, width, payload, padding.
+// that are packed by pack.h's block codec: residuals, ref, width, payload, padding.
 //
 //   stream 0 KIND, 1 IDX, then 2 + 6 * kind + field with the fields in kWPackField's order
 //
-// The element (what a value is extended from) and the scheme of a stream are kWPackField's and
-// part of the format.  A field a kind never uses is all zeros and costs a width-0 descriptor per
-// block; nothing about the values is assumed, so any w_* content round-trips.
+// The element and the scheme of a stream (pack.h's words) are kWPackField's and part of the
+// format.  A field a kind never uses is all zeros and costs a width-0 descriptor per block; nothing
+// about the values is assumed, so any w_* content round-trips.
 //
 // Plain C++: compiles under hipcc (host and device) and under g++ without HIP
 // (tests/wpack_host.cpp).
@@ -28,25 +28,21 @@ constexpr uint32_t kWPackStreams = CLG_WPACK_STREAMS;
 constexpr uint32_t kWPackFirstTag = 3;  // kind = tag - kWPackFirstTag
 static_assert(kWPackStreams == 2 + kWPackKinds * kWPackFields, "KIND, IDX and a stream per (kind, field)");
 
-// A stream's element: what its values are extended to 64 bits from.
-enum : uint32_t { kWElemU8 = 0, kWElemU32 = 1, kWElemI32 = 2, kWElemI64 = 3 };
-enum : uint32_t { kWFor = 0, kWDelta = 1 };
-
 // The scheme table.  V0 of kind 0 is a stream length (FOR); of kinds 1 - 3 a clock or a checkpoint
 // id (DELTA).
 struct WPackField {
   uint8_t elem, scheme_kind0, scheme_rest;
 };
 constexpr WPackField kWPackField[kWPackFields] = {
-    {kWElemI32, kWFor, kWFor},      // RC       w_rc
-    {kWElemI64, kWDelta, kWDelta},  // V1       w_v1
-    {kWElemU32, kWDelta, kWDelta},  // VAR_OFF  w_var_off
-    {kWElemU32, kWFor, kWFor},      // VAR_LEN  w_var_len
-    {kWElemU8, kWFor, kWFor},       // SUB      w_sub
-    {kWElemI64, kWFor, kWDelta},    // V0       w_v0
+    {kElemI32, kPackFor, kPackFor},      // RC       w_rc
+    {kElemI64, kPackDelta, kPackDelta},  // V1       w_v1
+    {kElemU32, kPackDelta, kPackDelta},  // VAR_OFF  w_var_off
+    {kElemU32, kPackFor, kPackFor},      // VAR_LEN  w_var_len
+    {kElemU8, kPackFor, kPackFor},       // SUB      w_sub
+    {kElemI64, kPackFor, kPackDelta},    // V0       w_v0
 };
-constexpr uint32_t kWPackKindElem = kWElemU8, kWPackKindScheme = kWFor;
-constexpr uint32_t kWPackIdxElem = kWElemU32, kWPackIdxScheme = kWDelta;
+constexpr uint32_t kWPackKindElem = kElemU8, kWPackKindScheme = kPackFor;
+constexpr uint32_t kWPackIdxElem = kElemU32, kWPackIdxScheme = kPackDelta;
 
 // The table folded into two words (two bits of element and one of scheme a stream), so that device
 // code indexes a constant and not an array.
@@ -67,37 +63,8 @@ constexpr uint64_t kWPackElemBits = wpack_fold_elem();
 constexpr uint32_t kWPackSchemeBits = wpack_fold_scheme();
 
 CLG_PACK_HD uint32_t wpack_stream(uint32_t kind, uint32_t field) { return 2 + kind * kWPackFields + field; }
-CLG_PACK_HD uint32_t wpack_elem(uint32_t stream) { return uint32_t(kWPackElemBits >> (2 * stream)) & 3u; }
+CLG_PACK_HD uint32_t wpack_stream_elem(uint32_t stream) { return uint32_t(kWPackElemBits >> (2 * stream)) & 3u; }
 CLG_PACK_HD bool wpack_is_delta(uint32_t stream) { return (kWPackSchemeBits >> stream & 1u) != 0; }
-CLG_PACK_HD uint32_t wpack_elem_bytes(uint32_t elem) { return elem == kWElemU8 ? 1u : elem == kWElemI64 ? 8u : 4u; }
-CLG_PACK_HD uint32_t wpack_resid(bool delta, uint32_t m) { return delta && m ? m - 1 : m; }
-
-// Value i of an array of `elem`, extended to 64 bits.
-CLG_PACK_HD int64_t wpack_load(uint32_t elem, const void* col, uint64_t i) {
-  switch (elem) {
-    case kWElemU8: return int64_t(static_cast<const uint8_t*>(col)[i]);
-    case kWElemU32: return int64_t(static_cast<const uint32_t*>(col)[i]);
-    case kWElemI32: return int64_t(static_cast<const int32_t*>(col)[i]);
-    default: return static_cast<const int64_t*>(col)[i];
-  }
-}
-// The element's bounds, for the unpack's value check.
-CLG_PACK_HD bool wpack_value_ok(uint32_t elem, int64_t v) {
-  switch (elem) {
-    case kWElemU8: return v >= 0 && v <= 255;
-    case kWElemU32: return v >= 0 && v <= int64_t(UINT32_MAX);
-    case kWElemI32: return v >= INT32_MIN && v <= INT32_MAX;
-    default: return true;
-  }
-}
-CLG_PACK_HD void wpack_store(uint32_t elem, void* col, uint64_t i, int64_t v) {
-  switch (elem) {
-    case kWElemU8: static_cast<uint8_t*>(col)[i] = uint8_t(v); break;
-    case kWElemU32: static_cast<uint32_t*>(col)[i] = uint32_t(v); break;
-    case kWElemI32: static_cast<int32_t*>(col)[i] = int32_t(v); break;
-    default: static_cast<int64_t*>(col)[i] = v; break;
-  }
-}
 
 // The row's kind, or kWPackKinds for a row that has none (w_idx past the tags, a narrow tag).
 CLG_PACK_HD uint32_t wpack_kind_of(const uint8_t* tag, uint64_t n_rec, uint32_t idx) {
@@ -120,7 +87,6 @@ inline void wpack_reset_result(clg_packed_wide* out) {
   out->n_bits = 0;
   out->bad_row = ~0ull;
 }
-inline bool wpack_sizes_only(const clg_packed_wide& p) { return !p.desc && !p.bits; }
 // n_val and blk_base from the rows and the kinds' totals.
 inline void wpack_layout(uint64_t n_wide, const uint64_t tot[kWPackKinds], clg_packed_wide* out) {
   out->n_val[CLG_WPACK_KIND] = out->n_val[CLG_WPACK_IDX] = n_wide;
@@ -129,56 +95,12 @@ inline void wpack_layout(uint64_t n_wide, const uint64_t tot[kWPackKinds], clg_p
   out->blk_base[0] = 0;
   for (uint32_t c = 0; c < kWPackStreams; ++c) out->blk_base[c + 1] = out->blk_base[c] + pack_blocks(out->n_val[c]);
 }
-// The first output that is too small (its name), or null.
-inline const char* wpack_short(const clg_packed_wide& p) {
-  if ((p.desc ? p.cap_desc : 0) < p.blk_base[kWPackStreams]) return "desc";
-  if ((p.bits ? p.cap_bits : 0) < p.n_bits) return "bits";
-  return nullptr;
+inline PackView pack_view(const clg_packed_wide& p) {
+  return PackView{p.desc, p.bits, p.cap_desc, p.cap_bits, p.out_kind, kWPackStreams, p.n_val, p.blk_base, &p.n_bits};
 }
 
-// One block's measure over m extended values: the descriptor but for pos.
-inline clg_pack_block wpack_measure_block(const int64_t* x, uint32_t m, bool delta) {
-  clg_pack_block b{};
-  b.count = m;
-  const uint32_t k = wpack_resid(delta, m);
-  if (delta && m) b.first = x[0];
-  if (!k) return b;
-  int64_t lo = INT64_MAX, hi = INT64_MIN;
-  for (uint32_t i = delta ? 1 : 0; i < m; ++i) {
-    const int64_t r = delta ? int64_t(uint64_t(x[i]) - uint64_t(x[i - 1])) : x[i];
-    lo = r < lo ? r : lo;
-    hi = r > hi ? r : hi;
-  }
-  b.ref = lo;
-  b.width = pack_width(uint64_t(hi) - uint64_t(lo));
-  return b;
-}
-// One block's payload into dst (pack_payload_bytes(k, width) bytes, written whole).
-inline void wpack_write_block(const int64_t* x, const clg_pack_block& b, bool delta, uint8_t* dst) {
-  const uint32_t k = wpack_resid(delta, b.count), w = b.width;
-  const uint32_t bytes = pack_payload_bytes(k, w);
-  if (!bytes) return;
-  memset(dst, 0, bytes);
-  uint64_t bit = 0;
-  for (uint32_t i = delta ? 1 : 0; i < b.count; ++i, bit += w) {
-    const uint64_t r = delta ? uint64_t(x[i]) - uint64_t(x[i - 1]) : uint64_t(x[i]);
-    const uint64_t p = r - uint64_t(b.ref);
-    const uint32_t sh = uint32_t(bit & 63);
-    uint8_t* at = dst + (bit >> 6) * 8;
-    uint64_t word;
-    memcpy(&word, at, 8);
-    word |= p << sh;
-    memcpy(at, &word, 8);
-    if (sh + w > 64) {  // (sh > 0 here: no shift by 64)
-      memcpy(&word, at + 8, 8);
-      word |= p >> (64 - sh);
-      memcpy(at + 8, &word, 8);
-    }
-  }
-}
-
-// The packed wide rows of host columns (clg_pack_wide_host): the split by kind, a measure pass
-// over each stream, then the write pass once the sizes are known to fit.
+// The packed wide rows of host columns (clg_pack_wide_host): the split by kind, then pack.h's
+// measure and write over the 26 streams.
 inline int wpack_build_host(const clg_columns* in, clg_packed_wide* out, const char** what = nullptr) {
   const char* dummy;
   if (!what) what = &dummy;
@@ -202,33 +124,12 @@ inline int wpack_build_host(const clg_columns* in, clg_packed_wide* out, const c
     val[CLG_WPACK_KIND].push_back(int64_t(kind));
     val[CLG_WPACK_IDX].push_back(int64_t(in->w_idx[k]));
     for (uint32_t f = 0; f < kWPackFields; ++f)
-      val[wpack_stream(kind, f)].push_back(wpack_load(kWPackField[f].elem, cols.col[f], k));
+      val[wpack_stream(kind, f)].push_back(pack_load(kWPackField[f].elem, cols.col[f], k));
     ++tot[kind];
   }
   wpack_layout(nw, tot, out);
-  const bool sizes_only = wpack_sizes_only(*out);
-  std::vector<clg_pack_block> desc;
-  if (!sizes_only) desc.reserve(size_t(out->blk_base[kWPackStreams]));
-  uint64_t pos = 0;
-  for (uint32_t c = 0; c < kWPackStreams; ++c)
-    for (uint64_t b = 0; b < pack_blocks(out->n_val[c]); ++b) {
-      const uint64_t i0 = b * kPackBlock;
-      const uint32_t m = uint32_t(out->n_val[c] - i0 < kPackBlock ? out->n_val[c] - i0 : kPackBlock);
-      clg_pack_block d = wpack_measure_block(val[c].data() + i0, m, wpack_is_delta(c));
-      d.pos = pos;
-      pos += pack_payload_bytes(wpack_resid(wpack_is_delta(c), m), d.width);
-      if (!sizes_only) desc.push_back(d);
-    }
-  out->n_bits = pos;
-  if (sizes_only) return CLG_OK;
-  if (const char* name = wpack_short(*out)) return *what = name, CLG_E_CAPACITY;
-  for (uint32_t c = 0; c < kWPackStreams; ++c)
-    for (uint64_t b = 0; b < pack_blocks(out->n_val[c]); ++b) {
-      const clg_pack_block& d = desc[size_t(out->blk_base[c] + b)];
-      out->desc[out->blk_base[c] + b] = d;
-      wpack_write_block(val[c].data() + b * kPackBlock, d, wpack_is_delta(c), out->bits + d.pos);
-    }
-  return CLG_OK;
+  const auto extend = [&](uint32_t c, uint64_t i0, uint32_t m, int64_t* x) { memcpy(x, val[c].data() + i0, m * sizeof(int64_t)); };
+  return pack_build_blocks(pack_view(*out), kWPackSchemeBits, extend, out->desc, out->bits, &out->n_bits, what);
 }
 
 // ---- a clg_packed_wide read as input (clg_unpack_wide_host) ----------------------------------
@@ -242,13 +143,7 @@ inline int wpack_build_host(const clg_columns* in, clg_packed_wide* out, const c
 //           (stream 0, block 0; tested once every KIND is a kind, before the other streams' values)
 
 inline bool wpack_layout_in_ok(const clg_packed_wide& p, uint32_t* stream) {
-  *stream = 0;
-  if (p.blk_base[0] != 0) return false;
-  for (uint32_t c = 0; c < kWPackStreams; ++c)
-    if (p.blk_base[c + 1] < p.blk_base[c] || p.blk_base[c + 1] - p.blk_base[c] != pack_blocks_of(p.n_val[c]))
-      return *stream = c, false;
-  if (p.cap_desc < p.blk_base[kWPackStreams] || p.cap_bits < p.n_bits) return false;
-  if ((p.blk_base[kWPackStreams] && !p.desc) || (p.n_bits && !p.bits)) return false;
+  if (!pack_layout_in_ok(pack_view(p), stream)) return false;
   if (p.n_val[CLG_WPACK_KIND] != p.n_val[CLG_WPACK_IDX]) return *stream = CLG_WPACK_IDX, false;
   uint64_t sum = 0;
   for (uint32_t t = 0; t < kWPackKinds; ++t) {
@@ -259,30 +154,6 @@ inline bool wpack_layout_in_ok(const clg_packed_wide& p, uint32_t* stream) {
     sum += n;
   }
   return sum == p.n_val[CLG_WPACK_KIND];
-}
-
-CLG_PACK_HD bool wpack_block_in_ok(const clg_pack_block& d, bool delta, uint64_t b, uint64_t n, uint64_t n_bits) {
-  const uint64_t nb = pack_blocks_of(n);
-  if (b >= nb) return false;
-  const uint32_t want = b + 1 < nb ? kPackBlock : uint32_t(n - b * kPackBlock);
-  if (d.width > 64 || d.count < 1 || d.count > kPackBlock || d.count != want) return false;
-  if (d.pos % 16) return false;
-  const uint64_t bytes = pack_payload_bytes(wpack_resid(delta, d.count), d.width);
-  return d.pos <= n_bits && bytes <= n_bits - d.pos;
-}
-
-// A well-formed block's values, extended, into x[0 .. count).
-inline void wpack_unpack_block(const clg_pack_block& d, bool delta, const uint8_t* bits, int64_t* x) {
-  const uint8_t* payload = bits + d.pos;
-  if (delta) {
-    uint64_t v = uint64_t(d.first);
-    for (uint32_t i = 0; i < d.count; ++i) {
-      if (i) v += pack_get(payload, d.width, i - 1) + uint64_t(d.ref);
-      x[i] = int64_t(v);
-    }
-  } else {
-    for (uint32_t i = 0; i < d.count; ++i) x[i] = int64_t(pack_get(payload, d.width, i) + uint64_t(d.ref));
-  }
 }
 
 inline int wpack_unpack_host(const clg_packed_wide* in, clg_columns* out, clg_unpack_bad* bad, const char** what = nullptr) {
@@ -304,18 +175,18 @@ inline int wpack_unpack_host(const clg_packed_wide* in, clg_columns* out, clg_un
   // every block, then every value
   for (uint32_t c = 0; c < kWPackStreams; ++c)
     for (uint64_t b = 0; b < pack_blocks_of(in->n_val[c]); ++b)
-      if (!wpack_block_in_ok(in->desc[in->blk_base[c] + b], wpack_is_delta(c), b, in->n_val[c], in->n_bits))
+      if (!pack_block_in_ok(in->desc[in->blk_base[c] + b], wpack_is_delta(c), b, in->n_val[c], in->n_bits))
         return *what = "malformed block descriptor", pack_bad_set(bad, CLG_UNPACK_BAD_BLOCK, c, b);
   std::vector<int64_t> val[kWPackStreams];
   for (uint32_t c = 0; c < kWPackStreams; ++c) {
     val[c].resize(size_t(in->n_val[c]));
-    const uint32_t elem = wpack_elem(c);
+    const uint32_t elem = wpack_stream_elem(c);
     for (uint64_t b = 0; b < pack_blocks_of(in->n_val[c]); ++b) {
       const clg_pack_block& d = in->desc[in->blk_base[c] + b];
       int64_t* x = val[c].data() + b * kPackBlock;
-      wpack_unpack_block(d, wpack_is_delta(c), in->bits, x);
+      pack_decode_block(d, wpack_is_delta(c), in->bits + d.pos, x);
       for (uint32_t i = 0; i < d.count; ++i)
-        if (!wpack_value_ok(elem, x[i]) || (c == CLG_WPACK_KIND && x[i] >= int64_t(kWPackKinds)))
+        if (!pack_elem_value_ok(elem, x[i]) ||(c == CLG_WPACK_KIND && x[i] >= int64_t(kWPackKinds)))
           return *what = "a value outside the stream's type", pack_bad_set(bad, CLG_UNPACK_BAD_VALUE, c, b);
     }
     if (c == CLG_WPACK_KIND) {
@@ -332,7 +203,7 @@ inline int wpack_unpack_host(const clg_packed_wide* in, clg_columns* out, clg_un
     const uint32_t kind = uint32_t(val[CLG_WPACK_KIND][size_t(k)]);
     const uint64_t r = rank[kind]++;
     out->w_idx[k] = uint32_t(val[CLG_WPACK_IDX][size_t(k)]);
-    for (uint32_t f = 0; f < kWPackFields; ++f) wpack_store(kWPackField[f].elem, cols.col[f], k, val[wpack_stream(kind, f)][size_t(r)]);
+    for (uint32_t f = 0; f < kWPackFields; ++f) pack_store(kWPackField[f].elem, cols.col[f], k, val[wpack_stream(kind, f)][size_t(r)]);
   }
   return CLG_OK;
 }

@@ -11,12 +11,12 @@
 //  * k_wpack_split    pass 3: a workgroup per tile; a row's rank is its tile's base for its kind
 //                     plus its rank inside the tile (ballot and mbcnt in the wave, LDS across the
 //                     waves and the four quarters); the six fields go to per-kind arrays
-//  * k_wpack_measure  pass 4a: pack.hip's measure over the 26 streams; then pack.hip's three scan
-//                     kernels, unchanged
-//  * k_wpack_write    pass 4b: pack.hip's write over the 26 streams
+//  * k_wpack_measure  pass 4a: the block codec's measure (pack_dev.h) over the 26 streams; then
+//                     pack.hip's three scan kernels, unchanged
+//  * k_wpack_write    pass 4b: the block codec's write over the 26 streams
 //
-// Measure and write are instantiated on (element, scheme); a block's stream is found from the
-// table's blk_base wave-uniformly.  Kernel boundaries order the passes.  No spin waits, no word
+// Measure and write are instantiated on (element, scheme), as pack.hip instantiates them; a
+// block's stream is found from the table's blk_base wave-uniformly.  Kernel boundaries order the passes.  No spin waits, no word
 // taken from another running workgroup, no scratch; LDS atomics only inside a workgroup.  The
 // result is a pure function of the rows.
 #include <hip/hip_runtime.h>
@@ -47,140 +47,24 @@ __device__ __forceinline__ uint32_t wpack_stream_of(const WPackTab* __restrict__
   for (uint32_t c = 1; c < kWPackStreams; ++c) s += uint32_t(blk >= tab->blk_base[c]);
   return s;
 }
-struct WPackAt {
-  const void* col;
-  uint64_t i0;  // the block's first value
-  uint32_t m;   // its values
-};
-__device__ __forceinline__ WPackAt wpack_at(const WPackTab* __restrict__ tab, uint32_t s, uint64_t blk) {
+__device__ __forceinline__ PackAt wpack_at(const WPackTab* __restrict__ tab, uint32_t s, uint64_t blk) {
   const uint64_t n = tab->n[s], i0 = (blk - tab->blk_base[s]) * kPackBlock;
   const uint64_t left = i0 < n ? n - i0 : 0;
-  return WPackAt{tab->col[s], i0, uint32_t(left < kPackBlock ? left : kPackBlock)};
+  return PackAt{tab->col[s], i0, uint32_t(left < kPackBlock ? left : kPackBlock)};
 }
 #define CLG_WPACK_CASE(body, e, d, at, ...) \
   case (e) * 2 + (d): body<e, d != 0>(at, __VA_ARGS__); break;
 #define CLG_WPACK_DISPATCH(s, body, at, ...)                                  \
-  switch (wpack_elem(s) * 2 + uint32_t(wpack_is_delta(s))) {                  \
-    CLG_WPACK_CASE(body, kWElemU8, 0, at, __VA_ARGS__)                        \
-    CLG_WPACK_CASE(body, kWElemU8, 1, at, __VA_ARGS__)                        \
-    CLG_WPACK_CASE(body, kWElemU32, 0, at, __VA_ARGS__)                       \
-    CLG_WPACK_CASE(body, kWElemU32, 1, at, __VA_ARGS__)                       \
-    CLG_WPACK_CASE(body, kWElemI32, 0, at, __VA_ARGS__)                       \
-    CLG_WPACK_CASE(body, kWElemI32, 1, at, __VA_ARGS__)                       \
-    CLG_WPACK_CASE(body, kWElemI64, 0, at, __VA_ARGS__)                       \
-    CLG_WPACK_CASE(body, kWElemI64, 1, at, __VA_ARGS__)                       \
+  switch (wpack_stream_elem(s) * 2 + uint32_t(wpack_is_delta(s))) {           \
+    CLG_WPACK_CASE(body, kElemU8, 0, at, __VA_ARGS__)                         \
+    CLG_WPACK_CASE(body, kElemU8, 1, at, __VA_ARGS__)                         \
+    CLG_WPACK_CASE(body, kElemU32, 0, at, __VA_ARGS__)                        \
+    CLG_WPACK_CASE(body, kElemU32, 1, at, __VA_ARGS__)                        \
+    CLG_WPACK_CASE(body, kElemI32, 0, at, __VA_ARGS__)                        \
+    CLG_WPACK_CASE(body, kElemI32, 1, at, __VA_ARGS__)                        \
+    CLG_WPACK_CASE(body, kElemI64, 0, at, __VA_ARGS__)                        \
+    CLG_WPACK_CASE(body, kElemI64, 1, at, __VA_ARGS__)                        \
   }
-
-template <uint32_t kElem, bool kDelta>
-__device__ __forceinline__ void wpack_measure_body(const WPackAt at, clg_pack_block* __restrict__ desc, int64_t* s_x,
-                                                   int64_t* s_lo, int64_t* s_hi) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  int64_t x[kPackPerThread];
-#pragma unroll
-  for (uint32_t k = 0; k < kPackPerThread; ++k) {
-    const uint32_t i = k * kPackThreads + tid;
-    x[k] = i < at.m ? wpack_load(kElem, at.col, at.i0 + i) : 0;
-  }
-  int64_t lo = INT64_MAX, hi = INT64_MIN;
-  if (kDelta) {
-#pragma unroll
-    for (uint32_t k = 0; k < kPackPerThread; ++k) s_x[k * kPackThreads + tid] = x[k];
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < kPackPerThread; ++k) {
-      const uint32_t i = k * kPackThreads + tid;
-      if (i >= 1 && i < at.m) {
-        const int64_t r = int64_t(uint64_t(x[k]) - uint64_t(s_x[i - 1]));
-        lo = pack_min(lo, r), hi = pack_max(hi, r);
-      }
-    }
-  } else {
-#pragma unroll
-    for (uint32_t k = 0; k < kPackPerThread; ++k)
-      if (k * kPackThreads + tid < at.m) lo = pack_min(lo, x[k]), hi = pack_max(hi, x[k]);
-  }
-  CLG_PACK_WAVE_REDUCE(pack_min, lo);
-  CLG_PACK_WAVE_REDUCE(pack_max, hi);
-  if (lane == 0) s_lo[w] = lo, s_hi[w] = hi;
-  __syncthreads();
-  if (tid == 0) {
-#pragma unroll
-    for (uint32_t j = 1; j < kPackWaves; ++j) lo = pack_min(lo, s_lo[j]), hi = pack_max(hi, s_hi[j]);
-    const uint32_t k = wpack_resid(kDelta, at.m);
-    clg_pack_block d;
-    d.ref = k ? lo : 0;
-    d.first = kDelta && at.m ? x[0] : 0;  // (thread 0's first value is the block's)
-    d.width = k ? pack_width(uint64_t(hi) - uint64_t(lo)) : 0;
-    d.count = at.m;
-    d.pos = pack_payload_bytes(k, d.width);  // the size; the scan turns it into the offset
-    desc[blockIdx.x] = d;
-  }
-}
-
-// s_w: 8 KiB, the block's values (the DELTA predecessors), then the payload's words.
-template <uint32_t kElem, bool kDelta>
-__device__ __forceinline__ void wpack_write_body(const WPackAt at, const clg_pack_block d, unsigned long long* s_w,
-                                                 uint8_t* __restrict__ bits, uint64_t lim_bits) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const uint32_t k = wpack_resid(kDelta, at.m), width = d.width;
-  const uint32_t bytes = pack_payload_bytes(k, width);
-  if (!bytes) return;  // (uniform: a constant block, or a DELTA block of one value)
-  const uint32_t n_words = bytes / 8;
-  uint64_t p[kPackPerThread];
-  uint32_t j[kPackPerThread];  // the residual's index; >= k: none
-#pragma unroll
-  for (uint32_t q = 0; q < kPackPerThread; ++q) {
-    const uint32_t i = q * kPackThreads + tid;
-    p[q] = i < at.m ? uint64_t(wpack_load(kElem, at.col, at.i0 + i)) : 0;
-    j[q] = i < at.m ? i : kPackBlock;
-  }
-  if (kDelta) {
-#pragma unroll
-    for (uint32_t q = 0; q < kPackPerThread; ++q) s_w[q * kPackThreads + tid] = p[q];
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < kPackPerThread; ++q) {
-      const uint32_t i = q * kPackThreads + tid;
-      if (i >= 1 && i < at.m) p[q] -= s_w[i - 1], j[q] = i - 1;
-      else j[q] = kPackBlock;
-    }
-    __syncthreads();  // (s_w is written again below)
-  }
-#pragma unroll
-  for (uint32_t q = 0; q < kPackPerThread; ++q) p[q] -= uint64_t(d.ref);
-
-  if (width == 64) {  // a word a value: no shifts
-#pragma unroll
-    for (uint32_t q = 0; q < kPackPerThread; ++q)
-      if (j[q] < k) s_w[j[q]] = p[q];
-    if (tid == 0 && (k & 1)) s_w[k] = 0;  // the padding word
-  } else if (width == 1 && !kDelta) {  // a wave's 64 values are one word: a ballot
-#pragma unroll
-    for (uint32_t q = 0; q < kPackPerThread; ++q) {
-      const uint64_t m = __ballot(j[q] < k && (p[q] & 1));
-      const uint32_t word = q * kPackWaves + wv;
-      if (lane == 0 && word < n_words) s_w[word] = m;
-    }
-  } else {
-    for (uint32_t i = tid; i < n_words; i += kPackThreads) s_w[i] = 0;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < kPackPerThread; ++q)
-      if (j[q] < k) {
-        const uint32_t bit = j[q] * width, sh = bit & 63;
-        atomicOr(&s_w[bit >> 6], (unsigned long long)(p[q] << sh));
-        if (sh + width > 64) atomicOr(&s_w[(bit >> 6) + 1], (unsigned long long)(p[q] >> (64 - sh)));  // (sh > 0)
-      }
-  }
-  __syncthreads();
-  for (uint32_t i = tid; i < bytes / 16; i += kPackThreads) {
-    const uint64_t a = d.pos + uint64_t(i) * 16;
-    if (a + 16 <= lim_bits) {
-      const unsigned long long lo = s_w[2 * i], hi = s_w[2 * i + 1];
-      *reinterpret_cast<uint4*>(bits + a) = make_uint4(uint32_t(lo), uint32_t(lo >> 32), uint32_t(hi), uint32_t(hi >> 32));
-    }
-  }
-}
 
 }  // namespace
 
@@ -220,26 +104,15 @@ __global__ __launch_bounds__(kPackTopThreads) void k_wpack_scan(const uint32_t* 
                                                                uint64_t* __restrict__ base,
                                                                const unsigned long long* __restrict__ bad,
                                                                WPackRes* __restrict__ res) {
-  constexpr uint32_t kW = kPackTopThreads / 64;
-  __shared__ uint64_t ws[kW];
+  __shared__ uint64_t ws[kPackTopThreads / 64];
   __shared__ uint64_t wtot;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
   for (uint32_t t = 0; t < kWPackKinds; ++t) {
     uint64_t carry = 0;
     for (uint32_t g0 = 0; g0 < n_tiles; g0 += kPackTopThreads) {
       const uint32_t g = g0 + tid;
-      const uint64_t x = g < n_tiles ? cnt[uint64_t(g) * kWPackKinds + t] : 0;
-      const uint64_t inc = pack_wave_incl64(x, lane);
-      if (lane == 63) ws[w] = inc;
-      __syncthreads();
-      if (tid < 64) {
-        const uint64_t y = lane < kW ? ws[lane] : 0;
-        const uint64_t s = pack_wave_incl64(y, lane);
-        if (lane < kW) ws[lane] = s - y;
-        if (lane == kW - 1) wtot = s;
-      }
-      __syncthreads();
-      if (g < n_tiles) base[uint64_t(g) * kWPackKinds + t] = carry + ws[w] + (inc - x);
+      const uint64_t before = pack_scan_round(g < n_tiles ? cnt[uint64_t(g) * kWPackKinds + t] : 0, lane, ws, &wtot);
+      if (g < n_tiles) base[uint64_t(g) * kWPackKinds + t] = carry + before;
       carry += wtot;
       __syncthreads();  // (ws is written again in the next round)
     }
@@ -306,8 +179,8 @@ __global__ __launch_bounds__(kPackThreads) void k_wpack_measure(const WPackTab* 
   __shared__ int64_t s_x[kPackBlock];  // the block's values: the DELTA predecessors
   __shared__ int64_t s_lo[kPackWaves], s_hi[kPackWaves];
   const uint32_t s = wpack_stream_of(tab, blockIdx.x);
-  const WPackAt at = wpack_at(tab, s, blockIdx.x);
-  CLG_WPACK_DISPATCH(s, wpack_measure_body, at, desc, s_x, s_lo, s_hi)
+  const PackAt at = wpack_at(tab, s, blockIdx.x);
+  CLG_WPACK_DISPATCH(s, pack_block_measure, at, desc, s_x, s_lo, s_hi)
 }
 
 __global__ __launch_bounds__(kPackThreads) void k_wpack_write(const WPackTab* __restrict__ tab,
@@ -319,8 +192,8 @@ __global__ __launch_bounds__(kPackThreads) void k_wpack_write(const WPackTab* __
   const clg_pack_block d = desc[blockIdx.x];  // (uniform)
   if (threadIdx.x == 0 && blockIdx.x < lim_desc) out_desc[blockIdx.x] = d;
   const uint32_t s = wpack_stream_of(tab, blockIdx.x);
-  const WPackAt at = wpack_at(tab, s, blockIdx.x);
-  CLG_WPACK_DISPATCH(s, wpack_write_body, at, d, s_w, bits, lim_bits)
+  const PackAt at = wpack_at(tab, s, blockIdx.x);
+  CLG_WPACK_DISPATCH(s, pack_block_write, at, d, s_w, bits, lim_bits)
 }
 
 int launch_wpack_count_scan(const WPackSrc& src, uint32_t n_tiles, uint8_t* d_kind, uint32_t* d_cnt, uint64_t* d_base,

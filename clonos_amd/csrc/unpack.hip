@@ -13,8 +13,8 @@
 //                     workgroup per block stages the payload (at most 8 KiB) in LDS with aligned
 //                     16-byte loads, each thread extracts four consecutive values, FOR adds ref,
 //                     DELTA takes the inclusive prefix sum of first and the residuals (the
-//                     thread's four, a wave scan, the four waves through LDS), and stores them
-//                     coalesced
+//                     thread's four, pack_dev.h's wave scan, the four waves through LDS), and
+//                     stores them coalesced
 //
 // Kernel boundaries order the passes.  No spin waits, no word taken from another running
 // workgroup, no scratch; LDS is private to a workgroup.  The output is a pure function of the
@@ -24,6 +24,7 @@
 
 #include "../../include/clonos_engine.h"
 #include "pack.h"
+#include "pack_dev.h"
 #include "kernels.h"
 
 namespace clg {
@@ -62,15 +63,6 @@ __device__ __forceinline__ bool unpack_values_ok(const clg_pack_block& d, const 
     ok = ok && pack_value_ok(kC, int64_t(p + uint64_t(d.ref)));
   }
   return __ballot(!ok) == 0;
-}
-
-__device__ __forceinline__ uint64_t unpack_wave_incl(uint64_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
 }
 
 // Four consecutive values to dst[0 .. n) (n <= 4) in the stream's element type: one store of
@@ -141,7 +133,7 @@ __device__ __forceinline__ void unpack_write_body(void* col, uint64_t i0, const 
   }
   if (delta) {  // the inclusive prefix sum, modulo 2^64: the thread's four, the wave, the four waves
     v[1] += v[0], v[2] += v[1], v[3] += v[2];
-    const uint64_t incl = unpack_wave_incl(v[3], lane);
+    const uint64_t incl = pack_wave_incl64(v[3], lane);
     if (lane == 63) s_ws[wv] = incl;
     __syncthreads();
     uint64_t before = incl - v[3];
@@ -168,20 +160,20 @@ __global__ __launch_bounds__(kUnpackThreads) void k_unpack_check(const UnpackIn 
   bool block_ok = false, values_ok = true;
   switch (c) {  // wave-uniform: the stream is a constant in each body
     case 0:
-      block_ok = pack_block_in_ok(d, 0, blk - in.blk_base[0], in.n[0], in.n_bits);
+      block_ok = pack_block_in_ok(d, pack_is_delta(0), blk - in.blk_base[0], in.n[0], in.n_bits);
       if (block_ok && !pack_range_inside(0, d.ref, d.width)) values_ok = unpack_values_ok<0>(d, in.bits, lane);
       break;
     case 1:
-      block_ok = pack_block_in_ok(d, 1, blk - in.blk_base[1], in.n[1], in.n_bits);
+      block_ok = pack_block_in_ok(d, pack_is_delta(1), blk - in.blk_base[1], in.n[1], in.n_bits);
       if (block_ok && !pack_range_inside(1, d.ref, d.width)) values_ok = unpack_values_ok<1>(d, in.bits, lane);
       break;
-    case 2: block_ok = pack_block_in_ok(d, 2, blk - in.blk_base[2], in.n[2], in.n_bits); break;  // 64 bits: every value passes
+    case 2: block_ok = pack_block_in_ok(d, pack_is_delta(2), blk - in.blk_base[2], in.n[2], in.n_bits); break;  // 64 bits: every value passes
     case 3:
-      block_ok = pack_block_in_ok(d, 3, blk - in.blk_base[3], in.n[3], in.n_bits);
+      block_ok = pack_block_in_ok(d, pack_is_delta(3), blk - in.blk_base[3], in.n[3], in.n_bits);
       if (block_ok && !pack_range_inside(3, d.ref, d.width)) values_ok = unpack_values_ok<3>(d, in.bits, lane);
       break;
     default:
-      block_ok = pack_block_in_ok(d, 4, blk - in.blk_base[4], in.n[4], in.n_bits);
+      block_ok = pack_block_in_ok(d, pack_is_delta(4), blk - in.blk_base[4], in.n[4], in.n_bits);
       if (block_ok && !pack_range_inside(4, d.ref, d.width)) values_ok = unpack_values_ok<4>(d, in.bits, lane);
       break;
   }
@@ -198,7 +190,7 @@ __global__ __launch_bounds__(kUnpackThreads) void k_unpack_write(const UnpackIn 
   const clg_pack_block d = in.desc[blk];  // (uniform)
   switch (unpack_stream_of(in, blk)) {
 #define CLG_UNPACK_CASE(c)                                                                             \
-  if (pack_block_in_ok(d, c, blk - in.blk_base[c], in.n[c], in.n_bits))                                \
+  if (pack_block_in_ok(d, pack_is_delta(c), blk - in.blk_base[c], in.n[c], in.n_bits))                                \
     unpack_write_body<c>(out.col[c], (blk - in.blk_base[c]) * kPackBlock, d, in.bits, s_w, s_ws);      \
   break
     case 0: CLG_UNPACK_CASE(0);

@@ -460,9 +460,12 @@ PACK_STREAM_FIELDS = (("tag", np.uint8), ("order", np.int8), ("timestamp", np.in
                       ("buffer_built", np.int32))
 
 
-def _packed_struct(desc: Optional[np.ndarray], bits: Optional[np.ndarray], kind: int = _lib.CLG_MEM_HOST) -> _lib.Packed:
-    """clg_packed over host arrays (capacity = their lengths); both None: sizes only."""
-    p = _lib.Packed()
+# The two packed families (clg_packed: _lib.Packed, clg_packed_wide: _lib.PackedWideC) share their
+# first six fields and n_val / blk_base / n_bits; the helpers below serve both, told apart by the
+# struct class (its n_val holds one entry per stream).
+def _packed_over(cls, desc: Optional[np.ndarray], bits: Optional[np.ndarray], kind: int = _lib.CLG_MEM_HOST):
+    """A cls struct over host arrays (capacity = their lengths); both None: sizes only."""
+    p = cls()
     if desc is not None:
         p.desc, p.cap_desc = _np_ptr(desc), desc.size
     if bits is not None:
@@ -471,10 +474,39 @@ def _packed_struct(desc: Optional[np.ndarray], bits: Optional[np.ndarray], kind:
     return p
 
 
-def _packed_error(st: int, p: _lib.Packed) -> ClonosError:
+def _packed_of(cls, obj):
+    """A cls struct over a PackedColumns' or PackedWide's arrays, with its n_val, blk_base and n_bits."""
+    p = _packed_over(cls, obj.desc, obj.bits)
+    p.n_val[:], p.blk_base[:], p.n_bits = obj.n_val, obj.blk_base, obj.bits.size
+    return p
+
+
+def _packed_error(st: int, p) -> ClonosError:
     err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
-    err.n_blocks, err.n_bits = int(p.blk_base[_lib.PACK_STREAMS]), int(p.n_bits)
+    err.n_blocks, err.n_bits = int(p.blk_base[len(p.n_val)]), int(p.n_bits)
+    if isinstance(p, _lib.PackedWideC):
+        err.bad_row = int(p.bad_row)
     return err
+
+
+def _pack_twice(cls, call):
+    """call(cls struct) -> status, first for the sizes, then into host arrays of exactly those:
+    the filled struct and its desc and bits."""
+    p = cls()
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _packed_error(st, p)
+    desc, bits = np.zeros(int(p.blk_base[len(p.n_val)]), PACK_BLOCK), np.zeros(int(p.n_bits), np.uint8)
+    p = _packed_over(cls, desc, bits)
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _packed_error(st, p)
+    return p, desc, bits
+
+
+def _packed_struct(desc: Optional[np.ndarray], bits: Optional[np.ndarray], kind: int = _lib.CLG_MEM_HOST) -> _lib.Packed:
+    """clg_packed over host arrays (capacity = their lengths); both None: sizes only."""
+    return _packed_over(_lib.Packed, desc, bits, kind)
 
 
 class PackedColumns:
@@ -550,13 +582,7 @@ class PackedColumns:
         return int(sum(a.nbytes for a in arrs if a is not None))
 
     def _struct(self) -> _lib.Packed:
-        p = _packed_struct(self.desc, self.bits)
-        for c in range(_lib.PACK_STREAMS):
-            p.n_val[c] = self.n_val[c]
-        for c in range(_lib.PACK_STREAMS + 1):
-            p.blk_base[c] = self.blk_base[c]
-        p.n_bits = self.bits.size
-        return p
+        return _packed_of(_lib.Packed, self)
 
     def unpack_stream(self, stream: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """clg_unpack_columns_host: values [first, first + count) of one stream, in its own type;
@@ -611,17 +637,9 @@ def _pack_in(cols: "DecodedColumns") -> Tuple[_lib.Columns, list]:
     return c, keep
 
 
-def _pack_twice(call, cols: "DecodedColumns") -> PackedColumns:
-    """call(clg_packed) -> status, first for the sizes, then into host arrays of exactly those."""
-    p = _lib.Packed()
-    st = call(p)
-    if st != _lib.CLG_OK:
-        raise _packed_error(st, p)
-    desc, bits = np.zeros(int(p.blk_base[_lib.PACK_STREAMS]), PACK_BLOCK), np.zeros(int(p.n_bits), np.uint8)
-    p = _packed_struct(desc, bits)
-    st = call(p)
-    if st != _lib.CLG_OK:
-        raise _packed_error(st, p)
+def _pack_narrow(call, cols: "DecodedColumns") -> PackedColumns:
+    """_pack_twice over a clg_packed; what is not packed is passed through from cols."""
+    p, desc, bits = _pack_twice(_lib.Packed, call)
     out = PackedColumns(desc, bits, p.n_val, p.blk_base, *[getattr(cols, k) for k in _COL_WIDE], cols.span_base,
                         cols.spans_bytes)
     out.var, out.var_pos, out.error = cols.var, cols.var_pos, cols.error
@@ -632,7 +650,7 @@ def pack_columns_host(cols: "DecodedColumns") -> PackedColumns:
     """clg_pack_columns_host: the five narrow columns bit-packed on the CPU (no engine, no GPU) --
     the same bytes Engine.pack_columns produces on the device."""
     cin, keep = _pack_in(cols)
-    return _pack_twice(lambda p: lib.clg_pack_columns_host(C.byref(cin), C.byref(p)), cols)
+    return _pack_narrow(lambda p: lib.clg_pack_columns_host(C.byref(cin), C.byref(p)), cols)
 
 
 def unpack_columns_host(packed: PackedColumns, stream: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
@@ -688,19 +706,7 @@ WPACK_FIELDS = (("w_rc", np.int32), ("w_v1", np.int64), ("w_var_off", np.uint32)
 def _packed_wide_struct(desc: Optional[np.ndarray], bits: Optional[np.ndarray],
                         kind: int = _lib.CLG_MEM_HOST) -> _lib.PackedWideC:
     """clg_packed_wide over host arrays (capacity = their lengths); both None: sizes only."""
-    p = _lib.PackedWideC()
-    if desc is not None:
-        p.desc, p.cap_desc = _np_ptr(desc), desc.size
-    if bits is not None:
-        p.bits, p.cap_bits = _np_ptr(bits), bits.size
-    p.out_kind = kind
-    return p
-
-
-def _packed_wide_error(st: int, p: _lib.PackedWideC) -> ClonosError:
-    err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
-    err.n_blocks, err.n_bits, err.bad_row = int(p.blk_base[_lib.WPACK_STREAMS]), int(p.n_bits), int(p.bad_row)
-    return err
+    return _packed_over(_lib.PackedWideC, desc, bits, kind)
 
 
 class PackedWide:
@@ -725,13 +731,7 @@ class PackedWide:
         return int(self.desc.nbytes + self.bits.nbytes)
 
     def _struct(self) -> _lib.PackedWideC:
-        p = _packed_wide_struct(self.desc, self.bits)
-        for c in range(_lib.WPACK_STREAMS):
-            p.n_val[c] = self.n_val[c]
-        for c in range(_lib.WPACK_STREAMS + 1):
-            p.blk_base[c] = self.blk_base[c]
-        p.n_bits = self.bits.size
-        return p
+        return _packed_of(_lib.PackedWideC, self)
 
     def unpack(self) -> dict:
         """clg_unpack_wide_host: the seven w_* arrays by name, in row order.  Invalid input raises
@@ -781,17 +781,9 @@ def _pack_wide_in(cols: "DecodedColumns") -> Tuple[_lib.Columns, list]:
     return c, keep
 
 
-def _pack_wide_twice(call) -> PackedWide:
-    """call(clg_packed_wide) -> status, first for the sizes, then into host arrays of exactly those."""
-    p = _lib.PackedWideC()
-    st = call(p)
-    if st != _lib.CLG_OK:
-        raise _packed_wide_error(st, p)
-    desc, bits = np.zeros(int(p.blk_base[_lib.WPACK_STREAMS]), PACK_BLOCK), np.zeros(int(p.n_bits), np.uint8)
-    p = _packed_wide_struct(desc, bits)
-    st = call(p)
-    if st != _lib.CLG_OK:
-        raise _packed_wide_error(st, p)
+def _pack_wide(call) -> PackedWide:
+    """_pack_twice over a clg_packed_wide."""
+    p, desc, bits = _pack_twice(_lib.PackedWideC, call)
     return PackedWide(desc, bits, p.n_val, p.blk_base)
 
 
@@ -800,7 +792,7 @@ def pack_wide_host(cols: "DecodedColumns") -> PackedWide:
     no GPU) -- the same bytes Engine.pack_wide produces on the device.  A row that is no wide
     record's raises ClonosError with bad_row."""
     cin, keep = _pack_wide_in(cols)
-    return _pack_wide_twice(lambda p: lib.clg_pack_wide_host(C.byref(cin), C.byref(p)))
+    return _pack_wide(lambda p: lib.clg_pack_wide_host(C.byref(cin), C.byref(p)))
 
 
 def unpack_wide_host(packed: PackedWide) -> dict:
@@ -1380,7 +1372,7 @@ class Engine:
         """clg_pack_columns: the five narrow columns of host columns bit-packed on the device (staged
         in, packed, read back); the bytes are pack_columns_host's."""
         cin, keep = _pack_in(cols)
-        return _pack_twice(lambda p: lib.clg_pack_columns(self._h, C.byref(cin), C.byref(p)), cols)
+        return _pack_narrow(lambda p: lib.clg_pack_columns(self._h, C.byref(cin), C.byref(p)), cols)
 
     def pack_columns_raw(self, cin: _lib.Columns, out: _lib.Packed) -> int:
         """clg_pack_columns over a clg_columns and a clg_packed the caller set up (any kinds; desc
@@ -1391,7 +1383,7 @@ class Engine:
         """clg_pack_wide: the wide rows of host columns partitioned by kind and bit-packed on the
         device (staged in, packed, read back); the bytes are pack_wide_host's."""
         cin, keep = _pack_wide_in(cols)
-        return _pack_wide_twice(lambda p: lib.clg_pack_wide(self._h, C.byref(cin), C.byref(p)))
+        return _pack_wide(lambda p: lib.clg_pack_wide(self._h, C.byref(cin), C.byref(p)))
 
     def pack_wide_raw(self, cin: _lib.Columns, out: _lib.PackedWideC) -> int:
         """clg_pack_wide over a clg_columns and a clg_packed_wide the caller set up (any kinds; desc

@@ -7,7 +7,7 @@ import mmap
 import numpy as np
 import pytest
 
-from _pack_util import STREAMS, Narrow, assert_same_packed, values_of_width
+from _pack_util import STREAMS, Narrow, assert_packed_equals_numpy, assert_same_packed, values_of_width
 
 pytestmark = pytest.mark.gpu
 
@@ -79,6 +79,24 @@ def test_int64_extremes_side_by_side(eng):
     got = eng.pack_columns(cols)
     assert_same_packed(got, pack_columns_host(cols))
     assert (got.unpack().timestamp == cols.timestamp).all()
+
+
+def test_order_extremes_across_a_block_seam(eng):
+    """ORDER is the signed 8-bit element: 1025 values with -128 and 127 in the full block and the
+    block of one value at either extreme, against the host packer and the numpy packer, and back
+    through the device unpack."""
+    from clonos_amd import pack_columns_host
+    for last in (-128, 127):
+        order = np.random.default_rng(0x0DE8).integers(-128, 127, 1025, endpoint=True).astype(np.int8)
+        order[[3, 700, 1024]] = -128, 127, last
+        cols = Narrow(order=order)
+        got = eng.pack_columns(cols)
+        assert_same_packed(got, pack_columns_host(cols))
+        assert_packed_equals_numpy(got, cols)
+        d = np.asarray(got.desc)[got.blk_base[1]:got.blk_base[2]]
+        assert list(d["ref"]) == [-128, last] and list(d["width"]) == [8, 0] and list(d["count"]) == [1024, 1]
+        back = eng.unpack_columns(got).order
+        assert back.dtype == np.int8 and (back == order).all()
 
 
 @pytest.mark.parametrize("n", [0, 1, 2, 1023, 1024, 1025, 3 * 1024 + 1])

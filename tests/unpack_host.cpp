@@ -81,7 +81,7 @@ struct Out {
     uint64_t cap[5];
     for (uint32_t s = 0; s < 5; ++s) {
       cap[s] = n[s] + spare - (int(s) == short_one ? 1 : 0);
-      buf[s].assign(2 * kGuard + cap[s] * clg::pack_elem(s), kFill);
+      buf[s].assign(2 * kGuard + cap[s] * clg::pack_stream_bytes(s), kFill);
     }
     c.tag = buf[0].data() + kGuard, c.order = reinterpret_cast<int8_t*>(buf[1].data() + kGuard);
     c.timestamp = reinterpret_cast<int64_t*>(buf[2].data() + kGuard), c.rng = reinterpret_cast<int32_t*>(buf[3].data() + kGuard);
@@ -98,7 +98,7 @@ struct Out {
   // the values are cols', and nothing outside [0, n) of any array was written
   bool holds(const Cols& cols) const {
     for (uint32_t s = 0; s < 5; ++s) {
-      const size_t nb = cols.n(s) * clg::pack_elem(s);
+      const size_t nb = cols.n(s) * clg::pack_stream_bytes(s);
       if (nb && memcmp(buf[s].data() + kGuard, cols.data(s), nb)) return false;
       for (size_t i = 0; i < buf[s].size(); ++i)
         if ((i < kGuard || i >= kGuard + nb) && buf[s][i] != kFill) return false;

@@ -446,10 +446,10 @@ void malformed() {
 // The scheme table is part of the format: held against the reference's copy.
 void table() {
   for (uint32_t s = 0; s < 26; ++s) REQUIRE(clg::wpack_is_delta(s) == (kDelta[s] != 0));
-  const uint32_t elem[6] = {clg::kWElemI32, clg::kWElemI64, clg::kWElemU32, clg::kWElemU32, clg::kWElemU8, clg::kWElemI64};
-  REQUIRE(clg::wpack_elem(0) == clg::kWElemU8 && clg::wpack_elem(1) == clg::kWElemU32);
+  const uint32_t elem[6] = {clg::kElemI32, clg::kElemI64, clg::kElemU32, clg::kElemU32, clg::kElemU8, clg::kElemI64};
+  REQUIRE(clg::wpack_stream_elem(0) == clg::kElemU8 && clg::wpack_stream_elem(1) == clg::kElemU32);
   for (uint32_t t = 0; t < 4; ++t)
-    for (uint32_t f = 0; f < 6; ++f) REQUIRE(clg::wpack_elem(clg::wpack_stream(t, f)) == elem[f] && clg::wpack_stream(t, f) == 2 + 6 * t + f);
+    for (uint32_t f = 0; f < 6; ++f) REQUIRE(clg::wpack_stream_elem(clg::wpack_stream(t, f)) == elem[f] && clg::wpack_stream(t, f) == 2 + 6 * t + f);
 }
 
 }  // namespace
