@@ -5,9 +5,11 @@ from . import determinants
 from ._lib import ClonosError
 from .engine import (DIFF, DIGEST, CausalLogID, DecodedBatch, DecodedColumns, Engine, ThreadCausalLog, columnize_host, gather_payloads_host,
                      digest_host, digest_prefixes_host, encode_columns_host, lcp_host, PackedColumns, pack_columns_host,
-                     unpack_columns_host, unpack_packed_host, PackedWide, pack_wide_host, unpack_wide_host)
+                     unpack_columns_host, unpack_packed_host, PackedWide, pack_wide_host, unpack_wide_host,
+                     encode_columns_packed_wide_host)
 
 __all__ = ["Engine", "ThreadCausalLog", "CausalLogID", "DecodedBatch", "ClonosError", "determinants", "DIGEST",
            "digest_host", "DIFF", "lcp_host", "digest_prefixes_host", "DecodedColumns", "columnize_host", "gather_payloads_host",
            "encode_columns_host", "PackedColumns", "pack_columns_host", "unpack_columns_host",
-           "unpack_packed_host", "PackedWide", "pack_wide_host", "unpack_wide_host"]
+           "unpack_packed_host", "PackedWide", "pack_wide_host", "unpack_wide_host",
+           "encode_columns_packed_wide_host"]

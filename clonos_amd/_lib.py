@@ -75,6 +75,8 @@ EXPORTED = [
     "clg_unpack_columns", "clg_unpack_columns_all_host", "clg_encode_columns_packed", "clg_append_columns_packed",
     "clg_pack_wide", "clg_pack_wide_host", "clg_unpack_wide_host",
     "clg_decode_logs_columns_packed_wide", "clg_decode_host_columns_packed_wide",
+    "clg_unpack_wide", "clg_encode_columns_packed_wide", "clg_append_columns_packed_wide",
+    "clg_encode_columns_packed_wide_host",
 ]
 
 
@@ -231,6 +233,8 @@ class PackedWideC(C.Structure):  # clg_packed_wide
 
 # clg_unpack_bad.what
 UNPACK_BAD_NONE, UNPACK_BAD_LAYOUT, UNPACK_BAD_BLOCK, UNPACK_BAD_VALUE = range(4)
+# in the calls that take both packed forms, a finding in the wide rows reports this + its stream
+UNPACK_WIDE_STREAM = 32
 
 
 class UnpackBad(C.Structure):  # clg_unpack_bad (16 bytes)
@@ -482,6 +486,13 @@ def _load() -> C.CDLL:
                                                           C.POINTER(Packed), C.POINTER(PackedWideC)]),
         "clg_decode_host_columns_packed_wide": (C.c_int, [P, P, P, P, C.c_uint32, C.POINTER(Columns), C.POINTER(Payloads),
                                                           C.POINTER(Packed), C.POINTER(PackedWideC)]),
+        "clg_unpack_wide": (C.c_int, [P, C.POINTER(PackedWideC), C.POINTER(Columns), P, C.POINTER(UnpackBad)]),
+        "clg_encode_columns_packed_wide": (C.c_int, [P, C.POINTER(Packed), C.POINTER(PackedWideC), C.POINTER(ColumnsIn),
+                                                     C.POINTER(Encoded), C.POINTER(UnpackBad)]),
+        "clg_append_columns_packed_wide": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Packed), C.POINTER(PackedWideC),
+                                                     C.POINTER(ColumnsIn), P, P, C.POINTER(UnpackBad)]),
+        "clg_encode_columns_packed_wide_host": (C.c_int, [C.POINTER(Packed), C.POINTER(PackedWideC), C.POINTER(ColumnsIn),
+                                                          C.POINTER(Encoded), C.POINTER(UnpackBad)]),
         "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),

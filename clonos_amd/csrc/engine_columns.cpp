@@ -2,7 +2,8 @@
 // columns of a decoded batch and the decodes into columns, the payload column, packed columns out
 // and in, packed wide rows, the encode of typed columns and their append to logs; clg_pack_columns to
 // clg_columnize_host, clg_pack_wide*, clg_unpack_wide_host, clg_decode_*_columns_packed_wide,
-// clg_encode_columns*, clg_append_columns*, clg_unpack_columns*.  The placement
+// clg_encode_columns*, clg_append_columns*, clg_unpack_columns*, clg_unpack_wide and the calls that
+// take both packed forms (clg_*_columns_packed_wide*).  The placement
 // helpers are file-local; decode_columns and decode_columns_var are declared in engine_impl.h for
 // replay preparation (engine_replay.cpp).
 #include "engine_impl.h"
@@ -1045,6 +1046,17 @@ struct EcolPlan {
   uint64_t in_bytes = 0;  // bytes of the input arrays (for the stats)
 };
 
+// The packed calls: device addresses of the leading n arrays in EcolIn's order (5: the narrow
+// columns; 12: the wide rows, w_idx and pos as well), used as they are whatever in_kind says of
+// the other arrays.  cross (the packed-wide calls): the cross rule's word in pinned memory, filled
+// by a copy queued before the sizes; it is read after their sync and before the encode's own checks.
+struct EcolDev {
+  const void* col[12] = {};
+  int n = 0;
+  const unsigned long long* cross = nullptr;
+  clg_unpack_bad* bad = nullptr;
+};
+
 int ecol_invalid(clg_encoded* out, uint32_t what, uint64_t index) {
   static const char* const kind[] = {"", "tag", "totals", "span", "row"};
   out->n_bytes = 0;
@@ -1055,10 +1067,9 @@ int ecol_invalid(clg_encoded* out, uint32_t what, uint64_t index) {
 
 // Count, scan, bytes, scan64 and span bases, then the host's check of their results (pinned) --
 // before any byte is written anywhere.  Fills out's results and, when given, sbb[ns + 1].
-// dev_narrow (the packed calls): device addresses of the five narrow columns, used as they are
-// whatever in_kind says of the other arrays.
+// dev (the packed calls): see EcolDev.
 int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPlan* p, uint64_t* sbb,
-               const void* const* dev_narrow = nullptr) {
+               const EcolDev* dev = nullptr) {
   clg::ecol_reset_result(out);
   if (!clg::ecol_args_ok(*in)) return fail(CLG_E_INVALID_ARG, "encode columns: null input array or unknown in_kind");
   const uint64_t n = in->n_rec, *nc = in->n_class, nw = nc[clg::kColWide];
@@ -1071,13 +1082,13 @@ int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPl
                        {in->w_idx, nw * 4, 4}, {in->pos, (nw + 1) * 8, 8},                             {in->var, in->n_var, 1}};
   for (const PlaceSpec& a : ins) p->in_bytes += a.p ? a.bytes : 0;
   // registered arrays must be registered whole; host arrays are staged, an empty one too (a valid
-  // address, never read).  With dev_narrow the first five take no part (no slot, no lookup, no
-  // copy): they are absent from the placement, and their addresses are set behind it.
-  for (int i = 0; dev_narrow && i < 5; ++i) ins[i].p = nullptr;
+  // address, never read).  With dev its arrays take no part (no slot, no lookup, no copy): they
+  // are absent from the placement, and their addresses are set behind it.
+  for (int i = 0; dev && i < dev->n; ++i) ins[i].p = nullptr;
   const size_t sb_bytes = in->n_spans ? size_t(ns + 1) * clg::kColClasses * 8 : 0;
   clg::Placement pl;
   CHK(place_in(e, e->d_ecolin, ins, 13, in->in_kind, PlacePolicy::reject_unresolved, "encode columns: input", &pl, sb_bytes));
-  for (int i = 0; dev_narrow && i < 5; ++i) pl.dev[i] = uintptr_t(dev_narrow[i]);
+  for (int i = 0; dev && i < dev->n; ++i) pl.dev[i] = uintptr_t(dev->col[i]);
   const size_t o_sb = pl.staged() ? pl.total : 0;  // the span bases lie behind the staged arrays
   if (!pl.staged()) CHK(e->d_ecolin.ensure(sb_bytes + 16));
   uint8_t* din = e->d_ecolin.as<uint8_t>();
@@ -1119,6 +1130,11 @@ int ecol_sizes(clg_engine* e, const clg_columns_in* in, clg_encoded* out, EcolPl
     return clg::launch_ecol_sizes(d, nt, d_base, d_sum, d_bad, d_bbase, cres, eres, d_sb, in->n_spans, span_out, e->stream);
   }));
   CHK(e->sync());
+  if (dev && dev->cross && *dev->cross != ~0ull) {
+    clg::wpack_bad_cross(dev->bad, *dev->cross);
+    return fail(CLG_E_INVALID_ARG, "unpack wide rows: row %llu's w_idx names no wide record of its kind",
+                (unsigned long long)*dev->cross);
+  }
   if (cres->bad_tile != clg::kColNoTile) {
     CHK(clg::launch_col_find_bad(cin, cres->bad_tile, cres, e->stream));
     CHK(e->sync());
@@ -1146,10 +1162,10 @@ int ecol_write(clg_engine* e, const EcolPlan& p, uint8_t* d_dst) {
   });
 }
 
-// clg_encode_columns after its argument checks (the engine guard held); dev_narrow as ecol_sizes'.
-int encode_columns_checked(clg_engine* e, const clg_columns_in* in, clg_encoded* out, const void* const* dev_narrow) {
+// clg_encode_columns after its argument checks (the engine guard held); dev as ecol_sizes'.
+int encode_columns_checked(clg_engine* e, const clg_columns_in* in, clg_encoded* out, const EcolDev* dev) {
   EcolPlan p;
-  CHK(ecol_sizes(e, in, out, &p, nullptr, dev_narrow));
+  CHK(ecol_sizes(e, in, out, &p, nullptr, dev));
   if (!out->bytes) return CLG_OK;  // sizes only
   if (out->cap < p.n_bytes) return fail(CLG_E_CAPACITY, "encode columns needs %llu bytes", (unsigned long long)p.n_bytes);
   if (!p.n_bytes) return CLG_OK;
@@ -1163,7 +1179,7 @@ int encode_columns_checked(clg_engine* e, const clg_columns_in* in, clg_encoded*
 }
 
 int append_columns_checked(clg_engine* e, const uint32_t* log, const int64_t* epoch, const clg_columns_in* in,
-                           uint64_t* span_bytes, int32_t* status, const void* const* dev_narrow);
+                           uint64_t* span_bytes, int32_t* status, const EcolDev* dev);
 
 }  // namespace
 
@@ -1196,16 +1212,16 @@ int clg_append_columns(clg_engine* e, const uint32_t* log, const int64_t* epoch,
 
 namespace {
 // clg_append_columns after its argument checks (the engine guard held, every status CLG_OK);
-// dev_narrow as ecol_sizes'.
+// dev as ecol_sizes'.
 int append_columns_checked(clg_engine* e, const uint32_t* log, const int64_t* epoch, const clg_columns_in* in,
-                           uint64_t* span_bytes, int32_t* status, const void* const* dev_narrow) {
+                           uint64_t* span_bytes, int32_t* status, const EcolDev* dev) {
   const uint32_t ns = clg::ecol_spans(*in);
   CHK(e->flush());  // pending host bytes first: the logs keep their byte order
   clg_encoded enc{};
   enc.out_kind = CLG_MEM_DEVICE;
   EcolPlan p;
   std::vector<uint64_t> sbb(size_t(ns) + 1);
-  CHK(ecol_sizes(e, in, &enc, &p, sbb.data(), dev_narrow));
+  CHK(ecol_sizes(e, in, &enc, &p, sbb.data(), dev));
   for (uint32_t s = 0; s < ns && span_bytes; ++s) span_bytes[s] = sbb[s + 1] - sbb[s];
   CHK(e->d_ecolout.ensure(p.n_bytes + 16));
   CHK(ecol_write(e, p, e->d_ecolout.as<uint8_t>()));
@@ -1264,17 +1280,22 @@ int unpack_input(clg_engine* e, const clg_packed* in, clg::UnpackIn* uin) {
 
 // The check pass and the host's reading of its verdict: CLG_E_INVALID_ARG with `bad` filled, or
 // CLG_OK with the stream idle and nothing written anywhere yet.
-int unpack_check(clg_engine* e, const clg::UnpackIn& uin, clg_unpack_bad* bad) {
+// In two halves, so that a combined call reads the narrow and the wide verdicts after one sync:
+// the check queued with the verdict's copy to pinned memory, then (after a sync) its reading.
+int unpack_check_queue(clg_engine* e, const clg::UnpackIn& uin) {
   const uint64_t nb = uin.blk_base[clg::kPackStreams];
   if (!nb) return CLG_OK;
   CHK(e->d_unpackres.ensure(sizeof(clg::UnpackVerdict)));
   CHK(e->h_unpackres.ensure(sizeof(clg::UnpackVerdict)));
-  clg::UnpackVerdict* res = e->h_unpackres.as<clg::UnpackVerdict>();
   // (bytes: a descriptor a block; payloads are read only where the type does not hold the range)
   CHK(e->timed("unpack_columns", nb * sizeof(clg_pack_block),
                [&] { return clg::launch_unpack_check(uin, uint32_t(nb), e->d_unpackres.as<clg::UnpackVerdict>(), e->stream); }));
-  HIPCHK(hipMemcpyAsync(res, e->d_unpackres.p, sizeof(clg::UnpackVerdict), hipMemcpyDeviceToHost, e->stream));
-  CHK(e->sync());
+  HIPCHK(hipMemcpyAsync(e->h_unpackres.p, e->d_unpackres.p, sizeof(clg::UnpackVerdict), hipMemcpyDeviceToHost, e->stream));
+  return CLG_OK;
+}
+int unpack_check_read(clg_engine* e, const clg::UnpackIn& uin, clg_unpack_bad* bad) {
+  if (!uin.blk_base[clg::kPackStreams]) return CLG_OK;
+  const clg::UnpackVerdict* res = e->h_unpackres.as<clg::UnpackVerdict>();
   const bool block = res->bad_block != 0;
   if (!block && !res->bad_value) return CLG_OK;
   const uint64_t blk = ~uint64_t(block ? res->bad_block : res->bad_value);
@@ -1284,6 +1305,12 @@ int unpack_check(clg_engine* e, const clg::UnpackIn& uin, clg_unpack_bad* bad) {
   return fail(CLG_E_INVALID_ARG, "unpack columns: %s (stream %u, block %llu)",
               block ? "malformed block descriptor" : "a value outside the stream's type", c,
               (unsigned long long)(blk - uin.blk_base[c]));
+}
+int unpack_check(clg_engine* e, const clg::UnpackIn& uin, clg_unpack_bad* bad) {
+  if (!uin.blk_base[clg::kPackStreams]) return CLG_OK;
+  CHK(unpack_check_queue(e, uin));
+  CHK(e->sync());
+  return unpack_check_read(e, uin, bad);
 }
 
 int unpack_write(clg_engine* e, const clg::UnpackIn& uin, const clg::UnpackOut& uout) {
@@ -1298,8 +1325,10 @@ int unpack_write(clg_engine* e, const clg::UnpackIn& uin, const clg::UnpackOut& 
 // `narrow` unpacked into engine scratch for the encode: the layout and `rest`'s totals on the
 // host, the check, then the write queued on the engine's stream (the encode's kernels follow it
 // there).  col[5]: the plain columns' device addresses.
-int unpack_for_encode(clg_engine* e, const clg_packed* narrow, const clg_columns_in* rest, clg_unpack_bad* bad,
-                      const void* col[clg::kPackStreams]) {
+// unpack_for_encode up to the check: the host's checks, the input placed and the scratch columns
+// laid out.  The packed-wide calls queue the wide rows' check behind the narrow one themselves.
+int unpack_for_encode_begin(clg_engine* e, const clg_packed* narrow, const clg_columns_in* rest, clg_unpack_bad* bad,
+                            const void* col[clg::kPackStreams], clg::UnpackIn* uin_out, clg::UnpackOut* uout_out) {
   clg::pack_bad_reset(bad);
   if (rest->tag || rest->order || rest->timestamp || rest->rng || rest->buffer_built)
     return fail(CLG_E_INVALID_ARG, "the narrow column pointers of `rest` must be NULL: those columns are given packed");
@@ -1315,14 +1344,22 @@ int unpack_for_encode(clg_engine* e, const clg_packed* narrow, const clg_columns
       return fail(CLG_E_INVALID_ARG, "stream %u holds %llu values, `rest` says %llu", c, (unsigned long long)narrow->n_val[c],
                   (unsigned long long)want[c]);
     }
-  clg::UnpackIn uin{};
+  clg::UnpackIn& uin = *uin_out;
+  uin = clg::UnpackIn{};
   CHK(unpack_input(e, narrow, &uin));
   uint64_t cb[clg::kPackStreams];
   for (uint32_t c = 0; c < clg::kPackStreams; ++c) cb[c] = narrow->n_val[c] * clg::pack_stream_bytes(c);
   size_t at[clg::kPackStreams + 1];
   CHK(e->d_unpackcol.ensure(clg::place_layout(cb, clg::kPackStreams, at) + 16));
-  clg::UnpackOut uout{};
-  for (uint32_t c = 0; c < clg::kPackStreams; ++c) col[c] = uout.col[c] = e->d_unpackcol.as<uint8_t>() + at[c];
+  *uout_out = clg::UnpackOut{};
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) col[c] = uout_out->col[c] = e->d_unpackcol.as<uint8_t>() + at[c];
+  return CLG_OK;
+}
+int unpack_for_encode(clg_engine* e, const clg_packed* narrow, const clg_columns_in* rest, clg_unpack_bad* bad,
+                      const void* col[clg::kPackStreams]) {
+  clg::UnpackIn uin;
+  clg::UnpackOut uout;
+  CHK(unpack_for_encode_begin(e, narrow, rest, bad, col, &uin, &uout));
   CHK(unpack_check(e, uin, bad));
   return unpack_write(e, uin, uout);
 }
@@ -1334,6 +1371,13 @@ clg_columns_in with_narrow(const clg_columns_in& rest, const void* const col[clg
   full.timestamp = static_cast<const int64_t*>(col[2]), full.rng = static_cast<const int32_t*>(col[3]);
   full.buffer_built = static_cast<const int32_t*>(col[4]);
   return full;
+}
+
+EcolDev ecol_dev_narrow(const void* const col[clg::kPackStreams]) {
+  EcolDev dev;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) dev.col[c] = col[c];
+  dev.n = int(clg::kPackStreams);
+  return dev;
 }
 
 }  // namespace
@@ -1379,7 +1423,8 @@ int clg_encode_columns_packed(clg_engine* e, const clg_packed* narrow, const clg
   const void* col[clg::kPackStreams];
   CHK(unpack_for_encode(e, narrow, rest, bad, col));
   const clg_columns_in full = with_narrow(*rest, col);
-  return encode_columns_checked(e, &full, out, col);
+  const EcolDev dev = ecol_dev_narrow(col);
+  return encode_columns_checked(e, &full, out, &dev);
 }
 
 int clg_append_columns_packed(clg_engine* e, const uint32_t* log, const int64_t* epoch, uint32_t n_spans,
@@ -1393,7 +1438,252 @@ int clg_append_columns_packed(clg_engine* e, const uint32_t* log, const int64_t*
   const void* col[clg::kPackStreams];
   CHK(unpack_for_encode(e, narrow, rest, bad, col));
   const clg_columns_in full = with_narrow(*rest, col);
-  return append_columns_checked(e, log, epoch, &full, span_bytes, status, col);
+  const EcolDev dev = ecol_dev_narrow(col);
+  return append_columns_checked(e, log, epoch, &full, span_bytes, status, &dev);
+}
+
+}  // extern "C"
+
+// ---- packed wide rows as input (pack_wide.h, unpack_wide.hip) ---------------------------------
+// The way back in for the wide rows: check, kind and scan, the host's reading of the verdict and
+// the histogram after one sync, then write, merge and (where wanted) pos.  Invalid input writes
+// nothing outside engine scratch.
+namespace {
+
+// What a checked clg_packed_wide's unpack works with between its two halves.
+struct WUnpackPlan {
+  uint64_t nw = 0, nb = 0;
+  uint32_t nt = 0;
+  uint32_t* d_cnt = nullptr;
+  uint64_t *d_base = nullptr, *d_tsum = nullptr;
+  clg::WUnpackVerdict* d_verdict = nullptr;
+  clg::WUnpackTab* tab = nullptr;  // pinned: the host's copy
+};
+
+// A packed input that passed the host's layout check, with rows: the input placed (device and
+// registered memory in place, host memory staged), the scratch laid out and the stream table
+// uploaded.  d_idx: where w_idx goes.
+int wunpack_begin(clg_engine* e, const clg_packed_wide* in, void* d_idx, WUnpackPlan* p) {
+  const uint64_t nw = in->n_val[CLG_WPACK_KIND], nb = in->blk_base[clg::kWPackStreams];
+  if (nw >> 32) return fail(CLG_E_INVALID_ARG, "%llu wide rows in one call", (unsigned long long)nw);
+  if (nb >> 31) return fail(CLG_E_INVALID_ARG, "%llu blocks in one call", (unsigned long long)nb);
+  CHK(pack_out_check(clg::pack_view(*in), "the packed input's "));
+  const PlaceSpec ins[2] = {{in->desc, nb * sizeof(clg_pack_block), 8}, {in->bits, in->n_bits, 16}};
+  clg::Placement pl;
+  CHK(place_in(e, e->d_wunpackin, ins, 2, in->out_kind, PlacePolicy::stage_if_unresolved, "packed input", &pl));
+  p->nw = nw, p->nb = nb, p->nt = uint32_t(clg::pack_blocks_of(nw));
+  const uint64_t nt = p->nt;
+  const uint64_t wb[5] = {nw, nt * clg::kWPackKinds * 4, nt * clg::kWPackKinds * 8, nt * 8, sizeof(clg::WUnpackVerdict)};
+  size_t wo[6];
+  CHK(e->d_wunpackwork.ensure(clg::place_layout(wb, 5, wo) + 16));
+  uint8_t* wk = e->d_wunpackwork.as<uint8_t>();
+  p->d_cnt = reinterpret_cast<uint32_t*>(wk + wo[1]);
+  p->d_base = reinterpret_cast<uint64_t*>(wk + wo[2]);
+  p->d_tsum = reinterpret_cast<uint64_t*>(wk + wo[3]);
+  p->d_verdict = reinterpret_cast<clg::WUnpackVerdict*>(wk + wo[4]);
+  constexpr int kArrays = int(clg::kWPackKinds * clg::kWPackFields);
+  uint64_t cb[kArrays];
+  size_t so[kArrays + 1];
+  for (uint32_t t = 0; t < clg::kWPackKinds; ++t)
+    for (uint32_t f = 0; f < clg::kWPackFields; ++f)
+      cb[t * clg::kWPackFields + f] = in->n_val[clg::wpack_stream(t, f)] * clg::pack_elem_bytes(clg::kWPackField[f].elem);
+  CHK(e->d_wunpacksoa.ensure(clg::place_layout(cb, kArrays, so) + 16));
+  CHK(e->h_wunpacktab.ensure(sizeof(clg::WUnpackTab)));
+  CHK(e->d_wunpacktab.ensure(sizeof(clg::WUnpackTab)));
+  CHK(e->h_wunpackres.ensure(sizeof(clg::WUnpackRes) + sizeof(clg::WUnpackVerdict)));
+  clg::WUnpackTab* tab = p->tab = e->h_wunpacktab.as<clg::WUnpackTab>();
+  tab->desc = pl.at<const clg_pack_block>(0), tab->bits = pl.at<const uint8_t>(1), tab->n_bits = in->n_bits;
+  for (uint32_t c = 0; c < clg::kWPackStreams; ++c) tab->n[c] = in->n_val[c];
+  for (uint32_t c = 0; c <= clg::kWPackStreams; ++c) tab->blk_base[c] = in->blk_base[c];
+  tab->col[CLG_WPACK_KIND] = wk + wo[0], tab->col[CLG_WPACK_IDX] = d_idx;
+  for (int i = 0; i < kArrays; ++i) tab->col[2 + i] = e->d_wunpacksoa.as<uint8_t>() + so[i];
+  HIPCHK(hipMemcpyAsync(e->d_wunpacktab.p, tab, sizeof(clg::WUnpackTab), hipMemcpyHostToDevice, e->stream));
+  return CLG_OK;
+}
+
+// The check passes queued, with the verdict's copy to pinned memory (the totals are written there
+// by the scan).
+int wunpack_check_queue(clg_engine* e, const WUnpackPlan& p) {
+  clg::WUnpackRes* res = e->h_wunpackres.as<clg::WUnpackRes>();
+  // (bytes: a descriptor a block, twice for KIND's; KIND's payload is below a byte a row, its
+  // plain byte written; the tile counts written, read and their bases written)
+  CHK(e->timed("unpack_wide", p.nb * sizeof(clg_pack_block) + p.nw * 2 + uint64_t(p.nt) * 96, [&] {
+    return clg::launch_wunpack_check(e->d_wunpacktab.as<clg::WUnpackTab>(), uint32_t(p.nb), p.nt, p.d_cnt, p.d_base, p.d_verdict,
+                                     res, e->stream);
+  }));
+  HIPCHK(hipMemcpyAsync(res + 1, p.d_verdict, sizeof(clg::WUnpackVerdict), hipMemcpyDeviceToHost, e->stream));
+  return CLG_OK;
+}
+
+// After the sync: BLOCK, then VALUE, then the histogram, in clg_unpack_wide_host's order.
+// offset: added to the stream reported (the combined calls: kWPackBadStream).
+int wunpack_check_read(clg_engine* e, const WUnpackPlan& p, clg_unpack_bad* bad, uint32_t offset) {
+  const clg::WUnpackRes* res = e->h_wunpackres.as<clg::WUnpackRes>();
+  const clg::WUnpackVerdict* v = reinterpret_cast<const clg::WUnpackVerdict*>(res + 1);
+  const auto found = [&](uint32_t what, uint64_t blk, const char* text) {
+    uint32_t c = 0;
+    while (c + 1 < clg::kWPackStreams && blk >= p.tab->blk_base[c + 1]) ++c;
+    clg::pack_bad_set(bad, what, offset + c, blk - p.tab->blk_base[c]);
+    return fail(CLG_E_INVALID_ARG, "unpack wide rows: %s (stream %u, block %llu)", text, c,
+                (unsigned long long)(blk - p.tab->blk_base[c]));
+  };
+  if (v->bad_block) return found(CLG_UNPACK_BAD_BLOCK, ~uint64_t(v->bad_block), "malformed block descriptor");
+  const uint64_t vblk = ~uint64_t(v->bad_value);
+  if (v->bad_value && vblk < p.tab->blk_base[1]) return found(CLG_UNPACK_BAD_VALUE, vblk, "a KIND above 3");
+  for (uint32_t t = 0; t < clg::kWPackKinds; ++t)
+    if (res->tot[t] != p.tab->n[clg::wpack_stream(t, 0)]) {
+      clg::pack_bad_set(bad, CLG_UNPACK_BAD_VALUE, offset, 0);
+      return fail(CLG_E_INVALID_ARG, "unpack wide rows: the kinds' counts differ from the streams' lengths");
+    }
+  if (v->bad_value) return found(CLG_UNPACK_BAD_VALUE, vblk, "a value outside the stream's type");
+  return CLG_OK;
+}
+
+// Write, merge and pos queued.  dst: the rows' device addresses; pos: null when not wanted.
+int wunpack_write_queue(clg_engine* e, const WUnpackPlan& p, const clg::WUnpackDst& dst, uint64_t* pos, uint64_t n_bits) {
+  // (bytes: the descriptors and payloads of streams 1 .. 25, their 37 B a row written and read
+  // again with the kind byte, 37 B a row written in row order; pos: the lengths read, 8 B written)
+  return e->timed("unpack_wide", p.nb * sizeof(clg_pack_block) + n_bits + p.nw * (37 + 38 + 37 + (pos ? 12 : 0)), [&] {
+    return clg::launch_wunpack_write(e->d_wunpacktab.as<clg::WUnpackTab>(), uint32_t(p.nb), p.nt, p.nt, p.d_base, dst, p.nw,
+                                     p.d_tsum, pos, p.d_verdict, e->stream);
+  });
+}
+
+// Both packed forms unpacked into engine scratch for the encode.  full: `rest` with the scratch
+// arrays in place of its null pointers; dev: their addresses for ecol_sizes, with the cross rule's
+// word.  The checks' order is wpack_unpack_both_host's.
+int unpack_both_for_encode(clg_engine* e, const clg_packed* narrow, const clg_packed_wide* wide, const clg_columns_in* rest,
+                           clg_unpack_bad* bad, clg_columns_in* full, EcolDev* dev) {
+  clg::pack_bad_reset(bad);
+  if (!clg::wpack_rest_ok(*rest))
+    return fail(CLG_E_INVALID_ARG, "the column pointers of `rest` that the packed forms give must be NULL");
+  const char* what = "";
+  if (const int st = clg::wpack_both_layout(*narrow, *wide, *rest, bad, &what)) return fail(st, "unpack columns: %s", what);
+  const void* col[clg::kPackStreams];
+  clg::UnpackIn uin;
+  clg::UnpackOut uout;
+  CHK(unpack_for_encode_begin(e, narrow, rest, bad, col, &uin, &uout));
+  *full = with_narrow(*rest, col);
+  *dev = ecol_dev_narrow(col);
+  const uint64_t nw = rest->n_class[4];
+  if (!nw) {  // no rows: nothing of the wide form is launched or waited for
+    CHK(unpack_check(e, uin, bad));
+    return unpack_write(e, uin, uout);
+  }
+  // the rows in EcolIn's order behind the narrow columns: w_rc, w_v1, w_var_len, w_sub, w_v0, w_idx, pos
+  const uint64_t rb[7] = {nw * 4, nw * 8, nw * 4, nw, nw * 8, nw * 4, (nw + 1) * 8};
+  size_t ro[8];
+  CHK(e->d_wunpackrow.ensure(clg::place_layout(rb, 7, ro) + 16));
+  uint8_t* rw = e->d_wunpackrow.as<uint8_t>();
+  for (int i = 0; i < 7; ++i) dev->col[5 + i] = rw + ro[i];
+  dev->n = 12;
+  WUnpackPlan p;
+  CHK(wunpack_begin(e, wide, rw + ro[5], &p));
+  CHK(unpack_check_queue(e, uin));
+  CHK(wunpack_check_queue(e, p));
+  CHK(e->sync());
+  CHK(unpack_check_read(e, uin, bad));
+  CHK(wunpack_check_read(e, p, bad, clg::kWPackBadStream));
+  CHK(unpack_write(e, uin, uout));
+  // (w_var_off is checked like every stream but not put back in row order: the encode does not read it)
+  const clg::WUnpackDst dst{{rw + ro[0], rw + ro[1], nullptr, rw + ro[2], rw + ro[3], rw + ro[4]},
+                            static_cast<const uint8_t*>(col[0]), rest->n_rec};
+  CHK(wunpack_write_queue(e, p, dst, reinterpret_cast<uint64_t*>(rw + ro[6]), wide->n_bits));
+  unsigned long long* cross = &reinterpret_cast<clg::WUnpackVerdict*>(e->h_wunpackres.as<clg::WUnpackRes>() + 1)->cross_row;
+  HIPCHK(hipMemcpyAsync(cross, &p.d_verdict->cross_row, sizeof *cross, hipMemcpyDeviceToHost, e->stream));
+  dev->cross = cross, dev->bad = bad;
+  full->w_rc = reinterpret_cast<const int32_t*>(dev->col[5]), full->w_v1 = reinterpret_cast<const int64_t*>(dev->col[6]);
+  full->w_var_len = reinterpret_cast<const uint32_t*>(dev->col[7]), full->w_sub = reinterpret_cast<const uint8_t*>(dev->col[8]);
+  full->w_v0 = reinterpret_cast<const int64_t*>(dev->col[9]), full->w_idx = reinterpret_cast<const uint32_t*>(dev->col[10]);
+  full->pos = reinterpret_cast<const uint64_t*>(dev->col[11]);
+  return CLG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int clg_unpack_wide(clg_engine* e, const clg_packed_wide* in, clg_columns* out, uint64_t* pos, clg_unpack_bad* bad) {
+  ENGINE_GUARD(e);
+  clg::pack_bad_reset(bad);
+  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  uint32_t stream;
+  if (!clg::wpack_layout_in_ok(*in, &stream)) {
+    clg::pack_bad_set(bad, CLG_UNPACK_BAD_LAYOUT, stream, 0);
+    return fail(CLG_E_INVALID_ARG, "unpack wide rows: blk_base, n_val, the capacities and the pointers disagree (stream %u)", stream);
+  }
+  const uint64_t nw = in->n_val[CLG_WPACK_KIND];
+  out->n_class[4] = nw;
+  const clg::WPackCols cols = clg::wpack_cols(*out);
+  bool any = out->w_idx != nullptr || pos != nullptr, all = out->w_idx != nullptr;
+  for (uint32_t f = 0; f < clg::kWPackFields; ++f) any = any || cols.col[f], all = all && cols.col[f];
+  if (!any) return CLG_OK;  // sizes only
+  if ((!all && nw) || out->cap_wide < nw) return fail(CLG_E_CAPACITY, "unpack wide rows: the wide rows' arrays are too small");
+  if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  if (!nw) {  // no rows: nothing is launched, and only a device pos is waited for
+    if (!pos) return CLG_OK;
+    if (out->out_kind != CLG_MEM_DEVICE) return pos[0] = 0, CLG_OK;
+    HIPCHK(hipMemsetAsync(pos, 0, 8, e->stream));
+    return e->sync();
+  }
+  // the outputs: w_idx, the six fields in kWPackField's order, pos
+  PlaceSpec outs[8] = {{out->w_idx, nw * 4, 4}};
+  for (uint32_t f = 0; f < clg::kWPackFields; ++f) {
+    const uint32_t eb = clg::pack_elem_bytes(clg::kWPackField[f].elem);
+    outs[1 + f] = {cols.col[f], nw * eb, eb};
+  }
+  outs[7] = {pos, (nw + 1) * 8, 8};
+  clg::Placement pl;
+  CHK(place_out(e->d_wunpackout, outs, 8, out->out_kind, PlacePolicy::stage_if_unresolved, "wide", &pl));
+  WUnpackPlan p;
+  CHK(wunpack_begin(e, in, pl.at<void>(0), &p));
+  CHK(wunpack_check_queue(e, p));
+  CHK(e->sync());
+  CHK(wunpack_check_read(e, p, bad, 0));
+  clg::WUnpackDst dst{};
+  for (uint32_t f = 0; f < clg::kWPackFields; ++f) dst.col[f] = pl.at<void>(1 + int(f));
+  CHK(wunpack_write_queue(e, p, dst, pl.at<uint64_t>(7), in->n_bits));
+  CHK(stage_out(e, outs, 8, pl));
+  return e->sync();
+}
+
+int clg_encode_columns_packed_wide(clg_engine* e, const clg_packed* narrow, const clg_packed_wide* wide,
+                                   const clg_columns_in* rest, clg_encoded* out, clg_unpack_bad* bad) {
+  ENGINE_GUARD(e);
+  if (!narrow || !wide || !rest || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  clg::ecol_reset_result(out);
+  clg_columns_in full;
+  EcolDev dev;
+  CHK(unpack_both_for_encode(e, narrow, wide, rest, bad, &full, &dev));
+  return encode_columns_checked(e, &full, out, &dev);
+}
+
+int clg_append_columns_packed_wide(clg_engine* e, const uint32_t* log, const int64_t* epoch, uint32_t n_spans,
+                                   const clg_packed* narrow, const clg_packed_wide* wide, const clg_columns_in* rest,
+                                   uint64_t* span_bytes, int32_t* status, clg_unpack_bad* bad) {
+  ENGINE_GUARD(e);
+  if (!narrow || !wide || !rest || !log || !epoch || !status) return fail(CLG_E_INVALID_ARG, "null argument");
+  const uint32_t ns = clg::ecol_spans(*rest);
+  if (n_spans != ns) return fail(CLG_E_INVALID_ARG, "%u logs for %u spans", n_spans, ns);
+  for (uint32_t s = 0; s < ns; ++s) status[s] = CLG_OK;
+  clg_columns_in full;
+  EcolDev dev;
+  CHK(unpack_both_for_encode(e, narrow, wide, rest, bad, &full, &dev));
+  return append_columns_checked(e, log, epoch, &full, span_bytes, status, &dev);
+}
+
+int clg_encode_columns_packed_wide_host(const clg_packed* narrow, const clg_packed_wide* wide, const clg_columns_in* rest,
+                                        clg_encoded* out, clg_unpack_bad* bad) {
+  if (!out) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::ecol_reset_result(out);
+  clg::WPackBothHost h;
+  clg_columns_in full;
+  const char* what = "";
+  int st = clg::wpack_unpack_both_host(narrow, wide, rest, bad, &h, &full, &what);
+  if (st != CLG_OK) return fail(st, "unpack columns: %s", what);
+  st = clg::ecol_build_host(&full, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "encode columns: %s", what);
 }
 
 }  // extern "C"

@@ -272,6 +272,11 @@ struct clg_engine {
   // the scan groups' sums, host-output staging; the scans' results (pinned: the kernels write them)
   DevBuf d_wpackin, d_wpackkind, d_wpacksoa, d_wpacktab, d_wpackdesc, d_wpacksum, d_wpackout;
   PinBuf h_wpacktab, h_wpackres;
+  // packed wide rows as input: staged host input, kind bytes | tile counts | tile bases | tile
+  // sums | the verdict words, the per-kind field arrays, the stream table (pinned, then device),
+  // host-output staging, the rows and pos for the encode; the totals and the verdict (pinned)
+  DevBuf d_wunpackin, d_wunpackwork, d_wunpacksoa, d_wunpacktab, d_wunpackout, d_wunpackrow;
+  PinBuf h_wunpacktab, h_wunpackres;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 

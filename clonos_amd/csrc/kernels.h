@@ -794,6 +794,52 @@ int launch_unpack_check(const UnpackIn& in, uint32_t n_blocks, UnpackVerdict* d_
 // input changed under the call) writes nothing; no store at or past a stream's n.
 int launch_unpack_write(const UnpackIn& in, const UnpackOut& out, uint32_t n_blocks, void* stream);
 
+// ---- packed wide rows as input (pack_wide.h, unpack_wide.hip) -----------------------
+// A clg_packed_wide read as input, after the host's layout check, and where its 26 streams'
+// plain values go: col[0] the kind bytes and col[2 ..] the per-kind field arrays, all in engine
+// scratch; col[1] w_idx of the rows (the caller's array or its scratch).  Device memory, passed by
+// address, as WPackTab is.
+struct WUnpackTab {
+  const clg_pack_block* desc;
+  const uint8_t* bits;
+  uint64_t n_bits;
+  uint64_t n[26];
+  uint64_t blk_base[27];
+  void* col[26];
+};
+// The rows in row order: the six field arrays in kWPackField's order (w_var_off may be null: not
+// written), each aligned to its element.  tag (the combined calls: the narrow unpack's tags, n_rec
+// of them) may be null: no cross rule.
+struct WUnpackDst {
+  void* col[6];
+  const uint8_t* tag;
+  uint64_t n_rec;
+};
+// The verdict words.  Device memory that launch_wunpack_check sets through the stream (the first
+// two to 0, cross_row to ~0) before the kernels' vector atomicMax / atomicMin; only a finding
+// issues one.  bad_block / bad_value: ~(the lowest bad block's index in desc).  cross_row: the
+// lowest row whose w_idx names no wide record of its kind (raised by the merge).
+struct WUnpackVerdict {
+  unsigned long long bad_block;
+  unsigned long long bad_value;
+  unsigned long long cross_row;
+};
+// The scan's totals (KIND's histogram over the values 0 .. 3), in pinned memory.
+struct WUnpackRes {
+  uint64_t tot[4];
+};
+// Check (a wave per block, all 26 streams), kind (a workgroup per KIND block: d_tab->col[0] and
+// d_cnt[tile * 4 + kind]) and the scan of the tile counts (one workgroup: d_base, *res).
+int launch_wunpack_check(const WUnpackTab* d_tab, uint32_t n_blocks, uint32_t n_tiles, uint32_t* d_cnt, uint64_t* d_base,
+                         WUnpackVerdict* d_verdict, WUnpackRes* res, void* stream);
+// After a clean verdict.  Write (a workgroup per block of streams 1 .. 25, to d_tab->col), then
+// merge (a workgroup per tile: the rows in row order to dst, the tile's sum of w_var_len to
+// d_tsum), then, with pos, the scan of the tile sums and pos[0 .. n_wide].  No store at or past a
+// stream's length or a row array's n_wide.
+int launch_wunpack_write(const WUnpackTab* d_tab, uint32_t n_blocks, uint32_t n_kind_blocks, uint32_t n_tiles,
+                         const uint64_t* d_base, const WUnpackDst& dst, uint64_t n_wide, uint64_t* d_tsum, uint64_t* pos,
+                         WUnpackVerdict* d_verdict, void* stream);
+
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {
   uint8_t* dst;        // inside one segment

@@ -1,6 +1,7 @@
 // pack_dev.h -- what the kernels of pack.hip, pack_wide.hip and unpack.hip share on the device:
 // the workgroup's shape, the wave's signed minimum / maximum by DPP, the wave scans, the round of a
-// one-workgroup scan, and the block codec's measure and write, instantiated on (element, scheme).
+// one-workgroup scan, and the block codec's measure, write and decode, instantiated on (element,
+// scheme).
 // Device code only, file-local in each unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -205,6 +206,143 @@ __device__ __forceinline__ void pack_block_write(const PackAt at, const clg_pack
       *reinterpret_cast<uint4*>(bits + a) = make_uint4(uint32_t(lo), uint32_t(lo >> 32), uint32_t(hi), uint32_t(hi >> 32));
     }
   }
+}
+
+// ---- the block codec's decode on the device ----------------------------------------------------
+
+// Residual j's p from 64-bit words, 1 <= w <= 63: no shift by 64 (sh + w > 64 implies sh > 0), and
+// the second word is read only when the value reaches into it, so never past the payload.
+__device__ __forceinline__ uint64_t unpack_bits(const unsigned long long* words, uint32_t w, uint32_t j) {
+  const uint32_t bit = j * w, sh = bit & 63;
+  uint64_t v = words[bit >> 6] >> sh;
+  if (sh + w > 64) v |= uint64_t(words[(bit >> 6) + 1]) << (64 - sh);
+  return v & ((uint64_t(1) << w) - 1);
+}
+__device__ __forceinline__ uint64_t unpack_resid(const unsigned long long* words, uint32_t w, uint32_t j) {
+  return w == 0 ? 0 : w == 64 ? uint64_t(words[j]) : unpack_bits(words, w, j);
+}
+
+// Every value of a well-formed block inside [lo, hi]?  A wave per block, the payload read from
+// global memory in place.  FOR: the lanes take the values 64 apart.  DELTA: 64 consecutive values a
+// round, the wave's inclusive scan of first and the residuals, the carry from lane 63.
+template <bool kDelta>
+__device__ __forceinline__ bool unpack_values_in(const clg_pack_block& d, const uint8_t* __restrict__ bits, uint32_t lane,
+                                                 int64_t lo, int64_t hi) {
+  const unsigned long long* words = reinterpret_cast<const unsigned long long*>(bits + d.pos);
+  const uint32_t w = d.width;
+  bool ok = true;
+  if (!kDelta) {
+    for (uint32_t i = lane; i < d.count; i += 64) {
+      const int64_t x = int64_t(unpack_resid(words, w, i) + uint64_t(d.ref));
+      ok = ok && x >= lo && x <= hi;
+    }
+  } else {
+    uint64_t carry = 0;
+    for (uint32_t i0 = 0; i0 < d.count; i0 += 64) {  // (wave-uniform)
+      const uint32_t i = i0 + lane;
+      uint64_t r = 0;
+      if (i == 0) r = uint64_t(d.first);
+      else if (i < d.count) r = unpack_resid(words, w, i - 1) + uint64_t(d.ref);
+      const uint64_t x = carry + pack_wave_incl64(r, lane);
+      ok = ok && (i >= d.count || (int64_t(x) >= lo && int64_t(x) <= hi));
+      carry = uint64_t(pack_lane63(int64_t(x)));
+    }
+  }
+  return __ballot(!ok) == 0;
+}
+
+// Four consecutive values to col[at .. at + n) (n <= 4) in the element's type: one store of four
+// elements where all four are there and the column allows it (wide), else an element at a time.
+template <uint32_t kElem>
+__device__ __forceinline__ void unpack_store4(void* col, uint64_t at, const uint64_t v[4], uint32_t n, bool wide) {
+  if (kElem == kElemI64) {
+    int64_t* dst = static_cast<int64_t*>(col) + at;
+    if (n == 4 && wide) {
+      reinterpret_cast<ulonglong2*>(dst)[0] = make_ulonglong2(v[0], v[1]);
+      reinterpret_cast<ulonglong2*>(dst)[1] = make_ulonglong2(v[2], v[3]);
+    } else {
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q)
+        if (q < n) dst[q] = int64_t(v[q]);
+    }
+  } else if (kElem == kElemI32 || kElem == kElemU32) {
+    uint32_t* dst = static_cast<uint32_t*>(col) + at;
+    if (n == 4 && wide) {
+      *reinterpret_cast<uint4*>(dst) = make_uint4(uint32_t(v[0]), uint32_t(v[1]), uint32_t(v[2]), uint32_t(v[3]));
+    } else {
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q)
+        if (q < n) dst[q] = uint32_t(v[q]);
+    }
+  } else {
+    uint8_t* dst = static_cast<uint8_t*>(col) + at;
+    if (n == 4 && wide) {
+      *reinterpret_cast<uint32_t*>(dst) = uint32_t(v[0] & 255) | uint32_t(v[1] & 255) << 8 | uint32_t(v[2] & 255) << 16 |
+                                          uint32_t(v[3] & 255) << 24;
+    } else {
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q)
+        if (q < n) dst[q] = uint8_t(v[q]);
+    }
+  }
+}
+
+// A well-formed block's values, four consecutive ones a thread (v[q] is value 4 * tid + q; those at
+// or past count are not values): the payload (at most 8 KiB) staged in LDS with aligned 16-byte
+// loads (bits is 16-byte aligned, pos a multiple of 16), FOR adds ref, DELTA takes the inclusive
+// prefix sum of first and the residuals, modulo 2^64: the thread's four, the wave scan, the four
+// waves through LDS.  s_w: the payload's words (8 KiB and one spare pair); s_ws: the waves' sums.
+template <bool kDelta>
+__device__ __forceinline__ void unpack_block_values(const clg_pack_block d, const uint8_t* __restrict__ bits,
+                                                    unsigned long long* s_w, unsigned long long* s_ws,
+                                                    uint64_t v[kPackPerThread]) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t m = d.count, k = pack_residuals(kDelta, m), width = d.width;
+  const uint32_t n16 = pack_payload_bytes(k, width) / 16;
+  const uint4* src = reinterpret_cast<const uint4*>(bits + d.pos);
+  for (uint32_t i = tid; i < n16; i += kPackThreads) reinterpret_cast<uint4*>(s_w)[i] = src[i];
+  if (n16) __syncthreads();  // (uniform)
+
+  const uint32_t first_i = tid * kPackPerThread;
+#pragma unroll
+  for (uint32_t q = 0; q < kPackPerThread; ++q) {
+    const uint32_t i = first_i + q;
+    // the residual's index: FOR i, DELTA i - 1 (value 0 is `first`)
+    const bool has = kDelta ? (i >= 1 && i < m) : i < m;
+    const uint32_t j = kDelta ? i - 1 : i;
+    uint64_t p = 0;
+    if (has) {
+      if (width == 64) p = s_w[j];  // (the widths 0 and 64 are uniform cases: no shifts)
+      else if (width) p = unpack_bits(s_w, width, j);
+      p += uint64_t(d.ref);
+    }
+    v[q] = kDelta && i == 0 ? uint64_t(d.first) : p;
+  }
+  if (kDelta) {
+    v[1] += v[0], v[2] += v[1], v[3] += v[2];
+    const uint64_t incl = pack_wave_incl64(v[3], lane);
+    if (lane == 63) s_ws[wv] = incl;
+    __syncthreads();
+    uint64_t before = incl - v[3];
+#pragma unroll
+    for (uint32_t w2 = 0; w2 < kPackWaves; ++w2) before += w2 < wv ? uint64_t(s_ws[w2]) : 0;
+#pragma unroll
+    for (uint32_t q = 0; q < kPackPerThread; ++q) v[q] += before;
+  }
+}
+
+// The write: the block's values stored coalesced to col[i0 .. i0 + count).
+template <uint32_t kElem, bool kDelta>
+__device__ __forceinline__ void unpack_block_write(void* col, uint64_t i0, const clg_pack_block d,
+                                                   const uint8_t* __restrict__ bits, unsigned long long* s_w,
+                                                   unsigned long long* s_ws) {
+  uint64_t v[kPackPerThread];
+  unpack_block_values<kDelta>(d, bits, s_w, s_ws, v);
+  const uint32_t first_i = threadIdx.x * kPackPerThread, m = d.count;
+  const uint32_t n = first_i < m ? (m - first_i < 4 ? m - first_i : 4) : 0;
+  constexpr uint32_t kWide = kElem == kElemU8 || kElem == kElemI8 ? 4 : 16;
+  const bool wide = (reinterpret_cast<uintptr_t>(col) & (kWide - 1)) == 0;  // (uniform; i0 keeps the alignment)
+  if (n) unpack_store4<kElem>(col, i0 + first_i, v, n, wide);
 }
 
 }  // namespace

@@ -156,7 +156,9 @@ inline bool wpack_layout_in_ok(const clg_packed_wide& p, uint32_t* stream) {
   return sum == p.n_val[CLG_WPACK_KIND];
 }
 
-inline int wpack_unpack_host(const clg_packed_wide* in, clg_columns* out, clg_unpack_bad* bad, const char** what = nullptr) {
+// kinds (optional): every row's kind, for the cross rule below.
+inline int wpack_unpack_host(const clg_packed_wide* in, clg_columns* out, clg_unpack_bad* bad, const char** what = nullptr,
+                             std::vector<uint8_t>* kinds = nullptr) {
   const char* dummy;
   if (!what) what = &dummy;
   *what = "";
@@ -204,7 +206,103 @@ inline int wpack_unpack_host(const clg_packed_wide* in, clg_columns* out, clg_un
     const uint64_t r = rank[kind]++;
     out->w_idx[k] = uint32_t(val[CLG_WPACK_IDX][size_t(k)]);
     for (uint32_t f = 0; f < kWPackFields; ++f) pack_store(kWPackField[f].elem, cols.col[f], k, val[wpack_stream(kind, f)][size_t(r)]);
+    if (kinds) kinds->push_back(uint8_t(kind));
   }
+  return CLG_OK;
+}
+
+// ---- both packed forms read together (clg_encode_columns_packed_wide and its kin) --------------
+// A finding in the wide rows reports stream kWPackBadStream + its stream.  One more rule, which
+// only a call that holds the tags can test (clg_pack_wide enforces it with bad_row): row k names
+// a wide record of its own kind.  The lowest offending row is reported as VALUE,
+// kWPackBadStream + IDX, block k / kPackBlock.
+constexpr uint32_t kWPackBadStream = CLG_UNPACK_WIDE_STREAM;
+CLG_PACK_HD bool wpack_cross_ok(const uint8_t* tag, uint64_t n_rec, uint32_t idx, uint32_t kind) {
+  return wpack_kind_of(tag, n_rec, idx) == kind;
+}
+inline int wpack_bad_wide(clg_unpack_bad* bad, uint32_t what, uint32_t stream, uint64_t block) {
+  return pack_bad_set(bad, what, kWPackBadStream + stream, block);
+}
+inline int wpack_bad_cross(clg_unpack_bad* bad, uint64_t row) {
+  return wpack_bad_wide(bad, CLG_UNPACK_BAD_VALUE, CLG_WPACK_IDX, row / kPackBlock);
+}
+// What `rest` may carry in the combined calls: none of the arrays that the packed forms give.
+inline bool wpack_rest_ok(const clg_columns_in& r) {
+  return !r.tag && !r.order && !r.timestamp && !r.rng && !r.buffer_built && !r.w_rc && !r.w_v1 && !r.w_var_len && !r.w_sub &&
+         !r.w_v0 && !r.w_idx && !r.pos;
+}
+// The checks a combined call makes on the host before it reads a descriptor, in their order: the
+// narrow layout and its totals against `rest`, the wide layout, the wide rows against n_class[4].
+inline int wpack_both_layout(const clg_packed& narrow, const clg_packed_wide& wide, const clg_columns_in& rest,
+                             clg_unpack_bad* bad, const char** what) {
+  uint32_t stream;
+  if (!pack_layout_in_ok(pack_view(narrow), &stream))
+    return *what = "narrow: blk_base, n_val, the capacities and the pointers disagree", pack_bad_set(bad, CLG_UNPACK_BAD_LAYOUT, stream, 0);
+  const uint64_t want[kPackStreams] = {rest.n_rec, rest.n_class[0], rest.n_class[1], rest.n_class[2], rest.n_class[3]};
+  for (uint32_t c = 0; c < kPackStreams; ++c)
+    if (want[c] != narrow.n_val[c])
+      return *what = "a narrow stream's length differs from `rest`", pack_bad_set(bad, CLG_UNPACK_BAD_LAYOUT, c, 0);
+  if (!wpack_layout_in_ok(wide, &stream))
+    return *what = "wide: blk_base, n_val, the capacities and the pointers disagree", wpack_bad_wide(bad, CLG_UNPACK_BAD_LAYOUT, stream, 0);
+  if (wide.n_val[CLG_WPACK_KIND] != rest.n_class[4])
+    return *what = "the packed wide rows differ from `rest`'s n_class[4]", wpack_bad_wide(bad, CLG_UNPACK_BAD_LAYOUT, 0, 0);
+  return CLG_OK;
+}
+
+// The exclusive prefix sum of n lengths: pos[0 .. n], pos[n] the total.
+inline void wpack_pos_host(const uint32_t* len, uint64_t n, uint64_t* pos) {
+  uint64_t at = 0;
+  for (uint64_t k = 0; k < n; ++k) pos[k] = at, at += len[k];
+  pos[n] = at;
+}
+
+// Host arrays for both unpacks and `rest` completed with them (clg_encode_columns_packed_wide_host):
+// the reference the device's combined calls are held to.
+struct WPackBothHost {
+  std::vector<uint8_t> tag, w_sub;
+  std::vector<int8_t> order;
+  std::vector<int64_t> timestamp, w_v1, w_v0;
+  std::vector<int32_t> rng, buffer_built, w_rc;
+  std::vector<uint32_t> w_idx, w_var_off, w_var_len;
+  std::vector<uint64_t> pos;
+};
+inline int wpack_unpack_both_host(const clg_packed* narrow, const clg_packed_wide* wide, const clg_columns_in* rest,
+                                  clg_unpack_bad* bad, WPackBothHost* h, clg_columns_in* full, const char** what) {
+  *what = "";
+  pack_bad_reset(bad);
+  if (!narrow || !wide || !rest) return *what = "null argument", CLG_E_INVALID_ARG;
+  if (!wpack_rest_ok(*rest)) return *what = "the column pointers of `rest` that the packed forms give must be NULL", CLG_E_INVALID_ARG;
+  if (const int st = wpack_both_layout(*narrow, *wide, *rest, bad, what)) return st;
+  const uint64_t nw = rest->n_class[4];
+  h->tag.resize(size_t(rest->n_rec) + 1), h->order.resize(size_t(rest->n_class[0]) + 1);
+  h->timestamp.resize(size_t(rest->n_class[1]) + 1), h->rng.resize(size_t(rest->n_class[2]) + 1);
+  h->buffer_built.resize(size_t(rest->n_class[3]) + 1);
+  h->w_sub.resize(size_t(nw) + 1), h->w_v1.resize(size_t(nw) + 1), h->w_v0.resize(size_t(nw) + 1), h->w_rc.resize(size_t(nw) + 1);
+  h->w_idx.resize(size_t(nw) + 1), h->w_var_off.resize(size_t(nw) + 1), h->w_var_len.resize(size_t(nw) + 1);
+  h->pos.resize(size_t(nw) + 1);
+  clg_columns c{};
+  c.tag = h->tag.data(), c.order = h->order.data(), c.timestamp = h->timestamp.data(), c.rng = h->rng.data();
+  c.buffer_built = h->buffer_built.data();
+  c.cap_tag = rest->n_rec, c.cap_order = rest->n_class[0], c.cap_timestamp = rest->n_class[1], c.cap_rng = rest->n_class[2];
+  c.cap_buffer_built = rest->n_class[3];
+  c.w_idx = h->w_idx.data(), c.w_rc = h->w_rc.data(), c.w_v1 = h->w_v1.data(), c.w_var_off = h->w_var_off.data();
+  c.w_var_len = h->w_var_len.data(), c.w_sub = h->w_sub.data(), c.w_v0 = h->w_v0.data();
+  c.cap_wide = nw;
+  if (const int st = pack_unpack_all_host(narrow, &c, bad, what)) return st;
+  std::vector<uint8_t> kinds;
+  kinds.reserve(size_t(nw));
+  if (const int st = wpack_unpack_host(wide, &c, bad, what, &kinds)) {
+    if (bad && bad->what != CLG_UNPACK_BAD_NONE) bad->stream += kWPackBadStream;
+    return st;
+  }
+  for (uint64_t k = 0; k < nw; ++k)
+    if (!wpack_cross_ok(c.tag, rest->n_rec, c.w_idx[k], kinds[size_t(k)]))
+      return *what = "a row's w_idx names no wide record of its kind", wpack_bad_cross(bad, k);
+  wpack_pos_host(c.w_var_len, nw, h->pos.data());
+  *full = *rest;
+  full->tag = c.tag, full->order = c.order, full->timestamp = c.timestamp, full->rng = c.rng, full->buffer_built = c.buffer_built;
+  full->w_rc = c.w_rc, full->w_v1 = c.w_v1, full->w_var_len = c.w_var_len, full->w_sub = c.w_sub, full->w_v0 = c.w_v0;
+  full->w_idx = c.w_idx, full->pos = h->pos.data();
   return CLG_OK;
 }
 

@@ -10,7 +10,8 @@
 //                     of its kind to ~index with one vector atomicMax (the host zeroes the words
 //                     through the stream; a clean input issues no atomic at all)
 //  * k_unpack_write   pass 2, queued by the host only after it has read a clean verdict: a
-//                     workgroup per block stages the payload (at most 8 KiB) in LDS with aligned
+//                     workgroup per block (pack_dev.h's decode, instantiated on the stream's
+//                     element and scheme) stages the payload (at most 8 KiB) in LDS with aligned
 //                     16-byte loads, each thread extracts four consecutive values, FOR adds ref,
 //                     DELTA takes the inclusive prefix sum of first and the residuals (the
 //                     thread's four, pack_dev.h's wave scan, the four waves through LDS), and
@@ -31,10 +32,8 @@ namespace clg {
 
 namespace {
 
-constexpr uint32_t kUnpackThreads = 256;
-constexpr uint32_t kUnpackWaves = kUnpackThreads / 64;
-constexpr uint32_t kUnpackPerThread = kPackBlock / kUnpackThreads;
-static_assert(kUnpackPerThread == 4, "four consecutive values a thread");
+constexpr uint32_t kUnpackThreads = kPackThreads;
+constexpr uint32_t kUnpackWaves = kPackWaves;
 
 // The stream that holds block blk (the bases do not decrease: the host's layout check).
 __device__ __forceinline__ uint32_t unpack_stream_of(const UnpackIn& in, uint64_t blk) {
@@ -42,110 +41,16 @@ __device__ __forceinline__ uint32_t unpack_stream_of(const UnpackIn& in, uint64_
          uint32_t(blk >= in.blk_base[4]);
 }
 
-// Residual j's p from 64-bit words, 1 <= w <= 63: no shift by 64 (sh + w > 64 implies sh > 0), and
-// the second word is read only when the value reaches into it, so never past the payload.
-__device__ __forceinline__ uint64_t unpack_bits(const unsigned long long* words, uint32_t w, uint32_t j) {
-  const uint32_t bit = j * w, sh = bit & 63;
-  uint64_t v = words[bit >> 6] >> sh;
-  if (sh + w > 64) v |= uint64_t(words[(bit >> 6) + 1]) << (64 - sh);
-  return v & ((uint64_t(1) << w) - 1);
-}
-
-// Every value of a well-formed block of stream kC (narrower than 64 bits) inside its type?  The
+// Every value of a well-formed block of stream kC (FOR, narrower than 64 bits) inside its type?  The
 // wave's lanes take the values 64 apart; the payload is read from global memory in place.
 template <uint32_t kC>
 __device__ __forceinline__ bool unpack_values_ok(const clg_pack_block& d, const uint8_t* __restrict__ bits, uint32_t lane) {
+  static_assert(!pack_is_delta(kC), "the narrow DELTA stream holds 64-bit values: every one passes");
   const unsigned long long* words = reinterpret_cast<const unsigned long long*>(bits + d.pos);
-  const uint32_t w = d.width;
   bool ok = true;
-  for (uint32_t i = lane; i < d.count; i += 64) {
-    const uint64_t p = w == 0 ? 0 : w == 64 ? uint64_t(words[i]) : unpack_bits(words, w, i);
-    ok = ok && pack_value_ok(kC, int64_t(p + uint64_t(d.ref)));
-  }
+  for (uint32_t i = lane; i < d.count; i += 64)
+    ok = ok && pack_value_ok(kC, int64_t(unpack_resid(words, d.width, i) + uint64_t(d.ref)));
   return __ballot(!ok) == 0;
-}
-
-// Four consecutive values to dst[0 .. n) (n <= 4) in the stream's element type: one store of
-// four elements where all four are there and the column allows it, else an element at a time.
-template <uint32_t kC>
-__device__ __forceinline__ void unpack_store4(void* col, uint64_t at, const uint64_t v[4], uint32_t n, bool wide) {
-  if (kC == CLG_PACK_TIMESTAMP) {
-    int64_t* dst = static_cast<int64_t*>(col) + at;
-    if (n == 4 && wide) {
-      reinterpret_cast<ulonglong2*>(dst)[0] = make_ulonglong2(v[0], v[1]);
-      reinterpret_cast<ulonglong2*>(dst)[1] = make_ulonglong2(v[2], v[3]);
-    } else {
-#pragma unroll
-      for (uint32_t q = 0; q < 4; ++q)
-        if (q < n) dst[q] = int64_t(v[q]);
-    }
-  } else if (kC >= CLG_PACK_RNG) {
-    int32_t* dst = static_cast<int32_t*>(col) + at;
-    if (n == 4 && wide) {
-      *reinterpret_cast<uint4*>(dst) = make_uint4(uint32_t(v[0]), uint32_t(v[1]), uint32_t(v[2]), uint32_t(v[3]));
-    } else {
-#pragma unroll
-      for (uint32_t q = 0; q < 4; ++q)
-        if (q < n) dst[q] = int32_t(uint32_t(v[q]));
-    }
-  } else {
-    uint8_t* dst = static_cast<uint8_t*>(col) + at;
-    if (n == 4 && wide) {
-      *reinterpret_cast<uint32_t*>(dst) = uint32_t(v[0] & 255) | uint32_t(v[1] & 255) << 8 | uint32_t(v[2] & 255) << 16 |
-                                          uint32_t(v[3] & 255) << 24;
-    } else {
-#pragma unroll
-      for (uint32_t q = 0; q < 4; ++q)
-        if (q < n) dst[q] = uint8_t(v[q]);
-    }
-  }
-}
-
-// s_w: the payload's words (8 KiB and one spare pair); s_ws: the waves' sums.
-template <uint32_t kC>
-__device__ __forceinline__ void unpack_write_body(void* col, uint64_t i0, const clg_pack_block d,
-                                                  const uint8_t* __restrict__ bits, unsigned long long* s_w,
-                                                  unsigned long long* s_ws) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  constexpr bool delta = kC == CLG_PACK_TIMESTAMP;
-  const uint32_t m = d.count, k = pack_resid(kC, m), width = d.width;
-  const uint32_t n16 = pack_payload_bytes(k, width) / 16;
-  // the payload into LDS: aligned 16-byte loads (bits is 16-byte aligned, pos a multiple of 16)
-  const uint4* src = reinterpret_cast<const uint4*>(bits + d.pos);
-  for (uint32_t i = tid; i < n16; i += kUnpackThreads) reinterpret_cast<uint4*>(s_w)[i] = src[i];
-  if (n16) __syncthreads();  // (uniform)
-
-  const uint32_t first_i = tid * kUnpackPerThread;
-  uint64_t v[kUnpackPerThread];
-#pragma unroll
-  for (uint32_t q = 0; q < kUnpackPerThread; ++q) {
-    const uint32_t i = first_i + q;
-    // the residual's index: FOR i, DELTA i - 1 (value 0 is `first`)
-    const bool has = delta ? (i >= 1 && i < m) : i < m;
-    const uint32_t j = delta ? i - 1 : i;
-    uint64_t p = 0;
-    if (has) {
-      if (width == 64) p = s_w[j];  // (the widths 0 and 64 are uniform cases: no shifts)
-      else if (width) p = unpack_bits(s_w, width, j);
-      p += uint64_t(d.ref);
-    }
-    v[q] = delta && i == 0 ? uint64_t(d.first) : p;
-  }
-  if (delta) {  // the inclusive prefix sum, modulo 2^64: the thread's four, the wave, the four waves
-    v[1] += v[0], v[2] += v[1], v[3] += v[2];
-    const uint64_t incl = pack_wave_incl64(v[3], lane);
-    if (lane == 63) s_ws[wv] = incl;
-    __syncthreads();
-    uint64_t before = incl - v[3];
-#pragma unroll
-    for (uint32_t w2 = 0; w2 < kUnpackWaves; ++w2) before += w2 < wv ? uint64_t(s_ws[w2]) : 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kUnpackPerThread; ++q) v[q] += before;
-  }
-  const uint32_t n = first_i < m ? (m - first_i < 4 ? m - first_i : 4) : 0;
-  constexpr uint32_t kWide = kC == CLG_PACK_TIMESTAMP || kC >= CLG_PACK_RNG ? 16 : 4;
-  const bool wide = (reinterpret_cast<uintptr_t>(col) & (kWide - 1)) == 0;  // (uniform; i0 keeps the alignment)
-  if (n) unpack_store4<kC>(col, i0 + first_i, v, n, wide);
 }
 
 }  // namespace
@@ -191,7 +96,8 @@ __global__ __launch_bounds__(kUnpackThreads) void k_unpack_write(const UnpackIn 
   switch (unpack_stream_of(in, blk)) {
 #define CLG_UNPACK_CASE(c)                                                                             \
   if (pack_block_in_ok(d, pack_is_delta(c), blk - in.blk_base[c], in.n[c], in.n_bits))                                \
-    unpack_write_body<c>(out.col[c], (blk - in.blk_base[c]) * kPackBlock, d, in.bits, s_w, s_ws);      \
+    unpack_block_write<pack_stream_elem(c), pack_is_delta(c)>(out.col[c], (blk - in.blk_base[c]) * kPackBlock, d, \
+                                                              in.bits, s_w, s_ws);                     \
   break
     case 0: CLG_UNPACK_CASE(0);
     case 1: CLG_UNPACK_CASE(1);

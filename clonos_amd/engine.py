@@ -814,6 +814,58 @@ def unpack_wide_host(packed: PackedWide) -> dict:
     return arrs
 
 
+def _wide_route(cols, wide: str) -> bool:
+    """Whether cols take the device route of the wide rows (clg_*_columns_packed_wide)."""
+    if wide not in ("host", "device"):
+        raise ValueError(f"wide={wide!r}: 'host' or 'device'")
+    if wide == "device" and (not isinstance(cols, PackedColumns) or cols.wide_packed is None):
+        raise ValueError("wide='device' takes PackedColumns whose wide rows came packed (wide_packed)")
+    return wide == "device"
+
+
+def _rest_in(cols: "PackedColumns") -> Tuple[_lib.ColumnsIn, list]:
+    """clg_columns_in for the calls that take both packed forms: the payload bytes, the span bases
+    and the totals.  No w_* array and no var_pos is read, so nothing is unpacked on the host."""
+    if cols.var is None:
+        raise ValueError("the columns carry no payload column (payloads=True)")
+    cin = _lib.ColumnsIn()
+    var = np.ascontiguousarray(cols.var, np.uint8)
+    keep = [var]
+    cin.var, cin.n_var = _np_ptr(var) or None, var.size
+    cin.n_rec = cols.n_rec
+    for c in range(4):
+        cin.n_class[c] = cols.n_val[c + 1]
+    cin.n_class[4] = cols.wide_packed.n_wide
+    if cols.n_spans:
+        sb = np.ascontiguousarray(cols.span_base, np.uint64).reshape(-1)
+        keep.append(sb)
+        cin.span_base, cin.n_spans = _np_ptr(sb), cols.n_spans
+    cin.in_kind = _lib.CLG_MEM_HOST
+    return cin, keep
+
+
+def _encode_packed_wide(call, cols: "PackedColumns", per_span: bool):
+    """_encode_twice over call(narrow, wide, rest, enc, bad) -> status, one of the two encodes that
+    take both packed forms."""
+    pk, pw, (rest, keep), bad = cols._struct(), cols.wide_packed._struct(), _rest_in(cols), _lib.UnpackBad()
+
+    def twice(enc):
+        st = call(C.byref(pk), C.byref(pw), C.byref(rest), C.byref(enc), C.byref(bad))
+        if st != _lib.CLG_OK and bad.what != _lib.UNPACK_BAD_NONE:
+            raise _unpack_error(st, bad, enc)
+        return st
+    return _encode_twice(twice, cols.n_spans, per_span)
+
+
+def encode_columns_packed_wide_host(cols: "PackedColumns", per_span: bool = False):
+    """clg_encode_columns_packed_wide_host: the log bytes of columns whose narrow columns and wide
+    rows are both packed, on the CPU (no engine, no GPU) -- what Engine.encode_columns(cols,
+    wide="device") computes.  A bad packed input raises ClonosError with bad_what, bad_stream
+    (UNPACK_WIDE_STREAM + the stream for the wide rows) and bad_block."""
+    _wide_route(cols, "device")
+    return _encode_packed_wide(lib.clg_encode_columns_packed_wide_host, cols, per_span)
+
+
 # clg_digest rows: two spans are equal only when both fields are equal
 DIGEST =np.dtype([("hash", np.uint64), ("len", np.uint64)])
 
@@ -1403,6 +1455,38 @@ class Engine:
             raise _unpack_error(st, bad)
         return _unpacked(packed, arrs)
 
+    def unpack_wide(self, packed_wide: PackedWide, pos: bool = False) -> dict:
+        """clg_unpack_wide: host packed wide rows unpacked on the device (staged in, checked,
+        unpacked, read back): the seven w_* arrays by name, in row order, as unpack_wide_host gives
+        them; pos=True adds "pos", the exclusive prefix sum of w_var_len (n_wide + 1 entries).
+        Invalid input raises ClonosError with bad_what, bad_stream and bad_block."""
+        p = packed_wide._struct()
+        c = _lib.Columns()
+        bad = _lib.UnpackBad()
+        st = lib.clg_unpack_wide(self._h, C.byref(p), C.byref(c), None, C.byref(bad))  # the layout check and the rows
+        if st != _lib.CLG_OK:
+            raise _unpack_error(st, bad)
+        n = int(c.n_class[4])
+        arrs = {}
+        for name, dt in _COL_FIELDS[5:]:
+            arrs[name] = np.empty(n, dt)
+            setattr(c, name, _np_ptr(arrs[name]) or None)
+        c.cap_wide, c.out_kind = n, _lib.CLG_MEM_HOST
+        if pos:
+            arrs["pos"] = np.empty(n + 1, np.uint64)
+        if n == 0 and not pos:  # (every pointer is null: that would be the sizes-only call again)
+            return arrs
+        st = lib.clg_unpack_wide(self._h, C.byref(p), C.byref(c), _np_ptr(arrs["pos"]) if pos else None, C.byref(bad))
+        if st != _lib.CLG_OK:
+            raise _unpack_error(st, bad)
+        return arrs
+
+    def unpack_wide_raw(self, pin: _lib.PackedWideC, cols: _lib.Columns, pos: Optional[int], bad: _lib.UnpackBad) -> int:
+        """clg_unpack_wide over a clg_packed_wide and a clg_columns the caller set up (any kinds; the
+        seven w_* pointers and pos null: sizes only); pos is an address or None.  Returns the
+        status; the results are in cols and bad."""
+        return lib.clg_unpack_wide(self._h, C.byref(pin), C.byref(cols), pos, C.byref(bad))
+
     def unpack_columns_raw(self, pin: _lib.Packed, cols: _lib.Columns, bad: _lib.UnpackBad) -> int:
         """clg_unpack_columns over a clg_packed and a clg_columns the caller set up (any kinds; the
         five narrow pointers null: sizes only).  Returns the status; the results are in cols and bad."""
@@ -1648,12 +1732,17 @@ class Engine:
                                    C.byref(bad)))
         return out[:n_out.value].tobytes()
 
-    def encode_columns(self, cols: "DecodedColumns", per_span: bool = False):
+    def encode_columns(self, cols: "DecodedColumns", per_span: bool = False, wide: str = "host"):
         """clg_encode_columns: re-encode columns that carry their payload column, on the GPU -- the
         batch's bytes, without the log crossing the link.  The columns go up as they are (no SoA
         rows are rebuilt).  per_span=True: one bytes per span instead of the whole stream.  A
         PackedColumns goes up packed and is unpacked on the device (clg_encode_columns_packed); a bad
-        packed input raises ClonosError with bad_what, bad_stream and bad_block."""
+        packed input raises ClonosError with bad_what, bad_stream and bad_block.  wide="device"
+        (PackedColumns with wide_packed only, else ValueError): the packed wide rows go up packed as
+        well and are unpacked on the device (clg_encode_columns_packed_wide); no w_* array and no
+        var_pos is built on the host.  wide="host": they are unpacked on the host first."""
+        if _wide_route(cols, wide):
+            return _encode_packed_wide(lambda *a: lib.clg_encode_columns_packed_wide(self._h, *a), cols, per_span)
         if isinstance(cols, PackedColumns):
             pk, (rest, keep), bad = cols._struct(), _columns_in(cols), _lib.UnpackBad()
 
@@ -1672,19 +1761,28 @@ class Engine:
         and out_kind; enc.bytes null: sizes only).  Returns the status; the results are in enc."""
         return lib.clg_encode_columns(self._h, C.byref(cin), C.byref(enc))
 
-    def append_columns(self, logs, epochs: Sequence[int], cols: "DecodedColumns", statuses: bool = False):
+    def append_columns(self, logs, epochs: Sequence[int], cols: "DecodedColumns", statuses: bool = False,
+                       wide: str = "host"):
         """clg_append_columns: encode cols on the device and append span s to logs[s] (a
         ThreadCausalLog or a handle) in epochs[s], as one appendDeterminant batch each, without an
         encoded byte crossing the link.  Returns the per-span byte counts; a span that could not be
         applied raises its status after the others were applied, or, with statuses=True, nothing
-        raises for a span and (byte counts, statuses) is returned."""
+        raises for a span and (byte counts, statuses) is returned.  wide: as encode_columns'
+        (clg_append_columns_packed_wide)."""
+        device_wide = _wide_route(cols, wide)
         h = np.array([getattr(l, "handle", l) for l in logs], np.uint32)
         ep = np.ascontiguousarray(epochs, np.int64)
         ns = max(cols.n_spans, 1)
         if len(h) != ns or len(ep) != ns:
             raise ValueError(f"{len(h)} logs and {len(ep)} epochs for {ns} spans")
         nb, st = np.zeros(ns, np.uint64), np.zeros(ns, np.int32)
-        if isinstance(cols, PackedColumns):  # goes up packed, unpacked on the device
+        if device_wide:  # both packed forms go up packed
+            pk, pw, (rest, keep), bad = cols._struct(), cols.wide_packed._struct(), _rest_in(cols), _lib.UnpackBad()
+            rc = lib.clg_append_columns_packed_wide(self._h, _np_ptr(h), _np_ptr(ep), ns, C.byref(pk), C.byref(pw),
+                                                    C.byref(rest), _np_ptr(nb), _np_ptr(st), C.byref(bad))
+            if rc != _lib.CLG_OK:
+                raise _unpack_error(rc, bad)
+        elif isinstance(cols, PackedColumns):  # goes up packed, unpacked on the device
             pk, (rest, keep), bad = cols._struct(), _columns_in(cols), _lib.UnpackBad()
             rc = lib.clg_append_columns_packed(self._h, _np_ptr(h), _np_ptr(ep), ns, C.byref(pk), C.byref(rest), _np_ptr(nb),
                                                _np_ptr(st), C.byref(bad))

@@ -808,6 +808,49 @@ int clg_append_columns_packed(clg_engine* e, const uint32_t* log, const int64_t*
                               const clg_packed* narrow, const clg_columns_in* rest,
                               uint64_t* span_bytes, int32_t* status, clg_unpack_bad* bad);
 
+/* ---- packed wide rows as input ----------------------------------------------
+ * clg_unpack_wide_host on the device: the seven w_* arrays of `out` are written under cap_wide and
+ * out->out_kind, n_class[4] is filled, nothing else of `out` is touched.  pos (optional; the same
+ * memory kind, 8-byte aligned, cap_wide + 1 entries) receives the exclusive prefix sum of w_var_len
+ * as u64, pos[n_wide] the total: the payload column's pos, which the packed-wide decodes do not
+ * deliver.  Statuses and their order are clg_unpack_wide_host's exactly: the layout, then the
+ * sizes; all seven pointers and pos NULL: sizes only (no descriptor is read); CLG_E_CAPACITY with
+ * nothing written; then every block (pos % 16 == 0 included), then every value (a KIND above 3;
+ * KIND's histogram, stream 0 block 0, before the other streams' values), each kind of finding
+ * with its lowest (stream, block).  Invalid input writes nothing to the caller's arrays, whatever
+ * their kind.  Memory rules are clg_unpack_columns': device and registered input is read in place
+ * (bits 16-byte, desc 8-byte aligned, else CLG_E_INVALID_ARG), host input is staged with one copy
+ * each; device and registered outputs aligned to their element are written by the kernels, host
+ * outputs through engine scratch and one copy each.  No byte outside [0, n_wide) of an array or
+ * [0, n_wide] of pos is written.  An input without rows launches nothing.  Synchronous; takes the
+ * engine guard; the kernels' time is the stat "unpack_wide". */
+int clg_unpack_wide(clg_engine* e, const clg_packed_wide* in, clg_columns* out, uint64_t* pos, clg_unpack_bad* bad);
+
+/* clg_encode_columns / clg_append_columns with the narrow columns AND the wide rows given packed:
+ * both are unpacked into engine-owned device scratch, pos is rebuilt there, and the existing
+ * encode runs on it, so no plain column, wide row or pos exists on the host.  `rest` carries var,
+ * n_var, span_base, n_spans, n_rec and n_class[0 .. 4]; its five narrow pointers, five w_*
+ * pointers, w_idx and pos must all be NULL (CLG_E_INVALID_ARG); rest->in_kind governs only var.
+ * The checks, in order: narrow's layout and totals (as clg_encode_columns_packed); wide's layout
+ * (LAYOUT, CLG_UNPACK_WIDE_STREAM + stream); wide->n_val[KIND] != rest->n_class[4] (LAYOUT, stream
+ * CLG_UNPACK_WIDE_STREAM, block 0); narrow's block and value findings; wide's, with stream
+ * CLG_UNPACK_WIDE_STREAM + c; the cross rule: row k names a wide record of its own kind,
+ * tag[w_idx[k]] - 3 == KIND[k] (the lowest offending row: VALUE, stream CLG_UNPACK_WIDE_STREAM +
+ * CLG_WPACK_IDX, block k / CLG_PACK_BLOCK); then the encode's own checks, results and per-span
+ * statuses, which are clg_encode_columns' / clg_append_columns' exactly (the unpacked w_idx is
+ * handed to the encode).  A bad packed input fails the whole call with CLG_E_INVALID_ARG and `bad`
+ * filled before any byte of `out` is written or any log changes (out->bad_what stays 0; every
+ * status[s] stays CLG_OK).  One engine guard covers the whole call.  The _host call is the same on
+ * the CPU (no engine, no GPU; every array host memory). */
+#define CLG_UNPACK_WIDE_STREAM 32   /* in the combined calls, a finding in `wide` reports stream 32 + its stream */
+int clg_encode_columns_packed_wide(clg_engine* e, const clg_packed* narrow, const clg_packed_wide* wide,
+                                   const clg_columns_in* rest, clg_encoded* out, clg_unpack_bad* bad);
+int clg_append_columns_packed_wide(clg_engine* e, const uint32_t* log, const int64_t* epoch, uint32_t n_spans,
+                                   const clg_packed* narrow, const clg_packed_wide* wide, const clg_columns_in* rest,
+                                   uint64_t* span_bytes, int32_t* status, clg_unpack_bad* bad);
+int clg_encode_columns_packed_wide_host(const clg_packed* narrow, const clg_packed_wide* wide,
+                                        const clg_columns_in* rest, clg_encoded* out, clg_unpack_bad* bad);
+
 /* ---- DeterminantResponseEvent (DeterminantResponseEvent.java:36-148) ---------------------
  * The event's map CausalLogID -> log bytes is held as an entry array in the iteration
  * order of the reference's java.util.HashMap (JDK 8: 2^k buckets from 16, load factor

@@ -553,6 +553,71 @@ JNIEXPORT jint JNICALL FN(nAppendColumnsPacked)(JNIEnv* env, jclass cls, jlong e
   return s;
 }
 
+/* clg_append_columns_packed_wide: nAppendColumnsPacked with the wide rows given packed as well
+ * (wdesc, wbits: direct buffers; w_n_val: 26 longs; w_blk_base: 27 longs): both forms are unpacked
+ * on the device, pos is rebuilt there, and no plain column, wide row or pos is handed over; var
+ * holds n_var payload bytes.  bad =
+ * {bad_what, bad_stream, bad_block}; a finding in the wide rows reports CLG_UNPACK_WIDE_STREAM + its
+ * stream. */
+JNIEXPORT jint JNICALL FN(nAppendColumnsPackedWide)(JNIEnv* env, jclass cls, jlong e, jintArray logs, jlongArray epochs,
+                                                    jobject desc, jobject bits, jlongArray n_val, jlongArray blk_base,
+                                                    jlong n_bits, jobject wdesc, jobject wbits, jlongArray w_n_val,
+                                                    jlongArray w_blk_base, jlong w_n_bits, jobject var, jlong n_var,
+                                                    jlongArray span_base, jlongArray span_bytes, jintArray status,
+                                                    jlongArray bad) {
+  (void)cls;
+  const jsize n = (*env)->GetArrayLength(env, logs);
+  const jsize n_spans = (*env)->GetArrayLength(env, span_base) / CLG_COL_CLASSES - 1;
+  jint* lg = (*env)->GetIntArrayElements(env, logs, NULL);
+  jlong* ep = (*env)->GetLongArrayElements(env, epochs, NULL);
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  jlong* nb = (*env)->GetLongArrayElements(env, span_bytes, NULL);
+  jint* st = (*env)->GetIntArrayElements(env, status, NULL);
+  clg_packed k;
+  memset(&k, 0, sizeof k);
+  k.desc = (clg_pack_block*)addr(env, desc, 0);
+  k.bits = addr(env, bits, 0);
+  k.cap_desc = cap(env, desc) / sizeof(clg_pack_block);
+  k.cap_bits = cap(env, bits);
+  k.out_kind = CLG_MEM_HOST;
+  jlong* nv = (*env)->GetLongArrayElements(env, n_val, NULL);
+  jlong* bb = (*env)->GetLongArrayElements(env, blk_base, NULL);
+  for (int i = 0; i < CLG_PACK_STREAMS; ++i) k.n_val[i] = (uint64_t)nv[i];
+  for (int i = 0; i <= CLG_PACK_STREAMS; ++i) k.blk_base[i] = (uint64_t)bb[i];
+  k.n_bits = (uint64_t)n_bits;
+  clg_packed_wide w;
+  memset(&w, 0, sizeof w);
+  w.desc = (clg_pack_block*)addr(env, wdesc, 0);
+  w.bits = addr(env, wbits, 0);
+  w.cap_desc = cap(env, wdesc) / sizeof(clg_pack_block);
+  w.cap_bits = cap(env, wbits);
+  w.out_kind = CLG_MEM_HOST;
+  jlong* wnv = (*env)->GetLongArrayElements(env, w_n_val, NULL);
+  jlong* wbb = (*env)->GetLongArrayElements(env, w_blk_base, NULL);
+  for (int i = 0; i < CLG_WPACK_STREAMS; ++i) w.n_val[i] = (uint64_t)wnv[i];
+  for (int i = 0; i <= CLG_WPACK_STREAMS; ++i) w.blk_base[i] = (uint64_t)wbb[i];
+  w.n_bits = (uint64_t)w_n_bits;
+  clg_columns_in in;
+  columns_in_of(env, &in, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, var, NULL, base, n_spans, nv[0]);
+  in.n_var = (uint64_t)n_var;  /* (no pos to read it from) */
+  clg_unpack_bad ub;
+  memset(&ub, 0, sizeof ub);
+  int s = clg_append_columns_packed_wide(ENG(e), (const uint32_t*)lg, (const int64_t*)ep, (uint32_t)n, &k, &w, &in,
+                                         (uint64_t*)nb, (int32_t*)st, &ub);
+  jlong r[3] = {(jlong)ub.what, (jlong)ub.stream, (jlong)ub.block};
+  (*env)->SetLongArrayRegion(env, bad, 0, 3, r);
+  (*env)->ReleaseLongArrayElements(env, w_blk_base, wbb, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, w_n_val, wnv, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, blk_base, bb, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, n_val, nv, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, status, st, 0);
+  (*env)->ReleaseLongArrayElements(env, span_bytes, nb, 0);
+  (*env)->ReleaseLongArrayElements(env, span_base, base, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, epochs, ep, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, logs, lg, JNI_ABORT);
+  return s;
+}
+
 /* clg_decode_logs_async: the decode is queued; ctx[0] receives a handle that nDecodeWait
  * completes and frees (the output ByteBuffers must stay reachable until then). */
 typedef struct {

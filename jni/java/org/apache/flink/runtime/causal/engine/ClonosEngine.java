@@ -325,9 +325,43 @@ public final class ClonosEngine implements AutoCloseable {
 		return spanBytes;
 	}
 
+	/**
+	 * appendColumnsPacked with the wide rows packed as well (clg_append_columns_packed_wide): what
+	 * decodeLogsColumnsPackedWide delivered goes up as it is -- both packed forms and the payload bytes --
+	 * and is checked and unpacked on the device, where pos is rebuilt; no plain column, wide row or pos
+	 * exists on this side.  cols is wide.narrow.  A finding throws as appendColumnsPacked's does; one in
+	 * the wide rows reports bad_stream 32 + its stream, and a row whose w_idx names no wide record of
+	 * its kind is {VALUE, 33, row / 1024}.
+	 */
+	public long[] appendColumnsPackedWide(int[] logs, long[] epochs, EnginePackedColumns cols, EnginePackedWide wide) {
+		if (!wide.hasPayloads()) {
+			throw new IllegalStateException("decoded without payloads");
+		}
+		if (cols != wide.narrow) {
+			throw new IllegalArgumentException("cols must be wide.narrow");
+		}
+		final long[] spanBytes = new long[logs.length];
+		final int[] status = new int[logs.length];
+		final long[] bad = new long[3];
+		final int st = nAppendColumnsPackedWide(handle, logs, epochs, cols.desc, cols.bits, cols.nVal, cols.blkBase, cols.nBits,
+			wide.desc, wide.bits, wide.nVal, wide.blkBase, wide.nBits, wide.var, wide.nVar, cols.spanBase, spanBytes, status, bad);
+		lastUnpackBad = bad;
+		if (st != CLG_OK && bad[0] != 0) {
+			throw new IllegalArgumentException("packed columns: bad_what " + bad[0] + ", bad_stream " + bad[1]
+				+ ", bad_block " + bad[2] + ": " + nLastError());
+		}
+		check(st);
+		for (int s = 0; s < logs.length; s++) {
+			if (status[s] != CLG_OK) {
+				spanBytes[s] = status[s];
+			}
+		}
+		return spanBytes;
+	}
+
 	private long[] lastUnpackBad = new long[3];
 
-	/** {bad_what, bad_stream, bad_block} of the last appendColumnsPacked call (all 0, 0, ~0 or zero when clean). */
+	/** {bad_what, bad_stream, bad_block} of the last appendColumnsPacked / appendColumnsPackedWide call (all 0, 0, ~0 or zero when clean). */
 	public long[] lastUnpackBad() {
 		return lastUnpackBad.clone();
 	}
@@ -509,6 +543,10 @@ public final class ClonosEngine implements AutoCloseable {
 		long[] nVal, long[] blkBase, long nBits, ByteBuffer wIdx, ByteBuffer wRc, ByteBuffer wV1, ByteBuffer wVarLen,
 		ByteBuffer wSub, ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos, long[] spanBase, long[] spanBytes,
 		int[] status, long[] bad);
+	/** clg_append_columns_packed_wide: both packed forms and the payload bytes; no rows and no pos. */
+	static native int nAppendColumnsPackedWide(long engine, int[] logs, long[] epochs, ByteBuffer desc, ByteBuffer bits,
+		long[] nVal, long[] blkBase, long nBits, ByteBuffer wDesc, ByteBuffer wBits, long[] wNVal, long[] wBlkBase,
+		long wNBits, ByteBuffer var, long nVar, long[] spanBase, long[] spanBytes, int[] status, long[] bad);
 
 	static native int nAppendColumns(long engine, int[] logs, long[] epochs, ByteBuffer tag, ByteBuffer order,
 									 ByteBuffer timestamp, ByteBuffer rng, ByteBuffer bufferBuilt, ByteBuffer wIdx,

@@ -38,6 +38,8 @@ public final class EnginePackedWide {
 	final long[] nVal = new long[STREAMS];
 	final long[] blkBase = new long[STREAMS + 1];
 	long nBits;
+	/** The payload bytes in var (0 without payloads). */
+	long nVar;
 
 	/** Direct buffers of exactly the sizes a sizes-only call reported. */
 	EnginePackedWide(long[] sizes, int nSpans, boolean withPayloads) {
@@ -61,6 +63,7 @@ public final class EnginePackedWide {
 		System.arraycopy(res, R_NVAL, nVal, 0, STREAMS);
 		System.arraycopy(res, R_BLKBASE, blkBase, 0, STREAMS + 1);
 		this.nBits = res[R_NBITS];
+		this.nVar = var != null ? res[11] : 0;
 	}
 
 	public static int stream(int kind, int field) {
