@@ -28,6 +28,7 @@
 #include "../../include/clonos_engine.h"
 #include "columns.h"
 #include "kernels.h"
+#include "wave_dev.h"
 
 namespace clg {
 
@@ -36,25 +37,6 @@ namespace {
 constexpr uint32_t kColWaves = kColThreads / 64;
 constexpr uint32_t kColChunks = kColPerThread * kColWaves;  // a tile's (round, wave) chunks, in record order
 static_assert(kColChunks == 64, "the chunk counts are scanned by one wave");
-
-__device__ __forceinline__ uint32_t col_lane_rank(uint64_t m) {  // set bits of m below this lane
-  return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
-}
-
-__device__ __forceinline__ uint32_t col_wave_sum(uint32_t x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o, 64);
-  return x;
-}
-
-__device__ __forceinline__ uint32_t col_wave_incl(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
 
 // The class counts of records i0 .. i0 + 15 (those below n) in 8-bit fields, at most 16 each:
 // field c < 5 counts class c, field 5 the tags above 7.
@@ -85,7 +67,7 @@ __global__ __launch_bounds__(kColThreads) void k_col_count(const uint8_t* __rest
   const uint64_t acc = col_count16(tag, i0, n);
 #pragma unroll
   for (uint32_t c = 0; c < 6; ++c) {
-    const uint32_t s = col_wave_sum(uint32_t(acc >> (8u * c)) & 0xFFu);
+    const uint32_t s = wave_sum(uint32_t(acc >> (8u * c)) & 0xFFu);
     if (lane == 0) ws[w][c] = s;
   }
   __syncthreads();
@@ -99,57 +81,24 @@ __global__ __launch_bounds__(kColThreads) void k_col_count(const uint8_t* __rest
 
 __global__ __launch_bounds__(kColScanThreads) void k_col_scan(const uint32_t* __restrict__ counts, uint32_t n_tiles,
                                                              uint64_t* __restrict__ base, ColRes* __restrict__ res) {
-  constexpr uint32_t kW = kColScanThreads / 64;
-  __shared__ uint32_t ws[kW][kColClasses];
-  __shared__ uint32_t wtot[kColClasses];
-  __shared__ uint32_t wbad[kW];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  uint64_t carry[kColClasses] = {0, 0, 0, 0, 0};
+  // (a round holds at most kColScanThreads * kColTile records: its sums fit 32 bits)
+  static_assert(uint64_t(kColScanThreads) * kColTile <= UINT32_MAX, "a round's class counts are summed in 32 bits");
   uint32_t bad = ~0u;  // this thread's first tile with a tag above 7
-  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kColScanThreads) {
-    const uint32_t t = t0 + tid;
-    uint32_t c[kColClasses], inc[kColClasses];
+  const auto tot = tile_scan<kColScanThreads, kColClasses, uint32_t>(
+      n_tiles,
+      [&](uint32_t t, uint32_t c[kColClasses]) {
+        const uint4 lo = *reinterpret_cast<const uint4*>(counts + size_t(t) * kColCountWords);
+        const uint2 hi = *reinterpret_cast<const uint2*>(counts + size_t(t) * kColCountWords + 4);
+        c[0] = lo.x, c[1] = lo.y, c[2] = lo.z, c[3] = lo.w, c[4] = hi.x;
+        if (hi.y && t < bad) bad = t;
+      },
+      [&](uint32_t t, const uint64_t before[kColClasses]) {
 #pragma unroll
-    for (uint32_t k = 0; k < kColClasses; ++k) c[k] = 0;
-    if (t < n_tiles) {
-      const uint4 lo = *reinterpret_cast<const uint4*>(counts + size_t(t) * kColCountWords);
-      const uint2 hi = *reinterpret_cast<const uint2*>(counts + size_t(t) * kColCountWords + 4);
-      c[0] = lo.x, c[1] = lo.y, c[2] = lo.z, c[3] = lo.w, c[4] = hi.x;
-      if (hi.y && t < bad) bad = t;
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < kColClasses; ++k) {
-      inc[k] = col_wave_incl(c[k], lane);
-      if (lane == 63) ws[w][k] = inc[k];
-    }
-    __syncthreads();
-    if (tid < 64) {  // the waves' totals -> their exclusive prefix, and the round's total
-#pragma unroll
-      for (uint32_t k = 0; k < kColClasses; ++k) {
-        const uint32_t x = lane < kW ? ws[lane][k] : 0u;
-        const uint32_t s = col_wave_incl(x, lane);
-        if (lane < kW) ws[lane][k] = s - x;
-        if (lane == kW - 1) wtot[k] = s;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < kColClasses; ++k) {
-      if (t < n_tiles) base[size_t(t) * kColClasses + k] = carry[k] + ws[w][k] + (inc[k] - c[k]);
-      carry[k] += wtot[k];  // (a round holds at most kColScanThreads * kColTile records: 32 bits)
-    }
-    __syncthreads();  // (ws is written again in the next round)
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint32_t x = (uint32_t)__shfl_xor((int)bad, o, 64);
-    bad = x < bad ? x : bad;
-  }
-  if (lane == 0) wbad[w] = bad;
-  __syncthreads();
-  if (tid == 0) {
-    for (uint32_t j = 1; j < kW; ++j) bad = wbad[j] < bad ? wbad[j] : bad;
-    for (uint32_t k = 0; k < kColClasses; ++k) res->total[k] = carry[k];
+        for (uint32_t k = 0; k < kColClasses; ++k) base[size_t(t) * kColClasses + k] = before[k];
+      });
+  bad = block_min<kColScanThreads>(bad);
+  if (threadIdx.x == 0) {
+    for (uint32_t k = 0; k < kColClasses; ++k) res->total[k] = tot.v[k];
     res->bad_tile = bad == ~0u ? kColNoTile : uint64_t(bad);
   }
 }
@@ -191,7 +140,7 @@ __device__ __forceinline__ void col_write_tile(const uint8_t* __restrict__ tag, 
 #pragma unroll
     for (uint32_t c = 0; c < 4; ++c) {
       const uint32_t x = cnt[tid][c];
-      cnt[tid][c] = col_wave_incl(x, lane) - x;
+      cnt[tid][c] = wave_incl(x, lane) - x;
     }
   }
   __syncthreads();
@@ -201,7 +150,7 @@ __device__ __forceinline__ void col_write_tile(const uint8_t* __restrict__ tag, 
 #pragma unroll
     for (uint32_t c = 0; c < 4; ++c) {
       const uint64_t m = __ballot(cls[k] == c);
-      if (cls[k] == c) rank = col_lane_rank(m);
+      if (cls[k] == c) rank = lane_rank(m);
     }
     const uint32_t c = cls[k];
     if (c < 4) {
@@ -251,7 +200,7 @@ __global__ __launch_bounds__(256) void k_col_span_base(const uint8_t* __restrict
   }
 #pragma unroll
   for (uint32_t k = 0; k < kColClasses; ++k) {
-    const uint32_t t = col_wave_sum(c[k]);
+    const uint32_t t = wave_sum(c[k]);
     if (lane == k) span_base[uint64_t(s) * kColClasses + k] = b[k] + t;
   }
 }
@@ -272,11 +221,7 @@ __global__ __launch_bounds__(64) void k_col_find_bad(const uint8_t* __restrict__
   uint64_t best = ~0ull;
   for (uint64_t i = t0 + lane; i < t1; i += 64)
     if (col_class(tag[i]) == kColBad && i < best) best = i;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t x = (uint64_t)__shfl_xor((unsigned long long)best, o, 64);
-    best = x < best ? x : best;
-  }
+  best = wave_min(best);
   if (lane == 0) {
     res->bad_index = best;
     res->bad_tag = best != ~0ull ? tag[best] : 0;
@@ -335,7 +280,7 @@ __global__ __launch_bounds__(kColScanThreads) void k_col_small(const ColSmallIn 
         }
 #pragma unroll
     for (uint32_t c = 0; c < 6; ++c) {
-      const uint32_t s = col_wave_sum(uint32_t(acc >> (8u * c)) & 0xFFu);
+      const uint32_t s = wave_sum(uint32_t(acc >> (8u * c)) & 0xFFu);
       if (lane == 0) ws[w][c] = s;
     }
     __syncthreads();
@@ -347,11 +292,7 @@ __global__ __launch_bounds__(kColScanThreads) void k_col_small(const ColSmallIn 
     }
     __syncthreads();  // (ws is written again in the next round)
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t x = (uint64_t)__shfl_xor((unsigned long long)bad, o, 64);
-    bad = x < bad ? x : bad;
-  }
+  bad = wave_min(bad);
   if (lane == 0) wbad[w] = bad;
   if (tid < kColClasses) {  // (the tiles' counts were written before the loop's last barrier)
     uint32_t run = 0;
@@ -385,7 +326,7 @@ __global__ __launch_bounds__(kColScanThreads) void k_col_small(const ColSmallIn 
       }
 #pragma unroll
       for (uint32_t k = 0; k < kColClasses; ++k) {
-        const uint32_t x = col_wave_sum(c[k]);
+        const uint32_t x = wave_sum(c[k]);
         if (lane == k) span_base[uint64_t(s) * kColClasses + k] = uint64_t(b[k]) + x;
       }
     }

@@ -37,6 +37,7 @@
 #include "copy_range.h"
 #include "encode_columns.h"
 #include "kernels.h"
+#include "wave_dev.h"
 
 namespace clg {
 
@@ -47,44 +48,6 @@ constexpr uint32_t kEcolChunks = kEcolPer * kEcolWaves;  // a tile's (round, wav
 constexpr uint32_t kEcolScanThreads = 1024;
 static_assert(kEcolChunks == 64, "the chunk counts are scanned by one wave");
 static_assert(kEcolLds / 16 % kEcolTileThreads == 0, "the threads clear the chunk flags evenly");
-
-__device__ __forceinline__ uint32_t ecol_lane_rank(uint64_t m) {  // set bits of m below this lane
-  return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
-}
-__device__ __forceinline__ uint32_t ecol_wave_sum(uint32_t x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o, 64);
-  return x;
-}
-__device__ __forceinline__ uint64_t ecol_wave_sum64(uint64_t x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += (uint64_t)__shfl_xor((unsigned long long)x, o, 64);
-  return x;
-}
-__device__ __forceinline__ uint64_t ecol_wave_min64(uint64_t x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t y = (uint64_t)__shfl_xor((unsigned long long)x, o, 64);
-    x = y < x ? y : x;
-  }
-  return x;
-}
-__device__ __forceinline__ uint32_t ecol_wave_incl(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-__device__ __forceinline__ uint64_t ecol_wave_incl64(uint64_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
 
 // A tile's tags (record k * kEcolTileThreads + tid of the tile for k < kEcolPer; 0xFF at and
 // past n) and, in cnt, the exclusive per-class count of every (round, wave) chunk in record
@@ -111,7 +74,7 @@ __device__ __forceinline__ void ecol_tile_tags(const uint8_t* __restrict__ tag, 
 #pragma unroll
     for (uint32_t c = 0; c < kColClasses; ++c) {
       const uint32_t x = cnt[tid][c];
-      cnt[tid][c] = ecol_wave_incl(x, lane) - x;
+      cnt[tid][c] = wave_incl(x, lane) - x;
     }
   }
   __syncthreads();
@@ -123,7 +86,7 @@ __device__ __forceinline__ uint32_t ecol_chunk_rank(uint32_t cls) {
 #pragma unroll
   for (uint32_t c = 0; c < kColClasses; ++c) {
     const uint64_t m = __ballot(cls == c);
-    if (cls == c) rank = ecol_lane_rank(m);
+    if (cls == c) rank = lane_rank(m);
   }
   return rank;
 }
@@ -182,8 +145,8 @@ __global__ __launch_bounds__(kEcolTileThreads) void k_ecol_bytes(const EcolIn in
       acc += ecol_head_len(t, 0);  // (0 for a tag above 7 and past n)
     }
   }
-  acc = ecol_wave_sum64(acc);
-  b = ecol_wave_min64(b);
+  acc = wave_sum(acc);
+  b = wave_min(b);
   if (lane == 0) ws[w] = acc, wb[w] = b;
   __syncthreads();
   if (tid == 0) {
@@ -197,39 +160,18 @@ __global__ __launch_bounds__(kEcolTileThreads) void k_ecol_bytes(const EcolIn in
 __global__ __launch_bounds__(kEcolScanThreads) void k_ecol_scan64(const uint64_t* __restrict__ sum,
                                                                  const uint64_t* __restrict__ bad, uint32_t n_tiles,
                                                                  uint64_t* __restrict__ bbase, EcolRes* __restrict__ res) {
-  constexpr uint32_t kW = kEcolScanThreads / 64;
-  __shared__ uint64_t ws[kW], wb[kW];
-  __shared__ uint64_t wtot;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  uint64_t carry = 0, b = kEcolNone;
-  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kEcolScanThreads) {
-    const uint32_t t = t0 + tid;
-    uint64_t c = 0;
-    if (t < n_tiles) {
-      c = sum[t];
-      const uint64_t x = bad[t];
-      b = x < b ? x : b;
-    }
-    const uint64_t inc = ecol_wave_incl64(c, lane);
-    if (lane == 63) ws[w] = inc;
-    __syncthreads();
-    if (tid < 64) {  // the waves' totals -> their exclusive prefix, and the round's total
-      const uint64_t x = lane < kW ? ws[lane] : 0;
-      const uint64_t s = ecol_wave_incl64(x, lane);
-      if (lane < kW) ws[lane] = s - x;
-      if (lane == kW - 1) wtot = s;
-    }
-    __syncthreads();
-    if (t < n_tiles) bbase[t] = carry + ws[w] + (inc - c);
-    carry += wtot;
-    __syncthreads();  // (ws is written again in the next round)
-  }
-  b = ecol_wave_min64(b);
-  if (lane == 0) wb[w] = b;
-  __syncthreads();
-  if (tid == 0) {
-    for (uint32_t j = 1; j < kW; ++j) b = wb[j] < b ? wb[j] : b;
-    res->n_bytes = carry;
+  uint64_t b = kEcolNone;  // this thread's lowest bad row
+  const auto tot = tile_scan<kEcolScanThreads, 1, uint64_t>(
+      n_tiles,
+      [&](uint32_t t, uint64_t c[1]) {
+        c[0] = sum[t];
+        const uint64_t x = bad[t];
+        b = x < b ? x : b;
+      },
+      [&](uint32_t t, const uint64_t before[1]) { bbase[t] = before[0]; });
+  b = block_min<kEcolScanThreads>(b);
+  if (threadIdx.x == 0) {
+    res->n_bytes = tot.v[0];
     res->bad_row = b;
   }
 }
@@ -264,7 +206,7 @@ __global__ __launch_bounds__(256) void k_ecol_span(const EcolIn in, const uint64
       for (uint32_t q = 0; q < kColClasses; ++q) c[q] += cls == q;
       const uint64_t m = __ballot(cls == kColWide);
       if (cls == kColWide) {
-        const EcolRow row = ecol_row(in, t, run4 + ecol_lane_rank(m));
+        const EcolRow row = ecol_row(in, t, run4 + lane_rank(m));
         bytes += ecol_len(t, row.sub, row.vl);
       } else {
         bytes += ecol_head_len(t, 0);
@@ -272,10 +214,10 @@ __global__ __launch_bounds__(256) void k_ecol_span(const EcolIn in, const uint64
       run4 += (uint32_t)__popcll(m);
     }
   }
-  bytes = ecol_wave_sum64(bytes);
+  bytes = wave_sum(bytes);
   bool ok = true;
 #pragma unroll
-  for (uint32_t k = 0; k < kColClasses; ++k) ok = ok && b[k] + ecol_wave_sum(c[k]) == want[k];
+  for (uint32_t k = 0; k < kColClasses; ++k) ok = ok && b[k] + wave_sum(c[k]) == want[k];
   if (lane == 0) {
     span_out[uint64_t(s) * 2] = at + bytes;
     span_out[uint64_t(s) * 2 + 1] = ok ? 0 : 1;
@@ -317,13 +259,13 @@ __global__ __launch_bounds__(kEcolTileThreads) void k_ecol_write(const EcolIn in
       const EcolRow r = ecol_row(in, t, tb[kColWide] + l.cnt[k * kEcolWaves + w][kColWide] + rank);
       len = ecol_len(t, r.sub, r.vl);
     }
-    const uint64_t inc = ecol_wave_incl64(len, lane);
+    const uint64_t inc = wave_incl(len, lane);
     excl[k] = inc - len;
     if (lane == 63) l.clen[k * kEcolWaves + w] = inc;
   }
   __syncthreads();
   if (tid < kEcolChunks) {
-    const uint64_t x = l.clen[tid], s = ecol_wave_incl64(x, lane);
+    const uint64_t x = l.clen[tid], s = wave_incl(x, lane);
     l.clen[tid] = s - x;
     if (tid == kEcolChunks - 1) l.total = s;
   }

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_scan_sums(const clg_pack_
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const uint64_t b = uint64_t(blockIdx.x) * kPackScanGroup + tid;
   const uint32_t x = b < n_blocks ? uint32_t(desc[b].pos) : 0u;  // (at most 8 KiB a block)
-  const uint32_t s = pack_wave_incl(x, lane);
+  const uint32_t s = wave_incl(x, lane);
   if (lane == 63) ws[w] = s;
   __syncthreads();
   if (tid == 0) {
@@ -86,18 +86,10 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_scan_sums(const clg_pack_
 // group a thread and round: no look-back.
 __global__ __launch_bounds__(kPackTopThreads) void k_pack_scan_top(uint64_t* __restrict__ gsum, uint32_t n_groups,
                                                                   PackRes* __restrict__ res) {
-  __shared__ uint64_t ws[kPackTopThreads / 64];
-  __shared__ uint64_t wtot;
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  uint64_t carry = 0;
-  for (uint32_t g0 = 0; g0 < n_groups; g0 += kPackTopThreads) {
-    const uint32_t g = g0 + tid;
-    const uint64_t before = pack_scan_round(g < n_groups ? gsum[g] : 0, lane, ws, &wtot);
-    if (g < n_groups) gsum[g] = carry + before;
-    carry += wtot;
-    __syncthreads();  // (ws is written again in the next round)
-  }
-  if (tid == 0) res->n_bits = carry;
+  const auto tot = tile_scan<kPackTopThreads, 1, uint64_t>(
+      n_groups, [&](uint32_t g, uint64_t c[1]) { c[0] = gsum[g]; },
+      [&](uint32_t g, const uint64_t before[1]) { gsum[g] = before[0]; });
+  if (threadIdx.x == 0) res->n_bits = tot.v[0];
 }
 
 __global__ __launch_bounds__(kPackThreads) void k_pack_scan_apply(clg_pack_block* __restrict__ desc, uint32_t n_blocks,
@@ -106,7 +98,7 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_scan_apply(clg_pack_block
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const uint64_t b = uint64_t(blockIdx.x) * kPackScanGroup + tid;
   const uint32_t x = b < n_blocks ? uint32_t(desc[b].pos) : 0u;
-  const uint32_t inc = pack_wave_incl(x, lane);
+  const uint32_t inc = wave_incl(x, lane);
   if (lane == 63) ws[w] = inc;
   __syncthreads();
   uint32_t before = 0;

@@ -1,13 +1,14 @@
-// pack_dev.h -- what the kernels of pack.hip, pack_wide.hip and unpack.hip share on the device:
-// the workgroup's shape, the wave's signed minimum / maximum by DPP, the wave scans, the round of a
-// one-workgroup scan, and the block codec's measure, write and decode, instantiated on (element,
-// scheme).
+// pack_dev.h -- what the kernels of pack.hip, pack_wide.hip, unpack.hip and unpack_wide.hip share
+// on the device: the workgroup's shape, the wave's signed minimum / maximum by DPP, and the block
+// codec's measure, write and decode, instantiated on (element, scheme).  The wave scans and the
+// one-workgroup scan are wave_dev.h's.
 // Device code only, file-local in each unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "pack.h"
+#include "wave_dev.h"
 
 namespace clg {
 namespace {
@@ -44,43 +45,6 @@ __device__ __forceinline__ int64_t pack_max(int64_t a, int64_t b) { return b > a
   v = op(v, pack_dpp<0x142>(v));          \
   v = op(v, pack_dpp<0x143>(v));          \
   v = pack_lane63(v)
-
-__device__ __forceinline__ uint32_t pack_wave_incl(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-__device__ __forceinline__ uint64_t pack_wave_incl64(uint64_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
-// One round of a one-workgroup scan over kPackTopThreads values, a value a thread: x's exclusive
-// prefix within the round; *wtot then holds the round's total.  The wave scan, then the waves
-// through LDS (ws: a word a wave).  The caller ends the round with a __syncthreads() before the
-// next one writes ws and *wtot again.
-__device__ __forceinline__ uint64_t pack_scan_round(uint64_t x, uint32_t lane, uint64_t* ws, uint64_t* wtot) {
-  constexpr uint32_t kW = kPackTopThreads / 64;
-  const uint32_t tid = threadIdx.x, w = tid >> 6;
-  const uint64_t inc = pack_wave_incl64(x, lane);
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  if (tid < 64) {
-    const uint64_t y = lane < kW ? ws[lane] : 0;
-    const uint64_t s = pack_wave_incl64(y, lane);
-    if (lane < kW) ws[lane] = s - y;
-    if (lane == kW - 1) *wtot = s;
-  }
-  __syncthreads();
-  return ws[w] + (inc - x);
-}
 
 // ---- the block codec on the device: a workgroup of kPackThreads per block ----------------------
 
@@ -243,7 +207,7 @@ __device__ __forceinline__ bool unpack_values_in(const clg_pack_block& d, const 
       uint64_t r = 0;
       if (i == 0) r = uint64_t(d.first);
       else if (i < d.count) r = unpack_resid(words, w, i - 1) + uint64_t(d.ref);
-      const uint64_t x = carry + pack_wave_incl64(r, lane);
+      const uint64_t x = carry + wave_incl(r, lane);
       ok = ok && (i >= d.count || (int64_t(x) >= lo && int64_t(x) <= hi));
       carry = uint64_t(pack_lane63(int64_t(x)));
     }
@@ -320,7 +284,7 @@ __device__ __forceinline__ void unpack_block_values(const clg_pack_block d, cons
   }
   if (kDelta) {
     v[1] += v[0], v[2] += v[1], v[3] += v[2];
-    const uint64_t incl = pack_wave_incl64(v[3], lane);
+    const uint64_t incl = wave_incl(v[3], lane);
     if (lane == 63) s_ws[wv] = incl;
     __syncthreads();
     uint64_t before = incl - v[3];

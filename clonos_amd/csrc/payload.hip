@@ -30,6 +30,7 @@
 #include "copy_range.h"
 #include "kernels.h"
 #include "payload.h"
+#include "wave_dev.h"
 
 namespace clg {
 
@@ -38,28 +39,6 @@ namespace {
 constexpr uint32_t kPayWaves = kPayThreads / 64;
 static_assert(kPayPerThread == 4, "a thread's offsets and lengths are one 16-byte load each");
 static_assert(kPayTile <= 65536, "a tile's long rows are listed as u16");
-
-__device__ __forceinline__ uint64_t pay_wave_sum(uint64_t x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += (uint64_t)__shfl_xor((unsigned long long)x, o, 64);
-  return x;
-}
-__device__ __forceinline__ uint64_t pay_wave_min(uint64_t x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t y = (uint64_t)__shfl_xor((unsigned long long)x, o, 64);
-    x = y < x ? y : x;
-  }
-  return x;
-}
-__device__ __forceinline__ uint64_t pay_wave_incl(uint64_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
 
 // Rows k0 .. k0 + 3 of a[] (n entries): zero at and past n.
 __device__ __forceinline__ void pay_load4(const uint32_t* __restrict__ a, uint64_t k0, uint64_t n, uint32_t v[4]) {
@@ -103,7 +82,7 @@ __device__ __forceinline__ void pay_rows(const PayIn& in, uint64_t k0, const uin
 // The bytes before this thread's rows inside the tile (exclusive scan of the threads' sums).
 __device__ __forceinline__ uint64_t pay_tile_excl(uint64_t tsum, uint32_t tid, uint64_t* ws) {
   const uint32_t lane = tid & 63, w = tid >> 6;
-  const uint64_t inc = pay_wave_incl(tsum, lane);
+  const uint64_t inc = wave_incl(tsum, lane);
   if (lane == 63) ws[w] = inc;
   __syncthreads();
   uint64_t before = 0;
@@ -170,8 +149,8 @@ __global__ __launch_bounds__(kPayThreads) void k_pay_size(const PayIn in, uint64
     if (pay_row_ok(r.off[j], r.len[j], in.spans[r.span[j]].len)) acc += r.len[j];
     else if (b == kPayNoRow) b = k0 + j;
   }
-  acc = pay_wave_sum(acc);
-  b = pay_wave_min(b);
+  acc = wave_sum(acc);
+  b = wave_min(b);
   if (lane == 0) ws[w] = acc, wb[w] = b;
   __syncthreads();
   if (tid == 0) {
@@ -184,39 +163,18 @@ __global__ __launch_bounds__(kPayThreads) void k_pay_size(const PayIn in, uint64
 __global__ __launch_bounds__(kPayScanThreads) void k_pay_scan(const uint64_t* __restrict__ sum,
                                                              const uint64_t* __restrict__ bad, uint32_t n_tiles,
                                                              uint64_t* __restrict__ base, PayRes* __restrict__ res) {
-  constexpr uint32_t kW = kPayScanThreads / 64;
-  __shared__ uint64_t ws[kW], wb[kW];
-  __shared__ uint64_t wtot;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  uint64_t carry = 0, b = kPayNoRow;
-  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kPayScanThreads) {
-    const uint32_t t = t0 + tid;
-    uint64_t c = 0;
-    if (t < n_tiles) {
-      c = sum[t];
-      const uint64_t x = bad[t];
-      b = x < b ? x : b;
-    }
-    const uint64_t inc = pay_wave_incl(c, lane);
-    if (lane == 63) ws[w] = inc;
-    __syncthreads();
-    if (tid < 64) {  // the waves' totals -> their exclusive prefix, and the round's total
-      const uint64_t x = lane < kW ? ws[lane] : 0;
-      const uint64_t s = pay_wave_incl(x, lane);
-      if (lane < kW) ws[lane] = s - x;
-      if (lane == kW - 1) wtot = s;
-    }
-    __syncthreads();
-    if (t < n_tiles) base[t] = carry + ws[w] + (inc - c);
-    carry += wtot;
-    __syncthreads();  // (ws is written again in the next round)
-  }
-  b = pay_wave_min(b);
-  if (lane == 0) wb[w] = b;
-  __syncthreads();
-  if (tid == 0) {
-    for (uint32_t j = 1; j < kW; ++j) b = wb[j] < b ? wb[j] : b;
-    res->n_var = carry;
+  uint64_t b = kPayNoRow;  // this thread's lowest bad row
+  const auto tot = tile_scan<kPayScanThreads, 1, uint64_t>(
+      n_tiles,
+      [&](uint32_t t, uint64_t c[1]) {
+        c[0] = sum[t];
+        const uint64_t x = bad[t];
+        b = x < b ? x : b;
+      },
+      [&](uint32_t t, const uint64_t before[1]) { base[t] = before[0]; });
+  b = block_min<kPayScanThreads>(b);
+  if (threadIdx.x == 0) {
+    res->n_var = tot.v[0];
     res->bad_row = b;
   }
 }
@@ -333,8 +291,8 @@ __global__ __launch_bounds__(kPayScanThreads) void k_pay_small(const PayIn in, u
       if (pay_row_ok(r.off[j], r.len[j], in.spans[r.span[j]].len)) acc += r.len[j];
       else if (b == kPayNoRow) b = k0 + j;
     }
-    acc = pay_wave_sum(acc);
-    b = pay_wave_min(b);
+    acc = wave_sum(acc);
+    b = wave_min(b);
     if (lane == 0) ws[w] = acc, wb[w] = b;
     __syncthreads();
     if (ttid == 0 && t0 + q < n_tiles) {

@@ -35,29 +35,15 @@
 
 #include "../../include/clonos_engine.h"
 #include "pack_wide.h"
-#include "pack_dev.h"
+#include "pack_wide_dev.h"
 #include "kernels.h"
 
 namespace clg {
 
 namespace {
 
-static_assert(kWPackTile == kPackBlock, "a tile of rows is a KIND block");
 static_assert(sizeof(WUnpackTab::col) / sizeof(void*) == kWPackStreams, "WUnpackTab holds the format's streams");
-constexpr uint32_t kWUnpackParts = kPackPerThread * kPackWaves;  // (quarter, wave) pieces of a tile, in row order
 
-// Lanes below this one whose bit is set in m.
-__device__ __forceinline__ uint32_t wunpack_below(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
-}
-// The stream that holds block blk: the last one whose base is at or below it (the bases do not
-// decrease: the host's layout check).
-__device__ __forceinline__ uint32_t wunpack_stream_of(const WUnpackTab* __restrict__ tab, uint64_t blk) {
-  uint32_t s = 0;
-#pragma unroll
-  for (uint32_t c = 1; c < kWPackStreams; ++c) s += uint32_t(blk >= tab->blk_base[c]);
-  return s;
-}
 __device__ __forceinline__ bool wunpack_block_ok(const WUnpackTab* __restrict__ tab, uint32_t s, uint64_t blk,
                                                  const clg_pack_block& d) {
   return pack_block_in_ok(d, wpack_is_delta(s), blk - tab->blk_base[s], tab->n[s], tab->n_bits);
@@ -72,9 +58,6 @@ __device__ __forceinline__ bool wunpack_range_inside(const clg_pack_block& d, bo
   return d.ref >= 0 && d.first >= lo && d.first <= hi && d.first + int64_t(d.count - 1) * top <= hi;
 }
 
-#define CLG_WUNPACK_CASE(e, dl, ...) \
-  case (e) * 2 + (dl): unpack_block_write<e, dl != 0>(__VA_ARGS__); break;
-
 }  // namespace
 
 __global__ __launch_bounds__(kPackThreads) void k_wunpack_check(const WUnpackTab* __restrict__ tab, uint32_t n_blocks,
@@ -82,7 +65,7 @@ __global__ __launch_bounds__(kPackThreads) void k_wunpack_check(const WUnpackTab
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t blk = uint64_t(blockIdx.x) * kPackWaves + (threadIdx.x >> 6);  // (wave-uniform)
   if (blk >= n_blocks) return;
-  const uint32_t s = wunpack_stream_of(tab, blk);
+  const uint32_t s = wpack_stream_of(tab, blk);
   const clg_pack_block d = tab->desc[blk];
   const bool delta = wpack_is_delta(s);
   const bool block_ok = wunpack_block_ok(tab, s, blk, d);
@@ -102,53 +85,29 @@ __global__ __launch_bounds__(kPackThreads) void k_wunpack_check(const WUnpackTab
 __global__ __launch_bounds__(kPackThreads) void k_wunpack_kind(const WUnpackTab* __restrict__ tab, uint32_t* __restrict__ cnt) {
   __shared__ __attribute__((aligned(16))) unsigned long long s_w[kPackBlock + 2];
   __shared__ unsigned long long s_ws[kPackWaves];
-  __shared__ uint32_t s_cnt[kPackWaves][kWPackKinds];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const clg_pack_block d = tab->desc[blockIdx.x];  // (uniform; KIND's blocks are the first: blk_base[0] == 0)
-  uint32_t c[kWPackKinds] = {};  // (the wave's counts: the same in every lane)
+  uint32_t kind[kPackPerThread] = {kWPackKinds, kWPackKinds, kWPackKinds, kWPackKinds};
   if (wunpack_block_ok(tab, CLG_WPACK_KIND, blockIdx.x, d)) {  // (uniform)
     uint64_t v[kPackPerThread];
     unpack_block_values<false>(d, tab->bits, s_w, s_ws, v);
-    const uint32_t first_i = tid * kPackPerThread, m = d.count;
+    const uint32_t first_i = threadIdx.x * kPackPerThread, m = d.count;
     const uint32_t n = first_i < m ? (m - first_i < 4 ? m - first_i : 4) : 0;
     if (n) unpack_store4<kElemU8>(tab->col[CLG_WPACK_KIND], uint64_t(blockIdx.x) * kPackBlock + first_i, v, n, true);
 #pragma unroll
-    for (uint32_t q = 0; q < kPackPerThread; ++q) {
-      const uint32_t kind = q < n && v[q] < kWPackKinds ? uint32_t(v[q]) : kWPackKinds;
-#pragma unroll
-      for (uint32_t t = 0; t < kWPackKinds; ++t) c[t] += uint32_t(__popcll(__ballot(kind == t)));
-    }
+    for (uint32_t q = 0; q < kPackPerThread; ++q)
+      if (q < n && v[q] < kWPackKinds) kind[q] = uint32_t(v[q]);
   }
-  if (lane == 0) {
-#pragma unroll
-    for (uint32_t t = 0; t < kWPackKinds; ++t) s_cnt[w][t] = c[t];
-  }
-  __syncthreads();
-  if (tid < kWPackKinds) {
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kPackWaves; ++j) s += s_cnt[j][tid];
-    cnt[uint64_t(blockIdx.x) * kWPackKinds + tid] = s;
-  }
+  wpack_kind_counts(kind, cnt);
 }
 
 // The tile counts -> base, the rows of each kind before the tile; the totals -> *res.  One
-// workgroup, a tile a thread and round: no look-back.
+// workgroup: wave_dev.h's scan, the four kinds at once.
 __global__ __launch_bounds__(kPackTopThreads) void k_wunpack_scan(const uint32_t* __restrict__ cnt, uint32_t n_tiles,
                                                                  uint64_t* __restrict__ base, WUnpackRes* __restrict__ res) {
-  __shared__ uint64_t ws[kPackTopThreads / 64];
-  __shared__ uint64_t wtot;
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  for (uint32_t t = 0; t < kWPackKinds; ++t) {
-    uint64_t carry = 0;
-    for (uint32_t g0 = 0; g0 < n_tiles; g0 += kPackTopThreads) {
-      const uint32_t g = g0 + tid;
-      const uint64_t before = pack_scan_round(g < n_tiles ? cnt[uint64_t(g) * kWPackKinds + t] : 0, lane, ws, &wtot);
-      if (g < n_tiles) base[uint64_t(g) * kWPackKinds + t] = carry + before;
-      carry += wtot;
-      __syncthreads();  // (ws is written again in the next round)
-    }
-    if (tid == 0) res->tot[t] = carry;
+  const auto tot = wpack_kind_scan(cnt, n_tiles, base);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (uint32_t t = 0; t < kWPackKinds; ++t) res->tot[t] = tot.v[t];
   }
 }
 
@@ -156,71 +115,38 @@ __global__ __launch_bounds__(kPackThreads) void k_wunpack_write(const WUnpackTab
   __shared__ __attribute__((aligned(16))) unsigned long long s_w[kPackBlock + 2];
   __shared__ unsigned long long s_ws[kPackWaves];
   const uint64_t blk = uint64_t(blockIdx.x) + first_blk;
-  const uint32_t s = wunpack_stream_of(tab, blk);  // (uniform)
+  const uint32_t s = wpack_stream_of(tab, blk);  // (uniform)
   const clg_pack_block d = tab->desc[blk];
   if (!wunpack_block_ok(tab, s, blk, d)) return;  // (the input changed under the call: nothing is written)
   void* col = tab->col[s];
   const uint64_t i0 = (blk - tab->blk_base[s]) * kPackBlock;
-  switch (wpack_stream_elem(s) * 2 + uint32_t(wpack_is_delta(s))) {
-    CLG_WUNPACK_CASE(kElemU8, 0, col, i0, d, tab->bits, s_w, s_ws)
-    CLG_WUNPACK_CASE(kElemU8, 1, col, i0, d, tab->bits, s_w, s_ws)
-    CLG_WUNPACK_CASE(kElemU32, 0, col, i0, d, tab->bits, s_w, s_ws)
-    CLG_WUNPACK_CASE(kElemU32, 1, col, i0, d, tab->bits, s_w, s_ws)
-    CLG_WUNPACK_CASE(kElemI32, 0, col, i0, d, tab->bits, s_w, s_ws)
-    CLG_WUNPACK_CASE(kElemI32, 1, col, i0, d, tab->bits, s_w, s_ws)
-    CLG_WUNPACK_CASE(kElemI64, 0, col, i0, d, tab->bits, s_w, s_ws)
-    CLG_WUNPACK_CASE(kElemI64, 1, col, i0, d, tab->bits, s_w, s_ws)
-  }
+  CLG_WPACK_DISPATCH(s, unpack_block_write, col, i0, d, tab->bits, s_w, s_ws)
 }
 
 __global__ __launch_bounds__(kPackThreads) void k_wunpack_merge(const WUnpackTab* __restrict__ tab,
                                                                const uint64_t* __restrict__ base, const WUnpackDst dst,
                                                                uint64_t n_wide, uint64_t* __restrict__ tsum,
                                                                WUnpackVerdict* __restrict__ verdict) {
-  __shared__ uint32_t s_pre[kWUnpackParts][kWPackKinds];  // a piece's counts, then the rows of the tile before it
-  __shared__ uint64_t s_col[kWPackKinds * kWPackFields];
-  __shared__ uint64_t s_n[kWPackKinds], s_base[kWPackKinds];
+  __shared__ WPackTileLds l;
   __shared__ uint64_t s_sum[kPackWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (tid < kWPackKinds * kWPackFields) s_col[tid] = uint64_t(reinterpret_cast<uintptr_t>(tab->col[2 + tid]));
-  if (tid < kWPackKinds) {
-    s_n[tid] = tab->n[wpack_stream(tid, 0)];
-    s_base[tid] = base[uint64_t(blockIdx.x) * kWPackKinds + tid];
-  }
   const uint8_t* __restrict__ kind_in = static_cast<const uint8_t*>(tab->col[CLG_WPACK_KIND]);
-  uint32_t kind[kPackPerThread], below[kPackPerThread];
+  uint32_t kind[kPackPerThread];
+  uint64_t rank[kPackPerThread];
 #pragma unroll
   for (uint32_t q = 0; q < kPackPerThread; ++q) {
     const uint64_t k = uint64_t(blockIdx.x) * kWPackTile + q * kPackThreads + tid;
     kind[q] = k < n_wide ? uint32_t(kind_in[k]) : kWPackKinds;
-    below[q] = 0;
-#pragma unroll
-    for (uint32_t t = 0; t < kWPackKinds; ++t) {
-      const uint64_t m = __ballot(kind[q] == t);
-      if (kind[q] == t) below[q] = wunpack_below(m);
-      if (lane == 0) s_pre[q * kPackWaves + w][t] = uint32_t(__popcll(m));
-    }
   }
-  __syncthreads();
-  if (tid < kWPackKinds) {
-    uint32_t run = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kWUnpackParts; ++j) {
-      const uint32_t x = s_pre[j][tid];
-      s_pre[j][tid] = run;
-      run += x;
-    }
-  }
-  __syncthreads();
+  wpack_tile_rank(tab, base, kind, l, rank);
   uint64_t len_sum = 0;
 #pragma unroll
   for (uint32_t q = 0; q < kPackPerThread; ++q) {
     const uint32_t t = kind[q];
-    if (t >= kWPackKinds || s_n[t] == 0) continue;  // (never, while the kind bytes are what pass 1 counted)
+    if (t >= kWPackKinds || l.n[t] == 0) continue;  // (the latter never, while the kind bytes are what pass 1 counted)
     const uint64_t k = uint64_t(blockIdx.x) * kWPackTile + q * kPackThreads + tid;
-    uint64_t r = s_base[t] + s_pre[q * kPackWaves + w][t] + below[q];
-    if (r >= s_n[t]) r = s_n[t] - 1;  // (never, likewise: no load leaves the kind's array)
-    const uint64_t* col = &s_col[t * kWPackFields];
+    const uint64_t r = rank[q] < l.n[t] ? rank[q] : l.n[t] - 1;  // (the clamp never, likewise: no load leaves the kind's array)
+    const uint64_t* col = &l.col[t * kWPackFields];
     const uint32_t len = reinterpret_cast<const uint32_t*>(uintptr_t(col[CLG_WPACK_VAR_LEN]))[r];
     static_cast<int32_t*>(dst.col[CLG_WPACK_RC])[k] = reinterpret_cast<const int32_t*>(uintptr_t(col[CLG_WPACK_RC]))[r];
     static_cast<int64_t*>(dst.col[CLG_WPACK_V1])[k] = reinterpret_cast<const int64_t*>(uintptr_t(col[CLG_WPACK_V1]))[r];
@@ -235,7 +161,7 @@ __global__ __launch_bounds__(kPackThreads) void k_wunpack_merge(const WUnpackTab
       if (!wpack_cross_ok(dst.tag, dst.n_rec, idx, t)) atomicMin(&verdict->cross_row, (unsigned long long)k);
     }
   }
-  const uint64_t incl = pack_wave_incl64(len_sum, lane);
+  const uint64_t incl = wave_incl(len_sum, lane);
   if (lane == 63) s_sum[w] = incl;
   __syncthreads();
   if (tid == 0) {
@@ -248,17 +174,9 @@ __global__ __launch_bounds__(kPackThreads) void k_wunpack_merge(const WUnpackTab
 
 // The tile sums -> in place, the bytes before each tile.  One workgroup.
 __global__ __launch_bounds__(kPackTopThreads) void k_wunpack_tscan(uint64_t* __restrict__ tsum, uint32_t n_tiles) {
-  __shared__ uint64_t ws[kPackTopThreads / 64];
-  __shared__ uint64_t wtot;
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  uint64_t carry = 0;
-  for (uint32_t g0 = 0; g0 < n_tiles; g0 += kPackTopThreads) {
-    const uint32_t g = g0 + tid;
-    const uint64_t before = pack_scan_round(g < n_tiles ? tsum[g] : 0, lane, ws, &wtot);
-    if (g < n_tiles) tsum[g] = carry + before;
-    carry += wtot;
-    __syncthreads();  // (ws is written again in the next round)
-  }
+  tile_scan<kPackTopThreads, 1, uint64_t>(
+      n_tiles, [&](uint32_t g, uint64_t c[1]) { c[0] = tsum[g]; },
+      [&](uint32_t g, const uint64_t before[1]) { tsum[g] = before[0]; });
 }
 
 // pos[k] for the tile's rows, four consecutive rows a thread, and pos[n_wide] behind the last row.
@@ -274,7 +192,7 @@ __global__ __launch_bounds__(kPackThreads) void k_wunpack_pos(const uint32_t* __
     x[q] = k0 + q < n_wide ? len[k0 + q] : 0;
     mine += x[q];
   }
-  const uint64_t incl = pack_wave_incl64(mine, lane);
+  const uint64_t incl = wave_incl(mine, lane);
   if (lane == 63) s_sum[w] = incl;
   __syncthreads();
   uint64_t run = tbase[blockIdx.x] + (incl - mine);

@@ -299,6 +299,16 @@ def test_one_block_more_than_a_scan_group(eng):
     assert got.blk_base[-1] > 256
 
 
+def test_one_tile_more_than_a_round_of_the_kind_scan(eng):
+    """1024 x 1024 + 1 rows: the kind counts' scan takes a second round, whose one tile gets the
+    first round's totals as its bases.  The kinds cycle in runs of three, so every kind has rows in
+    every tile of the first round; every field but w_var_len is constant, so the host's side stays
+    in seconds."""
+    n = 1024 * 1024 + 1
+    got = same_as_host(eng, Wide((np.arange(n) // 3) % 4, gap=0, w_var_len=np.arange(n, dtype=np.uint64) % 1000))
+    assert got.n_val[0] == n and all(got.n_val[2 + 6 * t] >= n // 4 - 3 for t in range(4))
+
+
 def test_the_stat_is_recorded(eng):
     eng.kernel_stats_reset()
     eng.pack_wide(scene())

@@ -210,8 +210,23 @@ def many_rows(data):
     return wo, wl, want, want_pos
 
 
-def test_more_tiles_than_one_scan_round(eng, data, many_rows):
-    wo, wl, want, want_pos = many_rows
+@pytest.fixture(scope="module")
+def round_rows(data):
+    """2 * T * S + 1 rows, lengths 0-3: the scan's rounds are S tiles, so the prefixes of T * S,
+    T * S + 1, 2 * T * S and 2 * T * S + 1 rows end exactly one full round, one tile into the second,
+    exactly two rounds and one tile into the third.  The expected column once; a prefix of the rows
+    has a prefix of it."""
+    rng = np.random.default_rng(34)
+    n = 2 * T * S + 1
+    wl = rng.integers(0, 4, n).astype(np.uint32)
+    wo = rng.integers(0, SPAN - 3, n).astype(np.uint32)
+    want, want_pos = expected([data], wo, wl, [0, n])
+    for a in (wo, wl, want, want_pos):
+        a.setflags(write=False)
+    return wo, wl, want, want_pos
+
+
+def gathers_as_expected(eng, data, wo, wl, want, want_pos):
     d = upload(data)
     g = GuardedPayloads("device", want.size, wo.size + 1)
     try:
@@ -223,6 +238,18 @@ def test_more_tiles_than_one_scan_round(eng, data, many_rows):
     finally:
         g.free()
         d.free()
+
+
+def test_more_tiles_than_one_scan_round(eng, data, many_rows):
+    gathers_as_expected(eng, data, *many_rows)
+
+
+@pytest.mark.parametrize("n", [T * S, T * S + 1, 2 * T * S, 2 * T * S + 1])
+def test_the_scan_round_edges(eng, data, round_rows, n):
+    """The one-workgroup scan's carry and partial last round (k_pay_scan, the cheapest instance of
+    the family's shared scan) at its round edges."""
+    wo, wl, want, want_pos = round_rows
+    gathers_as_expected(eng, data, wo[:n], wl[:n], want[:int(want_pos[n])], want_pos[:n + 1])
 
 
 def test_bad_row_in_the_middle_tile_gives_its_lowest_index(eng, data, many_rows):
