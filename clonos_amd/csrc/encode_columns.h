@@ -33,6 +33,7 @@
 // Plain C++: compiles under hipcc (host and device) and under g++ without HIP
 // (tests/encode_columns_host.cpp).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -174,14 +175,46 @@ inline int ecol_bad(clg_encoded* out, uint32_t what, uint64_t index, const char*
   return CLG_E_INVALID_ARG;
 }
 
-// Null arrays that the counts say are read.  (pos and var may be null when no row carries a
-// payload: that is a ROW matter only when one does, and then pos is read.)
+// ---- clg_columns_in's arrays, in EcolIn's order (host only; columns.h kColArray's counterpart) ----
+// len: the count the array's length follows -- class c's total (0 .. 4), or one of the three below.
+// needed: null is an error when that count is not 0 (w_idx is optional; pos may be null when no row
+// carries a payload: that is a ROW matter only when one does, and then pos is read).
+enum : uint8_t { kEcolLenRec = 5, kEcolLenPos = 6, kEcolLenVar = 7 };  // n_rec; n_class[4] + 1; n_var
+struct EcolArray {
+  uint8_t width;  // element bytes
+  uint8_t len;
+  bool needed;
+  size_t at;  // the member's offset in clg_columns_in
+};
+#define CLG_ECOL_ARRAY(m, width, len, needed) {width, len, needed, offsetof(clg_columns_in, m)}
+constexpr int kEcolArrays = 13;
+constexpr int kEcolNarrowArrays = 5;   // the leading ones, which a clg_packed gives: tag and the value columns
+constexpr int kEcolPackedArrays = 12;  // ... and which the two packed forms give together: all but var
+constexpr EcolArray kEcolArray[kEcolArrays] = {
+    CLG_ECOL_ARRAY(tag, 1, kEcolLenRec, true), CLG_ECOL_ARRAY(order, 1, 0, true),     CLG_ECOL_ARRAY(timestamp, 8, 1, true),
+    CLG_ECOL_ARRAY(rng, 4, 2, true),           CLG_ECOL_ARRAY(buffer_built, 4, 3, true), CLG_ECOL_ARRAY(w_rc, 4, 4, true),
+    CLG_ECOL_ARRAY(w_v1, 8, 4, true),          CLG_ECOL_ARRAY(w_var_len, 4, 4, true), CLG_ECOL_ARRAY(w_sub, 1, 4, true),
+    CLG_ECOL_ARRAY(w_v0, 8, 4, true),          CLG_ECOL_ARRAY(w_idx, 4, 4, false),    CLG_ECOL_ARRAY(pos, 8, kEcolLenPos, false),
+    CLG_ECOL_ARRAY(var, 1, kEcolLenVar, true)};
+#undef CLG_ECOL_ARRAY
+inline uint64_t ecol_array_len(const clg_columns_in& in, int i) {
+  const uint8_t len = kEcolArray[i].len;
+  return len < kColClasses ? in.n_class[len] : len == kEcolLenRec ? in.n_rec : len == kEcolLenPos ? in.n_class[kColWide] + 1 : in.n_var;
+}
+inline uint64_t ecol_array_bytes(const clg_columns_in& in, int i) { return ecol_array_len(in, i) * kEcolArray[i].width; }
+inline const void* ecol_in_ptr(const clg_columns_in& in, int i) {
+  const void* p;
+  memcpy(&p, reinterpret_cast<const char*>(&in) + kEcolArray[i].at, sizeof p);
+  return p;
+}
+inline void ecol_in_set(clg_columns_in* in, int i, const void* p) {
+  memcpy(reinterpret_cast<char*>(in) + kEcolArray[i].at, &p, sizeof p);
+}
+
+// Null arrays that the counts say are read.
 inline bool ecol_args_ok(const clg_columns_in& in) {
-  const uint64_t* n = in.n_class;
-  if (in.n_rec && !in.tag) return false;
-  if ((n[0] && !in.order) || (n[1] && !in.timestamp) || (n[2] && !in.rng) || (n[3] && !in.buffer_built)) return false;
-  if (n[4] && (!in.w_rc || !in.w_v1 || !in.w_var_len || !in.w_sub || !in.w_v0)) return false;
-  if (in.n_var && !in.var) return false;
+  for (int i = 0; i < kEcolArrays; ++i)
+    if (kEcolArray[i].needed && ecol_array_len(in, i) && !ecol_in_ptr(in, i)) return false;
   if (in.n_spans && !in.span_base) return false;
   if (in.in_kind != CLG_MEM_HOST && in.in_kind != CLG_MEM_DEVICE && in.in_kind != CLG_MEM_MAPPED) return false;
   return true;

@@ -13,8 +13,9 @@
 // the segment pool, flush, append and upstream deltas, checkpoints and truncation, consumer
 // seeks, jobs and log handles, the kernel statistics, the static_asserts on the ABI structs.
 // Slices and digests are in engine_gather.cpp, the decodes in engine_decode.cpp, the typed-columns
-// family in engine_columns.cpp, replay preparation with encode, enrich and process-delta in
-// engine_replay.cpp, the in-flight log in engine_inflight.cpp; what the units share is in
+// family in engine_columns.cpp, engine_pack.cpp and engine_encode_columns.cpp (what those share is
+// in engine_columns.h), replay preparation with encode, enrich and process-delta in
+// engine_replay.cpp, the in-flight log in engine_inflight.cpp; what all the units share is in
 // engine_impl.h.
 #include "engine_impl.h"
 

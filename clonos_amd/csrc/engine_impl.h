@@ -725,17 +725,7 @@ struct LogGuard {
   if (!(e)) return fail(CLG_E_INVALID_ARG, "null engine"); \
   LogGuard lguard_((e), (h))
 
-// The decodes into typed columns (engine_columns.cpp), which replay preparation's columns form
-// (engine_replay.cpp) runs once per batch: `run` decodes into the arrays it is given, `spans_of`
-// gives the decoded spans to the payload gather.
-struct ColKeep;
-namespace clg {
-struct PaySpan;
-}
-using DecodeRun = std::function<int(clg_decoded*, uint64_t*)>;
-using PaySpansOf = std::function<int(std::vector<clg::PaySpan>&, std::vector<uint32_t>&)>;
-int decode_columns(clg_engine* e, const DecodeRun& run, uint32_t n_spans, clg_columns* out, ColKeep* keep = nullptr);
-int decode_columns_var(clg_engine* e, const DecodeRun& run, uint32_t n, clg_columns* out, clg_payloads* var,
-                       const PaySpansOf& spans_of);
+// (What the typed-columns family's units share, the decodes into columns that replay preparation
+// runs among it, is in engine_columns.h.)
 
 #pragma GCC visibility pop

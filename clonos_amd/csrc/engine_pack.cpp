@@ -1,0 +1,373 @@
+// engine_pack.cpp -- the typed-columns family, columns -> packed: the five narrow columns bit-packed
+// (pack.h), the wide rows packed by record kind (pack_wide.h) and the decodes that deliver either or
+// both; clg_pack_columns*, clg_pack_wide* and clg_decode_{logs,host}_columns_packed[_wide].  The packed
+// decodes run engine_columns.cpp's decode, columns and payload gather, once per batch each.
+#include "engine_columns.h"
+#include "columns.h"
+#include "pack.h"
+#include "pack_wide.h"
+
+// A packed output's memory kind and alignment (engine_columns.h: the unpacks check their input with it).
+int pack_out_check(const clg::PackView& out, const char* what) {
+  if (!mem_kind_ok(out.out_kind)) return fail(CLG_E_INVALID_ARG, "%sout_kind %u", what, out.out_kind);
+  if (out.out_kind != CLG_MEM_HOST && (uintptr_t(out.desc) % 8 || uintptr_t(out.bits) % 16))
+    return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
+  return CLG_OK;
+}
+
+namespace {
+
+// ---- packed typed columns (pack.h) ----------------------------------------------------------
+// The five narrow columns bit-packed where they lie: measure and the offset scan, the host's
+// capacity check on the scan's total, then the write.  A LogReplayerImpl cursor
+// (LogReplayerImpl.java:61-119) pops one typed value at a time from the blocks.
+
+// Measure and scan over device-side streams: out's results are filled, the descriptors (with
+// their offsets) are left in d_packdesc.
+int pack_sizes(clg_engine* e, const clg::PackSrc& src, clg_packed* out, clg::PackIn* pin) {
+  clg::pack_reset_result(out);
+  clg::pack_layout(src.n, out);
+  const uint64_t nb = out->blk_base[clg::kPackStreams];
+  if (nb >> 31) return fail(CLG_E_INVALID_ARG, "%llu blocks in one call", (unsigned long long)nb);
+  uint64_t in_bytes = 0;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) {
+    if (src.n[c] && !src.col[c]) return fail(CLG_E_INVALID_ARG, "null input array (stream %u)", c);
+    if (uintptr_t(src.col[c]) % clg::pack_stream_bytes(c))
+      return fail(CLG_E_INVALID_ARG, "stream %u is not aligned to its element", c);
+    pin->col[c] = src.col[c], pin->n[c] = src.n[c];
+    in_bytes += src.n[c] * clg::pack_stream_bytes(c);
+  }
+  for (uint32_t c = 0; c <= clg::kPackStreams; ++c) pin->blk_base[c] = out->blk_base[c];
+  const uint64_t ng = (nb + clg::kPackScanGroup - 1) / clg::kPackScanGroup;
+  CHK(e->d_packdesc.ensure(size_t(nb) * sizeof(clg_pack_block) + 64));
+  CHK(e->d_packsum.ensure(size_t(ng) * 8 + 64));
+  CHK(e->h_packres.ensure(sizeof(clg::PackRes)));
+  clg::PackRes* res = e->h_packres.as<clg::PackRes>();
+  // (bytes: the columns once, a descriptor written, read and written again, the groups' sums)
+  CHK(e->timed("pack_columns", in_bytes + nb * 72 + ng * 24, [&] {
+    return clg::launch_pack_measure_scan(*pin, uint32_t(nb), e->d_packdesc.as<clg_pack_block>(), e->d_packsum.as<uint64_t>(),
+                                         res, e->stream);
+  }));
+  CHK(e->sync());
+  out->n_bits = res->n_bits;
+  return CLG_OK;
+}
+
+// ---- what the two packed families share, over a PackView of either's struct ---------------------
+
+// The write pass, after the sizes and the capacity check: device and registered outputs are
+// written by the kernel, host ones through engine staging and one copy each.  launch(desc, bits):
+// the family's write kernel over the placed outputs; in_bytes: what it reads of the values.
+template <class Launch>
+int pack_write(clg_engine* e, const clg::PackView& out, DevBuf& staging, const char* stat, uint64_t in_bytes,
+               const Launch& launch) {
+  const uint64_t nb = out.blocks(), nbits = *out.n_bits;
+  if (!nb) return CLG_OK;
+  const PlaceSpec dst[2] = {{out.desc, nb * sizeof(clg_pack_block), 8}, {out.bits, nbits, 16}};
+  clg::Placement pl;
+  CHK(place_out(staging, dst, 2, out.out_kind, PlacePolicy::stage_if_unresolved, "packed", &pl));
+  CHK(e->timed(stat, in_bytes + nb * 64 + nbits, [&] { return launch(pl.at<clg_pack_block>(0), pl.at<uint8_t>(1)); }));
+  CHK(stage_out(e, dst, 2, pl));
+  return e->sync();
+}
+
+// prefix: "packed columns" or "packed wide rows".
+int pack_capacity_error(const clg::PackView& out, const char* prefix, const char* name) {
+  return fail(CLG_E_CAPACITY, "%s: %s is too small (blocks %llu, payload bytes %llu)", prefix, name,
+              (unsigned long long)out.blocks(), (unsigned long long)*out.n_bits);
+}
+
+// Past the sizes: nothing more for the sizes-only call, the capacity error for a short output,
+// else the write.
+template <class Write>
+int pack_finish(const clg::PackView& out, const char* prefix, const Write& write) {
+  if (clg::pack_sizes_only(out)) return CLG_OK;
+  if (const char* name = clg::pack_short(out)) return pack_capacity_error(out, prefix, name);
+  return write();
+}
+
+int pack_write(clg_engine* e, const clg::PackIn& pin, const clg_packed* out) {
+  uint64_t in_bytes = 0;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) in_bytes += pin.n[c] * clg::pack_stream_bytes(c);
+  const uint64_t nb = out->blk_base[clg::kPackStreams];
+  const auto launch = [&](clg_pack_block* desc, uint8_t* bits) {
+    return clg::launch_pack_write(pin, uint32_t(nb), e->d_packdesc.as<clg_pack_block>(), desc, bits, nb, out->n_bits, e->stream);
+  };
+  return pack_write(e, clg::pack_view(*out), e->d_packout, "pack_columns", in_bytes, launch);
+}
+
+// ---- packed wide rows (pack_wide.h) ---------------------------------------------------------
+// Kind and count and the scan of the tile counts, the host's check of the bad-row word and its
+// layout of the 26 streams from the four totals, the split into per-kind arrays in engine scratch,
+// measure and the offset scan, the host's capacity check, then the write.
+
+// Everything up to the sizes, over device-side rows: out's results are filled, the stream table is
+// left in d_wpacktab and the descriptors (with their offsets) in d_wpackdesc.
+int wpack_sizes(clg_engine* e, const clg::WPackSrc& src, clg_packed_wide* out) {
+  clg::wpack_reset_result(out);
+  const uint64_t nw = src.n_wide;
+  if (nw >> 32) return fail(CLG_E_INVALID_ARG, "%llu wide rows in one call", (unsigned long long)nw);
+  if (!nw) return CLG_OK;  // no rows: 26 empty streams, nothing to launch (a log without wide records pays nothing)
+  const uint32_t nt = uint32_t((nw + clg::kWPackTile - 1) / clg::kWPackTile);
+  const uint64_t kb[4] = {nw, uint64_t(nt) * clg::kWPackKinds * 4, uint64_t(nt) * clg::kWPackKinds * 8, 8};
+  clg::Carve<4> ks;
+  CHK(carve(e->d_wpackkind, kb, &ks));
+  uint8_t* d_kind = ks.at<uint8_t>(0);
+  uint32_t* d_cnt = ks.at<uint32_t>(1);
+  uint64_t* d_base = ks.at<uint64_t>(2);
+  unsigned long long* d_bad = ks.at<unsigned long long>(3);
+  CHK(e->h_wpackres.ensure(sizeof(clg::WPackRes) + sizeof(clg::PackRes)));
+  clg::WPackRes* res = e->h_wpackres.as<clg::WPackRes>();
+  clg::PackRes* pres = reinterpret_cast<clg::PackRes*>(res + 1);
+  // (bytes: w_idx, a tag and the kind byte a row; the tile counts written, read and their bases written)
+  CHK(e->timed("pack_wide", nw * 6 + uint64_t(nt) * 64,
+               [&] { return clg::launch_wpack_count_scan(src, nt, d_kind, d_cnt, d_base, d_bad, res, e->stream); }));
+  CHK(e->sync());
+  if (res->bad_row != ~0ull) {
+    out->bad_row = res->bad_row;
+    return fail(CLG_E_INVALID_ARG, "packed wide rows: row %llu's w_idx or tag is not a wide record's", (unsigned long long)res->bad_row);
+  }
+  if (res->tot[0] + res->tot[1] + res->tot[2] + res->tot[3] != nw) return fail(CLG_E_DEVICE, "packed wide rows: the kinds' totals do not sum to the rows");
+  clg::wpack_layout(nw, res->tot, out);
+  const uint64_t nb = out->blk_base[clg::kWPackStreams];
+
+  // the per-kind arrays and the stream table
+  constexpr int kArrays = int(clg::kWPackKinds * clg::kWPackFields);
+  uint64_t cb[kArrays];
+  clg::Carve<kArrays> so;
+  for (uint32_t t = 0; t < clg::kWPackKinds; ++t)
+    for (uint32_t f = 0; f < clg::kWPackFields; ++f)
+      cb[t * clg::kWPackFields + f] = res->tot[t] * clg::pack_elem_bytes(clg::kWPackField[f].elem);
+  CHK(carve(e->d_wpacksoa, cb, &so));
+  CHK(e->h_wpacktab.ensure(sizeof(clg::WPackTab)));
+  CHK(e->d_wpacktab.ensure(sizeof(clg::WPackTab)));
+  clg::WPackTab* tab = e->h_wpacktab.as<clg::WPackTab>();
+  tab->col[CLG_WPACK_KIND] = d_kind, tab->col[CLG_WPACK_IDX] = src.w_idx;
+  for (int i = 0; i < kArrays; ++i) tab->col[2 + i] = so.at<uint8_t>(i);
+  for (uint32_t c = 0; c < clg::kWPackStreams; ++c) tab->n[c] = out->n_val[c];
+  for (uint32_t c = 0; c <= clg::kWPackStreams; ++c) tab->blk_base[c] = out->blk_base[c];
+  HIPCHK(hipMemcpyAsync(e->d_wpacktab.p, tab, sizeof(clg::WPackTab), hipMemcpyHostToDevice, e->stream));
+  const uint64_t ng = (nb + clg::kPackScanGroup - 1) / clg::kPackScanGroup;
+  CHK(e->d_wpackdesc.ensure(size_t(nb) * sizeof(clg_pack_block) + 64));
+  CHK(e->d_wpacksum.ensure(size_t(ng) * 8 + 64));
+  // (bytes: the split reads a kind byte and 29 B a row and writes them; the measure reads the 26
+  // streams, 34 B a row; a descriptor written, read and written again, the groups' sums)
+  CHK(e->timed("pack_wide", nw * (1 + 29 + 29 + 34) + nb * 72 + ng * 24, [&] {
+    const int st = clg::launch_wpack_split_measure(src, nt, d_kind, d_base, e->d_wpacktab.as<clg::WPackTab>(), uint32_t(nb),
+                                                   e->d_wpackdesc.as<clg_pack_block>(), e->stream);
+    if (st != CLG_OK) return st;
+    return clg::launch_pack_scan(uint32_t(nb), e->d_wpackdesc.as<clg_pack_block>(), e->d_wpacksum.as<uint64_t>(), pres, e->stream);
+  }));
+  CHK(e->sync());
+  out->n_bits = pres->n_bits;
+  return CLG_OK;
+}
+
+int wpack_write(clg_engine* e, const clg_packed_wide* out) {
+  const uint64_t nb = out->blk_base[clg::kWPackStreams];
+  const auto launch = [&](clg_pack_block* desc, uint8_t* bits) {
+    return clg::launch_wpack_write(e->d_wpacktab.as<clg::WPackTab>(), uint32_t(nb), e->d_wpackdesc.as<clg_pack_block>(), desc, bits,
+                                   nb, out->n_bits, e->stream);
+  };
+  return pack_write(e, clg::pack_view(*out), e->d_wpackout, "pack_wide", out->n_val[CLG_WPACK_KIND] * 34, launch);
+}
+
+// The decode into engine scratch and the columns of what it produced, also in engine scratch;
+// then the pack, the wide rows as they are and (var) the payload column of the same rows.
+// Every size is known before anything is written to the caller.  wpk (the packed-wide decodes):
+// the wide rows are delivered packed as well and no plain row is copied to the caller; `wide` then
+// carries only sizes, and var may come without pos, which is the prefix sum of w_var_len.
+int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_columns* wide, clg_payloads* var,
+                          clg_packed* out, const PaySpansOf& spans_of, clg_packed_wide* wpk = nullptr) {
+  if (wide->tag || wide->order || wide->timestamp || wide->rng || wide->buffer_built)
+    return fail(CLG_E_INVALID_ARG, "the narrow column pointers of `wide` must be NULL: those columns are delivered packed");
+  if (wpk)
+    for (int i = clg::kColNarrowArrays; i < clg::kColArrays; ++i)
+      if (clg::col_ptr(*wide, i)) return fail(CLG_E_INVALID_ARG, "every column pointer of `sizes` must be NULL: the wide rows are delivered packed");
+  if (!mem_kind_ok(wide->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", wide->out_kind);
+  CHK(pack_out_check(clg::pack_view(*out)));
+  if (wpk) CHK(pack_out_check(clg::pack_view(*wpk)));
+  clg::col_reset_result(wide);
+  clg::pack_reset_result(out);
+  if (wpk) clg::wpack_reset_result(wpk);
+  if (var) clg::pay_reset_result(var);
+  const bool no_pos = wpk && var && var->var && !var->pos;
+
+  // the decode, and the columns' sizes and span bases
+  std::vector<uint64_t> sb(size_t(n + 1) * clg::kColClasses, 0);
+  clg_columns sizes{};
+  sizes.span_base = sb.data();
+  sizes.out_kind = CLG_MEM_DEVICE;
+  ColKeep keep;
+  const int cs = decode_columns(e, run, n, &sizes, &keep);
+  const std::string col_err = g_err;
+  wide->n_rec = sizes.n_rec;
+  for (uint32_t c = 0; c < clg::kColClasses; ++c) wide->n_class[c] = sizes.n_class[c];
+  wide->err_status = sizes.err_status, wide->err_span = sizes.err_span;
+  wide->err_off = sizes.err_off, wide->err_tag = sizes.err_tag;
+  if (!keep.valid || keep.col_status != CLG_OK) return cs;
+  if (wide->span_base) memcpy(wide->span_base, sb.data(), sb.size() * 8);
+  const uint64_t nr = sizes.n_rec, nw = sizes.n_class[clg::kColWide];
+  const uint64_t* tot = sizes.n_class;
+
+  // the narrow columns and w_v0 into engine scratch (the tags and the side rows stay where the
+  // decode left them)
+  const uint64_t cb[5] = {tot[0], tot[1] * 8, tot[2] * 4, tot[3] * 4, nw * 8};
+  clg::Carve<5> sc;
+  CHK(carve(e->d_packcol, cb, &sc));
+  clg_columns full{};
+  full.tag = keep.d.tag, full.order = sc.at<int8_t>(0);
+  full.timestamp = sc.at<int64_t>(1), full.rng = sc.at<int32_t>(2);
+  full.buffer_built = sc.at<int32_t>(3), full.w_v0 = sc.at<int64_t>(4);
+  full.w_idx = keep.d.w_idx, full.w_rc = keep.d.w_rc, full.w_v1 = keep.d.w_v1, full.w_var_off = keep.d.w_var_off;
+  full.w_var_len = keep.d.w_var_len, full.w_sub = keep.d.w_sub;
+  full.cap_tag = nr, full.cap_order = tot[0], full.cap_timestamp = tot[1], full.cap_rng = tot[2];
+  full.cap_buffer_built = tot[3], full.cap_wide = nw;
+  full.out_kind = CLG_MEM_DEVICE;
+  CHK(columnize_device(e, keep.d, nullptr, 0, &full));
+
+  // every size, before anything is written to the caller
+  const clg::PackSrc src{{full.tag, full.order, full.timestamp, full.rng, full.buffer_built}, {nr, tot[0], tot[1], tot[2], tot[3]}};
+  clg::PackIn pin{};
+  CHK(pack_sizes(e, src, out, &pin));
+  if (wpk)
+    CHK(wpack_sizes(e, clg::WPackSrc{full.tag, full.w_idx, full.w_rc, full.w_v1, full.w_var_off, full.w_var_len, full.w_sub, full.w_v0, nr, nw},
+                    wpk));
+  int ps = CLG_OK;
+  std::vector<clg::PaySpan> spans;
+  std::vector<uint32_t> segtab;
+  const std::vector<uint64_t> row_base = wide_row_base(sb.data(), n);
+  if (var) {
+    ps = spans_of(spans, segtab);
+    if (ps == CLG_OK) ps = gather_payloads_device(e, spans, segtab, keep.d.w_var_off, keep.d.w_var_len, row_base.data(), var, true);
+  }
+  const std::string pay_err = g_err;
+  const int w0 = clg::kColNarrowArrays, w1 = clg::kColArrays;  // (the wide arrays: the table's last seven)
+  bool wide_any = false, wide_short = false;
+  for (int i = w0; i < w1; ++i) wide_any = wide_any || clg::col_ptr(*wide, i);
+  for (int i = w0; i < w1; ++i) wide_short = wide_short || (wide_any && clg::col_array_cap(*wide, i) < nw);
+  const clg::PackView pv = clg::pack_view(*out), wpv = wpk ? clg::pack_view(*wpk) : clg::PackView{};
+  const char* pk_short = clg::pack_sizes_only(pv) ? nullptr : clg::pack_short(pv);
+  const char* wpk_short = wpk && !clg::pack_sizes_only(wpv) ? clg::pack_short(wpv) : nullptr;
+  const char* pay_short = !var || ps != CLG_OK || clg::pay_sizes_only(*var) ? nullptr
+                          : !no_pos                                         ? clg::pay_short(*var, var->n_rows, var->n_var)
+                          : var->cap_var < var->n_var                       ? "var"
+                                                                            : nullptr;
+  if (wide_short) return fail(CLG_E_CAPACITY, "the wide rows' arrays are too small (rows %llu)", (unsigned long long)nw);
+  if (pk_short) return pack_capacity_error(pv, "packed columns", pk_short);
+  if (wpk_short) return pack_capacity_error(wpv, "packed wide rows", wpk_short);
+  if (pay_short) return pay_too_small(pay_short, var->n_rows, var->n_var);
+
+  // the writes
+  if (!clg::pack_sizes_only(pv)) CHK(pack_write(e, pin, out));
+  if (wpk && !clg::pack_sizes_only(wpv)) CHK(wpack_write(e, wpk));
+  if (wide_any && nw) {
+    for (int i = w0; i < w1; ++i)
+      CHK(copy_caller(e, clg::col_ptr(*wide, i), clg::col_ptr(full, i), nw * clg::kColArray[i].width, hipMemcpyDefault,
+                      wide->out_kind));
+    CHK(e->sync());
+  }
+  if (var && ps == CLG_OK && !clg::pay_sizes_only(*var))
+    ps = gather_payloads_device(e, spans, segtab, keep.d.w_var_off, keep.d.w_var_len, row_base.data(), var, false, no_pos);
+  else if (ps != CLG_OK)
+    g_err = pay_err;
+  if (cs != CLG_OK) {
+    g_err = col_err;
+    return cs;
+  }
+  return ps;
+}
+
+}  // namespace
+
+extern "C" {
+
+int clg_pack_columns(clg_engine* e, const clg_columns* in, clg_packed* out) {
+  ENGINE_GUARD(e);
+  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::pack_reset_result(out);
+  CHK(pack_out_check(clg::pack_view(*out)));
+  clg::PackSrc src = clg::pack_src(*in);
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c)
+    if (src.n[c] && !src.col[c]) return fail(CLG_E_INVALID_ARG, "null input array (stream %u)", c);
+  if (!mem_kind_ok(in->out_kind)) return fail(CLG_E_INVALID_ARG, "the columns' out_kind %u", in->out_kind);
+  PlaceSpec ins[clg::kPackStreams];
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c)
+    ins[c] = {src.col[c], src.n[c] * clg::pack_stream_bytes(c), clg::pack_stream_bytes(c)};
+  clg::Placement pl;
+  const int st = place_in(e, e->d_packin, ins, clg::kPackStreams, in->out_kind, PlacePolicy::stage_if_unresolved, "stream", &pl);
+  if (st != CLG_OK) return clg::pack_layout(src.n, out), st;  // (a misaligned stream: the layout is filled, as pack_sizes fills it)
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) src.col[c] = pl.at<const void>(c);
+  clg::PackIn pin{};
+  CHK(pack_sizes(e, src, out, &pin));
+  return pack_finish(clg::pack_view(*out), "packed columns", [&] { return pack_write(e, pin, out); });
+}
+
+int clg_pack_wide(clg_engine* e, const clg_columns* in, clg_packed_wide* out) {
+  ENGINE_GUARD(e);
+  if (!in || !out) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::wpack_reset_result(out);
+  CHK(pack_out_check(clg::pack_view(*out)));
+  if (!mem_kind_ok(in->out_kind)) return fail(CLG_E_INVALID_ARG, "the columns' out_kind %u", in->out_kind);
+  const uint64_t nr = in->n_rec, nw = in->n_class[clg::kColWide];
+  const PlaceSpec ins[8] = {{in->tag, nw ? nr : 0, 1},         {in->w_idx, nw * 4, 4},     {in->w_rc, nw * 4, 4}, {in->w_v1, nw * 8, 8},
+                            {in->w_var_off, nw * 4, 4}, {in->w_var_len, nw * 4, 4}, {in->w_sub, nw, 1},    {in->w_v0, nw * 8, 8}};
+  for (int i = 1; i < 8; ++i)
+    if (nw && !ins[i].p) return fail(CLG_E_INVALID_ARG, "null input array (%d)", i);
+  if (nw && !in->tag) return fail(CLG_E_INVALID_ARG, "null input array (tag)");
+  clg::Placement pl;
+  CHK(place_in(e, e->d_wpackin, ins, 8, in->out_kind, PlacePolicy::stage_if_unresolved, "wide", &pl));
+  const clg::WPackSrc src{pl.at<const uint8_t>(0),  pl.at<const uint32_t>(1), pl.at<const int32_t>(2), pl.at<const int64_t>(3),
+                          pl.at<const uint32_t>(4), pl.at<const uint32_t>(5), pl.at<const uint8_t>(6), pl.at<const int64_t>(7),
+                          nr,                       nw};
+  CHK(wpack_sizes(e, src, out));
+  return pack_finish(clg::pack_view(*out), "packed wide rows", [&] { return wpack_write(e, out); });
+}
+
+int clg_pack_wide_host(const clg_columns* in, clg_packed_wide* out) {
+  const char* what = "";
+  const int st = clg::wpack_build_host(in, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "packed wide rows: %s", what);
+}
+
+int clg_decode_logs_columns_packed(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                                   clg_columns* wide, clg_payloads* var, clg_packed* out) {
+  ENGINE_GUARD(e);
+  if (!wide || !out || (n && (!log || !start_epoch))) return fail(CLG_E_INVALID_ARG, "null argument");
+  const DecodeSource src = source_logs(e, log, start_epoch, n);
+  return decode_columns_packed(e, src.run, n, wide, var, out, src.spans_of);
+}
+
+int clg_decode_host_columns_packed(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off,
+                                   const uint64_t* span_len, uint32_t n, clg_columns* wide, clg_payloads* var,
+                                   clg_packed* out) {
+  ENGINE_GUARD(e);
+  if (!wide || !out || (n && (!span_off || !span_len))) return fail(CLG_E_INVALID_ARG, "null argument");
+  const DecodeSource src = source_host(e, bytes, span_off, span_len, n);
+  return decode_columns_packed(e, src.run, n, wide, var, out, src.spans_of);
+}
+
+int clg_decode_logs_columns_packed_wide(clg_engine* e, const uint32_t* log, const int64_t* start_epoch, uint32_t n,
+                                        clg_columns* sizes, clg_payloads* var, clg_packed* narrow, clg_packed_wide* wide) {
+  ENGINE_GUARD(e);
+  if (!sizes || !narrow || !wide || (n && (!log || !start_epoch))) return fail(CLG_E_INVALID_ARG, "null argument");
+  const DecodeSource src = source_logs(e, log, start_epoch, n);
+  return decode_columns_packed(e, src.run, n, sizes, var, narrow, src.spans_of, wide);
+}
+
+int clg_decode_host_columns_packed_wide(clg_engine* e, const uint8_t* bytes, const uint64_t* span_off,
+                                        const uint64_t* span_len, uint32_t n, clg_columns* sizes, clg_payloads* var,
+                                        clg_packed* narrow, clg_packed_wide* wide) {
+  ENGINE_GUARD(e);
+  if (!sizes || !narrow || !wide || (n && (!span_off || !span_len))) return fail(CLG_E_INVALID_ARG, "null argument");
+  const DecodeSource src = source_host(e, bytes, span_off, span_len, n);
+  return decode_columns_packed(e, src.run, n, sizes, var, narrow, src.spans_of, wide);
+}
+
+int clg_pack_columns_host(const clg_columns* in, clg_packed* out) {
+  const char* what = "";
+  const int st = clg::pack_build_host(in, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "packed columns: %s", what);
+}
+
+}  // extern "C"

@@ -2,9 +2,8 @@
 // clg_replay_prep, replay preparation in its soa and columns forms (clg_replay_prepare*),
 // clg_encode_batch, and the delta messages' headers written and parsed on the host
 // (clg_enrich_batch, clg_process_delta).
-#include "engine_impl.h"
+#include "engine_columns.h"
 #include "columns.h"
-#include "payload.h"
 
 extern "C" {
 

@@ -182,6 +182,12 @@ inline void pack_layout(const uint64_t n[kPackStreams], clg_packed* out) {
     out->blk_base[c + 1] = out->blk_base[c] + pack_blocks(n[c]);
   }
 }
+// The stream that holds block blk of a packed form of n_streams streams (either family's blk_base).
+inline uint32_t pack_stream_of_block(const uint64_t* blk_base, uint32_t n_streams, uint64_t blk) {
+  uint32_t c = 0;
+  while (c + 1 < n_streams && blk >= blk_base[c + 1]) ++c;
+  return c;
+}
 
 // ---- the block codec on the host, over a block's values extended to int64 ----------------------
 

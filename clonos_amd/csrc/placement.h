@@ -53,6 +53,13 @@ inline size_t place_layout(const uint64_t* bytes, int n, size_t* off) {
   for (int i = 0; i < n; ++i) off[i + 1] = (off[i] + size_t(bytes[i]) + 15) & ~size_t(15);
   return off[n];
 }
+// N pieces of one scratch buffer at `base`, their offsets place_layout's: at<T>(i) is piece i's address.
+template <int N>
+struct Carve {
+  size_t off[N + 1] = {};
+  uint8_t* base = nullptr;
+  template <class T> T* at(int i) const { return reinterpret_cast<T*>(base + off[i]); }
+};
 
 // Absent and empty arrays are neither looked up nor checked for alignment; in place they keep
 // the caller's pointer.  Alignment is checked only where the kernel touches the caller's memory,

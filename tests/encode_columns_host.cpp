@@ -283,6 +283,39 @@ int main() {
     clg_encoded out{};
     REQUIRE(clg::ecol_build_host(&x.in, &out) == CLG_OK && out.n_bytes == 2 + 9 + 13 + 5);
   }
+  // kEcolArray names clg_columns_in's thirteen arrays in the order of the struct (which is the
+  // kernels' EcolIn's: the engine asserts that), with their element widths and the counts they follow
+  {
+    clg_columns_in in{};
+    alignas(16) static const uint8_t store[16 * (clg::kEcolArrays + 1)] = {};  // array i "lies" at store + 16 * (i + 1)
+    const auto at = [&](int i) { return store + 16 * (i + 1); };
+    in.tag = at(0), in.order = reinterpret_cast<const int8_t*>(at(1)), in.timestamp = reinterpret_cast<const int64_t*>(at(2));
+    in.rng = reinterpret_cast<const int32_t*>(at(3)), in.buffer_built = reinterpret_cast<const int32_t*>(at(4));
+    in.w_rc = reinterpret_cast<const int32_t*>(at(5)), in.w_v1 = reinterpret_cast<const int64_t*>(at(6));
+    in.w_var_len = reinterpret_cast<const uint32_t*>(at(7)), in.w_sub = at(8);
+    in.w_v0 = reinterpret_cast<const int64_t*>(at(9)), in.w_idx = reinterpret_cast<const uint32_t*>(at(10));
+    in.pos = reinterpret_cast<const uint64_t*>(at(11)), in.var = at(12);
+    in.n_rec = 100, in.n_class[0] = 10, in.n_class[1] = 11, in.n_class[2] = 12, in.n_class[3] = 13, in.n_class[4] = 14, in.n_var = 99;
+    const uint32_t width[clg::kEcolArrays] = {sizeof *in.tag,   sizeof *in.order, sizeof *in.timestamp, sizeof *in.rng, sizeof *in.buffer_built,
+                                              sizeof *in.w_rc,  sizeof *in.w_v1,  sizeof *in.w_var_len, sizeof *in.w_sub, sizeof *in.w_v0,
+                                              sizeof *in.w_idx, sizeof *in.pos,   sizeof *in.var};
+    const uint64_t len[clg::kEcolArrays] = {100, 10, 11, 12, 13, 14, 14, 14, 14, 14, 14, 15, 99};
+    static_assert(clg::kEcolArrays == 13 && clg::kEcolNarrowArrays == 5 && clg::kEcolPackedArrays == 12, "tag .. buffer_built | .. pos | var");
+    for (int i = 0; i < clg::kEcolArrays; ++i) {
+      REQUIRE(clg::ecol_in_ptr(in, i) == at(i) && clg::kEcolArray[i].at == size_t(i) * sizeof(void*));
+      REQUIRE(clg::kEcolArray[i].width == width[i] && clg::ecol_array_len(in, i) == len[i]);
+      REQUIRE(clg::ecol_array_bytes(in, i) == len[i] * width[i]);
+      REQUIRE(clg::kEcolArray[i].needed == (i != 10 && i != 11));  // (w_idx and pos may be absent)
+    }
+    REQUIRE(clg::ecol_args_ok(in));
+    for (int i = 0; i < clg::kEcolArrays; ++i) {  // a null array is refused where it is needed, and set() puts one back
+      clg_columns_in x = in;
+      clg::ecol_in_set(&x, i, nullptr);
+      REQUIRE(clg::ecol_in_ptr(x, i) == nullptr && clg::ecol_args_ok(x) == !clg::kEcolArray[i].needed);
+      clg::ecol_in_set(&x, i, at(i));
+      REQUIRE(memcmp(&x, &in, sizeof x) == 0);
+    }
+  }
   printf("ok %llu\n", (unsigned long long)g_checks);
   return 0;
 }

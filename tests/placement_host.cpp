@@ -182,6 +182,15 @@ int main() {
     size_t off[kPlaceMax + 1];
     CHECK(place_layout(bytes, kPlaceMax, off) == pl.total);
     for (int i = 0; i <= kPlaceMax; ++i) CHECK(off[i] == pl.off[i]);
+    // the typed carve of pure scratch: place_layout's offsets from its base
+    Carve<kPlaceMax> cv;
+    CHECK(cv.base == nullptr && place_layout(bytes, kPlaceMax, cv.off) == pl.total);
+    alignas(16) static uint8_t scratch[kPlaceMax * 64 + 16];
+    CHECK(pl.total + 16 <= sizeof scratch);
+    cv.base = scratch;
+    for (int i = 0; i <= kPlaceMax; ++i) CHECK(cv.off[i] == off[i]);
+    for (int i = 0; i < kPlaceMax; ++i)
+      CHECK(cv.at<uint8_t>(i) == scratch + off[i] && reinterpret_cast<uint8_t*>(cv.at<uint64_t>(i)) == scratch + off[i]);
   }
 
   printf("ok %ld\n", checks);

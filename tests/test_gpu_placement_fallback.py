@@ -316,6 +316,108 @@ def test_unpack_columns(engines, which, scene, side):
         mout.free()
 
 
+# The wide family has no one-launch form: the engines differ only in how the input columns are made,
+# so one engine serves.  The pack reads the tags and the seven wide arrays, in this order.
+WIDE_DT = {name: dt for name, dt, _, _ in COLS}
+PACK_WIDE_IN = ("tag",) + WIDE
+UNPACK_WIDE_OUT = ("w_idx", "w_rc", "w_v1", "w_var_off", "w_var_len", "w_sub", "w_v0")   # then pos
+
+
+def wide_columns_over(names, ptrs, spans, kind, caps=False):
+    """clg_columns over the arrays `names` at ptrs, with the Spans input's counts."""
+    from clonos_amd import _lib
+    c = _lib.Columns()
+    for name, p in zip(names, ptrs):
+        setattr(c, name, p)
+    if caps:
+        c.cap_wide = spans.n_class[4]
+    else:
+        c.n_rec = spans.cols.n_rec
+        c.n_class[4] = spans.n_class[4]
+    c.out_kind = kind
+    return c
+
+
+def packed_wide_over(mem, cap_desc, cap_bits, kind):
+    from clonos_amd import _lib
+    p = _lib.PackedWideC()
+    p.desc, p.cap_desc, p.bits, p.cap_bits, p.out_kind = mem.ptr[0], cap_desc, mem.ptr[1], cap_bits, kind
+    return p
+
+
+@pytest.mark.parametrize("side", SIDES)
+@pytest.mark.parametrize("scene", SCENES)
+def test_pack_wide(engines, spans, scene, side):
+    from clonos_amd import _lib, pack_wide_host
+    eng = engines["small"]
+    arrs = [np.ascontiguousarray(getattr(spans.cols, name), WIDE_DT[name]) for name in PACK_WIDE_IN]
+    assert arrs[0].size == 301 and all(a.size == 56 for a in arrs[1:])
+    want = pack_wide_host(spans.cols)
+    nb, nbits = want.desc.size, want.bits.size
+    assert nb > 0 and nbits > 16
+    H, M = _lib.CLG_MEM_HOST, _lib.CLG_MEM_MAPPED
+    rin, rout = host_memory([a.nbytes for a in arrs]).put(arrs), host_memory([nb * 32, nbits])
+    min_ = Memory(scene, [a.nbytes for a in arrs]).put(arrs) if side != "output" else rin
+    mout = Memory(scene, [nb * 32, nbits]) if side != "input" else host_memory([nb * 32, nbits])
+    try:
+        ref = packed_wide_over(rout, nb, nbits, H)
+        assert ok(eng.pack_wide_raw(wide_columns_over(PACK_WIDE_IN, rin.ptr, spans, H), ref))
+        p = packed_wide_over(mout, nb, nbits, M if side != "input" else H)
+        assert ok(eng.pack_wide_raw(wide_columns_over(PACK_WIDE_IN, min_.ptr, spans, M if side != "output" else H), p))
+        assert list(p.n_val) == list(ref.n_val) == want.n_val and list(p.blk_base) == list(ref.blk_base) == want.blk_base
+        assert p.n_bits == ref.n_bits == nbits and p.bad_row == ref.bad_row
+        assert mout.data(0) == rout.data(0) == np.asarray(want.desc).tobytes()
+        assert mout.data(1) == rout.data(1) == np.asarray(want.bits).tobytes()
+        assert mout.guards_intact() and rout.guards_intact() and min_.guards_intact()
+        assert all(min_.data(k) == a.tobytes() for k, a in enumerate(arrs))
+    finally:
+        min_.free()
+        mout.free()
+
+
+@pytest.mark.parametrize("side", SIDES)
+@pytest.mark.parametrize("scene", SCENES)
+def test_unpack_wide(engines, spans, scene, side):
+    """The packed input and the eight outputs: w_idx, the six fields and pos."""
+    from clonos_amd import _lib, pack_wide_host, unpack_wide_host
+    eng = engines["small"]
+    packed = pack_wide_host(spans.cols)
+    st = packed._struct()
+    src = [np.asarray(packed.desc), np.asarray(packed.bits)]
+    want = unpack_wide_host(packed)
+    pos = np.concatenate([[0], np.cumsum(want["w_var_len"], dtype=np.uint64)]).astype(np.uint64)
+    outs = [want[name] for name in UNPACK_WIDE_OUT] + [pos]
+    assert all(want[name].tobytes() == np.ascontiguousarray(getattr(spans.cols, name), WIDE_DT[name]).tobytes()
+               for name in UNPACK_WIDE_OUT)
+    assert pos.size == 57 and int(pos[-1]) > 0
+    H, M = _lib.CLG_MEM_HOST, _lib.CLG_MEM_MAPPED
+
+    def packed_in(mem, kind):
+        p = _lib.PackedWideC()
+        C.memmove(C.byref(p), C.byref(st), C.sizeof(p))
+        p.desc, p.bits, p.out_kind = mem.ptr[0], mem.ptr[1], kind
+        return p
+
+    rin, rout = host_memory([a.nbytes for a in src]).put(src), host_memory([a.nbytes for a in outs])
+    min_ = Memory(scene, [a.nbytes for a in src]).put(src) if side != "output" else rin
+    mout = Memory(scene, [a.nbytes for a in outs]) if side != "input" else host_memory([a.nbytes for a in outs])
+    try:
+        bad = _lib.UnpackBad(9, 9, 9)
+        ref = wide_columns_over(UNPACK_WIDE_OUT, rout.ptr, spans, H, caps=True)
+        assert ok(eng.unpack_wide_raw(packed_in(rin, H), ref, rout.ptr[7], bad))
+        c = wide_columns_over(UNPACK_WIDE_OUT, mout.ptr, spans, M if side != "input" else H, caps=True)
+        assert ok(eng.unpack_wide_raw(packed_in(min_, M if side != "output" else H), c, mout.ptr[7], bad))
+        assert (bad.what, bad.stream, bad.block) == (0, 0, 2 ** 64 - 1)
+        assert int(c.n_class[4]) == int(ref.n_class[4]) == 56
+        for k, a in enumerate(outs):
+            assert mout.data(k) == rout.data(k) == a.tobytes(), (UNPACK_WIDE_OUT + ("pos",))[k]
+        assert mout.guards_intact() and rout.guards_intact() and min_.guards_intact()
+        assert all(min_.data(k) == a.tobytes() for k, a in enumerate(src))
+    finally:
+        min_.free()
+        mout.free()
+
+
 @pytest.mark.parametrize("scene", SCENES)
 @pytest.mark.parametrize("which", BOTH)
 def test_decode_host_columns_packed(engines, spans, which, scene):

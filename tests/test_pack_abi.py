@@ -109,7 +109,7 @@ def test_field_names_constants_and_what_stays():
 def test_the_format_is_defined_once_for_host_and_device():
     hdr = read("clonos_amd", "csrc", "pack.h")
     assert "kPackBlock = CLG_PACK_BLOCK" in hdr and "__host__ __device__" in hdr
-    for user in (("clonos_amd", "csrc", "pack.hip"), ("clonos_amd", "csrc", "engine_columns.cpp"), ("tests", "pack_host.cpp")):
+    for user in (("clonos_amd", "csrc", "pack.hip"), ("clonos_amd", "csrc", "engine_pack.cpp"), ("tests", "pack_host.cpp")):
         assert re.search(r'#include ".*pack\.h"', read(*user)), user
 
 

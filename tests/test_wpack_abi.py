@@ -107,11 +107,11 @@ def test_the_format_is_defined_once_for_host_and_device():
     hdr = read("clonos_amd", "csrc", "pack_wide.h")
     assert "kWPackStreams = CLG_WPACK_STREAMS" in hdr and "constexpr WPackField kWPackField[kWPackFields]" in hdr
     assert '#include "pack.h"' in hdr  # a block is packed as pack.h packs it
-    for user in (("clonos_amd", "csrc", "pack_wide.hip"), ("clonos_amd", "csrc", "engine_columns.cpp"), ("tests", "wpack_host.cpp")):
+    for user in (("clonos_amd", "csrc", "pack_wide.hip"), ("clonos_amd", "csrc", "engine_pack.cpp"), ("tests", "wpack_host.cpp")):
         assert re.search(r'#include ".*pack_wide\.h"', read(*user)), user
     # the three scan kernels are pack.hip's, launched for both families
     hip = read("clonos_amd", "csrc", "pack_wide.hip")
-    assert "k_pack_scan" not in re.sub(r"//.*", "", hip) and "launch_pack_scan" in read("clonos_amd", "csrc", "engine_columns.cpp")
+    assert "k_pack_scan" not in re.sub(r"//.*", "", hip) and "launch_pack_scan" in read("clonos_amd", "csrc", "engine_pack.cpp")
 
 
 def test_jni_shim_java_native_method_and_cursor():

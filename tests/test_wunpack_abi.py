@@ -49,7 +49,7 @@ def test_header_signatures_and_the_stream_offset():
     fmt = read("clonos_amd", "csrc", "pack_wide.h")
     assert "kWPackBadStream = CLG_UNPACK_WIDE_STREAM" in fmt and "CLG_PACK_HD bool wpack_cross_ok(" in fmt
     assert "wpack_cross_ok(" in read("clonos_amd", "csrc", "unpack_wide.hip")
-    assert "CLG_UNPACK_WIDE_STREAM" not in read("clonos_amd", "csrc", "engine_columns.cpp")
+    assert "CLG_UNPACK_WIDE_STREAM" not in read("clonos_amd", "csrc", "engine_encode_columns.cpp")
 
 
 def test_mirror_prototypes():
