@@ -77,6 +77,7 @@ EXPORTED = [
     "clg_decode_logs_columns_packed_wide", "clg_decode_host_columns_packed_wide",
     "clg_unpack_wide", "clg_encode_columns_packed_wide", "clg_append_columns_packed_wide",
     "clg_encode_columns_packed_wide_host",
+    "clg_replay_prepare_columns_packed", "clg_replay_prepare_columns_packed_device",
 ]
 
 
@@ -322,6 +323,22 @@ class ReplayColumnsOut(C.Structure):  # clg_replay_columns_out
     ]
 
 
+class ReplayPackedOut(C.Structure):  # clg_replay_packed_out
+    _fields_ = [
+        ("sizes", C.POINTER(Columns)),
+        ("var", C.POINTER(Payloads)),
+        ("narrow", C.POINTER(Packed)),
+        ("wide", C.POINTER(PackedWideC)),
+        ("buffer_sizes", C.c_void_p),
+        ("sizes_cap", C.c_uint64),
+        ("sizes_base", C.c_void_p),
+        ("sub_count", C.c_void_p),
+        ("sub_status", C.c_void_p),
+        ("sub_err_off", C.c_void_p),
+        ("sub_err_tag", C.c_void_p),
+    ]
+
+
 class EncodeIn(C.Structure):
     _fields_ = [
         ("tag", C.c_void_p), ("v0", C.c_void_p), ("n", C.c_uint64),
@@ -441,6 +458,10 @@ def _load() -> C.CDLL:
         "clg_replay_prepare_columns": (C.c_int, [P, C.POINTER(ReplayVertex), C.c_uint32, C.POINTER(ReplayColumnsOut)]),
         "clg_replay_prepare_columns_device": (C.c_int, [P, C.POINTER(ReplayVertex), C.c_uint32,
                                                         C.POINTER(ReplayColumnsOut)]),
+        "clg_replay_prepare_columns_packed": (C.c_int, [P, C.POINTER(ReplayVertex), C.c_uint32,
+                                                        C.POINTER(ReplayPackedOut)]),
+        "clg_replay_prepare_columns_packed_device": (C.c_int, [P, C.POINTER(ReplayVertex), C.c_uint32,
+                                                               C.POINTER(ReplayPackedOut)]),
         "clg_get_determinants_batch": (C.c_int, [P, P, P, C.c_uint32, P, C.c_uint64, C.c_uint32, P, P, u64p]),
         "clg_encode_batch": (C.c_int, [P, C.POINTER(EncodeIn), P, C.c_uint64, C.c_uint32, u64p, u64p]),
         "clg_enrich_batch": (C.c_int, [P, C.c_uint32, C.POINTER(EnrichReq), C.c_uint32, P, P, P, C.c_uint64,

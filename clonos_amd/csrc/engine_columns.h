@@ -3,7 +3,7 @@
 // hidden visibility.  Who defines what:
 //   engine_columns.cpp         decode -> columns: the placement helpers, columnize_device, decode_columns,
 //                              decode_columns_var, gather_payloads_device, wide_row_base, pay_too_small, source_*
-//   engine_pack.cpp            columns -> packed: pack_out_check
+//   engine_pack.cpp            columns -> packed: pack_out_check, decode_columns_packed
 //   engine_encode_columns.cpp  columns -> log bytes, packed -> columns: nothing that another unit calls
 //   here                       ColKeep, DecodeSource and carve
 #pragma once
@@ -68,5 +68,10 @@ DecodeSource source_host(clg_engine* e, const uint8_t* bytes, const uint64_t* sp
 
 // ---- packed outputs and inputs --------------------------------------------------------------
 int pack_out_check(const clg::PackView& out, const char* what = "");  // (a packed input's, too)
+// The packed decodes' one body, which replay preparation's packed form runs over its staged bytes:
+// `run`'s batch as packed narrow columns in `out`, the wide rows plain in `wide` or (wpk) packed,
+// and (var) their payloads from the spans `spans_of` gives.
+int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_columns* wide, clg_payloads* var,
+                          clg_packed* out, const PaySpansOf& spans_of, clg_packed_wide* wpk = nullptr);
 
 #pragma GCC visibility pop

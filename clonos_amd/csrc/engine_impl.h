@@ -132,6 +132,7 @@ struct DevSwitches {
   bool sidecar = env_num("CLONOS_SIDECAR", 1) != 0;           // 0: no Serializable candidate lists (developer A/B)
   bool keep_errors = env_num("CLONOS_KEEP_ERRORS", 1) != 0;   // 0: decode errors not kept on the fast path
   bool columns_small = env_num("CLONOS_COLUMNS_SMALL", 1) != 0;  // 0: no one-launch columns / payloads for small batches
+  bool pack_small = env_num("CLONOS_PACK_SMALL", 1) != 0;        // 0: no one-launch pack of small batches
   uint32_t fused_perturb = uint32_t(env_num("CLONOS_FUSED_PERTURB", 0, 0));  // test switch (FusedCtl::perturb)
   // initial spill arena bytes (tests: force its growth); 0: the default
   size_t jser_arena = getenv("CLONOS_JSER_ARENA") ? std::max<size_t>(256, size_t(env_num("CLONOS_JSER_ARENA", 0, 0))) : 0;
@@ -272,6 +273,9 @@ struct clg_engine {
   // the scan groups' sums, host-output staging; the scans' results (pinned: the kernels write them)
   DevBuf d_wpackin, d_wpackkind, d_wpacksoa, d_wpacktab, d_wpackdesc, d_wpacksum, d_wpackout;
   PinBuf h_wpacktab, h_wpackres;
+  // both packs in one launch: the result block (pinned: the kernel writes it), and desc | bits of a
+  // host caller read back in one copy a half
+  PinBuf h_packsmall, h_packland;
   // packed wide rows as input: staged host input, kind bytes | tile counts | tile bases | tile
   // sums | the verdict words, the per-kind field arrays, the stream table (pinned, then device),
   // host-output staging, the rows and pos for the encode; the totals and the verdict (pinned)

@@ -22,22 +22,33 @@ namespace {
 // capacity check on the scan's total, then the write.  A LogReplayerImpl cursor
 // (LogReplayerImpl.java:61-119) pops one typed value at a time from the blocks.
 
-// Measure and scan over device-side streams: out's results are filled, the descriptors (with
-// their offsets) are left in d_packdesc.
-int pack_sizes(clg_engine* e, const clg::PackSrc& src, clg_packed* out, clg::PackIn* pin) {
+// What either form of the narrow pack starts with, over device-side streams: out's n_val and
+// blk_base are filled, the streams checked and *pin filled from them.
+int pack_prepare(const clg::PackSrc& src, clg_packed* out, clg::PackIn* pin) {
   clg::pack_reset_result(out);
   clg::pack_layout(src.n, out);
   const uint64_t nb = out->blk_base[clg::kPackStreams];
   if (nb >> 31) return fail(CLG_E_INVALID_ARG, "%llu blocks in one call", (unsigned long long)nb);
-  uint64_t in_bytes = 0;
   for (uint32_t c = 0; c < clg::kPackStreams; ++c) {
     if (src.n[c] && !src.col[c]) return fail(CLG_E_INVALID_ARG, "null input array (stream %u)", c);
     if (uintptr_t(src.col[c]) % clg::pack_stream_bytes(c))
       return fail(CLG_E_INVALID_ARG, "stream %u is not aligned to its element", c);
     pin->col[c] = src.col[c], pin->n[c] = src.n[c];
-    in_bytes += src.n[c] * clg::pack_stream_bytes(c);
   }
   for (uint32_t c = 0; c <= clg::kPackStreams; ++c) pin->blk_base[c] = out->blk_base[c];
+  return CLG_OK;
+}
+uint64_t pack_in_bytes(const clg::PackIn& pin) {
+  uint64_t in_bytes = 0;
+  for (uint32_t c = 0; c < clg::kPackStreams; ++c) in_bytes += pin.n[c] * clg::pack_stream_bytes(c);
+  return in_bytes;
+}
+
+// The multi-kernel form's measure and scan, after pack_prepare: out->n_bits is filled, the
+// descriptors (with their offsets) are left in d_packdesc.
+int pack_sizes(clg_engine* e, clg_packed* out, const clg::PackIn* pin) {
+  const uint64_t nb = out->blk_base[clg::kPackStreams];
+  const uint64_t in_bytes = pack_in_bytes(*pin);
   const uint64_t ng = (nb + clg::kPackScanGroup - 1) / clg::kPackScanGroup;
   CHK(e->d_packdesc.ensure(size_t(nb) * sizeof(clg_pack_block) + 64));
   CHK(e->d_packsum.ensure(size_t(ng) * 8 + 64));
@@ -172,13 +183,153 @@ int wpack_write(clg_engine* e, const clg_packed_wide* out) {
   return pack_write(e, clg::pack_view(*out), e->d_wpackout, "pack_wide", out->n_val[CLG_WPACK_KIND] * 34, launch);
 }
 
+// ---- both packs in one launch of one workgroup (k_pack_small) ----------------------------------
+// A narrow input of at most kPackSmallBlocks blocks and at most kWPackSmallRows wide rows, either
+// or both: the kernel measures, scans, does the checks above itself and reports them in pinned
+// memory, and writes.  One launch and one host sync (two for outputs the engine stages, whose
+// size is known only then), where the multi-kernel forms take five and eight launches and two
+// syncs each.  Every batch that the one-launch columns and payload forms take is taken here too.
+static_assert(clg::kPackSmallBlocks >= (clg::kColSmallRecords + clg::kPackBlock - 1) / clg::kPackBlock +
+                                           clg::kColSmallRecords / clg::kPackBlock + 4,
+              "kPackSmallBlocks holds the five streams of kColSmallRecords records");
+static_assert(clg::kWPackSmallRows >= clg::kPaySmallRows, "kWPackSmallRows holds the one-launch payload form's rows");
+
+bool pack_small_takes(const clg_engine* e, const clg_packed& out) {
+  return e->sw.pack_small && out.blk_base[clg::kPackStreams] <= clg::kPackSmallBlocks;
+}
+bool wpack_small_takes(const clg_engine* e, uint64_t n_wide) { return e->sw.pack_small && n_wide <= clg::kWPackSmallRows; }
+
+// Where the kernel writes one half: the caller's device arrays, the device side of registered host
+// arrays, or engine staging (desc | bits in one piece) of at most blocks_bound descriptors and
+// bits_bound payload bytes.  The registry is asked for each array's capacity: the lengths are
+// known only after the one launch.
+int pack_small_place(const clg::PackView& v, DevBuf& staging, uint64_t blocks_bound, uint64_t bits_bound,
+                     clg::PackSmallOut* o) {
+  *o = clg::PackSmallOut{};
+  if (clg::pack_sizes_only(v)) return CLG_OK;
+  o->write = 1;
+  const uint64_t cap_desc = v.desc ? v.cap_desc : 0, cap_bits = v.bits ? v.cap_bits : 0;
+  // (CLG_MEM_MAPPED: a caller whose stated capacity passes the end of its registered range is staged
+  // and copied, where the multi-kernel form, which knows the lengths by then, writes in place)
+  const PlaceSpec dst[2] = {{v.desc, cap_desc * sizeof(clg_pack_block), 8}, {v.bits, cap_bits, 16}};
+  clg::Placement pl;
+  CHK(place_arrays(dst, 2, v.out_kind, PlacePolicy::stage_if_unresolved, "packed", &pl));
+  if (!pl.staged()) {
+    o->desc = pl.at<clg_pack_block>(0), o->bits = pl.at<uint8_t>(1);
+    o->cap_desc = cap_desc, o->cap_bits = cap_bits;
+    return CLG_OK;
+  }
+  o->cap_desc = std::min(cap_desc, blocks_bound), o->cap_bits = std::min(cap_bits, bits_bound);
+  CHK(staging.ensure(o->cap_desc * sizeof(clg_pack_block) + o->cap_bits + 16));
+  o->desc = staging.as<clg_pack_block>();
+  o->packed = 1;
+  return CLG_OK;
+}
+
+// pin, nout: the narrow half after pack_prepare (null: none).  wsrc, wout: the wide half, at least
+// one row (null: none).  hold: nothing is written whatever the outputs say, and every size is still
+// filled.  *short_cap (optional): the first capacity that is (hold: would be) short, as
+// PackSmallRes has it.
+struct PackSmallCall {
+  const clg::PackIn* pin = nullptr;
+  clg_packed* nout = nullptr;
+  const clg::WPackSrc* wsrc = nullptr;
+  clg_packed_wide* wout = nullptr;
+  bool hold = false;
+};
+int pack_small(clg_engine* e, const PackSmallCall& c, uint32_t* short_cap = nullptr) {
+  clg::PackSmallArgs a{};
+  const uint64_t nw = c.wsrc ? c.wsrc->n_wide : 0;
+  uint64_t moved = 0;
+  if (c.pin) a.narrow = *c.pin, moved += 2 * pack_in_bytes(*c.pin);
+  if (c.wsrc) {
+    a.wide = *c.wsrc;
+    CHK(e->d_wpackkind.ensure(nw + 16));
+    CHK(e->d_wpacksoa.ensure(clg::wpack_soa_field(clg::kWPackFields, nw) + 16));
+    a.d_kind = e->d_wpackkind.as<uint8_t>(), a.d_soa = e->d_wpacksoa.as<uint8_t>();
+    moved += nw * (6 + 1 + 29 + 29 + 34 + 34);  // (kinds, the split in and out, the streams read twice)
+  }
+  a.sizes_only = c.hold ? 1u : 0u;
+  clg::PackView nv{}, wv{};
+  if (c.pin) {
+    nv = clg::pack_view(*c.nout);
+    CHK(pack_small_place(nv, e->d_packout, nv.blocks(), clg::pack_bits_bound_narrow(c.pin->n), &a.out_narrow));
+  }
+  if (c.wsrc) {
+    wv = clg::pack_view(*c.wout);
+    CHK(pack_small_place(wv, e->d_wpackout, clg::wpack_blocks_bound(nw), clg::wpack_bits_bound(nw), &a.out_wide));
+  }
+  CHK(e->h_packsmall.ensure(sizeof(clg::PackSmallRes)));
+  clg::PackSmallRes* res = e->h_packsmall.as<clg::PackSmallRes>();
+  e->stats["pack_small"].launches++;
+  // The launch's time stands under the stat of the half that is most of it: the wide rows' where
+  // there are any (kinds, split and 26 streams against five), else the narrow columns'.
+  const bool timed_wide = c.wsrc != nullptr;
+  CHK(e->timed(timed_wide ? "pack_wide" : "pack_columns", moved, [&] { return clg::launch_pack_small(a, res, e->stream); }));
+  CHK(e->sync());
+  if (e->cfg.flags & CLG_F_TIMING) {
+    // `launches` of the two stats is a count of passes, not of kernels: the multi-kernel forms time
+    // sizes and write of the narrow half and kinds, sizes and write of the wide one as a section
+    // each.  The one launch did the same passes; the one above is timed, the others are counted here
+    // with no time of their own, so that a reader of either stat sees the work that was done for
+    // that half.  How many real launches there were is `pack_small`.
+    const bool wrote = res->verdict == clg::kPackSmallWritten;
+    if (c.pin) e->stats["pack_columns"].launches += (timed_wide ? 1 : 0) + (wrote && a.out_narrow.write ? 1 : 0);
+    if (c.wsrc) e->stats["pack_wide"].launches += 1 + (wrote && a.out_wide.write ? 1 : 0);
+  }
+  if (short_cap) *short_cap = res->short_cap;
+  if (res->verdict == clg::kPackSmallBadRow) {
+    c.wout->bad_row = res->bad_row;
+    return fail(CLG_E_INVALID_ARG, "packed wide rows: row %llu's w_idx or tag is not a wide record's", (unsigned long long)res->bad_row);
+  }
+  if (res->verdict > clg::kPackSmallCapacity) return fail(CLG_E_DEVICE, "the one-launch pack's verdict is %u", res->verdict);
+  if (c.pin) c.nout->n_bits = res->n_bits[0];
+  if (c.wsrc) {
+    if (res->tot[0] + res->tot[1] + res->tot[2] + res->tot[3] != nw) return fail(CLG_E_DEVICE, "packed wide rows: the kinds' totals do not sum to the rows");
+    clg::wpack_layout(nw, res->tot, c.wout);
+    c.wout->n_bits = res->n_bits[1];
+  }
+  if (res->verdict == clg::kPackSmallCapacity) {
+    const bool narrow = res->short_cap < 2;
+    const clg::PackView& v = narrow ? nv : wv;
+    const char* name = res->short_cap & 1 ? "bits" : "desc";
+    if (!clg::pack_short(v)) return fail(CLG_E_DEVICE, "the one-launch pack's staging is too small (%s)", name);
+    return pack_capacity_error(v, narrow ? "packed columns" : "packed wide rows", name);
+  }
+  if (res->verdict != clg::kPackSmallWritten) return CLG_OK;
+  // staged halves come back in one copy each: desc | bits, exactly what was written
+  const clg::PackSmallOut* so[2] = {&a.out_narrow, &a.out_wide};
+  const clg::PackView* vs[2] = {&nv, &wv};
+  uint64_t bytes[2] = {0, 0}, at[2] = {0, 0}, total = 0;
+  for (int h = 0; h < 2; ++h)
+    if (so[h]->write && so[h]->packed) {
+      bytes[h] = vs[h]->blocks() * sizeof(clg_pack_block) + *vs[h]->n_bits;
+      at[h] = total, total += (bytes[h] + 15) & ~uint64_t(15);
+    }
+  if (!total) return CLG_OK;
+  CHK(e->h_packland.ensure(total));
+  for (int h = 0; h < 2; ++h)
+    if (bytes[h]) HIPCHK(hipMemcpyAsync(e->h_packland.as<uint8_t>() + at[h], so[h]->desc, bytes[h], hipMemcpyDeviceToHost, e->stream));
+  CHK(e->sync());
+  for (int h = 0; h < 2; ++h)
+    if (bytes[h]) {
+      const uint64_t db = vs[h]->blocks() * sizeof(clg_pack_block);
+      const uint8_t* land = e->h_packland.as<uint8_t>() + at[h];
+      if (db) memcpy(const_cast<clg_pack_block*>(vs[h]->desc), land, db);
+      if (*vs[h]->n_bits) memcpy(const_cast<uint8_t*>(vs[h]->bits), land + db, *vs[h]->n_bits);
+    }
+  return CLG_OK;
+}
+
+}  // namespace
+
 // The decode into engine scratch and the columns of what it produced, also in engine scratch;
 // then the pack, the wide rows as they are and (var) the payload column of the same rows.
 // Every size is known before anything is written to the caller.  wpk (the packed-wide decodes):
 // the wide rows are delivered packed as well and no plain row is copied to the caller; `wide` then
 // carries only sizes, and var may come without pos, which is the prefix sum of w_var_len.
 int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_columns* wide, clg_payloads* var,
-                          clg_packed* out, const PaySpansOf& spans_of, clg_packed_wide* wpk = nullptr) {
+                          clg_packed* out, const PaySpansOf& spans_of, clg_packed_wide* wpk) {
   if (wide->tag || wide->order || wide->timestamp || wide->rng || wide->buffer_built)
     return fail(CLG_E_INVALID_ARG, "the narrow column pointers of `wide` must be NULL: those columns are delivered packed");
   if (wpk)
@@ -229,10 +380,14 @@ int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_c
   // every size, before anything is written to the caller
   const clg::PackSrc src{{full.tag, full.order, full.timestamp, full.rng, full.buffer_built}, {nr, tot[0], tot[1], tot[2], tot[3]}};
   clg::PackIn pin{};
-  CHK(pack_sizes(e, src, out, &pin));
-  if (wpk)
-    CHK(wpack_sizes(e, clg::WPackSrc{full.tag, full.w_idx, full.w_rc, full.w_v1, full.w_var_off, full.w_var_len, full.w_sub, full.w_v0, nr, nw},
-                    wpk));
+  CHK(pack_prepare(src, out, &pin));
+  const clg::WPackSrc wsrc{full.tag, full.w_idx, full.w_rc, full.w_v1, full.w_var_off, full.w_var_len, full.w_sub, full.w_v0, nr, nw};
+  // a small batch: k_pack_small sizes, checks and writes both halves, once the other checks are made
+  const bool small = pack_small_takes(e, *out) && (!wpk || wpack_small_takes(e, nw));
+  if (!small) {
+    CHK(pack_sizes(e, out, &pin));
+    if (wpk) CHK(wpack_sizes(e, wsrc, wpk));
+  }
   int ps = CLG_OK;
   std::vector<clg::PaySpan> spans;
   std::vector<uint32_t> segtab;
@@ -247,20 +402,35 @@ int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_c
   for (int i = w0; i < w1; ++i) wide_any = wide_any || clg::col_ptr(*wide, i);
   for (int i = w0; i < w1; ++i) wide_short = wide_short || (wide_any && clg::col_array_cap(*wide, i) < nw);
   const clg::PackView pv = clg::pack_view(*out), wpv = wpk ? clg::pack_view(*wpk) : clg::PackView{};
-  const char* pk_short = clg::pack_sizes_only(pv) ? nullptr : clg::pack_short(pv);
-  const char* wpk_short = wpk && !clg::pack_sizes_only(wpv) ? clg::pack_short(wpv) : nullptr;
   const char* pay_short = !var || ps != CLG_OK || clg::pay_sizes_only(*var) ? nullptr
                           : !no_pos                                         ? clg::pay_short(*var, var->n_rows, var->n_var)
                           : var->cap_var < var->n_var                       ? "var"
                                                                             : nullptr;
+  const char *pk_short = nullptr, *wpk_short = nullptr;
+  if (small) {
+    // The one launch, last of the checks: it fills every size, and writes unless a check before it
+    // failed (then it is held to its sizes) or one of its own does.
+    PackSmallCall c;
+    c.pin = &pin, c.nout = out;
+    if (wpk && nw) c.wsrc = &wsrc, c.wout = wpk;
+    c.hold = wide_short || pay_short;
+    uint32_t short_cap = clg::kPackSmallShortNone;
+    CHK(pack_small(e, c, &short_cap));  // (its own capacity error, when it was not held)
+    const char* name = short_cap & 1 ? "bits" : "desc";
+    if (short_cap < 2) pk_short = name;
+    else if (short_cap < clg::kPackSmallShortNone) wpk_short = name;
+  } else {
+    pk_short = clg::pack_sizes_only(pv) ? nullptr : clg::pack_short(pv);
+    wpk_short = wpk && !clg::pack_sizes_only(wpv) ? clg::pack_short(wpv) : nullptr;
+  }
   if (wide_short) return fail(CLG_E_CAPACITY, "the wide rows' arrays are too small (rows %llu)", (unsigned long long)nw);
   if (pk_short) return pack_capacity_error(pv, "packed columns", pk_short);
   if (wpk_short) return pack_capacity_error(wpv, "packed wide rows", wpk_short);
   if (pay_short) return pay_too_small(pay_short, var->n_rows, var->n_var);
 
   // the writes
-  if (!clg::pack_sizes_only(pv)) CHK(pack_write(e, pin, out));
-  if (wpk && !clg::pack_sizes_only(wpv)) CHK(wpack_write(e, wpk));
+  if (!small && !clg::pack_sizes_only(pv)) CHK(pack_write(e, pin, out));
+  if (!small && wpk && !clg::pack_sizes_only(wpv)) CHK(wpack_write(e, wpk));
   if (wide_any && nw) {
     for (int i = w0; i < w1; ++i)
       CHK(copy_caller(e, clg::col_ptr(*wide, i), clg::col_ptr(full, i), nw * clg::kColArray[i].width, hipMemcpyDefault,
@@ -277,8 +447,6 @@ int decode_columns_packed(clg_engine* e, const DecodeRun& run, uint32_t n, clg_c
   }
   return ps;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -299,7 +467,13 @@ int clg_pack_columns(clg_engine* e, const clg_columns* in, clg_packed* out) {
   if (st != CLG_OK) return clg::pack_layout(src.n, out), st;  // (a misaligned stream: the layout is filled, as pack_sizes fills it)
   for (uint32_t c = 0; c < clg::kPackStreams; ++c) src.col[c] = pl.at<const void>(c);
   clg::PackIn pin{};
-  CHK(pack_sizes(e, src, out, &pin));
+  CHK(pack_prepare(src, out, &pin));
+  if (pack_small_takes(e, *out)) {
+    PackSmallCall c;
+    c.pin = &pin, c.nout = out;
+    return pack_small(e, c);
+  }
+  CHK(pack_sizes(e, out, &pin));
   return pack_finish(clg::pack_view(*out), "packed columns", [&] { return pack_write(e, pin, out); });
 }
 
@@ -320,6 +494,11 @@ int clg_pack_wide(clg_engine* e, const clg_columns* in, clg_packed_wide* out) {
   const clg::WPackSrc src{pl.at<const uint8_t>(0),  pl.at<const uint32_t>(1), pl.at<const int32_t>(2), pl.at<const int64_t>(3),
                           pl.at<const uint32_t>(4), pl.at<const uint32_t>(5), pl.at<const uint8_t>(6), pl.at<const int64_t>(7),
                           nr,                       nw};
+  if (nw && wpack_small_takes(e, nw)) {
+    PackSmallCall c;
+    c.wsrc = &src, c.wout = out;
+    return pack_small(e, c);
+  }
   CHK(wpack_sizes(e, src, out));
   return pack_finish(clg::pack_view(*out), "packed wide rows", [&] { return wpack_write(e, out); });
 }

@@ -4,6 +4,7 @@
 // (clg_enrich_batch, clg_process_delta).
 #include "engine_columns.h"
 #include "columns.h"
+#include "pack_wide.h"
 
 extern "C" {
 
@@ -117,6 +118,41 @@ int clg_replay_prepare_columns(clg_engine* e, const clg_replay_vertex* v, uint32
 }
 int clg_replay_prepare_columns_device(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_columns_out* out) {
   return replay_prepare_columns(e, v, n, out, true);
+}
+
+}  // extern "C"
+
+// The packed form: the main step is the packed decodes' body (decode_columns_packed) over the
+// staged bytes, with the staged spans for the payload gather as above.
+static int replay_prepare_packed(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_packed_out* out, bool dev_in) {
+  ENGINE_GUARD(e);
+  if (!out || !out->sizes || !out->narrow || (n && !v)) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::col_reset_result(out->sizes);
+  clg::pack_reset_result(out->narrow);
+  if (out->wide) clg::wpack_reset_result(out->wide);
+  if (out->var) clg::pay_reset_result(out->var);
+  const ReplaySubOut so{out->buffer_sizes, out->sizes_cap,   out->sizes_base, out->sub_count,
+                        out->sub_status,   out->sub_err_off, out->sub_err_tag};
+  return replay_prepare(
+      e, v, n, &so, dev_in, true, [&](const ReplayBuild& build, uint64_t main_bytes, const std::vector<clg::PaySpan>& staged) {
+        const auto run = [&](clg_decoded* d, uint64_t* base) { return e->decode(build, main_bytes, d, base); };
+        return decode_columns_packed(
+            e, run, n, out->sizes, out->var, out->narrow,
+            [&](std::vector<clg::PaySpan>& spans, std::vector<uint32_t>&) {
+              spans = staged;
+              return CLG_OK;
+            },
+            out->wide);
+      });
+}
+
+extern "C" {
+
+int clg_replay_prepare_columns_packed(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_packed_out* out) {
+  return replay_prepare_packed(e, v, n, out, false);
+}
+int clg_replay_prepare_columns_packed_device(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_packed_out* out) {
+  return replay_prepare_packed(e, v, n, out, true);
 }
 
 }  // extern "C"

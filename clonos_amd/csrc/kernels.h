@@ -767,6 +767,40 @@ int launch_wpack_split_measure(const WPackSrc& src, uint32_t n_tiles, const uint
 int launch_wpack_write(const WPackTab* d_tab, uint32_t n_blocks, const clg_pack_block* d_desc, clg_pack_block* out_desc,
                        uint8_t* bits, uint64_t lim_desc, uint64_t lim_bits, void* stream);
 
+// ---- both packs in one launch of one workgroup (pack.h, pack_wide.h, pack_small.hip) ------------
+// A narrow input of at most kPackSmallBlocks blocks and at most kWPackSmallRows wide rows, either
+// or both: every pass of the two multi-kernel forms and the host's checks between them.
+struct PackSmallOut {  // one half's output and usable capacities (0 for a null array)
+  clg_pack_block* desc;
+  uint8_t* bits;  // packed: ignored, the payloads follow the descriptors at desc + blocks
+  uint64_t cap_desc, cap_bits;
+  uint32_t write;   // 0: this half is sizes only (or absent)
+  uint32_t packed;  // engine staging, desc | bits in one piece
+};
+struct PackSmallArgs {
+  PackIn narrow;   // n all zero: no narrow half
+  WPackSrc wide;   // n_wide 0: no wide half
+  uint8_t* d_kind;  // engine scratch: n_wide kind bytes, and the per-kind field arrays
+  uint8_t* d_soa;   // (wpack_soa_field's layout, 16-byte aligned)
+  PackSmallOut out_narrow, out_wide;
+  uint32_t sizes_only;  // nothing is written, whatever the outputs say
+};
+enum : uint32_t {
+  kPackSmallWritten = 0,   // every half with `write` set is written
+  kPackSmallSizes = 1,     // sizes_only, or no half to write
+  kPackSmallBadRow = 2,    // bad_row; no size of the wide half is filled
+  kPackSmallCapacity = 3,  // short_cap
+};
+enum : uint32_t { kPackSmallShortNone = 4 };  // short_cap: 0 narrow desc, 1 narrow bits, 2 wide desc, 3 wide bits
+struct PackSmallRes {  // pinned memory; with any verdict but kPackSmallWritten nothing is written
+  uint64_t n_bits[2];  // narrow, wide
+  uint64_t tot[4];     // the kinds' totals
+  uint64_t bad_row;    // ~0: none
+  uint32_t verdict;
+  uint32_t short_cap;  // the first short capacity (also filled with kPackSmallSizes), or kPackSmallShortNone
+};
+int launch_pack_small(const PackSmallArgs& a, PackSmallRes* res, void* stream);
+
 // ---- packed typed columns as input (pack.h, unpack.hip) -----------------------------
 struct UnpackIn {  // device addresses of a clg_packed read as input, after the host's layout check
   const clg_pack_block* desc;

@@ -138,6 +138,35 @@ CLG_PACK_HD uint32_t pack_payload_bytes(uint32_t k, uint32_t width) {
 }
 CLG_PACK_HD uint64_t pack_blocks(uint64_t n) { return (n + kPackBlock - 1) / kPackBlock; }
 
+// ---- the one-launch form (pack_small.hip) ------------------------------------------------------
+// A narrow input of at most kPackSmallBlocks blocks is packed by one launch of one workgroup
+// (k_pack_small).  The floor is what five streams of the one-launch columns form's largest batch
+// (columns.h kColSmallRecords = 32 769 records) can hold: 33 tag blocks and 32 + 4 of the other
+// four; the engine asserts it.
+constexpr uint32_t kPackSmallBlocks = 69;
+
+// The widest residual a block of (elem, scheme) can hold, in bits.  FOR: the element's.  DELTA: a
+// difference of two values of a narrow element needs one bit more than the element (a zero-extended
+// u32 gives residuals from -(2^32 - 1) to 2^32 - 1: 33 bits); of i64 it wraps inside 64.
+CLG_PACK_HD uint32_t pack_width_bound(uint32_t elem, bool delta) {
+  const uint32_t bits = 8u * pack_elem_bytes(elem);
+  return delta && bits < 64 ? bits + 1 : bits;
+}
+// The payload bytes of a stream of n values of (elem, scheme), at most: what the one-launch form
+// sizes its staging by before anything is measured.
+CLG_PACK_HD uint64_t pack_bits_bound(uint32_t elem, bool delta, uint64_t n) {
+  const uint32_t w = pack_width_bound(elem, delta);
+  const uint64_t whole = n / kPackBlock;
+  const uint32_t rest = uint32_t(n % kPackBlock);
+  return whole * pack_payload_bytes(pack_residuals(delta, kPackBlock), w) + pack_payload_bytes(pack_residuals(delta, rest), w);
+}
+// ... of the five narrow streams of lengths n.
+CLG_PACK_HD uint64_t pack_bits_bound_narrow(const uint64_t n[kPackStreams]) {
+  uint64_t b = 0;
+  for (uint32_t c = 0; c < kPackStreams; ++c) b += pack_bits_bound(pack_stream_elem(c), pack_is_delta(c), n[c]);
+  return b;
+}
+
 // The five input arrays and their lengths, from a clg_columns.
 struct PackSrc {
   const void* col[kPackStreams];

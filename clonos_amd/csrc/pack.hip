@@ -38,12 +38,6 @@ __device__ __forceinline__ uint32_t pack_stream_of(const PackIn& in, uint64_t bl
   return uint32_t(blk >= in.blk_base[1]) + uint32_t(blk >= in.blk_base[2]) + uint32_t(blk >= in.blk_base[3]) +
          uint32_t(blk >= in.blk_base[4]);
 }
-// The block's place in its stream.
-__device__ __forceinline__ PackAt pack_at(const void* col, uint64_t n, uint64_t base, uint64_t blk) {
-  const uint64_t i0 = (blk - base) * kPackBlock;
-  const uint64_t left = i0 < n ? n - i0 : 0;
-  return PackAt{col, i0, uint32_t(left < kPackBlock ? left : kPackBlock)};
-}
 // pack_dev.h's bodies are instantiated per stream (the element and the scheme are kPackStream's
 // constants) and the argument arrays are only ever indexed by constants.
 #define CLG_PACK_CASE(c, in, blk, body, ...) \
@@ -62,7 +56,7 @@ __device__ __forceinline__ PackAt pack_at(const void* col, uint64_t n, uint64_t 
 __global__ __launch_bounds__(kPackThreads) void k_pack_measure(const PackIn in, clg_pack_block* __restrict__ desc) {
   __shared__ int64_t s_x[kPackBlock];  // the block's values: the DELTA predecessors
   __shared__ int64_t s_lo[kPackWaves], s_hi[kPackWaves];
-  CLG_PACK_DISPATCH(in, blockIdx.x, pack_block_measure, desc, s_x, s_lo, s_hi)
+  CLG_PACK_DISPATCH(in, blockIdx.x, pack_block_measure, desc + blockIdx.x, s_x, s_lo, s_hi)
 }
 
 __global__ __launch_bounds__(kPackThreads) void k_pack_scan_sums(const clg_pack_block* __restrict__ desc, uint32_t n_blocks,

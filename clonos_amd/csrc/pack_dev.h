@@ -55,13 +55,21 @@ struct PackAt {
   uint64_t i0;
   uint32_t m;
 };
+// Block blk of a stream of n values in col whose first block is `base`.
+__device__ __forceinline__ PackAt pack_at(const void* col, uint64_t n, uint64_t base, uint64_t blk) {
+  const uint64_t i0 = (blk - base) * kPackBlock;
+  const uint64_t left = i0 < n ? n - i0 : 0;
+  return PackAt{col, i0, uint32_t(left < kPackBlock ? left : kPackBlock)};
+}
 // The measure: four coalesced values a thread, the DELTA predecessor through LDS (s_x: kPackBlock
 // words), the residuals' signed minimum and maximum by the wave reduction and LDS across the waves
 // (s_lo, s_hi: a word a wave); thread 0 writes ref, first, width, count and, in pos, the payload's
-// size to desc[blockIdx.x].  The element and the scheme are constants in each instance.
+// size to *slot (global memory or LDS).  The element and the scheme are constants in each instance.
+// A caller that measures block after block in one workgroup puts a __syncthreads between two
+// calls: thread 0 reads s_lo and s_hi last.
 template <uint32_t kElem, bool kDelta>
-__device__ __forceinline__ void pack_block_measure(const PackAt at, clg_pack_block* __restrict__ desc, int64_t* s_x,
-                                                   int64_t* s_lo, int64_t* s_hi) {
+__device__ __forceinline__ void pack_block_measure(const PackAt at, clg_pack_block* slot, int64_t* s_x, int64_t* s_lo,
+                                                   int64_t* s_hi) {
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   int64_t x[kPackPerThread];
 #pragma unroll
@@ -101,7 +109,7 @@ __device__ __forceinline__ void pack_block_measure(const PackAt at, clg_pack_blo
     d.width = k ? pack_width(uint64_t(hi) - uint64_t(lo)) : 0;
     d.count = at.m;
     d.pos = pack_payload_bytes(k, d.width);  // the size; the scan turns it into the offset
-    desc[blockIdx.x] = d;
+    *slot = d;
   }
 }
 

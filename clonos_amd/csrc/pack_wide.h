@@ -87,13 +87,52 @@ inline void wpack_reset_result(clg_packed_wide* out) {
   out->n_bits = 0;
   out->bad_row = ~0ull;
 }
-// n_val and blk_base from the rows and the kinds' totals.
-inline void wpack_layout(uint64_t n_wide, const uint64_t tot[kWPackKinds], clg_packed_wide* out) {
-  out->n_val[CLG_WPACK_KIND] = out->n_val[CLG_WPACK_IDX] = n_wide;
+// The 26 streams' lengths and block bases from the rows and the kinds' totals: n_val[26],
+// blk_base[27].  Stated once for the host and for the one-launch form, which lays its table out in LDS.
+CLG_PACK_HD void wpack_layout_streams(uint64_t n_wide, const uint64_t tot[kWPackKinds], uint64_t* n_val, uint64_t* blk_base) {
+  n_val[CLG_WPACK_KIND] = n_val[CLG_WPACK_IDX] = n_wide;
   for (uint32_t t = 0; t < kWPackKinds; ++t)
-    for (uint32_t f = 0; f < kWPackFields; ++f) out->n_val[wpack_stream(t, f)] = tot[t];
-  out->blk_base[0] = 0;
-  for (uint32_t c = 0; c < kWPackStreams; ++c) out->blk_base[c + 1] = out->blk_base[c] + pack_blocks(out->n_val[c]);
+    for (uint32_t f = 0; f < kWPackFields; ++f) n_val[wpack_stream(t, f)] = tot[t];
+  blk_base[0] = 0;
+  for (uint32_t c = 0; c < kWPackStreams; ++c) blk_base[c + 1] = blk_base[c] + pack_blocks(n_val[c]);
+}
+// n_val and blk_base of `out` from the rows and the kinds' totals.
+inline void wpack_layout(uint64_t n_wide, const uint64_t tot[kWPackKinds], clg_packed_wide* out) {
+  wpack_layout_streams(n_wide, tot, out->n_val, out->blk_base);
+}
+
+// ---- the one-launch form (pack_small.hip) ------------------------------------------------------
+// At most kWPackSmallRows rows are packed by one launch of one workgroup (k_pack_small).  The
+// floor is the one-launch payload form's largest batch (payload.h kPaySmallRows); the engine
+// asserts it.
+constexpr uint32_t kWPackSmallRows = 8193;
+// The blocks n_wide rows can make, however the kinds share them: KIND and IDX hold
+// pack_blocks(n_wide) each, and the four kinds' blocks of one field sum to at most
+// (n_wide + 4 * (kPackBlock - 1)) / kPackBlock.
+constexpr uint64_t wpack_kind_blocks_bound(uint64_t n_wide) { return (n_wide + kWPackKinds * (kPackBlock - 1)) / kPackBlock; }
+constexpr uint64_t wpack_blocks_bound(uint64_t n_wide) {
+  return n_wide ? 2 * ((n_wide + kPackBlock - 1) / kPackBlock) + kWPackFields * wpack_kind_blocks_bound(n_wide) : 0;
+}
+constexpr uint32_t kWPackSmallBlocks = uint32_t(wpack_blocks_bound(kWPackSmallRows));
+// The payload bytes n_wide rows can make, however the kinds share them (pack.h's bound per stream;
+// a field's bits once for all rows and a block's padding, below 16 bytes, for every block it can have).
+inline uint64_t wpack_bits_bound(uint64_t n_wide) {
+  if (!n_wide) return 0;
+  uint64_t b = pack_bits_bound(kWPackKindElem, kWPackKindScheme != kPackFor, n_wide) +
+               pack_bits_bound(kWPackIdxElem, kWPackIdxScheme != kPackFor, n_wide);
+  for (uint32_t f = 0; f < kWPackFields; ++f) {
+    const bool delta = kWPackField[f].scheme_kind0 != kPackFor || kWPackField[f].scheme_rest != kPackFor;
+    b += (n_wide * pack_width_bound(kWPackField[f].elem, delta) + 7) / 8 + 16 * wpack_kind_blocks_bound(n_wide);
+  }
+  return b;
+}
+// The one-launch form's per-kind field arrays in engine scratch: a field's four kinds one behind
+// the other in one array of n_wide elements, the fields at 16-byte-aligned offsets in kWPackField's
+// order.  wpack_soa_field(f, n_wide): the field's offset ([kWPackFields]: the end).
+CLG_PACK_HD uint64_t wpack_soa_field(uint32_t field, uint64_t n_wide) {
+  uint64_t at = 0;
+  for (uint32_t f = 0; f < field; ++f) at += (n_wide * pack_elem_bytes(wpack_stream_elem(wpack_stream(0, f))) + 15) & ~uint64_t(15);
+  return at;
 }
 inline PackView pack_view(const clg_packed_wide& p) {
   return PackView{p.desc, p.bits, p.cap_desc, p.cap_bits, p.out_kind, kWPackStreams, p.n_val, p.blk_base, &p.n_bits};

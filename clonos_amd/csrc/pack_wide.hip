@@ -44,17 +44,9 @@ __device__ __forceinline__ PackAt wpack_at(const WPackTab* __restrict__ tab, uin
 __global__ __launch_bounds__(kPackThreads) void k_wpack_kind(const WPackSrc src, uint8_t* __restrict__ kind_out,
                                                             uint32_t* __restrict__ cnt, unsigned long long* __restrict__ bad) {
   uint32_t kind[kPackPerThread];
-#pragma unroll
-  for (uint32_t q = 0; q < kPackPerThread; ++q) {
-    const uint64_t k = uint64_t(blockIdx.x) * kWPackTile + q * kPackThreads + threadIdx.x;
-    kind[q] = kWPackKinds;
-    if (k < src.n_wide) {
-      kind[q] = wpack_kind_of(src.tag, src.n_rec, src.w_idx[k]);
-      if (kind[q] >= kWPackKinds) atomicMin(bad, (unsigned long long)k);
-      kind_out[k] = uint8_t(kind[q]);  // (kWPackKinds: the split passes the row by; the host rejects the call)
-    }
-  }
-  wpack_kind_counts(kind, cnt);
+  const uint64_t mine = wpack_row_kinds(src, blockIdx.x, kind_out, kind);
+  if (mine != ~0ull) atomicMin(bad, (unsigned long long)mine);
+  wpack_kind_counts(kind, cnt, blockIdx.x);
 }
 
 // The tile counts -> d_base, the rows of each kind before the tile; the totals and the bad-row
@@ -82,20 +74,8 @@ __global__ __launch_bounds__(kPackThreads) void k_wpack_split(const WPackSrc src
     const uint64_t k = uint64_t(blockIdx.x) * kWPackTile + q * kPackThreads + threadIdx.x;
     kind[q] = k < src.n_wide ? uint32_t(kind_in[k]) : kWPackKinds;
   }
-  wpack_tile_rank(tab, base, kind, l, r);
-#pragma unroll
-  for (uint32_t q = 0; q < kPackPerThread; ++q) {
-    const uint32_t t = kind[q];
-    if (t >= kWPackKinds || r[q] >= l.n[t]) continue;  // (the latter never, while the kind bytes are what pass 1 counted)
-    const uint64_t k = uint64_t(blockIdx.x) * kWPackTile + q * kPackThreads + threadIdx.x;
-    const uint64_t* col = &l.col[t * kWPackFields];
-    reinterpret_cast<int32_t*>(uintptr_t(col[CLG_WPACK_RC]))[r[q]] = src.w_rc[k];
-    reinterpret_cast<int64_t*>(uintptr_t(col[CLG_WPACK_V1]))[r[q]] = src.w_v1[k];
-    reinterpret_cast<uint32_t*>(uintptr_t(col[CLG_WPACK_VAR_OFF]))[r[q]] = src.w_var_off[k];
-    reinterpret_cast<uint32_t*>(uintptr_t(col[CLG_WPACK_VAR_LEN]))[r[q]] = src.w_var_len[k];
-    reinterpret_cast<uint8_t*>(uintptr_t(col[CLG_WPACK_SUB]))[r[q]] = src.w_sub[k];
-    reinterpret_cast<int64_t*>(uintptr_t(col[CLG_WPACK_V0]))[r[q]] = src.w_v0[k];
-  }
+  wpack_tile_rank(tab, base, blockIdx.x, kind, l, r);
+  wpack_split_rows(src, blockIdx.x, kind, r, l);
 }
 
 __global__ __launch_bounds__(kPackThreads) void k_wpack_measure(const WPackTab* __restrict__ tab,
@@ -104,7 +84,7 @@ __global__ __launch_bounds__(kPackThreads) void k_wpack_measure(const WPackTab* 
   __shared__ int64_t s_lo[kPackWaves], s_hi[kPackWaves];
   const uint32_t s = wpack_stream_of(tab, blockIdx.x);
   const PackAt at = wpack_at(tab, s, blockIdx.x);
-  CLG_WPACK_DISPATCH(s, pack_block_measure, at, desc, s_x, s_lo, s_hi)
+  CLG_WPACK_DISPATCH(s, pack_block_measure, at, desc + blockIdx.x, s_x, s_lo, s_hi)
 }
 
 __global__ __launch_bounds__(kPackThreads) void k_wpack_write(const WPackTab* __restrict__ tab,

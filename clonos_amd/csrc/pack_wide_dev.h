@@ -43,10 +43,32 @@ __device__ __forceinline__ uint32_t wpack_stream_of(const Tab* __restrict__ tab,
     CLG_WPACK_CASE(body, kElemI64, 1, __VA_ARGS__)                    \
   }
 
-// The tile's four kind counts -> cnt[tile * 4 + kind], from the kinds of the thread's four rows
-// (kWPackKinds or above: counted nowhere): ballots per wave, LDS across the waves.  All
-// kPackThreads threads call it; one __syncthreads inside.
-__device__ __forceinline__ void wpack_kind_counts(const uint32_t kind[kPackPerThread], uint32_t* __restrict__ cnt) {
+// The kinds of the thread's four rows of `tile` (row q * kPackThreads + tid of the tile; a row past
+// n_wide and a row without a kind: kWPackKinds), from w_idx against n_rec and the tag; a row's kind
+// byte goes to kind_out (kWPackKinds: the split passes the row by, the call is rejected).  Returns
+// the lowest of the thread's rows that have no kind, ~0 for none.
+__device__ __forceinline__ uint64_t wpack_row_kinds(const WPackSrc& src, uint32_t tile, uint8_t* __restrict__ kind_out,
+                                                    uint32_t kind[kPackPerThread]) {
+  uint64_t bad = ~0ull;
+#pragma unroll
+  for (uint32_t q = 0; q < kPackPerThread; ++q) {
+    const uint64_t k = uint64_t(tile) * kWPackTile + q * kPackThreads + threadIdx.x;
+    kind[q] = kWPackKinds;
+    if (k < src.n_wide) {
+      kind[q] = wpack_kind_of(src.tag, src.n_rec, src.w_idx[k]);
+      if (kind[q] >= kWPackKinds && k < bad) bad = k;
+      kind_out[k] = uint8_t(kind[q]);
+    }
+  }
+  return bad;
+}
+
+// The tile's four kind counts -> cnt[tile * 4 + kind] (global memory or LDS), from the kinds of the
+// thread's four rows (kWPackKinds or above: counted nowhere): ballots per wave, LDS across the
+// waves.  All kPackThreads threads call it; one __syncthreads inside, and a caller that counts tile
+// after tile in one workgroup puts another between two calls.
+__device__ __forceinline__ void wpack_kind_counts(const uint32_t kind[kPackPerThread], uint32_t* __restrict__ cnt,
+                                                  uint32_t tile) {
   __shared__ uint32_t s_cnt[kPackWaves][kWPackKinds];
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint32_t c[kWPackKinds] = {};  // (the wave's counts: the same in every lane)
@@ -63,7 +85,7 @@ __device__ __forceinline__ void wpack_kind_counts(const uint32_t kind[kPackPerTh
     uint32_t s = 0;
 #pragma unroll
     for (uint32_t j = 0; j < kPackWaves; ++j) s += s_cnt[j][tid];
-    cnt[uint64_t(blockIdx.x) * kWPackKinds + tid] = s;
+    cnt[uint64_t(tile) * kWPackKinds + tid] = s;
   }
 }
 
@@ -92,20 +114,21 @@ struct WPackTileLds {
   uint64_t n[kWPackKinds], base[kWPackKinds];
 };
 
-// r[q]: the rank of the thread's row q (row q * kPackThreads + tid of the tile) among all rows of
+// r[q]: the rank of the thread's row q (row q * kPackThreads + tid of `tile`) among all rows of
 // its kind: its tile's base for the kind plus its rank inside the tile (ballot and mbcnt in the
 // wave, LDS across the (quarter, wave) pieces in row order).  A kind of kWPackKinds or above has
-// no rank.  Also fills l.col and l.n from the table.  All kPackThreads threads call it; two
-// __syncthreads inside, the second after l's last write.
+// no rank.  Also fills l.col and l.n from the table (global memory or LDS, as base is).  All
+// kPackThreads threads call it; two __syncthreads inside, the second after l's last write; a
+// caller that ranks tile after tile in one workgroup puts another between two calls.
 template <class Tab>
-__device__ __forceinline__ void wpack_tile_rank(const Tab* __restrict__ tab, const uint64_t* __restrict__ base,
+__device__ __forceinline__ void wpack_tile_rank(const Tab* __restrict__ tab, const uint64_t* __restrict__ base, uint32_t tile,
                                                 const uint32_t kind[kPackPerThread], WPackTileLds& l,
                                                 uint64_t r[kPackPerThread]) {
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid < kWPackKinds * kWPackFields) l.col[tid] = uint64_t(reinterpret_cast<uintptr_t>(tab->col[2 + tid]));
   if (tid < kWPackKinds) {
     l.n[tid] = tab->n[wpack_stream(tid, 0)];
-    l.base[tid] = base[uint64_t(blockIdx.x) * kWPackKinds + tid];
+    l.base[tid] = base[uint64_t(tile) * kWPackKinds + tid];
   }
   uint32_t below[kPackPerThread];
 #pragma unroll
@@ -133,6 +156,25 @@ __device__ __forceinline__ void wpack_tile_rank(const Tab* __restrict__ tab, con
   for (uint32_t q = 0; q < kPackPerThread; ++q) {
     const uint32_t t = kind[q];
     r[q] = t < kWPackKinds ? l.base[t] + l.pre[q * kPackWaves + w][t] + below[q] : 0;
+  }
+}
+
+// The split of a tile, after wpack_tile_rank: the six fields of the thread's four rows to the
+// per-kind arrays (l.col) at the rows' ranks; no store at or past a kind's length.
+__device__ __forceinline__ void wpack_split_rows(const WPackSrc& src, uint32_t tile, const uint32_t kind[kPackPerThread],
+                                                 const uint64_t r[kPackPerThread], const WPackTileLds& l) {
+#pragma unroll
+  for (uint32_t q = 0; q < kPackPerThread; ++q) {
+    const uint32_t t = kind[q];
+    if (t >= kWPackKinds || r[q] >= l.n[t]) continue;  // (the latter never, while the kind bytes are what pass 1 counted)
+    const uint64_t k = uint64_t(tile) * kWPackTile + q * kPackThreads + threadIdx.x;
+    const uint64_t* col = &l.col[t * kWPackFields];
+    reinterpret_cast<int32_t*>(uintptr_t(col[CLG_WPACK_RC]))[r[q]] = src.w_rc[k];
+    reinterpret_cast<int64_t*>(uintptr_t(col[CLG_WPACK_V1]))[r[q]] = src.w_v1[k];
+    reinterpret_cast<uint32_t*>(uintptr_t(col[CLG_WPACK_VAR_OFF]))[r[q]] = src.w_var_off[k];
+    reinterpret_cast<uint32_t*>(uintptr_t(col[CLG_WPACK_VAR_LEN]))[r[q]] = src.w_var_len[k];
+    reinterpret_cast<uint8_t*>(uintptr_t(col[CLG_WPACK_SUB]))[r[q]] = src.w_sub[k];
+    reinterpret_cast<int64_t*>(uintptr_t(col[CLG_WPACK_V0]))[r[q]] = src.w_v0[k];
   }
 }
 

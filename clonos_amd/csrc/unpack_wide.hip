@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kPackThreads) void k_wunpack_kind(const WUnpackTab*
     for (uint32_t q = 0; q < kPackPerThread; ++q)
       if (q < n && v[q] < kWPackKinds) kind[q] = uint32_t(v[q]);
   }
-  wpack_kind_counts(kind, cnt);
+  wpack_kind_counts(kind, cnt, blockIdx.x);
 }
 
 // The tile counts -> base, the rows of each kind before the tile; the totals -> *res.  One
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(kPackThreads) void k_wunpack_merge(const WUnpackTab
     const uint64_t k = uint64_t(blockIdx.x) * kWPackTile + q * kPackThreads + tid;
     kind[q] = k < n_wide ? uint32_t(kind_in[k]) : kWPackKinds;
   }
-  wpack_tile_rank(tab, base, kind, l, rank);
+  wpack_tile_rank(tab, base, blockIdx.x, kind, l, rank);
   uint64_t len_sum = 0;
 #pragma unroll
   for (uint32_t q = 0; q < kPackPerThread; ++q) {

@@ -385,11 +385,17 @@ class ReplayColumns:
 
 
 def prepare_replay_columns(engine: Engine, jobs: Sequence[Tuple[int, DeterminantResponseEvent, Sequence]],
-                           device_input: bool = False, payloads: bool = True) -> ReplayColumns:
+                           device_input: bool = False, payloads: bool = True, packed: bool = False,
+                           pack_wide: bool = False) -> ReplayColumns:
     """clg_replay_prepare_columns over jobs (vertex_id, merged response, subpartition table: a
     LOG_ID array or a sequence of CausalLogID, in the task's order): prepare_replay with the main
     logs delivered as typed columns and, with payloads, the wide rows' payload bytes -- one engine
-    call.  device_input: the responses' bytes are in device memory."""
+    call.  device_input: the responses' bytes are in device memory.  packed=True
+    (clg_replay_prepare_columns_packed): `main` is a PackedColumns, the five narrow columns
+    bit-packed; pack_wide=True with it: the wide rows come packed by kind too (main.wide_packed).
+    replayer(i) pops from either as it does from plain columns."""
+    if pack_wide and not packed:
+        raise ValueError("pack_wide needs packed=True")
     n = len(jobs)
     vs = (_lib.ReplayVertex * max(1, n))()
     tables = []
@@ -413,6 +419,18 @@ def prepare_replay_columns(engine: Engine, jobs: Sequence[Tuple[int, Determinant
     sst = np.zeros(max(1, n_sub), np.int32)
     soff = np.zeros(max(1, n_sub), np.int64)
     stag = np.zeros(max(1, n_sub), np.int32)
+    if packed:  # the outputs sized and finished as the packed decodes' are
+        fn = lib.clg_replay_prepare_columns_packed_device if device_input else lib.clg_replay_prepare_columns_packed
+
+        def call(c, p, pk, wpk=None):
+            out = _lib.ReplayPackedOut(C.pointer(c), C.pointer(p) if p is not None else None, C.pointer(pk),
+                                       C.pointer(wpk) if wpk is not None else None, _np_ptr(sizes), sizes.size,
+                                       _np_ptr(sbase), _np_ptr(cnt), _np_ptr(sst), _np_ptr(soff), _np_ptr(stag))
+            return fn(engine.handle, vs, n, C.byref(out))
+
+        main = engine._decode_packed(call, main_bytes, n, None, True, payloads, pack_wide=pack_wide)
+        return ReplayColumns(main, sizes, sbase[:n_sub], cnt[:n_sub], sst[:n_sub], soff[:n_sub], stag[:n_sub],
+                             [int(j[0]) for j in jobs], tables)
     fn = lib.clg_replay_prepare_columns_device if device_input else lib.clg_replay_prepare_columns
     arrs = engine._column_bounds(main_bytes, n)
     var, pos = engine._payload_bounds(main_bytes, n) if payloads else (None, None)

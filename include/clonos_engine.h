@@ -958,6 +958,36 @@ int clg_replay_prepare_columns(clg_engine* e, const clg_replay_vertex* v, uint32
 int clg_replay_prepare_columns_device(clg_engine* e, const clg_replay_vertex* v, uint32_t n,
                                       clg_replay_columns_out* out);
 
+/* Replay preparation that delivers the main logs as packed typed columns: what a recovering task
+ * calls to get the blocks its cursor pops one typed value at a time from.  Lookup, staging, the
+ * subpartition kernels and every subpartition output are clg_replay_prepare's; the main step is
+ * clg_decode_host_columns_packed over the staged bytes (with `wide`:
+ * clg_decode_host_columns_packed_wide), and statuses, decode errors and capacities are that
+ * call's: with a decode error each vertex's records up to its first error are packed, the error
+ * fields of `sizes` are filled and the decode's status is returned; on CLG_E_CAPACITY every size is
+ * filled and nothing is written.  The sizes_cap check comes first; the subpartition outputs are
+ * complete whenever the call got past it.  An absent main log is an empty span; n == 0 is valid.
+ * A batch within the one-launch limits (at most 69 narrow blocks and 8 193 wide rows) is packed by
+ * one kernel launch. */
+typedef struct clg_replay_packed_out {
+  clg_columns* sizes;      /* totals, span_base ((n + 1) * 5 host entries or NULL), error fields; the narrow
+                              pointers NULL; with `wide` every column pointer NULL, else the seven w_* arrays plain */
+  clg_payloads* var;       /* the wide rows' payloads; NULL: none; with `wide`, pos may be NULL */
+  clg_packed* narrow;      /* the five narrow columns, packed */
+  clg_packed_wide* wide;   /* the wide rows, packed; NULL: plain in `sizes` */
+  int32_t* buffer_sizes;   /* from here on exactly clg_replay_out's subpartition fields */
+  uint64_t sizes_cap;
+  uint64_t* sizes_base;
+  uint64_t* sub_count;
+  int32_t* sub_status;
+  int64_t* sub_err_off;
+  int32_t* sub_err_tag;
+} clg_replay_packed_out;   /* 88 bytes */
+int clg_replay_prepare_columns_packed(clg_engine* e, const clg_replay_vertex* v, uint32_t n, clg_replay_packed_out* out);
+/* ... with every response entry's bytes in device memory (clg_replay_prepare_device's rules). */
+int clg_replay_prepare_columns_packed_device(clg_engine* e, const clg_replay_vertex* v, uint32_t n,
+                                             clg_replay_packed_out* out);
+
 /* getDeterminants(start_epoch[i]) of log[i] (:285-313) for n logs -- the copies
  * respondToDeterminantRequest answers with (JobCausalLogImpl.java:188-204) -- gathered by ONE
  * kernel back to back in request order into `out` (host or device); len[i] and out_off[i]

@@ -1106,6 +1106,119 @@ JNIEXPORT jint JNICALL FN(nReplayPrepareColumns)(JNIEnv* env, jclass cls, jlong 
   return s;
 }
 
+/* nReplayPrepare with the main log delivered as packed typed columns (clg_replay_prepare_columns_packed):
+ * nReplayPrepare's inputs, then nDecodeLogsColumnsPackedWide's output buffers (every buffer null: the
+ * sizes of both packed forms and of the payload bytes), its result array (80 longs) and its span-base array
+ * ((1 + 1) * 5 longs), then `sizes` and sub_res as in nReplayPrepare. */
+JNIEXPORT jint JNICALL FN(nReplayPrepareColumnsPacked)(JNIEnv* env, jclass cls, jlong e, jshort vertex, jobjectArray bufs,
+                                                       jintArray lens, jlongArray subparts, jobject desc, jobject bits,
+                                                       jobject wdesc, jobject wbits, jobject var, jboolean with_payloads,
+                                                       jlongArray res, jlongArray span_base, jobject sizes,
+                                                       jlongArray sub_res) {
+  (void)cls;
+  const jsize ns = (*env)->GetArrayLength(env, subparts) / 3;
+  jlong* sp = (*env)->GetLongArrayElements(env, subparts, NULL);
+  jint* ln = (*env)->GetIntArrayElements(env, lens, NULL);
+  jlong* base = (*env)->GetLongArrayElements(env, span_base, NULL);
+  clg_response_entry* ents = (clg_response_entry*)calloc((size_t)ns + 1u, sizeof(clg_response_entry));
+  clg_causal_log_id* ids = (clg_causal_log_id*)calloc((size_t)ns + 1u, sizeof(clg_causal_log_id));
+  uint64_t* sbase = (uint64_t*)calloc((size_t)ns + 1u, 8);
+  uint64_t* cnt = (uint64_t*)calloc((size_t)ns + 1u, 8);
+  int32_t* sst = (int32_t*)calloc((size_t)ns + 1u, 4);
+  int64_t* soff = (int64_t*)calloc((size_t)ns + 1u, 8);
+  int32_t* stg = (int32_t*)calloc((size_t)ns + 1u, 4);
+  clg_response acc;
+  memset(&acc, 0, sizeof acc);
+  acc.found = 1;
+  acc.vertex_id = vertex;
+  acc.entries = ents;
+  acc.cap = (uint32_t)ns + 1u;
+  int s = CLG_OK;
+  for (jsize i = 0; i <= ns && s == CLG_OK; ++i) {
+    jobject b = (*env)->GetObjectArrayElement(env, bufs, i);
+    clg_causal_log_id id;
+    memset(&id, 0, sizeof id);
+    id.vertex_id = vertex;
+    id.is_main = i == 0;
+    if (i > 0) {
+      id.irp_lower = sp[3 * (i - 1)];
+      id.irp_upper = sp[3 * (i - 1) + 1];
+      id.subpartition = (int8_t)sp[3 * (i - 1) + 2];
+      ids[i - 1] = id;
+    }
+    if (b) {
+      s = clg_response_put(&acc, &id, addr(env, b, 0), (uint64_t)(uint32_t)ln[i]);
+      (*env)->DeleteLocalRef(env, b);
+    }
+  }
+  clg_columns c;
+  memset(&c, 0, sizeof c);
+  c.span_base = (uint64_t*)base;
+  c.out_kind = CLG_MEM_HOST;
+  clg_payloads p;
+  memset(&p, 0, sizeof p);
+  p.var = addr(env, var, 0);
+  p.cap_var = cap(env, var);
+  p.out_kind = CLG_MEM_HOST;
+  clg_packed k;
+  memset(&k, 0, sizeof k);
+  k.desc = (clg_pack_block*)addr(env, desc, 0);
+  k.bits = addr(env, bits, 0);
+  k.cap_desc = cap(env, desc) / sizeof(clg_pack_block);
+  k.cap_bits = cap(env, bits);
+  k.out_kind = CLG_MEM_HOST;
+  clg_packed_wide w;
+  memset(&w, 0, sizeof w);
+  w.desc = (clg_pack_block*)addr(env, wdesc, 0);
+  w.bits = addr(env, wbits, 0);
+  w.cap_desc = cap(env, wdesc) / sizeof(clg_pack_block);
+  w.cap_bits = cap(env, wbits);
+  w.out_kind = CLG_MEM_HOST;
+  w.bad_row = ~0ull;
+  if (s == CLG_OK) {
+    clg_replay_vertex v;
+    memset(&v, 0, sizeof v);
+    v.acc = &acc;
+    v.subpartitions = ids;
+    v.n_subpartitions = (uint32_t)ns;
+    v.vertex_id = vertex;
+    clg_replay_packed_out o;
+    memset(&o, 0, sizeof o);
+    o.sizes = &c;
+    o.var = with_payloads ? &p : NULL;
+    o.narrow = &k;
+    o.wide = &w;  /* (always: the sizes call, every buffer null, fills the wide sizes too) */
+    o.buffer_sizes = (int32_t*)addr(env, sizes, 0);
+    o.sizes_cap = cap(env, sizes) / 4u;
+    o.sizes_base = sbase;
+    o.sub_count = cnt;
+    o.sub_status = sst;
+    o.sub_err_off = soff;
+    o.sub_err_tag = stg;
+    s = clg_replay_prepare_columns_packed(ENG(e), &v, 1, &o);
+  }
+  jlong r[80] = {(jlong)c.n_rec,      (jlong)c.n_class[0], (jlong)c.n_class[1], (jlong)c.n_class[2], (jlong)c.n_class[3],
+                 (jlong)c.n_class[4], c.err_status,        c.err_span,          c.err_off,           c.err_tag,
+                 (jlong)p.n_rows,     (jlong)p.n_var,      (jlong)p.bad_row};
+  for (int i = 0; i < CLG_PACK_STREAMS; ++i) r[13 + i] = (jlong)k.n_val[i];
+  for (int i = 0; i <= CLG_PACK_STREAMS; ++i) r[18 + i] = (jlong)k.blk_base[i];
+  r[24] = (jlong)k.n_bits;
+  for (int i = 0; i < CLG_WPACK_STREAMS; ++i) r[25 + i] = (jlong)w.n_val[i];
+  for (int i = 0; i <= CLG_WPACK_STREAMS; ++i) r[51 + i] = (jlong)w.blk_base[i];
+  r[78] = (jlong)w.n_bits;
+  r[79] = (jlong)w.bad_row;
+  (*env)->SetLongArrayRegion(env, res, 0, 80, r);
+  for (jsize i = 0; i < ns; ++i) {
+    jlong q[5] = {(jlong)cnt[i], sst[i], soff[i], stg[i], (jlong)sbase[i]};
+    (*env)->SetLongArrayRegion(env, sub_res, 5 * i, 5, q);
+  }
+  (*env)->ReleaseLongArrayElements(env, span_base, base, 0);
+  (*env)->ReleaseLongArrayElements(env, subparts, sp, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, lens, ln, JNI_ABORT);
+  free(ids), free(sbase), free(cnt), free(sst), free(soff), free(stg), free(ents);
+  return s;
+}
+
 /* ---- in-flight (data) log: InMemorySubpartitionInFlightLogger (inflightlogging/, :28-207) or
  * SpillableSubpartitionInFlightLogger (:45-341), by type (CLG_IFL_IN_MEMORY / CLG_IFL_SPILLABLE) ---- */
 JNIEXPORT jint JNICALL FN(nIflOpen)(JNIEnv* env, jclass cls, jlong e, jint type, jintArray out) {

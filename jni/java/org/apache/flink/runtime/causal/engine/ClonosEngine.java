@@ -393,6 +393,35 @@ public final class ClonosEngine implements AutoCloseable {
 		return c;
 	}
 
+	/**
+	 * Replay preparation for one failed task with the main log delivered as packed typed columns
+	 * (clg_replay_prepare_columns_packed): the five narrow columns and the wide rows both bit-packed, the
+	 * payload bytes without pos -- what the cursors of EnginePackedColumns and EnginePackedWide pop from.
+	 * Two native calls, as decodeLogsColumnsPackedWide makes: the sizes, then the blocks into buffers of
+	 * exactly those sizes.  buffers / lens / subpartitions / bufferSizes / subpartitionResults are
+	 * nReplayPrepare's.  A decode error of the main log is in the result's narrow.errStatus(); the blocks
+	 * then hold the records before it.  result.narrow is the EnginePackedColumns.
+	 */
+	public EnginePackedWide replayPrepareColumnsPacked(short vertexId, ByteBuffer[] buffers, int[] lens,
+													   long[] subpartitions, ByteBuffer bufferSizes,
+													   long[] subpartitionResults, boolean withPayloads) {
+		final long[] res = new long[EnginePackedWide.R_LEN];
+		final long[] spanBase = new long[5 * 2];
+		int st = nReplayPrepareColumnsPacked(handle, vertexId, buffers, lens, subpartitions, null, null, null, null,
+			null, withPayloads, res, spanBase, bufferSizes, subpartitionResults);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st); // an engine failure, not a decode error of the main log
+		}
+		final EnginePackedWide c = new EnginePackedWide(res, 1, withPayloads);
+		st = nReplayPrepareColumnsPacked(handle, vertexId, buffers, lens, subpartitions, c.narrow.desc, c.narrow.bits,
+			c.desc, c.bits, c.var, withPayloads, res, c.narrow.spanBase, bufferSizes, subpartitionResults);
+		if (st != CLG_OK && res[6] == CLG_OK) {
+			check(st);
+		}
+		c.setResult(res);
+		return c;
+	}
+
 	@Override
 	public void close() {
 		nDestroy(handle);
@@ -596,4 +625,11 @@ public final class ClonosEngine implements AutoCloseable {
 											ByteBuffer wV1, ByteBuffer wVarOff, ByteBuffer wVarLen, ByteBuffer wSub,
 											ByteBuffer wV0, ByteBuffer var, ByteBuffer varPos, long[] result,
 											long[] spanBase, ByteBuffer bufferSizes, long[] subpartitionResults);
+	/** clg_replay_prepare_columns_packed: nReplayPrepare's inputs, nDecodeLogsColumnsPackedWide's outputs (result:
+	 *  80 longs; spanBase: 10; every buffer null: the sizes only), then
+	 *  nReplayPrepare's subpartition outputs. */
+	static native int nReplayPrepareColumnsPacked(long engine, short vertexId, ByteBuffer[] buffers, int[] lens,
+												  long[] subpartitions, ByteBuffer desc, ByteBuffer bits, ByteBuffer wdesc,
+												  ByteBuffer wbits, ByteBuffer var, boolean withPayloads, long[] result,
+												  long[] spanBase, ByteBuffer bufferSizes, long[] subpartitionResults);
 }

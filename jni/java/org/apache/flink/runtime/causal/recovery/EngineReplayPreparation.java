@@ -26,6 +26,8 @@ import org.apache.flink.runtime.causal.DeterminantResponseEvent;
 import org.apache.flink.runtime.causal.engine.ClonosEngine;
 import org.apache.flink.runtime.causal.engine.EngineDecodedColumns;
 import org.apache.flink.runtime.causal.engine.EngineDecodedLog;
+import org.apache.flink.runtime.causal.engine.EnginePackedColumns;
+import org.apache.flink.runtime.causal.engine.EnginePackedWide;
 import org.apache.flink.runtime.causal.log.job.CausalLogID;
 import org.apache.flink.runtime.io.network.partition.PipelinedSubpartition;
 import org.apache.flink.runtime.jobgraph.IntermediateResultPartitionID;
@@ -75,23 +77,35 @@ public final class EngineReplayPreparation {
 	private final ByteBuffer tag;
 	private final long[] mainResult = new long[6];
 	private final EngineDecodedColumns mainColumns; // the columns form: the main log with its payload column
+	private final EnginePackedWide mainPacked;      // the packed form: both packed halves and the payload bytes
 	private final Map<IntermediateResultPartitionID, Map<Integer, SubpartitionSizes>> bySubpartition = new HashMap<>();
 
 	public EngineReplayPreparation(ClonosEngine engine, RecoveryManagerContext context,
 								   DeterminantResponseEvent determinantAccumulator) {
-		this(engine, context, determinantAccumulator, false);
+		this(engine, context, determinantAccumulator, FORM_SOA);
 	}
+
+	private static final int FORM_SOA = 0, FORM_COLUMNS = 1, FORM_PACKED = 2;
 
 	/** The columns form (nReplayPrepareColumns -> clg_replay_prepare_columns): the same sizes, and the main
 	 *  log as {@link #mainColumns()} -- typed columns with the payload column, what a columns cursor in
 	 *  LogReplayerImpl consumes -- instead of {@link #mainLog}. */
 	public static EngineReplayPreparation columns(ClonosEngine engine, RecoveryManagerContext context,
 												  DeterminantResponseEvent determinantAccumulator) {
-		return new EngineReplayPreparation(engine, context, determinantAccumulator, true);
+		return new EngineReplayPreparation(engine, context, determinantAccumulator, FORM_COLUMNS);
+	}
+
+	/** The packed form (nReplayPrepareColumnsPacked -> clg_replay_prepare_columns_packed): the same sizes, and
+	 *  the main log bit-packed as {@link #mainPacked()} (the five narrow columns) and
+	 *  {@link #mainPackedWide()} (the wide rows by kind, with the payload bytes): the cursors of both pop one
+	 *  typed value at a time from the blocks, and nothing is unpacked on this side. */
+	public static EngineReplayPreparation packed(ClonosEngine engine, RecoveryManagerContext context,
+												 DeterminantResponseEvent determinantAccumulator) {
+		return new EngineReplayPreparation(engine, context, determinantAccumulator, FORM_PACKED);
 	}
 
 	private EngineReplayPreparation(ClonosEngine engine, RecoveryManagerContext context,
-									DeterminantResponseEvent determinantAccumulator, boolean columns) {
+									DeterminantResponseEvent determinantAccumulator, int form) {
 		this.engine = engine;
 		this.context = context;
 		final short vertex = context.getTaskVertexID().getVertexID();
@@ -128,9 +142,15 @@ public final class EngineReplayPreparation {
 		}
 		final ByteBuffer sizes = ByteBuffer.allocateDirect((int) Math.max(4, 4 * sizeSlots)).order(ByteOrder.nativeOrder());
 		final long[] subRes = new long[5 * Math.max(1, ns)];
-		if (columns) {
+		if (form == FORM_PACKED) {
 			this.recOff = null;
 			this.tag = null;
+			this.mainColumns = null;
+			this.mainPacked = engine.replayPrepareColumnsPacked(vertex, bufs, lens, subs, sizes, subRes, true);
+		} else if (form == FORM_COLUMNS) {
+			this.recOff = null;
+			this.tag = null;
+			this.mainPacked = null;
 			this.mainColumns = engine.replayPrepareColumns(vertex, bufs, lens, subs, sizes, subRes);
 		} else {
 			final int mainLen = lens[0];
@@ -138,6 +158,7 @@ public final class EngineReplayPreparation {
 			this.recOff = ByteBuffer.allocateDirect(4 * cap).order(ByteOrder.nativeOrder());
 			this.tag = ByteBuffer.allocateDirect(cap);
 			this.mainColumns = null;
+			this.mainPacked = null;
 			final ByteBuffer v0 = ByteBuffer.allocateDirect(8 * cap);
 			final ByteBuffer wIdx = ByteBuffer.allocateDirect(4 * wcap), wRc = ByteBuffer.allocateDirect(4 * wcap);
 			final ByteBuffer wV1 = ByteBuffer.allocateDirect(8 * wcap), wVo = ByteBuffer.allocateDirect(4 * wcap);
@@ -163,6 +184,18 @@ public final class EngineReplayPreparation {
 	 *  and streams (null unless built by {@link #columns}).  An absent main log is an empty span. */
 	public EngineDecodedColumns mainColumns() {
 		return mainColumns;
+	}
+
+	/** The packed form's narrow columns: EnginePackedColumns.Cursor pops tags and values from the blocks
+	 *  (null unless built by {@link #packed}). */
+	public EnginePackedColumns mainPacked() {
+		return mainPacked == null ? null : mainPacked.narrow;
+	}
+
+	/** The packed form's wide rows and payload bytes: its cursor() serves the wide records (null unless
+	 *  built by {@link #packed}). */
+	public EnginePackedWide mainPackedWide() {
+		return mainPacked;
 	}
 
 	/** The main log's records for LogReplayerImpl (null when the response holds no main log). */
