@@ -78,6 +78,7 @@ EXPORTED = [
     "clg_unpack_wide", "clg_encode_columns_packed_wide", "clg_append_columns_packed_wide",
     "clg_encode_columns_packed_wide_host",
     "clg_replay_prepare_columns_packed", "clg_replay_prepare_columns_packed_device",
+    "clg_pack_payloads", "clg_pack_payloads_host", "clg_unpack_payloads", "clg_unpack_payloads_host",
 ]
 
 
@@ -234,12 +235,26 @@ class PackedWideC(C.Structure):  # clg_packed_wide
 
 # clg_unpack_bad.what
 UNPACK_BAD_NONE, UNPACK_BAD_LAYOUT, UNPACK_BAD_BLOCK, UNPACK_BAD_VALUE = range(4)
+UNPACK_BAD_TOTAL = 4  # the packed payload column's totals
 # in the calls that take both packed forms, a finding in the wide rows reports this + its stream
 UNPACK_WIDE_STREAM = 32
 
 
 class UnpackBad(C.Structure):  # clg_unpack_bad (16 bytes)
     _fields_ = [("what", C.c_uint32), ("stream", C.c_uint32), ("block", C.c_uint64)]
+
+
+PPAY_STREAM = 64  # clg_unpack_bad.stream of a finding in a packed payload column
+
+
+class PackedPayloadsC(C.Structure):  # clg_packed_payloads
+    _fields_ = [
+        ("desc", C.c_void_p), ("bits", C.c_void_p), ("tail", C.c_void_p),
+        ("cap_desc", C.c_uint64), ("cap_bits", C.c_uint64), ("cap_tail", C.c_uint64),
+        ("out_kind", C.c_uint32), ("reserved", C.c_uint32),
+        ("n_rows", C.c_uint64), ("n_var", C.c_uint64), ("n_bits", C.c_uint64), ("n_tail", C.c_uint64),
+        ("bad_row", C.c_uint64),
+    ]
 
 
 class ColumnsIn(C.Structure):  # clg_columns_in
@@ -514,6 +529,11 @@ def _load() -> C.CDLL:
                                                      C.POINTER(ColumnsIn), P, P, C.POINTER(UnpackBad)]),
         "clg_encode_columns_packed_wide_host": (C.c_int, [C.POINTER(Packed), C.POINTER(PackedWideC), C.POINTER(ColumnsIn),
                                                           C.POINTER(Encoded), C.POINTER(UnpackBad)]),
+        "clg_pack_payloads": (C.c_int, [P, P, P, C.c_uint64, C.c_uint32, C.POINTER(PackedPayloadsC)]),
+        "clg_pack_payloads_host": (C.c_int, [P, P, C.c_uint64, C.POINTER(PackedPayloadsC)]),
+        "clg_unpack_payloads": (C.c_int, [P, C.POINTER(PackedPayloadsC), P, C.c_uint32, C.POINTER(Payloads),
+                                          C.POINTER(UnpackBad)]),
+        "clg_unpack_payloads_host": (C.c_int, [C.POINTER(PackedPayloadsC), P, C.POINTER(Payloads), C.POINTER(UnpackBad)]),
         "clg_lcp_host": (C.c_int, [P, C.c_uint64, P, C.c_uint64, u64p]),
         "clg_ifl_open": (C.c_int, [P, u32p]),
         "clg_ifl_open_typed": (C.c_int, [P, C.c_uint32, u32p]),

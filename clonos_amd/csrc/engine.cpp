@@ -28,6 +28,7 @@ static_assert(sizeof(clg_packed) == 136, "clg_packed layout");
 static_assert(sizeof(clg_unpack_bad) == 16, "clg_unpack_bad layout");
 static_assert(sizeof(clg_packed_wide) == 480, "clg_packed_wide layout");
 static_assert(sizeof(clg_encoded) == 56, "clg_encoded layout");
+static_assert(sizeof(clg_packed_payloads) == 96, "clg_packed_payloads layout");
 
 namespace clg_internal {
 

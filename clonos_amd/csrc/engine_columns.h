@@ -3,7 +3,8 @@
 // hidden visibility.  Who defines what:
 //   engine_columns.cpp         decode -> columns: the placement helpers, columnize_device, decode_columns,
 //                              decode_columns_var, gather_payloads_device, wide_row_base, pay_too_small, source_*
-//   engine_pack.cpp            columns -> packed: pack_out_check, decode_columns_packed
+//   engine_pack.cpp            columns -> packed: pack_out_check, decode_columns_packed; the packed payload
+//                              column both ways, nothing of which another unit calls
 //   engine_encode_columns.cpp  columns -> log bytes, packed -> columns: nothing that another unit calls
 //   here                       ColKeep, DecodeSource and carve
 #pragma once

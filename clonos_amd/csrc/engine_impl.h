@@ -281,6 +281,11 @@ struct clg_engine {
   // host-output staging, the rows and pos for the encode; the totals and the verdict (pinned)
   DevBuf d_wunpackin, d_wunpackwork, d_wunpacksoa, d_wunpacktab, d_wunpackout, d_wunpackrow;
   PinBuf h_wunpacktab, h_wunpackres;
+  // the packed payload column: staged host input (var | pos, or desc | bits | tail), the unpack's
+  // staged pos, lcps | descriptors | tile sums | tile bases | findings, host-output staging; the
+  // scans' results (pinned: the kernels write them)
+  DevBuf d_ppayin, d_ppaypos, d_ppaywork, d_ppayout;
+  PinBuf h_ppayres;
   bool fused_decode = true;  // CLG_F_ROBUST_DECODE / CLONOS_DECODE=robust: robust pipeline only
   bool small_decode = true;  // CLG_F_NO_SMALL_DECODE / CLONOS_SMALL=0: no single-launch small batches
 

@@ -1,11 +1,13 @@
 // engine_pack.cpp -- the typed-columns family, columns -> packed: the five narrow columns bit-packed
 // (pack.h), the wide rows packed by record kind (pack_wide.h) and the decodes that deliver either or
 // both; clg_pack_columns*, clg_pack_wide* and clg_decode_{logs,host}_columns_packed[_wide].  The packed
-// decodes run engine_columns.cpp's decode, columns and payload gather, once per batch each.
+// decodes run engine_columns.cpp's decode, columns and payload gather, once per batch each.  The
+// packed payload column (ppay.h) is here both ways: clg_pack_payloads* and clg_unpack_payloads*.
 #include "engine_columns.h"
 #include "columns.h"
 #include "pack.h"
 #include "pack_wide.h"
+#include "ppay.h"
 
 // A packed output's memory kind and alignment (engine_columns.h: the unpacks check their input with it).
 int pack_out_check(const clg::PackView& out, const char* what) {
@@ -321,6 +323,35 @@ int pack_small(clg_engine* e, const PackSmallCall& c, uint32_t* short_cap = null
   return CLG_OK;
 }
 
+
+// ---- the packed payload column (ppay.h) -----------------------------------------------------
+// The pack: lcp and the scan, the host's checks on the scan's results (the lowest bad row, the
+// capacities), then the write.  The unpack: the check and the scan, the host's reading of the
+// findings and the totals, then the write; invalid input writes nothing.
+
+// A packed payload column's memory kind and alignment, as an output or an input.
+int ppay_kind_check(const clg_packed_payloads& p, const char* what) {
+  if (!mem_kind_ok(p.out_kind)) return fail(CLG_E_INVALID_ARG, "%sout_kind %u", what, p.out_kind);
+  if (p.out_kind != CLG_MEM_HOST && (uintptr_t(p.desc) % 8 || uintptr_t(p.bits) % 16))
+    return fail(CLG_E_INVALID_ARG, "desc must be aligned to 8 bytes and bits to 16");
+  return CLG_OK;
+}
+int ppay_pos_check(const uint64_t* pos, uint32_t kind) {
+  if (!mem_kind_ok(kind)) return fail(CLG_E_INVALID_ARG, "pos: memory kind %u", kind);
+  if (kind != CLG_MEM_HOST && uintptr_t(pos) % 8) return fail(CLG_E_INVALID_ARG, "pos must be aligned to 8 bytes");
+  return CLG_OK;
+}
+// The scratch of either direction for n rows in nt tiles.
+int ppay_work(clg_engine* e, uint64_t n, uint64_t nt, clg::PpayWork* w, clg::PpayRes** res) {
+  const uint64_t wb[5] = {n * 4, nt * sizeof(clg_pack_block), nt * 8, nt * 8, nt * 16};
+  clg::Carve<5> c;
+  CHK(carve(e->d_ppaywork, wb, &c));
+  *w = clg::PpayWork{c.at<uint32_t>(0), c.at<clg_pack_block>(1), c.at<uint64_t>(2), c.at<uint64_t>(3), c.at<uint64_t>(4)};
+  CHK(e->h_ppayres.ensure(sizeof(clg::PpayRes)));
+  *res = e->h_ppayres.as<clg::PpayRes>();
+  return CLG_OK;
+}
+
 }  // namespace
 
 // The decode into engine scratch and the columns of what it produced, also in engine scratch;
@@ -501,6 +532,128 @@ int clg_pack_wide(clg_engine* e, const clg_columns* in, clg_packed_wide* out) {
   }
   CHK(wpack_sizes(e, src, out));
   return pack_finish(clg::pack_view(*out), "packed wide rows", [&] { return wpack_write(e, out); });
+}
+
+int clg_pack_payloads(clg_engine* e, const uint8_t* var, const uint64_t* pos, uint64_t n_rows, uint32_t in_kind,
+                      clg_packed_payloads* out) {
+  ENGINE_GUARD(e);
+  if (!out) return fail(CLG_E_INVALID_ARG, "null argument");
+  clg::ppay_reset_result(out);
+  out->n_rows = n_rows;
+  CHK(ppay_kind_check(*out, ""));
+  CHK(ppay_pos_check(pos, in_kind));
+  if (!n_rows) return CLG_OK;  // nothing to launch
+  if (!pos) return fail(CLG_E_INVALID_ARG, "null pos");
+  const uint64_t nt = clg::ppay_blocks(n_rows);
+  if (nt >> 31) return fail(CLG_E_INVALID_ARG, "%llu rows in one call", (unsigned long long)n_rows);
+  // How many bytes of var there are is pos's last entry.  Host-readable input is checked here,
+  // before that entry sizes a copy; device input is checked by the kernel, which reads no byte
+  // of var at or past that entry, and a null var must not have any.
+  uint64_t claim = 0;
+  if (in_kind != CLG_MEM_DEVICE) {
+    for (uint64_t k = 0; k < n_rows; ++k)
+      if (clg::ppay_row_bad(k, pos[k], pos[k + 1])) {
+        out->bad_row = k;
+        return fail(CLG_E_INVALID_ARG, "packed payloads: row %llu of pos is not a row", (unsigned long long)k);
+      }
+    claim = pos[n_rows];
+  } else if (!var) {
+    CHK(e->h_ppayres.ensure(sizeof(clg::PpayRes)));
+    HIPCHK(hipMemcpyAsync(e->h_ppayres.p, pos + n_rows, 8, hipMemcpyDeviceToHost, e->stream));
+    CHK(e->sync());
+    claim = *e->h_ppayres.as<uint64_t>();
+  }
+  if (claim && !var) return fail(CLG_E_INVALID_ARG, "null var");
+  const PlaceSpec ins[2] = {{var, claim, 1}, {pos, (n_rows + 1) * 8, 8}};
+  clg::Placement pin;
+  CHK(place_in(e, e->d_ppayin, ins, 2, in_kind, PlacePolicy::stage_if_unresolved, "payload", &pin));
+  const uint8_t* d_var = pin.at<const uint8_t>(0);
+  const uint64_t* d_pos = pin.at<const uint64_t>(1);
+  clg::PpayWork w;
+  clg::PpayRes* res;
+  CHK(ppay_work(e, n_rows, nt, &w, &res));
+  // (bytes: pos, both rows of a pair at most, the lcps and a descriptor a tile)
+  CHK(e->timed("pack_payloads", n_rows * 12 + 2 * claim + nt * 56,
+               [&] { return clg::launch_ppay_lcp_scan(d_var, d_pos, n_rows, uint32_t(nt), w, res, e->stream); }));
+  CHK(e->sync());
+  if (res->bad_row != clg::kPpayNoRow) {
+    out->bad_row = res->bad_row;
+    return fail(CLG_E_INVALID_ARG, "packed payloads: row %llu of pos is not a row", (unsigned long long)res->bad_row);
+  }
+  out->n_var = res->n_var, out->n_bits = res->n_bits, out->n_tail = res->n_tail;
+  if (clg::ppay_sizes_only(*out)) return CLG_OK;
+  if (const char* name = clg::ppay_short(*out))
+    return fail(CLG_E_CAPACITY, "packed payloads: %s is too small (blocks %llu, payload bytes %llu, tail bytes %llu)", name,
+                (unsigned long long)nt, (unsigned long long)out->n_bits, (unsigned long long)out->n_tail);
+  const PlaceSpec dst[3] = {{out->desc, nt * sizeof(clg_pack_block), 8}, {out->bits, out->n_bits, 16}, {out->tail, out->n_tail, 1}};
+  clg::Placement pl;
+  CHK(place_out(e->d_ppayout, dst, 3, out->out_kind, PlacePolicy::stage_if_unresolved, "packed payload", &pl));
+  CHK(e->timed("pack_payloads", n_rows * 12 + nt * 64 + out->n_bits + 2 * out->n_tail, [&] {
+    return clg::launch_ppay_write(d_var, d_pos, n_rows, uint32_t(nt), w, pl.at<clg_pack_block>(0), pl.at<uint8_t>(1),
+                                  pl.at<uint8_t>(2), out->n_bits, out->n_tail, e->stream);
+  }));
+  CHK(stage_out(e, dst, 3, pl));
+  return e->sync();
+}
+
+int clg_pack_payloads_host(const uint8_t* var, const uint64_t* pos, uint64_t n_rows, clg_packed_payloads* out) {
+  const char* what = "";
+  const int st = clg::ppay_build_host(var, pos, n_rows, out, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "packed payloads: %s", what);
+}
+
+int clg_unpack_payloads(clg_engine* e, const clg_packed_payloads* in, const uint64_t* pos, uint32_t pos_kind,
+                        clg_payloads* out, clg_unpack_bad* bad) {
+  ENGINE_GUARD(e);
+  bool done;
+  const char* what = "";
+  const int st = clg::ppay_unpack_begin(in, pos, out, bad, &done, &what);
+  if (st != CLG_OK) return fail(st, "unpack payloads: %s", what);
+  if (done) return CLG_OK;
+  if (!mem_kind_ok(out->out_kind)) return fail(CLG_E_INVALID_ARG, "out_kind %u", out->out_kind);
+  CHK(ppay_kind_check(*in, "the packed input's "));
+  CHK(ppay_pos_check(pos, pos_kind));
+  const auto finding = [&](uint32_t kind, uint64_t block, const char* text) {
+    clg::pack_bad_set(bad, kind, CLG_PPAY_STREAM, block);
+    return fail(CLG_E_INVALID_ARG, "unpack payloads: %s (block %llu)", text, (unsigned long long)block);
+  };
+  const char* const totals = "the tails do not sum to n_tail, or pos does not end at n_var";
+  const uint64_t n = in->n_rows, nt = clg::ppay_blocks(n);
+  if (!n) return in->n_tail || in->n_var ? finding(CLG_UNPACK_BAD_TOTAL, 0, totals) : CLG_OK;  // nothing to launch
+  if (nt >> 31) return fail(CLG_E_INVALID_ARG, "%llu rows in one call", (unsigned long long)n);
+  const PlaceSpec ins[3] = {{in->desc, nt * sizeof(clg_pack_block), 8}, {in->bits, in->n_bits, 16}, {in->tail, in->n_tail, 1}};
+  const PlaceSpec pin[1] = {{pos, (n + 1) * 8, 8}};
+  const PlaceSpec dst[1] = {{out->var, in->n_var, 1}};
+  clg::Placement pl_in, pl_pos, pl_out;
+  CHK(place_in(e, e->d_ppayin, ins, 3, in->out_kind, PlacePolicy::stage_if_unresolved, "packed payload input", &pl_in));
+  CHK(place_in(e, e->d_ppaypos, pin, 1, pos_kind, PlacePolicy::stage_if_unresolved, "pos", &pl_pos));
+  CHK(place_out(e->d_ppayout, dst, 1, out->out_kind, PlacePolicy::stage_if_unresolved, "var", &pl_out));
+  const uint64_t* d_pos = pl_pos.at<const uint64_t>(0);
+  clg::PpayWork w;
+  clg::PpayRes* res;
+  CHK(ppay_work(e, n, nt, &w, &res));
+  // (bytes: a descriptor and its payload, pos, the lcps written)
+  CHK(e->timed("unpack_payloads", nt * 56 + in->n_bits + n * 12, [&] {
+    return clg::launch_ppay_in_scan(pl_in.at<const clg_pack_block>(0), pl_in.at<const uint8_t>(1), in->n_bits, d_pos, n,
+                                    uint32_t(nt), w, res, e->stream);
+  }));
+  CHK(e->sync());
+  if (res->bad_block != clg::kPpayNoRow) return finding(CLG_UNPACK_BAD_BLOCK, res->bad_block, "malformed block descriptor");
+  if (res->bad_value != clg::kPpayNoRow)
+    return finding(CLG_UNPACK_BAD_VALUE, res->bad_value, "an lcp or a length breaks the format's rules");
+  if (res->n_tail != in->n_tail || res->n_var != in->n_var) return finding(CLG_UNPACK_BAD_TOTAL, 0, totals);
+  CHK(e->timed("unpack_payloads", n * 12 + nt * 8 + in->n_tail + 2 * in->n_var, [&] {
+    return clg::launch_ppay_out(pl_in.at<const uint8_t>(2), d_pos, n, uint32_t(nt), w, pl_out.at<uint8_t>(0), in->n_tail,
+                                in->n_var, e->stream);
+  }));
+  CHK(stage_out(e, dst, 1, pl_out));
+  return e->sync();
+}
+
+int clg_unpack_payloads_host(const clg_packed_payloads* in, const uint64_t* pos, clg_payloads* out, clg_unpack_bad* bad) {
+  const char* what = "";
+  const int st = clg::ppay_unpack_host(in, pos, out, bad, &what);
+  return st == CLG_OK ? CLG_OK : fail(st, "unpack payloads: %s", what);
 }
 
 int clg_pack_wide_host(const clg_columns* in, clg_packed_wide* out) {

@@ -874,6 +874,43 @@ int launch_wunpack_write(const WUnpackTab* d_tab, uint32_t n_blocks, uint32_t n_
                          const uint64_t* d_base, const WUnpackDst& dst, uint64_t n_wide, uint64_t* d_tsum, uint64_t* pos,
                          WUnpackVerdict* d_verdict, void* stream);
 
+// ---- the packed payload column (ppay.h, ppay.hip) -----------------------------------
+// The pack's scratch: a row's lcp, a tile's descriptor (pos: the payload's size, then its offset),
+// tail sum, tail base and lowest bad row.
+struct PpayWork {
+  uint32_t* lcp;
+  clg_pack_block* desc;
+  uint64_t* tsum;
+  uint64_t* tbase;
+  uint64_t* bad;  // the pack: a tile's lowest bad row; the unpack: [2 * tile] block, [2 * tile + 1] value finding
+};
+// The scans' results, in pinned memory the host reads before anything is written to the caller.
+struct PpayRes {
+  uint64_t n_tail;     // the sum of len - lcp
+  uint64_t n_bits;     // the pack only
+  uint64_t n_var;      // pos[n_rows] as the device read it
+  uint64_t bad_row;    // the pack: the lowest bad row, ~0: none
+  uint64_t bad_block;  // the unpack: the lowest tile that fails the block check, ~0: none
+  uint64_t bad_value;  // ... the value rules
+};
+// The pack's lcp pass (a workgroup per tile: lcp, the tile's descriptor, tail sum and lowest bad
+// row) and the scan (one workgroup: tail bases, the payloads' offsets, *res).  No byte of var at or
+// past pos[n_rows] is read, and none of a tile that holds a bad row.
+int launch_ppay_lcp_scan(const uint8_t* var, const uint64_t* pos, uint64_t n_rows, uint32_t n_tiles, const PpayWork& w,
+                         PpayRes* res, void* stream);
+// The pack's write, after the host's checks: the descriptors, the blocks' payloads below n_bits
+// and the tails below n_tail.
+int launch_ppay_write(const uint8_t* var, const uint64_t* pos, uint64_t n_rows, uint32_t n_tiles, const PpayWork& w,
+                      clg_pack_block* desc, uint8_t* bits, uint8_t* tail, uint64_t n_bits, uint64_t n_tail, void* stream);
+// The unpack's check (a workgroup per tile: the block check, the lcps, the pos and lcp rules, the
+// tail sum) and the scan (one workgroup: tail bases, the lowest findings, *res).  No address is
+// formed from a descriptor that failed the block check.
+int launch_ppay_in_scan(const clg_pack_block* desc, const uint8_t* bits, uint64_t n_bits, const uint64_t* pos, uint64_t n_rows,
+                        uint32_t n_tiles, const PpayWork& w, PpayRes* res, void* stream);
+// The unpack's write, after a clean verdict: every row's prefix and tail to var + pos[k], below n_var.
+int launch_ppay_out(const uint8_t* tail, const uint64_t* pos, uint64_t n_rows, uint32_t n_tiles, const PpayWork& w,
+                    uint8_t* var, uint64_t n_tail, uint64_t n_var, void* stream);
+
 // ---- append scatter ---------------------------------------------------------------
 struct ScatterChunk {
   uint8_t* dst;        // inside one segment

@@ -79,18 +79,6 @@ __device__ __forceinline__ void pay_rows(const PayIn& in, uint64_t k0, const uin
   }
 }
 
-// The bytes before this thread's rows inside the tile (exclusive scan of the threads' sums).
-__device__ __forceinline__ uint64_t pay_tile_excl(uint64_t tsum, uint32_t tid, uint64_t* ws) {
-  const uint32_t lane = tid & 63, w = tid >> 6;
-  const uint64_t inc = wave_incl(tsum, lane);
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  uint64_t before = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < kPayWaves; ++k) before += k < w ? ws[k] : 0;
-  return before + inc - tsum;
-}
-
 // One lane copies a short row: loads and stores stay inside the row's own bytes, across a
 // segment boundary too.
 __device__ __forceinline__ void pay_copy_lane(const PayIn& in, const PaySpan& sp, uint32_t off, uint32_t len,
@@ -186,7 +174,7 @@ __global__ __launch_bounds__(kPayThreads) void k_pay_pos(const PayIn in, const u
   const uint64_t k0 = uint64_t(blockIdx.x) * kPayTile + uint64_t(tid) * kPayPerThread;
   uint32_t len[kPayPerThread];
   pay_load4(in.len, k0, in.n_rows, len);
-  uint64_t at = base[blockIdx.x] + pay_tile_excl(uint64_t(len[0]) + len[1] + len[2] + len[3], tid, ws);
+  uint64_t at = base[blockIdx.x] + tile_excl<kPayWaves>(uint64_t(len[0]) + len[1] + len[2] + len[3], tid, ws);
 #pragma unroll
   for (uint32_t j = 0; j < kPayPerThread; ++j) {
     if (k0 + j < in.n_rows) pos[k0 + j] = at;
@@ -219,7 +207,7 @@ __device__ __forceinline__ void pay_copy_tile(const PayIn& in, uint64_t tile0, u
   __syncthreads();
   PayRows r;
   pay_rows(in, k0, l.rng, r);
-  uint64_t at = base + pay_tile_excl(uint64_t(r.len[0]) + r.len[1] + r.len[2] + r.len[3], tid, l.ws);
+  uint64_t at = base + tile_excl<kPayWaves>(uint64_t(r.len[0]) + r.len[1] + r.len[2] + r.len[3], tid, l.ws);
 #pragma unroll
   for (uint32_t j = 0; j < kPayPerThread; ++j) {
     const uint32_t L = r.len[j];

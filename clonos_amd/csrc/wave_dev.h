@@ -1,7 +1,8 @@
 // wave_dev.h -- what the kernels of the typed-columns family (columns.hip, payload.hip,
 // encode_columns.hip and, through pack_dev.h, the four pack files) share below the level of a
-// format: the wave's primitives on 32- and 64-bit unsigned words, the workgroup's minimum, and the
-// one-workgroup scan of per-tile values that every "ONE workgroup" pass of the family is.
+// format: the wave's primitives on 32- and 64-bit unsigned words, the workgroup's minimum, a tile's
+// exclusive scan across its threads, and the one-workgroup scan of per-tile values that every
+// "ONE workgroup" pass of the family is.
 // Device code only, file-local in each unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -69,6 +70,21 @@ __device__ __forceinline__ T block_min(T x) {
     for (uint32_t j = 1; j < kThreads / 64; ++j) x = wb[j] < x ? wb[j] : x;
   }
   return x;
+}
+
+// The values before this thread's among kWaves * 64 threads numbered tid (a workgroup, or the part
+// of one that works on a tile): the exclusive scan of the threads' x.  ws: kWaves words of LDS of
+// those threads' own.  All of them call it; one __syncthreads inside.
+template <uint32_t kWaves>
+__device__ __forceinline__ uint64_t tile_excl(uint64_t x, uint32_t tid, uint64_t* ws) {
+  const uint32_t lane = tid & 63, w = tid >> 6;
+  const uint64_t inc = wave_incl(x, lane);
+  if (lane == 63) ws[w] = inc;
+  __syncthreads();
+  uint64_t before = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kWaves; ++k) before += k < w ? ws[k] : 0;
+  return before + inc - x;
 }
 
 // The one-workgroup scan of per-tile values: kLanes independent columns of n_tiles values each

@@ -814,6 +814,110 @@ def unpack_wide_host(packed: PackedWide) -> dict:
     return arrs
 
 
+class PackedPayloads:
+    """The payload column front-coded against same-length anchor rows (layout: include/clonos_engine.h
+    clg_packed_payloads; the format: clonos_amd/csrc/ppay.h): desc and bits, the rows' lcps as one
+    FOR stream of PACK_BLOCK blocks, and tail, the bytes behind each row's lcp, in row order.  The
+    lengths are not part of it: unpack(pos) takes the column's pos."""
+
+    def __init__(self, desc, bits, tail, n_rows, n_var):
+        self.desc, self.bits, self.tail = desc, bits, tail
+        self.n_rows, self.n_var = int(n_rows), int(n_var)
+
+    @property
+    def n_bytes(self) -> int:
+        """The delivered size: descriptors, payload bits and tails."""
+        return int(self.desc.nbytes + self.bits.nbytes + self.tail.nbytes)
+
+    def _struct(self) -> _lib.PackedPayloadsC:
+        p = _packed_payloads_struct(self.desc, self.bits, self.tail)
+        p.n_rows, p.n_var, p.n_bits, p.n_tail = self.n_rows, self.n_var, self.bits.size, self.tail.size
+        return p
+
+    def unpack(self, pos) -> np.ndarray:
+        """clg_unpack_payloads_host: var of the column whose pos is given.  Invalid input raises
+        ClonosError with bad_what, bad_stream and bad_block."""
+        return unpack_payloads_host(self, pos)
+
+
+def _packed_payloads_struct(desc: Optional[np.ndarray], bits: Optional[np.ndarray], tail: Optional[np.ndarray],
+                            kind: int = _lib.CLG_MEM_HOST) -> _lib.PackedPayloadsC:
+    """clg_packed_payloads over host arrays (capacity = their lengths); all None: sizes only."""
+    p = _lib.PackedPayloadsC()
+    if desc is not None:
+        p.desc, p.cap_desc = _np_ptr(desc), desc.size
+    if bits is not None:
+        p.bits, p.cap_bits = _np_ptr(bits), bits.size
+    if tail is not None:
+        p.tail, p.cap_tail = _np_ptr(tail), tail.size
+    p.out_kind = kind
+    return p
+
+
+def _packed_payloads_error(st: int, p: _lib.PackedPayloadsC) -> ClonosError:
+    err = ClonosError(st, lib.clg_last_error().decode(errors="replace"))
+    err.n_rows, err.n_var, err.n_bits, err.n_tail = int(p.n_rows), int(p.n_var), int(p.n_bits), int(p.n_tail)
+    err.bad_row = int(p.bad_row)
+    return err
+
+
+def _pack_payloads_twice(call) -> PackedPayloads:
+    """call(clg_packed_payloads) -> status, first for the sizes, then into host arrays of exactly those."""
+    p = _lib.PackedPayloadsC()
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _packed_payloads_error(st, p)
+    desc = np.zeros((int(p.n_rows) + _lib.PACK_BLOCK - 1) // _lib.PACK_BLOCK, PACK_BLOCK)
+    bits, tail = np.zeros(int(p.n_bits), np.uint8), np.zeros(int(p.n_tail), np.uint8)
+    if int(p.n_rows) == 0:  # (every pointer would be null: the sizes-only call again)
+        return PackedPayloads(desc, bits, tail, 0, 0)
+    # (arrays without bytes still need an address: a null one of three is an array that holds nothing)
+    keep = [a if a.size else np.zeros(1, a.dtype) for a in (desc, bits, tail)]
+    p = _packed_payloads_struct(*keep)
+    p.cap_desc, p.cap_bits, p.cap_tail = desc.size, bits.size, tail.size
+    st = call(p)
+    if st != _lib.CLG_OK:
+        raise _packed_payloads_error(st, p)
+    return PackedPayloads(desc, bits, tail, p.n_rows, p.n_var)
+
+
+def _payload_column(var, pos) -> Tuple[np.ndarray, np.ndarray]:
+    buf = np.frombuffer(bytes(var), np.uint8) if not isinstance(var, np.ndarray) else np.ascontiguousarray(var, np.uint8)
+    pos = np.ascontiguousarray(pos, np.uint64)
+    if pos.size == 0:
+        raise ValueError("pos holds n_rows + 1 entries")
+    return buf, pos
+
+
+def pack_payloads_host(var, pos) -> PackedPayloads:
+    """clg_pack_payloads_host: the payload column (var, pos) front-coded on the CPU (no engine, no
+    GPU) -- the same bytes Engine.pack_payloads produces on the device.  A pos that is no prefix
+    sum of row lengths below 2^32 raises ClonosError with bad_row."""
+    buf, pos = _payload_column(var, pos)
+    return _pack_payloads_twice(lambda p: lib.clg_pack_payloads_host(_np_ptr(buf) or None, _np_ptr(pos), pos.size - 1, C.byref(p)))
+
+
+def _unpack_payloads(call, packed: PackedPayloads) -> np.ndarray:
+    """call(clg_packed_payloads, clg_payloads, clg_unpack_bad) -> status, into a host var of n_var bytes."""
+    p = packed._struct()
+    var = np.empty(max(packed.n_var, 1), np.uint8)  # (one spare byte: a null var is the sizes-only call)
+    out = _payloads_struct(var, None)
+    out.cap_var = packed.n_var
+    bad = _lib.UnpackBad()
+    st = call(p, out, bad)
+    if st != _lib.CLG_OK:
+        raise _unpack_error(st, bad)
+    return var[:packed.n_var]
+
+
+def unpack_payloads_host(packed: PackedPayloads, pos) -> np.ndarray:
+    """clg_unpack_payloads_host: var of a packed payload column whose pos is given, on the CPU.
+    Invalid input raises ClonosError with bad_what, bad_stream (PPAY_STREAM) and bad_block."""
+    pos = np.ascontiguousarray(pos, np.uint64)
+    return _unpack_payloads(lambda p, out, bad: lib.clg_unpack_payloads_host(C.byref(p), _np_ptr(pos) or None, C.byref(out),
+                                                                             C.byref(bad)), packed)
+
+
 def _wide_route(cols, wide: str) -> bool:
     """Whether cols take the device route of the wide rows (clg_*_columns_packed_wide)."""
     if wide not in ("host", "device"):
@@ -1491,6 +1595,38 @@ class Engine:
         """clg_unpack_columns over a clg_packed and a clg_columns the caller set up (any kinds; the
         five narrow pointers null: sizes only).  Returns the status; the results are in cols and bad."""
         return lib.clg_unpack_columns(self._h, C.byref(pin), C.byref(cols), C.byref(bad))
+
+    # ---- the packed payload column (clg_packed_payloads)
+    def pack_payloads(self, var, pos, device: bool = False, n_rows: Optional[int] = None) -> PackedPayloads:
+        """clg_pack_payloads: the payload column (var, pos) front-coded on the device; the bytes are
+        pack_payloads_host's.  device=False: var and pos are host arrays (staged); device=True: they
+        are device addresses (ints) and n_rows is given.  The packed form is read back."""
+        if device:
+            vp, pp, n, kind, keep = int(var or 0), int(pos or 0), int(n_rows), _lib.CLG_MEM_DEVICE, None
+        else:
+            keep = _payload_column(var, pos)
+            vp, pp, n, kind = _np_ptr(keep[0]), _np_ptr(keep[1]), keep[1].size - 1, _lib.CLG_MEM_HOST
+        return _pack_payloads_twice(lambda p: lib.clg_pack_payloads(self._h, vp or None, pp or None, n, kind, C.byref(p)))
+
+    def pack_payloads_raw(self, var: Optional[int], pos: Optional[int], n_rows: int, in_kind: int,
+                          out: _lib.PackedPayloadsC) -> int:
+        """clg_pack_payloads over addresses and a clg_packed_payloads the caller set up (any kinds;
+        desc, bits and tail null: sizes only).  Returns the status; the results are in out."""
+        return lib.clg_pack_payloads(self._h, var or None, pos or None, n_rows, in_kind, C.byref(out))
+
+    def unpack_payloads(self, packed: PackedPayloads, pos) -> np.ndarray:
+        """clg_unpack_payloads: a host packed payload column unpacked on the device (staged in,
+        checked, unpacked, read back): var of the column whose pos (a host array) is given.  Invalid
+        input raises ClonosError with bad_what, bad_stream and bad_block."""
+        pos = np.ascontiguousarray(pos, np.uint64)
+        return _unpack_payloads(lambda p, out, bad: lib.clg_unpack_payloads(
+            self._h, C.byref(p), _np_ptr(pos) or None, _lib.CLG_MEM_HOST, C.byref(out), C.byref(bad)), packed)
+
+    def unpack_payloads_raw(self, pin: _lib.PackedPayloadsC, pos: Optional[int], pos_kind: int, out: _lib.Payloads,
+                            bad: _lib.UnpackBad) -> int:
+        """clg_unpack_payloads over a clg_packed_payloads, a pos address and a clg_payloads the
+        caller set up (any kinds; var null: sizes only).  Returns the status."""
+        return lib.clg_unpack_payloads(self._h, C.byref(pin), pos or None, pos_kind, C.byref(out), C.byref(bad))
 
     def _decode_packed(self, call, total: int, n: int, spans_bytes, partial: bool, payloads: bool,
                        pack_wide: bool = False) -> PackedColumns:

@@ -540,7 +540,8 @@ int clg_unpack_columns_host(const clg_packed* in, uint32_t stream, uint64_t firs
  *           rule and is unchanged).  Blocks may lie in any payload order and may share payload bytes
  *   VALUE   an unpacked value outside its stream's type (timestamps always pass)
  * With what == NONE, stream is 0 and block ~0. */
-enum { CLG_UNPACK_BAD_NONE = 0, CLG_UNPACK_BAD_LAYOUT = 1, CLG_UNPACK_BAD_BLOCK = 2, CLG_UNPACK_BAD_VALUE = 3 };
+enum { CLG_UNPACK_BAD_NONE = 0, CLG_UNPACK_BAD_LAYOUT = 1, CLG_UNPACK_BAD_BLOCK = 2, CLG_UNPACK_BAD_VALUE = 3,
+       CLG_UNPACK_BAD_TOTAL = 4 /* the packed payload column's totals (4.11) */ };
 typedef struct clg_unpack_bad { uint32_t what; uint32_t stream; uint64_t block; } clg_unpack_bad;  /* 16 bytes */
 
 /* The whole unpack on the device: out->tag / order / timestamp / rng / buffer_built are written
@@ -850,6 +851,70 @@ int clg_append_columns_packed_wide(clg_engine* e, const uint32_t* log, const int
                                    uint64_t* span_bytes, int32_t* status, clg_unpack_bad* bad);
 int clg_encode_columns_packed_wide_host(const clg_packed* narrow, const clg_packed_wide* wide,
                                         const clg_columns_in* rest, clg_encoded* out, clg_unpack_bad* bad);
+
+/* ---- the packed payload column ---------------------------------------------
+ * The payload column (clg_payloads: var, pos) front-coded against same-length anchor rows, so that
+ * the repeated names and Java streams cross the link once (clonos_amd/csrc/ppay.h is the format's
+ * one definition).  For a column of n_rows rows, len_k = pos[k + 1] - pos[k]:
+ *   tile t     rows [1024 t, min(1024 (t + 1), n_rows)), one block of the LCP stream
+ *   anchor(k)  the lowest row j of k's tile with len_j == len_k; it depends on the lengths alone,
+ *              so nothing about it is stored
+ *   lcp_k      0 when anchor(k) == k, else the count of leading bytes in which rows k and anchor(k)
+ *              agree, 0 .. len_k (the pack emits the maximum)
+ *   tail_k     bytes [lcp_k, len_k) of row k
+ * desc and bits hold the stream lcp u32[n_rows], FOR, in clg_packed's block format exactly, one
+ * block a tile; tail holds the tails back to back in row order, n_tail bytes.  Row k decodes to
+ * tail_anchor(k)[0 : lcp_k] followed by tail_k: every row is packed and unpacked on its own.  The
+ * lengths are not stored (the wide rows carry them as w_var_len), so the unpack takes pos.
+ * n_tail <= n_var and n_bits is at most that of 1024-value blocks of 32-bit values. */
+#define CLG_PPAY_STREAM 64   /* clg_unpack_bad.stream of a finding in a packed payload column */
+typedef struct clg_packed_payloads {
+  clg_pack_block* desc;
+  uint8_t* bits;
+  uint8_t* tail;
+  uint64_t cap_desc;      /* blocks */
+  uint64_t cap_bits;      /* bytes */
+  uint64_t cap_tail;      /* bytes */
+  uint32_t out_kind;      /* CLG_MEM_HOST / CLG_MEM_DEVICE / CLG_MEM_MAPPED (all three arrays) */
+  uint32_t reserved;
+  /* results */
+  uint64_t n_rows;
+  uint64_t n_var;
+  uint64_t n_bits;        /* bytes used of bits */
+  uint64_t n_tail;        /* bytes used of tail */
+  uint64_t bad_row;       /* ~0 when none */
+} clg_packed_payloads;
+
+/* Pack the payload column var (pos[n_rows] bytes), pos (n_rows + 1 entries), both under in_kind.
+ * The rules are clg_pack_columns': device and registered memory are read and written in place
+ * (bits 16-byte aligned, desc and pos 8-byte aligned, else CLG_E_INVALID_ARG), host memory goes
+ * through engine staging; all three outputs NULL is the sizes-only call; a capacity below its
+ * total is CLG_E_CAPACITY with every result filled and nothing written.  pos[0] != 0, a decreasing
+ * pos or a row of 2^32 bytes or more: CLG_E_INVALID_ARG with the lowest such row in bad_row and
+ * nothing written; no byte of var outside [0, pos[n_rows]) is read, and none of a tile that holds
+ * such a row.  n_rows == 0 launches nothing.  Synchronous; takes the engine guard; the kernels'
+ * time is the stat "pack_payloads". */
+int clg_pack_payloads(clg_engine* e, const uint8_t* var, const uint64_t* pos, uint64_t n_rows,
+                      uint32_t in_kind, clg_packed_payloads* out);
+/* The same bytes and rules on the CPU (no engine, no GPU): every array is host memory. */
+int clg_pack_payloads_host(const uint8_t* var, const uint64_t* pos, uint64_t n_rows, clg_packed_payloads* out);
+/* The way back: out->var is written under cap_var and out->out_kind, n_rows and n_var are filled,
+ * out->pos is not touched.  pos (under pos_kind) is the column's pos, as clg_unpack_wide delivers
+ * it.  var NULL: sizes only.  cap_var < n_var: CLG_E_CAPACITY with nothing written.  The input is
+ * not trusted (in->out_kind names where desc, bits and tail live; the memory rules are
+ * clg_unpack_columns').  Findings are reported with stream = CLG_PPAY_STREAM and write nothing, in
+ * this order, each with its lowest block (a tile):
+ *   LAYOUT  cap_desc below ceil(n_rows / 1024), a capacity below its total, a null array that
+ *           would be read (pos among them); block 0; checked on the host before the sizes
+ *   BLOCK   clg_unpack_columns' block rules, pos % 16 == 0 included
+ *   VALUE   an lcp above its row's length, a non-zero lcp on a row that is its own anchor,
+ *           pos[0] != 0, a decreasing pos, a row of 2^32 bytes or more
+ *   TOTAL   the sum of len_k - lcp_k differs from n_tail, or pos[n_rows] from in->n_var; block 0
+ * Synchronous; takes the engine guard; the kernels' time is the stat "unpack_payloads". */
+int clg_unpack_payloads(clg_engine* e, const clg_packed_payloads* in, const uint64_t* pos, uint32_t pos_kind,
+                        clg_payloads* out, clg_unpack_bad* bad);
+/* The same call on the CPU (no engine, no GPU): every array is host memory. */
+int clg_unpack_payloads_host(const clg_packed_payloads* in, const uint64_t* pos, clg_payloads* out, clg_unpack_bad* bad);
 
 /* ---- DeterminantResponseEvent (DeterminantResponseEvent.java:36-148) ---------------------
  * The event's map CausalLogID -> log bytes is held as an entry array in the iteration
